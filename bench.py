@@ -20,9 +20,14 @@ Multi-GPU (N > 1, strong scaling of the same pair): every rank holds 1/N of each
 the files); one all-to-all moves every point to the rank that owns its slab or needs it as halo, then each rank sorts,
 indexes and searches only that (cloud_map_evaluation_amd/dist.py::suite_step_dist).
 
-Extra objects on the JSON line: "roofline" (dominant kernel, HIP-event timed inside this process), "h2d_inclusive", and
-"cpu_baseline" (the CPU oracle = port of the reference's CPU path, on this box's host cores: full-size KD-trees, 1 % query
-subsample, best of 3 — BASELINE.md section 3).
+A plain run sets up, settles and warms up, times the K steps and prints the line (`ms_per_step` = one timed step).
+--full adds, after the timed steps, the extra objects on the JSON line: "cross_checks" (N = 1: the other driver and the copying
+upload, interleaved), "roofline" (dominant kernel, HIP-event timed inside this process), "h2d_inclusive", and "cpu_baseline"
+(the CPU oracle = port of the reference's CPU path, on this box's host cores: full-size KD-trees, 1 % query subsample, best
+of 3 — BASELINE.md section 3).  --no-roofline / --no-h2d / --cpu-baseline select among them.
+
+--dump-outputs DIR writes what the last timed step returned (the suite's scalars and 5-level vectors) as DIR/<name>.npy,
+float64; the inputs are seeded, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -82,6 +87,9 @@ def parse():
     ap.add_argument("--settle-max", type=int, default=12, help="N = 1: at most this many untimed settling steps before the warm-up (0 = none)")
     ap.add_argument("--no-overlap", action="store_true", help="single lane: every stage back to back on one stream")
     ap.add_argument("--py-driver", action="store_true", help="N = 1: drive the step from Python (round 4's bench) instead of me_run_suite_from")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the cross-checks, the roofline pass, the H2D-inclusive timing and the CPU baselines after the timed steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's results as DIR/<name>.npy (float64)")
     a = ap.parse_args()
     w = WORKLOADS[a.workload]
     a.points = a.points or w["points"]
@@ -133,6 +141,23 @@ def suite_step(eng, dist, world, est_d, gt_d, P, evaluate_gt_mme, comm_dev=None)
     from cloud_map_evaluation_amd.engine import Engine
 
     return Engine.suite_dict(eng.run_suite_from(est_d, gt_d, P, overlap=OVERLAP))
+
+
+DIRECTION_OUTPUTS = ("number", "mean", "rmse", "fitness", "sigma", "n_corr", "mean_nn")
+SCALAR_OUTPUTS = ("cd", "mme_est", "mme_gt", "mme_valid", "awd", "scs", "n_w", "n_est", "n_gt")
+
+
+def dump_outputs(path, res):
+    """--dump-outputs: what one step hands its caller (every driver returns these keys), one float64 .npy per name — the two
+    1-NN directions' 5-level statistics (`est_gt_rmse` = AC, `est_gt_fitness` = COM, ...) and the suite's scalars.  `ac` / `com`
+    are the same arrays as est_gt's rmse / fitness; the stage timings are not outputs."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    arrays = {f"{d}_{k}": res[d][k] for d in ("est_gt", "gt_est") for k in DIRECTION_OUTPUTS}
+    arrays.update({k: res[k] for k in SCALAR_OUTPUTS})
+    for name, v in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.atleast_1d(np.asarray(v, dtype=np.float64)))
 
 
 def _best_of(fn, reps=3):
@@ -362,12 +387,19 @@ def main():
     step_ms = []
     ms_per_step, res = timed(est_d, gt_d, args.steps, args.warmup, step_ms)
     value = (n_e + n_g) / 1e6 / (ms_per_step / 1e3)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res)
+
+    # Everything below the headline runs with --full only: a plain run is set-up, warm-up, the timed steps and the line.
+    roofline = args.full and not args.no_roofline
+    h2d = args.full and not args.no_h2d
+    cpu_baseline = args.cpu_baseline if args.full else "off"
 
     # cross-checks of the headline (N = 1): the same schedule driven from Python, and the engine without ME_FLAG_BORROW_DEVICE_INPUT
     # (the default of me_create: the upload copies the resident cloud first).  INTERLEAVED (A / B / C / A / B / C ..., one step each,
     # round 6): three blocks one after the other compared three moments of the box (clocks, temperature) as much as three drivers.
     xcheck = {}
-    if world == 1 and not args.no_roofline:
+    if world == 1 and roofline:
         k = max(3, min(8, args.steps))
         eng_copy = Engine(local_rank, borrow_device_input=False)
         eng_main = eng
@@ -433,7 +465,7 @@ def main():
         line["cross_checks"] = xcheck
 
     # ---- roofline of the dominant kernel: HIP events on the library's own stream, one extra (untimed) step ----
-    if not args.no_roofline:
+    if roofline:
         eng.timers_enable(True)
         eng.timers_reset()
         OVERLAP = False  # kernels timed one at a time
@@ -510,10 +542,10 @@ def main():
 
     # ---- the same step from pinned HOST buffers (SURVEY.md 8d span: H2D included) ----
     est_h = gt_h = None
-    need_host = world == 1 and rank == 0 and (not args.no_h2d or args.cpu_baseline == "full")
+    need_host = world == 1 and rank == 0 and (h2d or cpu_baseline == "full")
     if need_host:
         est_h, gt_h = est_d.cpu(), gt_d.cpu()
-    if world == 1 and not args.no_h2d:
+    if world == 1 and h2d:
         est_p, gt_p = est_h.pin_memory(), gt_h.pin_memory()
         h_ms, h_res = timed(est_p, gt_p, max(2, min(3, args.steps)), 1)
         # the two spans side by side (small items): SURVEY 8(d) words the span from HOST memory, the task contract
@@ -537,10 +569,10 @@ def main():
                                  "same_results": bool(h_res["mme_valid"] == res["mme_valid"] and h_res["cd"] == res["cd"])}
         del est_p, gt_p
 
-    if rank == 0 and world == 1 and args.cpu_baseline != "off":
+    if rank == 0 and world == 1 and cpu_baseline != "off":
         del est_d, gt_d
         torch.cuda.empty_cache()
-        if args.cpu_baseline == "full":
+        if cpu_baseline == "full":
             line["cpu_baseline"] = cpu_baseline_full(est_h.numpy(), gt_h.numpy(), P, evaluate_gt_mme)
         else:
             line["cpu_baseline"] = cpu_baseline_sample(args, P, evaluate_gt_mme)
@@ -548,7 +580,7 @@ def main():
             line["cpu_baseline"]["reference_run"] = cpu_baseline_reference(args, P, evaluate_gt_mme)
         except Exception as e:  # (a checker, never the product: its absence or failure does not fail the bench)
             line["cpu_baseline"]["reference_run"] = {"error": str(e)[:200]}
-        if args.cpu_baseline == "full":
+        if cpu_baseline == "full":
             try:  # ... and on a 5 M + 5 M pair WITHOUT the GT-MME (its serial loop, map_eval.cpp:1451, is what makes 50 M impractical): the
                 #     reference's scaling with tree depth
                 r5 = cpu_baseline_reference(args, P, False, n=5_000_000)

@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B of the MME kernels (round 3): parity tests on the default library, then timings of the variants of the -DME_AB build
 python -m pytest tests/test_gpu_parity.py tests/test_gpu_degenerate.py tests/test_gpu_ref.py -x -q -m gpu -k "mme or degenerate or tunnel or c1_process or 1m_three" 2>&1 | tail -5
-run() { python bench.py --cpu-baseline off --no-h2d --steps 3 2>/dev/null | python -c "
+run() { python bench.py --full --cpu-baseline off --no-h2d --steps 3 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); r=d['roofline']
 print('ms/step', round(d['ms_per_step'],2), 'kernel ms', {k:round(v,2) for k,v in r['kernel_ms_per_step'].items()}, 'MMEvalid', d['results']['MME_valid'], 'MME', d['results']['MME_est'], d['results']['MME_gt'])"; }

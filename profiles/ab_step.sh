@@ -3,7 +3,7 @@
 # library, alternating on ONE box:   bash profiles/ab_step.sh [libA.so] [rounds] [extra bench args...]
 A=${1:-$PWD/scratch/libmapeval_hip_r05.so}; R=${2:-2}; shift 2 2>/dev/null
 B=$PWD/cloud_map_evaluation_amd/libmapeval_hip.so
-run() { MAPEVAL_HIP_LIB=$1 python bench.py --cpu-baseline off --no-h2d --steps 10 --warmup 3 "${@:2}" 2>/dev/null | python -c "
+run() { MAPEVAL_HIP_LIB=$1 python bench.py --full --cpu-baseline off --no-h2d --steps 10 --warmup 3 "${@:2}" 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); r=d.get('roofline') or {}
 k=r.get('kernel_ms_per_step',{})

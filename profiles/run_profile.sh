@@ -7,7 +7,7 @@ ROOT=$(pwd)
 OUT=$ROOT/gpurun_out/prof_$TAG
 rm -rf "$OUT"; mkdir -p "$OUT"
 export TMPDIR=/tmp
-BENCH="python $ROOT/bench.py --cpu-baseline off --no-h2d"
+BENCH="python $ROOT/bench.py --full --cpu-baseline off --no-h2d"
 cd /tmp
 timeout 240 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -- $BENCH --steps 3 --warmup 1 > "$OUT/bench_under_rocprof.json" 2> "$OUT/stats.err"
 # the same with ONE lane (round 5): per-launch averages that are not stretched by the other lane's kernels — what

@@ -7,7 +7,7 @@
 TAG=${1:-r04}
 OUT=gpurun_out/summary_$TAG
 mkdir -p "$OUT"
-python bench.py > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"
+python bench.py --full > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"
 python - "$OUT" <<'PY'
 import json, os, re, subprocess, sys
 out = {}
@@ -16,7 +16,7 @@ out = {}
 def bench(extra, env=None):
     e = dict(os.environ)
     e.update(env or {})
-    r = subprocess.run([sys.executable, "bench.py", "--cpu-baseline", "off", "--steps", "3"] + extra, capture_output=True, text=True, env=e)
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--cpu-baseline", "off", "--steps", "3"] + extra, capture_output=True, text=True, env=e)
     return json.loads(r.stdout.strip().splitlines()[-1]), r.stderr
 
 
@@ -52,7 +52,7 @@ for rho in (2500, 10000, 40000):
             e["mme_ns_per_accepted_pair"] = e["kernel_ms_per_step"]["mme"] * 1e6 / pairs
     dens[str(rho)] = e
 out["density_sweep_c4_multisession"] = dens
-out["_note"] = ("python bench.py --workload <w> --cpu-baseline off --steps 3 (profiles/run_workloads.sh); density sweep: --density <rho> on the "
+out["_note"] = ("python bench.py --full --workload <w> --cpu-baseline off --steps 3 (profiles/run_workloads.sh); density sweep: --density <rho> on the "
                 "c4_multisession pair, group statistics from the -DME_MME_STATS build")
 json.dump(out, open(sys.argv[1] + "/workloads.json", "w"), indent=1)
 PY

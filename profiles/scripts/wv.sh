@@ -1,5 +1,5 @@
 #!/bin/bash
-run() { MAPEVAL_HIP_LIB=$1 python bench.py --cpu-baseline off --no-h2d --steps 6 --warmup 2 2>/dev/null | python -c "
+run() { MAPEVAL_HIP_LIB=$1 python bench.py --full --cpu-baseline off --no-h2d --steps 6 --warmup 2 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); k=d['roofline']['kernel_ms_per_step']
 print('  ms/step %.2f' % d['ms_per_step'], '| mme %.2f nn_grid %.2f' % (k['mme'], k['nn_grid']), '| MME', d['results']['MME_est'], d['results']['MME_valid'])"; }

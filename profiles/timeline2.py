@@ -1,5 +1,5 @@
 """Timeline of one TWO-LANE step (the last timed one, before the per-kernel timing pass) from a rocprofv3 kernel trace:
-   cd /tmp && rocprofv3 --kernel-trace --output-format csv -d $OUT -- python bench.py --cpu-baseline off --no-h2d --steps 3 --warmup 1
+   cd /tmp && rocprofv3 --kernel-trace --output-format csv -d $OUT -- python bench.py --full --cpu-baseline off --no-h2d --steps 3 --warmup 1
    python profiles/timeline2.py $OUT
 Per queue: busy time, first / last kernel; the union of both queues (time the GPU ran nothing); the long kernels in order."""
 import csv

@@ -68,3 +68,34 @@ def test_cpu_baseline_full_arithmetic_on_a_small_pair():
     np.testing.assert_allclose(r["extrapolated_suite_seconds"], ref, rtol=0.02)  # (the dict is rounded to ms)
     np.testing.assert_allclose(r["value"], 0.08 / r["extrapolated_suite_seconds"], rtol=1e-9)
     assert r["all_parallel"]["value"] >= 0.5 * r["value"]  # all-parallel is never much slower than the reference's structure
+
+
+def test_plain_run_options_and_the_output_dump(monkeypatch, tmp_path):
+    """--full is off by default (a plain run times the steps and prints the headline only); --dump-outputs writes the step's
+    results one float64 .npy per name, the names every driver's result dict carries."""
+    import bench
+
+    monkeypatch.setattr("sys.argv", ["bench.py", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    monkeypatch.setattr("sys.argv", ["bench.py", "--full", "--dump-outputs", str(tmp_path / "out")])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == str(tmp_path / "out") and a.cpu_baseline == "full"
+
+    def direction(k):
+        return dict(n_corr=1000 + k, number=np.arange(5.0) + k, mean=np.full(5, 0.1 * k), rmse=np.full(5, 0.2 * k),
+                    fitness=np.full(5, 0.3 * k), sigma=np.full(5, 0.4 * k), mean_nn=0.5 * k)
+
+    eg, ge = direction(1), direction(2)
+    res = dict(est_gt=eg, gt_est=ge, ac=eg["rmse"], com=eg["fitness"], cd=0.25, mme_est=-9.5, mme_gt=-9.25, mme_valid=123456,
+               awd=0.125, scs=0.75, n_w=321, n_est=50_000_000, n_gt=49_999_999, stage_ms=[1.0] * 8)
+    bench.dump_outputs(str(tmp_path / "out"), res)
+    names = {f[:-4] for f in os.listdir(tmp_path / "out")}
+    assert names == {f"{d}_{k}" for d in ("est_gt", "gt_est") for k in bench.DIRECTION_OUTPUTS} | set(bench.SCALAR_OUTPUTS)
+    for d, s in (("est_gt", eg), ("gt_est", ge)):
+        for k in bench.DIRECTION_OUTPUTS:
+            v = np.load(tmp_path / "out" / f"{d}_{k}.npy")
+            assert v.dtype == np.float64 and np.array_equal(v, np.atleast_1d(s[k]))
+    for k in bench.SCALAR_OUTPUTS:
+        v = np.load(tmp_path / "out" / f"{k}.npy")
+        assert v.dtype == np.float64 and v.shape == (1,) and v[0] == res[k]

@@ -336,7 +336,7 @@ def test_bench_py_two_rank_path_runs_end_to_end():
     import sys
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    common = ["--workload", "campus", "--points", "400000", "--steps", "2", "--warmup", "1", "--cpu-baseline", "off", "--no-h2d"]
+    common = ["--workload", "campus", "--points", "400000", "--steps", "2", "--warmup", "1", "--full", "--cpu-baseline", "off", "--no-h2d"]
     env = dict(os.environ, ME_BENCH_BACKEND="gloo", ME_BENCH_SINGLE_DEVICE="1")
     for attempt in range(3):  # (a rendezvous can fail on a busy box — port taken between probe and bind; the RESULTS are never retried)
         r2 = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",

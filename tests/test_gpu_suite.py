@@ -307,3 +307,42 @@ def test_the_lane_thread_belongs_to_the_context(pair):
         with Engine(0) as e:
             _same(want, e.run_suite_from(est, gt, P, overlap=True))
     assert len(os.listdir("/proc/self/task")) <= native + 1  # (native threads: every context's worker was joined)
+
+
+@pytest.mark.timeout(600)
+def test_bench_py_plain_run_times_its_steps_and_dumps_what_they_computed(tmp_path):
+    """`bench.py` without --full: the headline line only (no cross-checks, roofline, H2D or CPU legs), exactly --steps timed steps,
+    and --dump-outputs holds the last timed step's results — the same numbers as the line, the same from run to run."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    lines, dumps = [], []
+    for i in range(2):
+        out = tmp_path / f"out{i}"
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--workload", "campus", "--points", "200000",
+                            "--steps", "3", "--warmup", "1", "--dump-outputs", str(out)], capture_output=True, text=True, timeout=500, cwd=root)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines.append(json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1]))
+        dumps.append({f[:-4]: np.load(out / f) for f in sorted(os.listdir(out))})
+    d = lines[0]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["steps"] == 3 and len(d["step_ms"]) == 3 and d["higher_is_better"] is True and d["dtype"] == "f64"
+    assert not {"cross_checks", "roofline", "h2d_inclusive", "cpu_baseline"} & set(d)
+    n = d["config"]["n_est"] + d["config"]["n_gt"]
+    np.testing.assert_allclose(d["value"], n / 1e6 / (d["ms_per_step"] / 1e3), rtol=1e-12)
+    o, res = dumps[0], d["results"]
+    assert all(v.dtype == np.float64 for v in o.values())
+    assert sum(v.nbytes for v in o.values()) < 64 << 20
+    assert list(o["est_gt_rmse"]) == res["AC"] and list(o["est_gt_fitness"]) == res["COM"]
+    for name, key in (("cd", "CD"), ("mme_est", "MME_est"), ("mme_gt", "MME_gt"), ("awd", "AWD"), ("scs", "SCS"), ("n_w", "W_voxels"),
+                      ("mme_valid", "MME_valid")):
+        assert o[name][0] == res[key], name
+    assert o["n_est"][0] == d["config"]["n_est"] and o["n_gt"][0] == d["config"]["n_gt"]
+    # seeded inputs: the second run computes the same outputs
+    assert set(dumps[1]) == set(o)
+    for name in o:
+        np.testing.assert_allclose(dumps[1][name], o[name], rtol=1e-12, atol=0, err_msg=name)

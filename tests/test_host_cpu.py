@@ -81,12 +81,11 @@ def test_optional_keys_and_the_shipped_reference_configs(exe, tmp_path):
     cfg.write_text(CONFIG.format(est="/a", gt="/b.ply") + "pcd_file_name: final_map_lidar.pcd\ngpu_device: 3\nstrict_reference: true\n")
     p = json.loads(run(exe, "--parse-config", str(cfg)).stdout)
     assert p["pcd_file_name"] == "final_map_lidar.pcd" and p["gpu_device"] == 3 and p["strict_reference"] is True
-    ref_dir = "/root/reference/map_eval/config"
-    if os.path.isdir(ref_dir):  # only where the reference tree is mounted
-        for name in ("config.yaml", "config_building_day.yaml", "config_corridor.yaml", "config_geode.yaml"):
-            r = run(exe, "--parse-config", os.path.join(ref_dir, name))
-            assert r.returncode == 0, (name, r.stderr)
-            assert len(json.loads(r.stdout)["accuracy_level"]) == 5
+    ref_dir = os.path.join(ROOT, "tests", "golden", "reference_configs")  # the reference's map_eval/config/*.yaml, as shipped
+    for name in ("config.yaml", "config_building_day.yaml", "config_corridor.yaml", "config_geode.yaml"):
+        r = run(exe, "--parse-config", os.path.join(ref_dir, name))
+        assert r.returncode == 0, (name, r.stderr)
+        assert len(json.loads(r.stdout)["accuracy_level"]) == 5
 
 
 def _lzf_literal(data: bytes) -> bytes:
