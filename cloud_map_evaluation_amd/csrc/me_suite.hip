@@ -380,7 +380,9 @@ int me_run_suite_from(me_ctx *ctx, const double *est, int64_t n_est, const doubl
         void also(me_ctx *t, double v) {
             b = t;
             if (b) {
-                keep_b = b->vox_hint;
+                // the caller's hint is the primary's (me_set_voxel_hint sets both): a twin that me_twin made inside this call copied
+                // the call's value, and would keep it afterwards
+                keep_b = keep_a;
                 b->vox_hint = v;
                 b->defer_octree = defer;
             }

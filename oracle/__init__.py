@@ -86,6 +86,7 @@ def lib():
         L.orc_voxel_downsample.argtypes = [dp, C.c_int64, C.c_double, dp, C.c_int64]
         L.orc_reg_stats_run.argtypes = [dp, C.c_int64, dp, C.c_int64, C.c_double, C.c_int, dp,
                                         C.POINTER(_RegStats), C.c_int]
+        L.orc_reg_stats_from_nn.argtypes = [ip, dp, C.c_int64, C.c_double, C.c_int, dp, C.POINTER(_RegStats)]
         L.orc_chamfer.restype = C.c_double
         L.orc_chamfer.argtypes = [dp, C.c_int64, dp, C.c_int64, C.c_int]
         L.orc_mme.restype = C.c_double
@@ -215,6 +216,21 @@ def reg_stats(src, tgt, gate: float, gate_mode: int, trunc, threads: int = 1) ->
     out = _RegStats()
     lib().orc_reg_stats_run(_dp(src), src.shape[0], _dp(tgt), tgt.shape[0], float(gate), int(gate_mode),
                             _dp(tr), C.byref(out), threads)
+    f = lambda x: np.array(list(x), dtype=np.float64)
+    return RegStats(out.n_src, out.n_corr, f(out.number), f(out.mean), f(out.rmse), f(out.fitness),
+                    f(out.sigma), out.sum_sqrt_all)
+
+
+def reg_stats_from_nn(idx, d2, gate: float, gate_mode: int, trunc) -> RegStats:
+    """The reduction of reg_stats alone (the same loop, the reference's order) over 1-NN results computed elsewhere:
+    idx int32[N] (< 0: no neighbour), d2 float64[N]."""
+    idx = np.ascontiguousarray(idx, dtype=np.int32)
+    d2 = np.ascontiguousarray(d2, dtype=np.float64)
+    assert idx.ndim == 1 and idx.shape == d2.shape
+    tr = np.ascontiguousarray(trunc, dtype=np.float64)
+    assert tr.shape == (5,)
+    out = _RegStats()
+    lib().orc_reg_stats_from_nn(_ip(idx), _dp(d2), idx.shape[0], float(gate), int(gate_mode), _dp(tr), C.byref(out))
     f = lambda x: np.array(list(x), dtype=np.float64)
     return RegStats(out.n_src, out.n_corr, f(out.number), f(out.mean), f(out.rmse), f(out.fitness),
                     f(out.sigma), out.sum_sqrt_all)

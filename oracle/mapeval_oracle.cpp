@@ -627,14 +627,8 @@ void orc_transform(double *xyz, int64_t n, const double T[16]) {
     }
 }
 
-void orc_reg_stats_run(const double *src, int64_t ns, const double *tgt, int64_t nt_, double gate, int gate_mode,
-                       const double trunc[5], orc_reg_stats *out, int threads) {
-    orc_kdtree *tree = orc_kdtree_build(tgt, nt_);
-    std::vector<double> d2((size_t) ns);
-    std::vector<int32_t> idx((size_t) ns);
-    orc_kdtree_nn1(tree, src, ns, idx.data(), d2.data(), threads);  // (:1215-1223), serial in the reference
-    orc_kdtree_free(tree);
-
+void orc_reg_stats_from_nn(const int32_t *idx, const double *d2, int64_t ns, double gate, int gate_mode, const double trunc[5],
+                           orc_reg_stats *out) {
     std::memset(out, 0, sizeof(*out));
     out->n_src = ns;
     std::vector<double> dis;  // est_gt_dis (:1076)
@@ -677,6 +671,16 @@ void orc_reg_stats_run(const double *src, int64_t ns, const double *tgt, int64_t
         sigma /= C;                       // (:1137)
         out->sigma[k] = std::sqrt(sigma);  // (:1138)
     }
+}
+
+void orc_reg_stats_run(const double *src, int64_t ns, const double *tgt, int64_t nt_, double gate, int gate_mode,
+                       const double trunc[5], orc_reg_stats *out, int threads) {
+    orc_kdtree *tree = orc_kdtree_build(tgt, nt_);
+    std::vector<double> d2((size_t) ns);
+    std::vector<int32_t> idx((size_t) ns);
+    orc_kdtree_nn1(tree, src, ns, idx.data(), d2.data(), threads);  // (:1215-1223), serial in the reference
+    orc_kdtree_free(tree);
+    orc_reg_stats_from_nn(idx.data(), d2.data(), ns, gate, gate_mode, trunc, out);
 }
 
 double orc_chamfer(const double *a, int64_t na, const double *b, int64_t nb, int threads) {

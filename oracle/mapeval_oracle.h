@@ -72,6 +72,9 @@ void orc_transform(double *xyz, int64_t n, const double T_rowmajor[16]);
  *      gate_mode 1: d2 < gate*gate (Open3D EvaluateRegistration, :1168); gate < 0: no gate. ---- */
 void orc_reg_stats_run(const double *src, int64_t ns, const double *tgt, int64_t nt, double gate,
                        int gate_mode, const double trunc[5], orc_reg_stats *out, int threads);
+/* The reduction of orc_reg_stats_run alone, over 1-NN results computed elsewhere (idx < 0: no neighbour), in the same order. */
+void orc_reg_stats_from_nn(const int32_t *idx, const double *d2, int64_t ns, double gate, int gate_mode,
+                           const double trunc[5], orc_reg_stats *out);
 
 /* ---- Chamfer distance (map_eval.cpp:1398-1431) ---- */
 double orc_chamfer(const double *a, int64_t na, const double *b, int64_t nb, int threads);

@@ -6,6 +6,10 @@ C3 / C4  20 M / 50 M pairs, full suite (:1666-1701): the oracle builds its KD-tr
     the reference's tree, built by OpenMP tasks) and answers a seeded 1 % query subsample: per-point entropy and valid flag
     of me_mme for both min_k, 1-NN squared distance and index, bit for bit (entropies: 1e-9); the voxel tables of the
     whole clouds (keys and populations exact) and AWD / SCS.
+C3 - C5 also through the call bench.py times (me_run_suite_from, borrowed device input, both lanes), on the same clouds: its
+    per-point MME and 1-NN results equal the separate calls' bit for bit and the oracle's on the subsample; its statistics equal the
+    oracle's reduction of its own (idx, d2); its voxel tables — reduced from the run records the index build's gather emits — equal
+    the oracle's, and the voxel timer shows that path ran.  C3 once more with a non-identity initial_matrix.
 dense  one 10^4 pts/m^2 scene (the reference's default downsample_size 0.01 gives that density: ~314 neighbours in 0.1 m).
 Counts bit-exact, floating point within 1e-9 relative, at every size."""
 import numpy as np
@@ -62,7 +66,7 @@ def test_c2_5m_pair_cd_ac_com_against_the_whole_oracle():
             t.close()
 
 
-def _full_tree_subsample_check(make_pair, n, voxel, radius=0.1, frac=0.01, seed=5, expect_cascade=False):
+def _full_tree_subsample_check(make_pair, n, voxel, radius=0.1, frac=0.01, seed=5, expect_cascade=False, T=None):
     import oracle
     from cloud_map_evaluation_amd.engine import Engine
 
@@ -71,13 +75,13 @@ def _full_tree_subsample_check(make_pair, n, voxel, radius=0.1, frac=0.01, seed=
     assert gt_d.shape[0] == n and est_d.shape[0] == n
     est, gt = est_d.cpu().numpy(), gt_d.cpu().numpy()
     rng = np.random.default_rng(seed)
+    sep, orc = {}, {}  # slot -> the separate calls' per-point arrays / the seeded subsample and the oracle's answers for it
     with Engine(0) as eng:
         if expect_cascade:
             eng.timers_enable(True)
             eng.timers_reset()
         eng.upload(0, est_d, cell_size=radius)
         eng.upload(1, gt_d, cell_size=radius)
-        del est_d, gt_d
         clouds = {0: est, 1: gt}
         trees = {0: oracle.KDTree(est, 0), 1: oracle.KDTree(gt, 0)}  # FULL-size trees
         for slot, min_k in ((0, 10), (1, 5)):  # est k >= 10 (:1675), gt k >= 5 (:1458)
@@ -88,12 +92,13 @@ def _full_tree_subsample_check(make_pair, n, voxel, radius=0.1, frac=0.01, seed=
             np.testing.assert_allclose(ent[sel], o_ent, rtol=RTOL, atol=0)
             assert n_valid == int(val.sum()) and 0.5 * n < n_valid <= n
             np.testing.assert_allclose(mean, ent[val.astype(bool)].mean(), rtol=1e-12)
-            del ent, val
             # 1-NN of the subsample against the FULL other cloud
             idx, d2 = eng.nn1(slot, 1 - slot)
             oidx, od2 = trees[1 - slot].nn1(clouds[slot][sel], threads=0)
             assert np.array_equal(d2[sel], od2) and np.array_equal(idx[sel], oidx)
-            del idx, d2
+            sep[slot] = (ent, val, idx, d2)
+            orc[slot] = (sel, o_ent, o_val, oidx, od2)
+        gt_tree = trees.pop(1) if T is not None else None  # (the moved map's 1-NN against the ground truth, below)
         for t in trees.values():
             t.close()
         if expect_cascade:  # the 1-NN passes above went through the multi-level list passes (k_nn_grid<FROM_LIST>), not only the fine grid
@@ -102,26 +107,155 @@ def _full_tree_subsample_check(make_pair, n, voxel, radius=0.1, frac=0.01, seed=
         # voxel tables of the WHOLE clouds + AWD / SCS (voxel_calculator.cpp:21-56, map_eval.cpp:240-390)
         og, oe = oracle.VoxelMap(gt, voxel), oracle.VoxelMap(est, voxel)
         for slot, om in ((0, oe), (1, og)):
-            keys, npts, mu, sigma, ent = eng.voxel_gaussians(slot, voxel)
-            ok, on, omu, osig, oent = om.export()
-            assert np.array_equal(keys, ok) and np.array_equal(npts, on), "voxel keys / populations differ from the oracle"
-            np.testing.assert_allclose(mu, omu, rtol=RTOL, atol=1e-12)
-            # two-pass (device) vs streaming Welford (reference order): compared against each matrix's own scale — a
-            # single entry may cancel to nothing, the matrix as a whole may not
-            scale = np.maximum(np.abs(osig).max(axis=(1, 2), keepdims=True), 1e-300)
-            assert np.max(np.abs(sigma - osig) / scale) < SIGMA_TOL
+            _voxel_table_equal(eng.voxel_gaussians(slot, voxel), om)
         v, ov = eng.calculateVMD(voxel), oracle.awd_scs(og, oe)
         assert v["n_rows"] == len(ov["rows"]) > 100 and v["counts"] == tuple(ov["counts"])
         np.testing.assert_allclose(v["awd"], ov["awd"], rtol=RTOL)
         np.testing.assert_allclose(v["scs"], ov["scs"], rtol=RTOL)
         np.testing.assert_allclose(v["w_sorted"], ov["w_sorted"], rtol=1e-8)
-        return v, ov
+    _benched_call_check(est_d, gt_d, est, gt, radius, voxel, sep, orc, og, oe, ov, T, gt_tree)
+    return v, ov
+
+
+def _voxel_table_equal(table, om):
+    keys, npts, mu, sigma, ent = table
+    ok, on, omu, osig, oent = om.export()
+    assert np.array_equal(keys, ok) and np.array_equal(npts, on), "voxel keys / populations differ from the oracle"
+    np.testing.assert_allclose(mu, omu, rtol=RTOL, atol=1e-12)
+    # two-pass (device) vs streaming Welford (reference order): compared against each matrix's own scale — a
+    # single entry may cancel to nothing, the matrix as a whole may not
+    scale = np.maximum(np.abs(osig).max(axis=(1, 2), keepdims=True), 1e-300)
+    assert np.max(np.abs(sigma - osig) / scale) < SIGMA_TOL
+
+
+def _suite_stats_equal(dev_st, orc_st):
+    """A SuiteOut statistics block against the oracle's reduction of the same (idx, d2)."""
+    assert dev_st.n_src == orc_st.n_src and dev_st.n_corr == orc_st.n_corr
+    assert list(dev_st.number) == list(orc_st.number), "inlier counts differ from the oracle"
+    for k in ("mean", "rmse", "sigma", "fitness"):
+        np.testing.assert_allclose(list(getattr(dev_st, k)), getattr(orc_st, k), rtol=RTOL, err_msg=k)
+    np.testing.assert_allclose(dev_st.mean_nn_dist, orc_st.sum_sqrt_all / orc_st.n_src, rtol=RTOL)
+
+
+def _benched_call_check(est_d, gt_d, est, gt, radius, voxel, sep, orc, og, oe, ov, T, gt_tree):
+    """The call bench.py times — me_run_suite_from on borrowed device input, both lanes — against the separate calls above and the
+    oracle: its voxel tables come from the run records the index build's gather emits (k_gather<true, 2>), not from k_vox_records,
+    and its statistics from the on-device reduction (k_nn_partial / k_nn_sigma / me_nn_finalize).  The statistics are pinned by the
+    oracle's own reduction loop over the call's fetched (idx, d2); those arrays are pinned by the separate calls and the subsample."""
+    import oracle
+    from cloud_map_evaluation_amd.engine import Engine, Param
+
+    P = Param(icp_max_distance_=1.0, nn_radius_=radius, vmd_voxel_size_=voxel, evaluate_gt_mme_=True)  # as bench.py builds it
+    with Engine(0, borrow_device_input=True) as eng:
+        one = eng.run_suite_from(est_d, gt_d, P, overlap=True)
+        _per_point_and_stats(eng, one, sep, orc, P)
+        # the tables the call cached: voxel_gaussians finds them (me_voxel.hip: the cache check) and builds nothing
+        eng.timers_enable(True)
+        eng.timers_reset()
+        for slot, om in ((0, oe), (1, og)):
+            _voxel_table_equal(eng.voxel_gaussians(slot, voxel), om)
+        assert eng.timer("voxel")[1] == 0 and eng.timer("gather")[1] == 0, "the call's voxel tables were not cached"
+        assert one.n_w_voxels == len(ov["rows"]) and one.awd == pytest.approx(ov["awd"], rel=RTOL) and one.scs == pytest.approx(ov["scs"], rel=RTOL)
+        # the fused path ran: on one context (the twin lane keeps its own timers), one k_vox_reduce scope per cloud — the standalone
+        # one-pass build opens two (k_vox_records + k_vox_reduce), the three-pass build three or more
+        eng.timers_reset()
+        seq = eng.run_suite_from(est_d, gt_d, P, overlap=False)
+        assert eng.timer("voxel")[1] == 2, f"voxel scopes {eng.timer('voxel')[1]}: the fused voxel records were not used"
+        eng.timers_enable(False)
+        _same_scalars(one, seq)
+        if T is None:
+            return
+        # a non-identity initial_matrix: MME of the map AS LOADED (map_eval.cpp:56), the transform afterwards (:1206) — the index of the
+        # moved map is built again, and its gather emits the run records again (cloud_transform -> cloud_finish -> cloud_build_index)
+        PT = Param(icp_max_distance_=1.0, nn_radius_=radius, vmd_voxel_size_=voxel, evaluate_gt_mme_=True)
+        PT.initial_matrix_ = np.asarray(T, dtype=np.float64)
+        mv = eng.run_suite_from(est_d, gt_d, PT, overlap=True)
+        moved = eng.download(0)
+        assert np.array_equal(moved, oracle.transform(est, T)), "the moved map differs from Open3D's Transform"
+        assert (mv.mme_est, mv.mme_est_valid, mv.mme_gt, mv.mme_gt_valid) == (one.mme_est, one.mme_est_valid, one.mme_gt, one.mme_gt_valid)
+        for slot in (0, 1):
+            ent, val = eng.mme_fetch(slot)
+            assert np.array_equal(ent, sep[slot][0]) and np.array_equal(val, sep[slot][1]), "MME must see the map as loaded"
+            del ent, val
+        # 1-NN on the subsamples: est -> gt against the ground truth's tree, gt -> est against a tree over the moved map
+        sel0, sel1 = orc[0][0], orc[1][0]
+        idx, d2 = eng.nn_fetch(0)
+        oidx, od2 = gt_tree.nn1(moved[sel0], threads=0)
+        gt_tree.close()
+        assert np.array_equal(d2[sel0], od2) and np.array_equal(idx[sel0], oidx)
+        o_eg = oracle.reg_stats_from_nn(idx, d2, P.icp_max_distance_, 0, P.trunc_dist_)
+        _suite_stats_equal(mv.est_gt, o_eg)
+        del idx, d2
+        mt = oracle.KDTree(moved, build_threads=0)
+        idx, d2 = eng.nn_fetch(1)
+        oidx, od2 = mt.nn1(gt[sel1], threads=0)
+        mt.close()
+        assert np.array_equal(d2[sel1], od2) and np.array_equal(idx[sel1], oidx)
+        o_ge = oracle.reg_stats_from_nn(idx, d2, P.icp_max_distance_, 0, P.trunc_dist_)
+        _suite_stats_equal(mv.gt_est, o_ge)
+        np.testing.assert_allclose(mv.full_chamfer, o_eg.sum_sqrt_all / o_eg.n_src + o_ge.sum_sqrt_all / o_ge.n_src, rtol=RTOL)
+        del idx, d2
+        # voxel tables and AWD / SCS of the moved map
+        om = oracle.VoxelMap(moved, voxel)
+        _voxel_table_equal(eng.voxel_gaussians(0, voxel), om)
+        _voxel_table_equal(eng.voxel_gaussians(1, voxel), og)
+        omv = oracle.awd_scs(og, om)
+        assert mv.n_w_voxels == len(omv["rows"])
+        np.testing.assert_allclose([mv.awd, mv.scs], [omv["awd"], omv["scs"]], rtol=RTOL)
+        eng.timers_enable(True)
+        eng.timers_reset()
+        seq = eng.run_suite_from(est_d, gt_d, PT, overlap=False)
+        assert eng.timer("voxel")[1] == 2, "the moved map's voxel records were not emitted again"
+        eng.timers_enable(False)
+        _same_scalars(mv, seq)
+        assert np.array_equal(eng.download(0), moved)
+
+
+def _per_point_and_stats(eng, one, sep, orc, P):
+    import math
+
+    import oracle
+
+    o_st = {}
+    for slot in (0, 1):
+        s_ent, s_val, s_idx, s_d2 = sep[slot]
+        sel, o_ent, o_val, oidx, od2 = orc[slot]
+        ent, val = eng.mme_fetch(slot)
+        assert np.array_equal(ent, s_ent) and np.array_equal(val, s_val), "the benched call's MME differs from the separate call"
+        assert np.array_equal(val[sel], o_val), "MME valid flags differ from the oracle"
+        np.testing.assert_allclose(ent[sel], o_ent, rtol=RTOL, atol=0)
+        ok = val.astype(bool)
+        n_valid = int(ok.sum())
+        mean = math.fsum(memoryview(np.ascontiguousarray(ent[ok]))) / n_valid
+        got, got_n = (one.mme_est, one.mme_est_valid) if slot == 0 else (one.mme_gt, one.mme_gt_valid)
+        assert got_n == n_valid and abs(got - mean) <= 1e-12 * abs(mean), (slot, got, mean)
+        del ent, val, ok
+        idx, d2 = eng.nn_fetch(slot)
+        assert np.array_equal(d2, s_d2) and np.array_equal(idx, s_idx), "the benched call's 1-NN differs from the separate call"
+        assert np.array_equal(d2[sel], od2) and np.array_equal(idx[sel], oidx)
+        o_st[slot] = oracle.reg_stats_from_nn(idx, d2, P.icp_max_distance_, 0, P.trunc_dist_)
+        _suite_stats_equal(one.est_gt if slot == 0 else one.gt_est, o_st[slot])
+        del idx, d2
+    # computeChamferDistance (map_eval.cpp:1429): both directions' mean 1-NN distance
+    np.testing.assert_allclose(one.full_chamfer, sum(o.sum_sqrt_all / o.n_src for o in o_st.values()), rtol=RTOL)
+
+
+def _same_scalars(a, b):
+    for k in ("full_chamfer", "mme_est", "mme_gt", "mme_est_valid", "mme_gt_valid", "awd", "scs", "n_w_voxels"):
+        assert getattr(a, k) == getattr(b, k), k
+    for side in ("est_gt", "gt_est"):
+        x, y = getattr(a, side), getattr(b, side)
+        assert (x.n_src, x.n_corr, x.mean_nn_dist) == (y.n_src, y.n_corr, y.mean_nn_dist), side
+        for k in ("mean", "rmse", "fitness", "sigma", "number"):
+            assert list(getattr(x, k)) == list(getattr(y, k)), (side, k)
 
 
 def test_c3_20m_pair_full_suite_against_the_full_tree_oracle():
     from cloud_map_evaluation_amd import synth
 
-    _full_tree_subsample_check(lambda dev: synth.scan_pair(20_000_000, density=2500.0, seed=100, device=dev), 20_000_000, 3.0)
+    c, s = np.cos(0.01), np.sin(0.01)  # the benched call is also run with a small rotation + translation as initial_matrix
+    T = np.array([[c, -s, 0, 0.03], [s, c, 0, -0.02], [0, 0, 1, 0.01], [0, 0, 0, 1.0]])
+    _full_tree_subsample_check(lambda dev: synth.scan_pair(20_000_000, density=2500.0, seed=100, device=dev), 20_000_000, 3.0, T=T)
 
 
 def test_c4_50m_multisession_pair_full_suite_against_the_full_tree_oracle():

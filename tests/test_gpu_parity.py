@@ -215,7 +215,12 @@ def test_voxel_gaussians_of_scattered_points_take_the_three_pass_build(eng):
     rng = np.random.default_rng(5)
     pts = np.concatenate([rng.uniform(-60.0, 60.0, (150_000, 3)), rng.normal(0.0, 0.8, (60_000, 3)) + np.array([7.3, -2.1, 4.4])])
     eng.upload(1, pts)
+    eng.timers_enable(True)
+    eng.timers_reset()
     keys, n, mu, sig, ent = eng.voxel_gaussians(1, 1.0)
+    # the path that ran: k_vox_records (one "voxel" scope), its regions overflowed, the three-pass build (three more)
+    assert eng.timer("voxel")[1] == 4, f"{eng.timer('voxel')[1]} voxel scopes: the three-pass build was meant to follow the one-pass records"
+    eng.timers_enable(False)
     okeys, on, omu, osig, oent = oracle.VoxelMap(pts, 1.0).export()
     assert np.array_equal(keys, okeys) and np.array_equal(n, on) and n.max() > 100 and (n == 1).sum() > 10_000
     np.testing.assert_allclose(mu, omu, rtol=1e-13, atol=1e-13)

@@ -47,6 +47,24 @@ def test_reg_stats_vs_numpy(gate, mode):
     np.testing.assert_allclose(got.sum_sqrt_all, exp["sum_sqrt_all"], rtol=1e-12)
 
 
+@pytest.mark.parametrize("gate,mode", [(1.0, 0), (0.01, 0), (0.15, 1), (-1.0, 0)])
+def test_reg_stats_from_nn_is_the_same_reduction(gate, mode):
+    """The reduction-only entry over the oracle's own 1-NN output equals reg_stats bit for bit (one loop, one order); an idx < 0
+    (no neighbour) is skipped by both the statistics and the Chamfer sum."""
+    est, gt = synth.cube_pair(3000, seed=43)
+    est, gt = est.numpy(), gt.numpy()[:2500]
+    idx, d2 = oracle.nn1(gt, est)
+    got, exp = oracle.reg_stats_from_nn(idx, d2, gate, mode, TRUNC), oracle.reg_stats(est, gt, gate, mode, TRUNC)
+    assert (got.n_src, got.n_corr, got.sum_sqrt_all) == (exp.n_src, exp.n_corr, exp.sum_sqrt_all)
+    for k in ("number", "mean", "rmse", "fitness", "sigma"):
+        assert np.array_equal(getattr(got, k), getattr(exp, k), equal_nan=True), k
+    idx[::7] = -1
+    part = oracle.reg_stats_from_nn(idx, d2, gate, mode, TRUNC)
+    keep = idx >= 0
+    assert part.n_src == len(est) and part.sum_sqrt_all == oracle.reg_stats_from_nn(idx[keep], d2[keep], gate, mode, TRUNC).sum_sqrt_all
+    assert part.n_corr == oracle.reg_stats_from_nn(idx[keep], d2[keep], gate, mode, TRUNC).n_corr < exp.n_corr
+
+
 def test_reg_stats_squared_vs_unsquared_gate_is_reproduced():
     # d = 0.9 m: d2 = 0.81 <= icp_max_distance 0.85 -> kept by the reference's gate (map_eval.cpp:1219)
     # although 0.9 > 0.85; gate_mode 1 (Open3D semantics) rejects it.
