@@ -4,6 +4,8 @@ from __future__ import annotations
 import ctypes as C
 import os
 
+import numpy as np
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # MAPEVAL_HIP_LIB: another build of the same library (e.g. the -DME_MME_STATS one, profiles/README.md); still no fallback
 LIB_PATH = os.environ.get("MAPEVAL_HIP_LIB") or os.path.join(_HERE, "libmapeval_hip.so")
@@ -30,7 +32,7 @@ SYMBOLS = [
     "me_transform_cloud",
     "me_set_normals", "me_get_normals", "me_estimate_normals", "me_gicp_covariances", "me_get_covariances", "me_icp_lsq_sums",
     "me_nn1", "me_icp_p2p_sums", "me_render_distance", "me_render_entropy", "me_nn_stats", "me_nn_partial_sums", "me_nn_sigma_sums", "me_nn_finalize", "me_chamfer",
-    "me_mme", "me_voxel_gaussians", "me_awd_scs", "me_w2_batch", "me_scs_table", "me_run_suite", "me_run_suite_from", "me_mme_fetch",
+    "me_mme", "me_voxel_gaussians", "me_voxel_metrics", "me_awd_scs", "me_w2_batch", "me_scs_table", "me_run_suite", "me_run_suite_from", "me_mme_fetch",
     "me_set_voxel_hint", "me_timers_enable", "me_timers_reset", "me_timer_get",
 ]
 
@@ -44,6 +46,12 @@ class NNPartial(C.Structure):
         ("sum_d2", C.c_double * 5),
         ("sum_sqrt_all", C.c_double),
     ]
+
+
+# me_nn_partial as a numpy record (the rows of me_voxel_metrics)
+NN_PARTIAL_DTYPE = np.dtype([("n_query", "<i8"), ("n_corr", "<i8"), ("n_inl", "<i8", (5,)), ("sum_d", "<f8", (5,)), ("sum_d2", "<f8", (5,)),
+                             ("sum_sqrt_all", "<f8")])
+assert NN_PARTIAL_DTYPE.itemsize == C.sizeof(NNPartial)
 
 
 class IcpSums(C.Structure):
@@ -203,6 +211,9 @@ def load():
     L.me_chamfer.argtypes = [vp, C.POINTER(C.c_double)]
     L.me_mme.argtypes = [vp, C.c_int, C.c_double, C.c_int, dp, dp, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
     L.me_voxel_gaussians.argtypes = [vp, C.c_int, C.c_double, ip, ip, dp, dp, dp, C.POINTER(C.c_int64)]
+    L.me_voxel_metrics.argtypes = [vp, C.c_int, C.c_double, C.c_double, C.c_int, dp, ip, vp, dp, vp, C.POINTER(C.c_int),
+                                   C.POINTER(C.c_int64)]
+    L.me_voxel_metrics.restype = C.c_int
     L.me_awd_scs.argtypes = [vp, C.c_double, C.c_int, C.c_int, dp, dp, C.POINTER(C.c_int64), C.POINTER(C.c_double),
                              C.POINTER(C.c_double), dp]
     L.me_run_suite.argtypes = [vp, C.POINTER(SuiteParams), C.POINTER(SuiteOut)]

@@ -398,6 +398,12 @@ int me_voxel_gaussians(me_ctx *ctx, int slot, double voxel_size, int32_t *keys, 
     return me::voxel_export(ctx, slot, keys, npts, mu, sigma, entropy, n_voxels);
 }
 
+int me_voxel_metrics(me_ctx *ctx, int slot, double voxel_size, double gate, int gate_mode, const double trunc[5], int32_t *keys,
+                     me_nn_partial *nn, double *sum_H, int64_t *n_H, int *have_mme, int64_t *n_voxels) {
+    if (!ctx) return ME_ERR_ARG;
+    return me::voxel_metrics(ctx, slot, voxel_size, gate, gate_mode, trunc, keys, nn, sum_H, n_H, have_mme, n_voxels);
+}
+
 int me_voxel_partials(me_ctx *ctx, int slot, double voxel_size, int32_t *keys, int32_t *npts, double *mu, double *m2,
                       int64_t *n_voxels) {
     if (!ctx) return ME_ERR_ARG;

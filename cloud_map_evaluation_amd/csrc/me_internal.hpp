@@ -521,6 +521,8 @@ int awd_scs(me_ctx *ctx, double voxel_size, int min_pts, int scs_radius, double 
 int w2_batch(me_ctx *ctx, const double *mu1, const double *sigma1, const int32_t *n1, const double *mu2,
              const double *sigma2, const int32_t *n2, long long count, double *w);
 int scs_table(me_ctx *ctx, const int32_t *keys, const double *w, long long n, int scs_radius, double *scs);
+int voxel_metrics(me_ctx *ctx, int slot, double voxel_size, double gate, int gate_mode, const double trunc[5], int32_t *keys,
+                  me_nn_partial *nn, double *sum_H, int64_t *n_H, int *have_mme, int64_t *n_voxels);
 
 // ---- shared device helpers ----
 #ifdef __HIPCC__

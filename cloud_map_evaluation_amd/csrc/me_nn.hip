@@ -16,6 +16,7 @@
 #include <cstdlib>
 
 #include "me_internal.hpp"
+#include "me_stat.hpp"
 
 #ifndef ME_NN_DBG
 #define ME_NN_DBG 0  // measurement builds of k_nn_grid (profiles/EXPERIMENTS.md "Round 6"): 1 no ranking loop, 2 no staging either, 3 no exact epilogue loads, 4 ranking without note()
@@ -896,19 +897,9 @@ __global__ void k_nn_unpermute(const SPoint *__restrict__ qsp, long long q_begin
 }
 
 // ---- statistics ----
-struct StatParams {
-    double gate;      // threshold on d2 (already squared if the mode says so); < 0 = no gate
-    int gate_strict;  // 1: d2 < gate, 0: d2 <= gate
-    double t2max[5];  // largest d2 whose correctly rounded sqrt is <= trunc[k]
-};
-
+// (StatParams, gate_pass, make_params: me_stat.hpp)
 constexpr int kStatD = 11;  // sum_d[5], sum_d2[5], sum_sqrt_all
 constexpr int kStatI = 6;   // n_corr, n_inl[5]
-
-__device__ __forceinline__ bool gate_pass(const StatParams &sp, double d2) {
-    if (sp.gate < 0) return true;
-    return sp.gate_strict ? (d2 < sp.gate) : (d2 <= sp.gate);
-}
 
 __global__ void __launch_bounds__(256)
 k_nn_partial(const double *__restrict__ d2s, long long q_begin, long long q_end, StatParams sp,
@@ -1015,34 +1006,6 @@ k_final_sum_i(const long long *__restrict__ part, int nblocks, int ncomp, long l
     __shared__ long long sm[4];
     const long long r = block_sum_256_ll(s, sm);
     if (threadIdx.x == 0) out[k] = r;
-}
-
-static StatParams make_params(double gate, int gate_mode, const double trunc[5]) {
-    StatParams sp;
-    if (gate < 0) {
-        sp.gate = -1.0;
-        sp.gate_strict = 0;
-    } else if (gate_mode == ME_GATE_LT_SQUARED) {
-        sp.gate = gate * gate;
-        sp.gate_strict = 1;
-    } else {
-        sp.gate = gate;
-        sp.gate_strict = 0;
-    }
-    for (int k = 0; k < 5; ++k) {
-        // largest double x with sqrt_rn(x) <= t, so the device compares d2 against it and the inlier count does
-        // not depend on the device's sqrt rounding
-        const double t = trunc ? trunc[k] : 0.0;
-        if (!(t >= 0)) {
-            sp.t2max[k] = -1.0;
-            continue;
-        }
-        double x = t * t;
-        while (std::sqrt(std::nextafter(x, INFINITY)) <= t) x = std::nextafter(x, INFINITY);
-        while (x > 0 && std::sqrt(x) > t) x = std::nextafter(x, -INFINITY);
-        sp.t2max[k] = x;
-    }
-    return sp;
 }
 
 // ---- slab mode helpers -------------------------------------------------------------------------------------

@@ -4,6 +4,7 @@
 //   VoxelCalculator::updateVoxelMap(gt)                    voxel_calculator.cpp:142-172
 //   computeWassersteinDistanceGaussian                     voxel_calculator.cpp:115-140
 //   MapEval::calculateVMD (AWD mean, CDF, SCS)             map_eval.cpp:240-390
+//   per-voxel AC / COM / CD / MME sums (me_voxel_metrics)  map_eval.cpp:1069-1145, 1416, 1692-1697 on getVoxelIndex's lattice
 //
 // The reference inserts every point into an unordered_map with an XOR hash (99 % of its AWD stage time) and updates
 // a streaming Welford mean/M2.  Here: pack floor(p/voxel) into a 63-bit key and reduce the Morton-sorted cloud run by run
@@ -14,6 +15,7 @@
 
 #include "me_internal.hpp"
 #include "me_vox_rows.hpp"
+#include "me_stat.hpp"
 
 namespace me {
 
@@ -1206,6 +1208,269 @@ int voxel_downsample(me_ctx *ctx, int slot, double voxel_size, long long *n_out)
     c.n_total = V;
     if (n_out) *n_out = V;
     return cloud_finish(ctx, slot);  // output order: ascending voxel index (Open3D: hash-map iteration order)
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// Per-voxel breakdown of the AC / COM / CD statistics and of the MME (me_voxel_metrics).  The rows of me_voxel_gaussians — same
+// lattice (voxel_key_of: getVoxelIndex's division), same keys, same populations — each holding the me_nn_partial of the voxel's points
+// (the per-point predicate of k_nn_partial, me_stat.hpp) and the entropy sum / count of its valid points.  ONE pass over the sorted
+// cloud reads the point, its d2, its entropy and its validity byte and reduces every row of 64 points run by run, exactly like the
+// one-pass voxel build (k_vox_records): wave_sum_to_lane0 when the row is one run, seg_sum_to_head otherwise, two record slots per
+// row and the further runs in overflow regions.  The records carry their row and run number (`rec_pos`): sorted by it, then stably by
+// voxel key, the records of a voxel are in the sorted cloud's order, and one wavefront per voxel adds them up in a fixed order —
+// bit-identical from run to run (no floating-point atomics: the only atomic reserves the overflow slots of a row).
+// ------------------------------------------------------------------------------------------------------------
+constexpr int kVmD = 12;  // doubles per record: sum_d[5], sum_d2[5], sum_sqrt_all, sum_H
+// the counts of a record, four 8-bit fields per word (a row of 64 points never counts more than 64 in one field):
+//   x = n_query | n_corr << 8 | n_inl[0] << 16 | n_inl[1] << 24,   y = n_inl[2] | n_inl[3] << 8 | n_inl[4] << 16 | n_H << 24
+
+__global__ void __launch_bounds__(256)
+k_voxm_records(const SPoint *__restrict__ sp, const double *__restrict__ d2s, const double *__restrict__ ent,
+               const unsigned char *__restrict__ val, long long n, double vs, SlabView slab, StatParams st,
+               unsigned long long *__restrict__ rec_pos, unsigned long long *__restrict__ rec_vkey, uint2 *__restrict__ rec_c,
+               double *__restrict__ rec_d, unsigned int *__restrict__ region_count, unsigned int n_rows, unsigned int region_size,
+               int *__restrict__ err) {
+    const long long i = (long long) blockIdx.x * blockDim.x + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    const bool valid = i < n;
+    unsigned long long key = ~0ULL;
+    unsigned int ca = 0, cb = 0;
+    double v[kVmD];
+#pragma unroll
+    for (int k = 0; k < kVmD; ++k) v[k] = 0.0;
+    if (valid) {
+        const SPoint p = sp[i];
+        key = voxel_key_of(p.x, p.y, p.z, vs, slab, err);
+        const double d2 = d2s[i];
+        ca = 1u;            // n_query: every point of the voxel (me_nn_partial::n_query)
+        if (d2 >= 0.0) {    // (as k_nn_partial: a negative d2 is no query of this context)
+            const double d = sqrt(d2);  // (map_pt - gt_pt).norm(), map_eval.cpp:1095
+            v[10] = d;                  // computeChamferDistance, ungated (map_eval.cpp:1416)
+            if (gate_pass(st, d2)) {
+                ca |= 1u << 8;
+#pragma unroll
+                for (int k = 0; k < 5; ++k)
+                    if (d2 <= st.t2max[k]) {  // <=> norm_dis <= trunc_dist_[k] (map_eval.cpp:1099-1123)
+                        v[k] = d;
+                        v[5 + k] = d2;
+                        if (k < 2) ca |= 1u << (16 + 8 * k);
+                        else cb |= 1u << (8 * (k - 2));
+                    }
+            }
+        }
+        if (val && val[i]) {  // a valid entropy (map_eval.cpp:1692-1697)
+            cb |= 1u << 24;
+            v[11] = ent[i];
+        }
+    }
+    const unsigned long long prev = __shfl_up(key, 1, 64);
+    const bool head = valid && (lane == 0 || key != prev);
+    const unsigned long long hm = __ballot(head);
+    if (!hm) return;  // (a row past the end)
+    const int run_local = __popcll(hm & ((2ULL << lane) - 1ULL)) - 1;
+    if (hm == 1ULL) {  // the row is one run: plain sums on the vector unit (the packed counts are exact in a double: < 2^31)
+        ca = (unsigned int) wave_sum_to_lane0((double) ca);
+        cb = (unsigned int) wave_sum_to_lane0((double) cb);
+#pragma unroll
+        for (int k = 0; k < kVmD; ++k) v[k] = wave_sum_to_lane0(v[k]);
+    } else {
+        const int seg = valid ? run_local : 64 + lane;
+        ca = (unsigned int) seg_sum_to_head_i((int) ca, seg, lane);
+        cb = (unsigned int) seg_sum_to_head_i((int) cb, seg, lane);
+#pragma unroll
+        for (int k = 0; k < kVmD; ++k) v[k] = seg_sum_to_head(v[k], seg, lane);
+    }
+    // record slots as vox_emit_row (me_vox_rows.hpp): two per row, the further runs of a row in the overflow region r mod kVoxRegions
+    unsigned int base = 0;
+    const int extra = __popcll(hm) - 2;
+    const unsigned int region = (unsigned int) (i >> 6) & (kVoxRegions - 1);
+    if (extra > 0) {
+        if (lane == 0) base = atomicAdd(region_count + region, (unsigned int) extra);
+        base = (unsigned int) __builtin_amdgcn_readfirstlane((int) base);
+    }
+    if (head) {
+        const bool fits = run_local < 2 || base + (unsigned int) (run_local - 2) < region_size;
+        const unsigned long long r = run_local < 2 ? 2ULL * (unsigned long long) (i >> 6) + (unsigned long long) run_local
+                                                   : 2ULL * n_rows + (unsigned long long) region * region_size + base + (unsigned long long) (run_local - 2);
+        if (fits) {
+            rec_pos[r] = ((unsigned long long) (i >> 6) << 6) | (unsigned long long) run_local;
+            rec_vkey[r] = key;
+            rec_c[r] = make_uint2(ca, cb);
+#pragma unroll
+            for (int k = 0; k < kVmD; ++k) rec_d[kVmD * r + k] = v[k];
+        }
+    }
+}
+
+__global__ void k_voxm_gather_keys(const unsigned int *__restrict__ perm, const unsigned long long *__restrict__ vkey, long long m,
+                                   unsigned long long *__restrict__ out) {
+    const long long i = (long long) blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < m) out[i] = vkey[perm[i]];
+}
+
+// one wavefront per voxel: its records in sorted order (= the sorted cloud's order) -> one row
+__global__ void __launch_bounds__(256)
+k_voxm_reduce(const unsigned int *__restrict__ perm, const unsigned int *__restrict__ seg_start, const unsigned long long *__restrict__ vkey,
+              long long n_vox, const uint2 *__restrict__ rec_c, const double *__restrict__ rec_d, int *__restrict__ keys3,
+              me_nn_partial *__restrict__ nn, double *__restrict__ sum_h, long long *__restrict__ n_h) {
+    const int lane = threadIdx.x & 63;
+    const long long v = (long long) blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (v >= n_vox) return;
+    const long long b = seg_start[v], e = seg_start[v + 1];
+    long long c[8];
+    double a[kVmD];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) c[q] = 0;
+#pragma unroll
+    for (int k = 0; k < kVmD; ++k) a[k] = 0.0;
+    for (long long j = b + lane; j < e; j += 64) {
+        const long long r = perm[j];
+        const uint2 w = rec_c[r];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            c[q] += (long long) ((w.x >> (8 * q)) & 0xffu);
+            c[4 + q] += (long long) ((w.y >> (8 * q)) & 0xffu);
+        }
+#pragma unroll
+        for (int k = 0; k < kVmD; ++k) a[k] += rec_d[kVmD * r + k];
+    }
+#pragma unroll
+    for (int q = 0; q < 8; ++q)
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) c[q] += __shfl_xor(c[q], o, 64);
+#pragma unroll
+    for (int k = 0; k < kVmD; ++k) a[k] = wave_allsum(a[k]);
+    if (lane != 0) return;
+    int kx, ky, kz;
+    unpack_key(vkey[v], kx, ky, kz);
+    keys3[3 * v] = kx;
+    keys3[3 * v + 1] = ky;
+    keys3[3 * v + 2] = kz;
+    me_nn_partial o;
+    o.n_query = c[0];
+    o.n_corr = c[1];
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+        o.n_inl[k] = c[2 + k];
+        o.sum_d[k] = a[k];
+        o.sum_d2[k] = a[5 + k];
+    }
+    o.sum_sqrt_all = a[10];
+    nn[v] = o;
+    sum_h[v] = a[11];
+    n_h[v] = c[7];
+}
+
+int voxel_metrics(me_ctx *ctx, int slot, double voxel_size, double gate, int gate_mode, const double trunc[5], int32_t *keys,
+                  me_nn_partial *nn, double *sum_H, int64_t *n_H, int *have_mme, int64_t *n_voxels) {
+    if (slot < 0 || slot > 1 || !trunc || !n_voxels) return ctx->fail(ME_ERR_ARG, "me_voxel_metrics: bad argument");
+    if (!(voxel_size > 0)) return ctx->fail(ME_ERR_ARG, "me_voxel_metrics: voxel_size must be > 0");
+    Cloud &c = ctx->cloud[slot];
+    if (c.slab.axis >= 0 || ctx->shard_world > 1)
+        return ctx->fail(ME_ERR_STATE, "me_voxel_metrics: single GPU only (no slab or shard mode)");
+    if (!c.uploaded) return ctx->fail(ME_ERR_STATE, "me_voxel_metrics: cloud not uploaded");
+    if (c.nn_ref_slot < 0)
+        return ctx->fail(ME_ERR_STATE, "me_voxel_metrics: no me_nn1 with this slot as the query since its last upload or transform");
+    ME_CHECK(ctx, hipSetDevice(ctx->device));
+    const long long n = c.n;
+    const bool mme = c.mme_have;
+    const StatParams st = make_params(gate, gate_mode, trunc);
+    const long long n_rows = (n + 63) / 64;
+    long long rsize = vox_region_size(n), cap = 0;
+    DevBuf &pbuf = ctx->tmp[0], &cbuf = ctx->tmp[1], &dbuf = ctx->tmp[2], &kbuf = ctx->tmp[3], &ibuf = ctx->tmp[4];  // (tmp[5]: sort / scan scratch)
+    ME_CHECK(ctx, ctx->red.ensure(kVoxCounterBytes));
+    unsigned int *cnt = ctx->red.as<unsigned int>();  // [range error, fullest region, the regions' counters]
+    for (int attempt = 0;; ++attempt) {
+        cap = 2 * n_rows + (long long) kVoxRegions * rsize;
+        ME_CHECK(ctx, pbuf.ensure((size_t) cap * 16));  // rec_pos | rec_vkey
+        ME_CHECK(ctx, cbuf.ensure((size_t) cap * 8));
+        ME_CHECK(ctx, dbuf.ensure((size_t) cap * 8 * kVmD));
+        ME_CHECK(ctx, hipMemsetAsync(pbuf.p, 0xFF, (size_t) cap * 8, ctx->stream));  // kVoxEmptySlot
+        ME_CHECK(ctx, hipMemsetAsync(cnt, 0, kVoxCounterBytes, ctx->stream));
+        {
+            TimerScope ts(ctx, "voxel_metrics");
+            hipLaunchKernelGGL(k_voxm_records, dim3(grid_for(n)), dim3(256), 0, ctx->stream, c.sp.as<SPoint>(), c.nn_d2.as<double>(),
+                               mme ? c.mme_ent.as<double>() : nullptr, mme ? c.mme_val.as<unsigned char>() : nullptr, n, voxel_size, c.slab,
+                               st, pbuf.as<unsigned long long>(), pbuf.as<unsigned long long>() + cap, cbuf.as<uint2>(), dbuf.as<double>(),
+                               cnt + 2, (unsigned int) n_rows, (unsigned int) rsize, reinterpret_cast<int *>(cnt));
+        }
+        hipLaunchKernelGGL(k_vox_region_max, dim3(1), dim3(256), 0, ctx->stream, cnt);
+        unsigned int h2[2] = {0, 0};
+        {
+            MailGuard mg(ctx);
+            ME_TRY(mail_post(ctx, h2, cnt, 8));
+            ME_TRY(mg.sync());
+        }
+        if (h2[0]) return ctx->fail(ME_ERR_ARG, "me_voxel_metrics: voxel index out of range (|floor(p/voxel_size)| must be < 2^20)");
+        if ((long long) h2[1] <= rsize) break;
+        if (attempt > 0) return ctx->fail(ME_ERR_HIP, "me_voxel_metrics: overflow regions still too small");
+        rsize = (long long) h2[1];  // (a region overflowed: once more with regions as large as the fullest one needs; the same records)
+    }
+    const long long S = cap;
+    const unsigned long long *rec_pos = pbuf.as<unsigned long long>(), *rec_vkey = rec_pos + cap;
+    ME_CHECK(ctx, kbuf.ensure((size_t) cap * 16));
+    ME_CHECK(ctx, ibuf.ensure((size_t) cap * 20 + 64));
+    unsigned long long *ka = kbuf.as<unsigned long long>(), *kb = ka + cap;
+    unsigned int *flags = ibuf.as<unsigned int>(), *pos = flags + cap, *cidx = pos + cap, *perm1 = cidx + cap, *perm2 = perm1 + cap;
+    // the used slots, compacted in slot order
+    hipLaunchKernelGGL(k_used_flags, dim3(grid_for(S)), dim3(256), 0, ctx->stream, rec_pos, S, flags);
+    ME_TRY(exclusive_scan_u32_plain(ctx, flags, pos, S));
+    unsigned int last_pos = 0, last_flag = 0;
+    {
+        MailGuard mg(ctx);
+        ME_TRY(mail_post(ctx, &last_pos, pos + (S - 1), 4));
+        ME_TRY(mail_post(ctx, &last_flag, flags + (S - 1), 4));
+        ME_TRY(mg.sync());
+    }
+    const long long R = (long long) last_pos + last_flag;  // run records (>= 1: the cloud is not empty)
+    hipLaunchKernelGGL(k_compact_used, dim3(grid_for(S)), dim3(256), 0, ctx->stream, rec_pos, (const unsigned int *) flags,
+                       (const unsigned int *) pos, S, ka, cidx);
+    // records in cloud order (row, run), then stably by voxel: a fixed order inside every voxel
+    ME_TRY(sort_pairs_merge_u64_u32(ctx, ka, kb, cidx, perm1, R));
+    hipLaunchKernelGGL(k_voxm_gather_keys, dim3(grid_for(R)), dim3(256), 0, ctx->stream, (const unsigned int *) perm1, rec_vkey, R, ka);
+    ME_TRY(sort_pairs_merge_u64_u32(ctx, ka, kb, perm1, perm2, R));
+    hipLaunchKernelGGL(k_head_flags, dim3(grid_for(R)), dim3(256), 0, ctx->stream, (const unsigned long long *) kb, R, flags);
+    ME_TRY(exclusive_scan_u32_plain(ctx, flags, pos, R));
+    {
+        MailGuard mg(ctx);
+        ME_TRY(mail_post(ctx, &last_pos, pos + (R - 1), 4));
+        ME_TRY(mail_post(ctx, &last_flag, flags + (R - 1), 4));
+        ME_TRY(mg.sync());
+    }
+    const long long V = (long long) last_pos + last_flag;
+    DevBuf vkey_d, seg_d, keys_d, nn_d, sh_d, nh_d;
+    ME_CHECK(ctx, vkey_d.ensure((size_t) V * 8));
+    ME_CHECK(ctx, seg_d.ensure((size_t) (V + 1) * 4));
+    ME_CHECK(ctx, keys_d.ensure((size_t) V * 12));
+    ME_CHECK(ctx, nn_d.ensure((size_t) V * sizeof(me_nn_partial)));
+    ME_CHECK(ctx, sh_d.ensure((size_t) V * 8));
+    ME_CHECK(ctx, nh_d.ensure((size_t) V * 8));
+    hipLaunchKernelGGL(k_seg_scatter, dim3(grid_for(R)), dim3(256), 0, ctx->stream, (const unsigned long long *) kb, (const unsigned int *) flags,
+                       (const unsigned int *) pos, R, vkey_d.as<unsigned long long>(), seg_d.as<unsigned int>());
+    hipLaunchKernelGGL(k_set_u32v, dim3(1), dim3(1), 0, ctx->stream, seg_d.as<unsigned int>(), V, (unsigned int) R);
+    {
+        TimerScope ts(ctx, "voxel_metrics");
+        hipLaunchKernelGGL(k_voxm_reduce, dim3((unsigned int) ((V + 3) / 4)), dim3(256), 0, ctx->stream, (const unsigned int *) perm2,
+                           (const unsigned int *) seg_d.as<unsigned int>(), (const unsigned long long *) vkey_d.as<unsigned long long>(), V,
+                           (const uint2 *) cbuf.as<uint2>(), (const double *) dbuf.as<double>(), keys_d.as<int>(), nn_d.as<me_nn_partial>(),
+                           sh_d.as<double>(), nh_d.as<long long>());
+    }
+    ME_CHECK(ctx, hipGetLastError());
+    const long long capacity = *n_voxels;
+    *n_voxels = V;
+    if (have_mme) *have_mme = mme ? 1 : 0;
+    if (keys || nn || sum_H || n_H) {
+        if (capacity < V) {
+            ME_CHECK(ctx, hipStreamSynchronize(ctx->stream));  // (the local buffers die with this frame)
+            return ctx->fail(ME_ERR_CAPACITY, "me_voxel_metrics: capacity too small");
+        }
+        if (keys) ME_TRY(copy_d2h(ctx, keys, keys_d.p, (size_t) V * 12));
+        if (nn) ME_TRY(copy_d2h(ctx, nn, nn_d.p, (size_t) V * sizeof(me_nn_partial)));
+        if (sum_H) ME_TRY(copy_d2h(ctx, sum_H, sh_d.p, (size_t) V * 8));
+        if (n_H) ME_TRY(copy_d2h(ctx, n_H, nh_d.p, (size_t) V * 8));
+    }
+    ME_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    return ME_OK;
 }
 
 }  // namespace me

@@ -62,6 +62,18 @@ def _addr(a) -> int:
     return a.data_ptr()  # torch.Tensor
 
 
+# the 44 columns of voxel_metrics.txt (Engine.voxel_metrics_table)
+_NN_COLUMNS = ["n_corr"] + [f"n_inl{k}" for k in range(5)] + [f"sum_d{k}" for k in range(5)] + [f"sum_d2_{k}" for k in range(5)] + ["sum_sqrt_all"]
+VOXEL_METRICS_COLUMNS = (["ix", "iy", "iz", "n_est", "n_gt"] + [c + "_est" for c in _NN_COLUMNS] + [c + "_gt" for c in _NN_COLUMNS]
+                         + ["n_H_est", "sum_H_est", "n_H_gt", "sum_H_gt", "w2"])
+
+
+def _pack_keys(k) -> np.ndarray:
+    """(V, 3) voxel indices -> int64 keys whose order is the ascending (ix, iy, iz) order of the library's tables."""
+    k = np.asarray(k, dtype=np.int64) + (1 << 20)
+    return (k[:, 0] << 42) | (k[:, 1] << 21) | k[:, 2]
+
+
 class Engine:
     def __init__(self, device: int = 0, borrow_device_input: bool = False, morton_order: bool = False):
         """borrow_device_input: ME_FLAG_BORROW_DEVICE_INPUT — cuda tensors uploaded without a transform are read where they lie
@@ -330,6 +342,55 @@ class Engine:
         self._ck(self._L.me_voxel_gaussians(self._ctx, slot, float(voxel_size), _addr(keys), _addr(n), _addr(mu), _addr(sg),
                                             _addr(en), C.byref(nv)))
         return keys, n, mu, sg.reshape(v, 3, 3), en
+
+    def voxel_metrics(self, slot: int, voxel_size: float, gate: float, gate_mode: int, trunc) -> dict:
+        """me_voxel_metrics: the last me_nn1(slot, ..) statistics and the slot's last MME per voxel of the getVoxelIndex lattice
+        (voxel_calculator.cpp:241-245), rows in ascending key order = the rows of voxel_gaussians(slot, voxel_size).
+        -> dict(keys (V, 3) int32, n_query, n_corr, n_inl (V, 5), sum_d (V, 5), sum_d2 (V, 5), sum_sqrt_all, sum_H, n_H, have_mme)."""
+        tr = np.ascontiguousarray(trunc, dtype=np.float64)
+        nv, hm = C.c_int64(0), C.c_int(0)
+        self._ck(self._L.me_voxel_metrics(self._ctx, slot, float(voxel_size), float(gate), int(gate_mode), _addr(tr), 0, 0, 0, 0,
+                                          C.byref(hm), C.byref(nv)))
+        v = nv.value
+        keys = np.empty((v, 3), np.int32)
+        nn = np.empty(v, _lib.NN_PARTIAL_DTYPE)
+        sum_h = np.empty(v, np.float64)
+        n_h = np.empty(v, np.int64)
+        nv = C.c_int64(v)
+        self._ck(self._L.me_voxel_metrics(self._ctx, slot, float(voxel_size), float(gate), int(gate_mode), _addr(tr), _addr(keys),
+                                          _addr(nn), _addr(sum_h), _addr(n_h), C.byref(hm), C.byref(nv)))
+        out = {f: np.ascontiguousarray(nn[f]) for f in _lib.NN_PARTIAL_DTYPE.names}
+        out.update(keys=keys, sum_H=sum_h, n_H=n_h, have_mme=bool(hm.value))
+        return out
+
+    def voxel_metrics_table(self, voxel_size: float, gate: float, gate_mode: int, trunc, min_pts: int = 100,
+                            scs_radius: int = 5) -> np.ndarray:
+        """The joined per-voxel table of a finished suite — what the C++ host writes to voxel_metrics.txt: one row per voxel of
+        the union of both clouds' keys, ascending, in the columns of VOXEL_METRICS_COLUMNS (a cloud without points in the voxel
+        has zeros there); w2 = the voxel's W of me_awd_scs (voxel_errors.txt) where AWD defines one, NaN elsewhere."""
+        e = self.voxel_metrics(ME_SLOT_EST, voxel_size, gate, gate_mode, trunc)
+        g = self.voxel_metrics(ME_SLOT_GT, voxel_size, gate, gate_mode, trunc)
+        vmd = self.calculateVMD(voxel_size, min_pts, scs_radius, rows=True)
+        keys = np.unique(np.concatenate([e["keys"], g["keys"]]), axis=0)
+        packed = _pack_keys(keys)
+        t = np.zeros((keys.shape[0], len(VOXEL_METRICS_COLUMNS)), np.float64)
+        t[:, 0:3] = keys
+        for side, base, nq_col, h_col in ((e, 5, 3, 39), (g, 22, 4, 41)):
+            at = np.searchsorted(packed, _pack_keys(side["keys"]))
+            t[at, nq_col] = side["n_query"]
+            t[at, base] = side["n_corr"]
+            t[at, base + 1:base + 6] = side["n_inl"]
+            t[at, base + 6:base + 11] = side["sum_d"]
+            t[at, base + 11:base + 16] = side["sum_d2"]
+            t[at, base + 16] = side["sum_sqrt_all"]
+            t[at, h_col] = side["n_H"]
+            t[at, h_col + 1] = side["sum_H"]
+        t[:, 43] = np.nan
+        rows = vmd["rows"]
+        if rows.shape[0]:
+            wk = np.rint(rows[:, 0:3] / voxel_size).astype(np.int64)  # (columns 0-2 of voxel_errors.txt: key * voxel_size)
+            t[np.searchsorted(packed, _pack_keys(wk)), 43] = rows[:, 9]
+        return t
 
     def calculateVMD(self, voxel_size: float, min_pts: int = 100, scs_radius: int = 5, rows: bool = True):
         """map_eval.cpp:240-390 -> dict(awd, scs, rows, w_sorted, counts)."""

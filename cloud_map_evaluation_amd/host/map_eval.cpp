@@ -4,6 +4,8 @@
 
 #include <algorithm>
 #include <chrono>
+#include <climits>
+#include <cstdio>
 #include <cmath>
 #include <ctime>
 #include <filesystem>
@@ -131,6 +133,9 @@ Param loadParametersFromYAML(const std::string &yaml_file_path) {
     if (config.has("strict_reference")) param.strict_reference = config.as_bool("strict_reference");
     if (config.has("num_gpus")) param.num_gpus = config.as_int("num_gpus");
     if (param.num_gpus < 1 || param.num_gpus > 64) throw std::runtime_error("num_gpus must be in 1..64");
+    if (config.has("save_voxel_metrics")) param.save_voxel_metrics = config.as_bool("save_voxel_metrics");
+    if (param.save_voxel_metrics && param.num_gpus > 1)
+        throw std::runtime_error("save_voxel_metrics: single GPU only (num_gpus must be 1)");
     return param;
 }
 
@@ -151,7 +156,7 @@ std::string paramToJson(const Param &p) {
       << p.pcd_file_name_ << "\", \"enable_debug\": " << b(p.enable_debug) << ", \"use_tbb_mme\": " << b(p.use_tbb_mme)
       << ", \"use_visualization\": " << b(p.use_visualization) << ", \"result_path\": \"" << p.result_path_
       << "\", \"gpu_device\": " << p.gpu_device << ", \"strict_reference\": " << b(p.strict_reference) << ", \"num_gpus\": " << p.num_gpus
-      << "}";
+      << ", \"save_voxel_metrics\": " << b(p.save_voxel_metrics) << "}";
     return o.str();
 }
 
@@ -295,6 +300,18 @@ int MapEval::process() {
 
     calculateVMD();
     if (!last_error.empty()) return -1;
+    if (param_.save_voxel_metrics) {  // (only the registration path gets here on one GPU: the initial-matrix one is processOneCall)
+        // the transforms of the registration discarded the map's MME result on the device: hand back the entropies computeMME
+        // fetched (those of map_entropy.txt), and the ground truth's with them
+        if (param_.evaluate_mme_ &&
+            me_set_mme_result(ctx_, ME_SLOT_EST, est_entropies.data(), valid_entropy_points.data()) != ME_OK)
+            return fail(me_last_error(ctx_));
+        if (param_.evaluate_mme_ && param_.evaluate_gt_mme_ &&
+            me_set_mme_result(ctx_, ME_SLOT_GT, gt_entropies.data(), gt_valid_entropy_points.data()) != ME_OK)
+            return fail(me_last_error(ctx_));
+        saveVoxelMetrics(ME_GATE_LT_SQUARED);  // the gate of calculateMetrics (:1168)
+        if (!last_error.empty()) return -1;
+    }
     if (param_.enable_debug) std::cout << "INFO: VMD calculation completed." << std::endl;
     if (param_.save_immediate_result_) saveRegistrationResults();
     if (param_.enable_debug) std::cout << "INFO: Results saved successfully." << std::endl;
@@ -668,6 +685,10 @@ int MapEval::processOneCall(bool from_host, double t_loaded) {
     // ---- calculateVMD (:240-390): the voxel tables are cached on the clouds, AWD / CDF / SCS are O(voxels) ----
     calculateVMD();
     if (!last_error.empty()) return -1;
+    if (param_.save_voxel_metrics) {
+        saveVoxelMetrics(ME_GATE_LE_UNSQUARED);  // the gate of the statistics above (:1219)
+        if (!last_error.empty()) return -1;
+    }
     if (param_.enable_debug) std::cout << "INFO: VMD calculation completed." << std::endl;
     if (param_.save_immediate_result_) saveRegistrationResults();
     if (param_.enable_debug) std::cout << "INFO: Results saved successfully." << std::endl;
@@ -692,7 +713,8 @@ void MapEval::computeMME(PointCloud &cloud, PointCloud &gt) {
     if (nv * 100.0 / (double) cloud.size() < 0.6) std::cerr << "valid points is too small, please check the input point cloud" << std::endl;
     if (param_.evaluate_gt_mme_) {
         gt_entropies.assign(gt.size(), 0.0);
-        std::vector<uint8_t> gv(gt.size(), 0);
+        std::vector<uint8_t> &gv = gt_valid_entropy_points;
+        gv.assign(gt.size(), 0);
         if (me_mme(ctx_, ME_SLOT_GT, param_.nn_radius_, 5, gt_entropies.data(), gv.data(), &s, &nv) != ME_OK) {
             fail(me_last_error(ctx_));
             return;
@@ -813,6 +835,105 @@ void MapEval::calculateVMD(bool tables_ready, bool write_files) {
     t_cdf = ticToc.toc();
     t_scs = t_cdf;  // SCS ran inside me_awd_scs
     std::cout << "INFO: Spatial Consistency Score (SCS): " << scs_overall << std::endl;
+}
+
+// voxel_metrics.txt (save_voxel_metrics: true; no reference counterpart): the AC / COM / CD statistics of both search directions and
+// the MME, broken down by the voxels of calculateVMD's lattice (getVoxelIndex, voxel_calculator.cpp:241-245) — me_voxel_metrics on
+// both clouds, joined on the voxel key with the W of voxel_errors.txt.  One row per voxel of the union of both clouds' voxels,
+// ascending (ix, iy, iz); 44 columns: ix iy iz n_est n_gt, the 17 sums of me_nn_partial est -> gt (n_corr n_inl[5] sum_d[5]
+// sum_d2[5] sum_sqrt_all), the same gt -> est, n_H_est sum_H_est n_H_gt sum_H_gt w2 (nan where AWD defines no W).  A cloud with no
+// point in a voxel has zeros there.  Doubles as %.17g: the file round-trips.
+void MapEval::saveVoxelMetrics(int gate_mode) {
+    const double vs = param_.vmd_voxel_size_;
+    struct Side {
+        std::vector<int32_t> keys;
+        std::vector<me_nn_partial> nn;
+        std::vector<double> sum_h;
+        std::vector<int64_t> n_h;
+    } side[2];
+    for (int s = 0; s < 2; ++s) {
+        int have = 0;
+        int64_t v = 0;
+        if (me_voxel_metrics(ctx_, s, vs, param_.icp_max_distance_, gate_mode, param_.trunc_dist_.data(), nullptr, nullptr, nullptr,
+                             nullptr, &have, &v) != ME_OK) {
+            fail(me_last_error(ctx_));
+            return;
+        }
+        side[s].keys.resize((size_t) v * 3);
+        side[s].nn.resize((size_t) v);
+        side[s].sum_h.resize((size_t) v);
+        side[s].n_h.resize((size_t) v);
+        if (me_voxel_metrics(ctx_, s, vs, param_.icp_max_distance_, gate_mode, param_.trunc_dist_.data(), side[s].keys.data(),
+                             side[s].nn.data(), side[s].sum_h.data(), side[s].n_h.data(), &have, &v) != ME_OK) {
+            fail(me_last_error(ctx_));
+            return;
+        }
+    }
+    // W of the voxels AWD pairs (voxel_errors.txt: columns 0-2 = key * voxel size, column 9 = W), ascending key order
+    int64_t n_rows = 0;
+    double awd = 0, scs = 0;
+    if (me_awd_scs(ctx_, vs, 100, 5, nullptr, nullptr, &n_rows, &awd, &scs, nullptr) != ME_OK) {
+        fail(me_last_error(ctx_));
+        return;
+    }
+    std::vector<double> rows((size_t) n_rows * 27);
+    if (n_rows > 0 && me_awd_scs(ctx_, vs, 100, 5, rows.data(), nullptr, &n_rows, &awd, &scs, nullptr) != ME_OK) {
+        fail(me_last_error(ctx_));
+        return;
+    }
+    auto pack = [](long long x, long long y, long long z) {
+        return ((x + (1LL << 20)) << 42) | ((y + (1LL << 20)) << 21) | (z + (1LL << 20));
+    };
+    std::vector<long long> wkey((size_t) n_rows);
+    for (int64_t r = 0; r < n_rows; ++r) {
+        const double *p = rows.data() + 27 * r;
+        wkey[r] = pack(std::llrint(p[0] / vs), std::llrint(p[1] / vs), std::llrint(p[2] / vs));
+    }
+    std::ofstream out(results_subfolder + "voxel_metrics.txt");
+    if (!out.is_open()) {
+        fail("failed to open " + results_subfolder + "voxel_metrics.txt");
+        return;
+    }
+    char buf[64];
+    auto put_i = [&](long long v) { out << ' ' << v; };
+    auto put_d = [&](double v) {
+        std::snprintf(buf, sizeof buf, " %.17g", v);
+        out << buf;
+    };
+    auto put_nn = [&](const me_nn_partial *q) {
+        const me_nn_partial z{};
+        if (!q) q = &z;
+        put_i(q->n_corr);
+        for (int k = 0; k < 5; ++k) put_i(q->n_inl[k]);
+        for (int k = 0; k < 5; ++k) put_d(q->sum_d[k]);
+        for (int k = 0; k < 5; ++k) put_d(q->sum_d2[k]);
+        put_d(q->sum_sqrt_all);
+    };
+    size_t i[2] = {0, 0}, w = 0;
+    const size_t n[2] = {side[0].nn.size(), side[1].nn.size()};
+    while (i[0] < n[0] || i[1] < n[1]) {  // merge of the two ascending key lists
+        long long k[2];
+        for (int s = 0; s < 2; ++s)
+            k[s] = i[s] < n[s] ? pack(side[s].keys[3 * i[s]], side[s].keys[3 * i[s] + 1], side[s].keys[3 * i[s] + 2]) : LLONG_MAX;
+        const long long key = std::min(k[0], k[1]);
+        const bool in[2] = {k[0] == key, k[1] == key};
+        const int s0 = in[0] ? 0 : 1;
+        out << side[s0].keys[3 * i[s0]] << ' ' << side[s0].keys[3 * i[s0] + 1] << ' ' << side[s0].keys[3 * i[s0] + 2];
+        put_i(in[0] ? side[0].nn[i[0]].n_query : 0);
+        put_i(in[1] ? side[1].nn[i[1]].n_query : 0);
+        put_nn(in[0] ? &side[0].nn[i[0]] : nullptr);
+        put_nn(in[1] ? &side[1].nn[i[1]] : nullptr);
+        for (int s = 0; s < 2; ++s) {
+            put_i(in[s] ? side[s].n_h[i[s]] : 0);
+            put_d(in[s] ? side[s].sum_h[i[s]] : 0.0);
+        }
+        while (w < wkey.size() && wkey[w] < key) ++w;
+        put_d(w < wkey.size() && wkey[w] == key ? rows[27 * w + 9] : std::nan(""));
+        out << '\n';
+        for (int s = 0; s < 2; ++s) i[s] += in[s] ? 1 : 0;
+    }
+    out.close();
+    std::cout << "INFO: Saved per-voxel metrics to " << results_subfolder + "voxel_metrics.txt" << std::endl;
 }
 
 void MapEval::saveMmeResults() {

@@ -50,6 +50,8 @@ struct Param {
                                     // (the reference never calls computeChamferDistance there, map_eval.cpp:1204-1260)
     int num_gpus = 1;               // `num_gpus:` N > 1 = one process per GPU (devices gpu_device .. gpu_device + N - 1), the
                                     // clouds cut into N slabs, collectives over RCCL (map_eval_dist.cpp)
+    bool save_voxel_metrics = false;  // `save_voxel_metrics:` true = also write map_results/voxel_metrics.txt, the per-voxel AC / COM / CD /
+                                      // MME sums on the AWD lattice (single GPU only; saveVoxelMetrics)
     int dist_rank = 0;              // (set by the launcher, not a YAML key)
     void printParam() const;
 };
@@ -77,6 +79,7 @@ public:
     bool renderEntropy(int slot, std::vector<double> &xyz, std::vector<double> &rgb, bool want_points);  // :686-735
     void saveMmeResults();                                 // map_eval.cpp:392-421
     void saveRegistrationResults();                        // map_eval.cpp:424-482 (text lines; renderers out of scope)
+    void saveVoxelMetrics(int gate_mode);                  // voxel_metrics.txt (save_voxel_metrics; no reference counterpart)
 
     // multi-GPU (map_eval_dist.cpp): the communicator of this rank; forced = take the distributed path with one rank too
     void setComm(medist::Comm *comm, bool forced) {
@@ -93,7 +96,7 @@ public:
     double vmd = 0.0, full_chamfer_dist = 0.0, scs_overall = 0.0;
     double mme_est = 0.0, mme_gt = 0.0, max_abs_entropy = 0.0, min_abs_entropy = 0.0;
     std::vector<double> est_entropies, gt_entropies;
-    std::vector<uint8_t> valid_entropy_points;
+    std::vector<uint8_t> valid_entropy_points, gt_valid_entropy_points;
     std::vector<double> map_entropy_xyz, map_entropy_rgb, gt_entropy_xyz, gt_entropy_rgb;  // map_3d_entropy / gt_3d_entropy (:330)
     std::string last_error;
 

@@ -356,6 +356,26 @@ int me_mme_fetch(me_ctx *ctx, int slot, double *entropies, uint8_t *valid);
 int me_voxel_gaussians(me_ctx *ctx, int slot, double voxel_size, int32_t *keys /*V x 3*/, int32_t *npts /*V*/,
                        double *mu /*V x 3*/, double *sigma /*V x 9*/, double *entropy /*V*/, int64_t *n_voxels);
 
+/* ---- per-voxel AC / COM / CD / MME on the AWD voxel lattice (no reference counterpart: the reference reports one scalar per map) -- */
+/* Per-voxel breakdown of the last me_nn1(slot, other) statistics and the slot's last MME, on the voxel lattice of
+ * VoxelCalculator::getVoxelIndex (voxel_calculator.cpp:241-245).  Rows in ascending (ix,iy,iz) order = the rows of
+ * me_voxel_gaussians(slot, voxel_size).  nn[v] sums exactly what me_nn_partial_sums sums (map_eval.cpp:1069-1145, 1416),
+ * over the points of voxel v (n_query = its point count).  sum_H / n_H: entropies of the valid points
+ * (map_eval.cpp:1692-1697).  *have_mme = 0 (and zero columns) when the slot has no MME result.
+ * *n_voxels in: capacity, out: count (all-NULL arrays: count only; ME_ERR_CAPACITY if too small).  Host pointers.
+ * Points are binned by their CURRENT coordinates: after me_run_suite_from(T) or a registration transform that is the transformed
+ * frame, the one AC and AWD are measured in.  Entropies stay with their points by point index, and MME runs on the map AS LOADED
+ * (map_eval.cpp:56, before the transform at :1206): a point's entropy describes its neighbourhood before the transform.
+ * me_transform_cloud discards the slot's MME result (me_run_suite_from carries it across its own transform); hand it back with
+ * me_set_mme_result to keep the entropy columns after a registration.
+ * Summed over all rows: the integer columns equal me_nn_partial_sums exactly, the doubles to rounding; sum n_H = the MME valid
+ * count, sum sum_H = the MME sum.  Bit-identical from call to call.  ME_ERR_STATE: slot not uploaded, no me_nn1 with this slot as
+ * the query since its last upload or transform, or slab / shard mode.  ME_ERR_ARG: voxel_size <= 0, or a voxel index outside
+ * |floor(p / voxel_size)| < 2^20.  One pass over the sorted cloud plus a sort of ~n / 60 run records (device timer "voxel_metrics"). */
+int me_voxel_metrics(me_ctx *ctx, int slot, double voxel_size, double gate, int gate_mode, const double trunc[5],
+                     int32_t *keys /*V x 3*/, me_nn_partial *nn /*V*/, double *sum_H /*V*/, int64_t *n_H /*V*/,
+                     int *have_mme, int64_t *n_voxels);
+
 /* ---- AWD + CDF + SCS: MapEval::calculateVMD (map_eval.cpp:240-390) with updateVoxelMap (voxel_calculator.cpp:
  *      142-172) and computeWassersteinDistanceGaussian (:115-140) ------------------------------------------------ */
 /* rows: n x 27 doubles in the column order of voxel_errors.txt (map_eval.cpp:292-302), ascending key order;
@@ -434,7 +454,7 @@ int me_run_suite_from(me_ctx *ctx, const double *est, int64_t n_est, const doubl
 
 /* ---- instrumentation (bench.py roofline leg) ------------------------------------------------------------- */
 /* Average device time (ms, HIP events on the context's stream) and launch count of a named kernel family since
- * the last me_timers_reset: "nn_grid", "nn1", "mme", "sort", "morton", "gather", "cells" (the cell tables), "octree", "nn_stats", "voxel", "w2", "scs", "slab_filter", "halo_pack".  Enabled by me_timers_enable(1).
+ * the last me_timers_reset: "nn_grid", "nn1", "mme", "sort", "morton", "gather", "cells" (the cell tables), "octree", "nn_stats", "voxel", "voxel_metrics", "w2", "scs", "slab_filter", "halo_pack".  Enabled by me_timers_enable(1).
  * Counters (total_ms = 0, value in *launches): "mme_pairs" (accepted (query, neighbour) pairs of the MME launches: the useful work of
  * the VALU-bound kernel, bench.py's roofline.valu), "mme_refined" (queries whose thin neighbourhood — smallest covariance eigenvalue below ~1.8e-6 cell^2 — the MME pass
  * recomputed two-pass about the query itself; counted whether or not timers are on), "nn_queries" / "nn_fallback_queries" (1-NN queries, and those that needed the
