@@ -29,7 +29,7 @@ SYMBOLS = [
     "me_nn_unresolved", "me_nn_points", "me_nn_points_bounded", "me_nn_points_covered", "me_nn_cross_message", "me_nn_cross_answer", "me_nn_cross_patch", "me_nn_patch", "me_nn_fetch", "me_slab_points", "me_set_mme_result", "me_set_nn_result", "me_voxel_partials",
     "me_transform_points_device", "me_upload_slab_device", "me_halo_pack_device", "me_halo_pack_tagged_device", "me_lattice_histograms_device", "me_lattice_messages_device", "me_lattice_plan_device", "me_voxel_partial_rows_device", "me_voxel_merge_device",
     "me_upload_cloud", "me_upload_cloud_device", "me_cloud_size", "me_download_cloud", "me_voxel_downsample",
-    "me_transform_cloud",
+    "me_transform_cloud", "me_perturb_cloud",
     "me_set_normals", "me_get_normals", "me_estimate_normals", "me_gicp_covariances", "me_get_covariances", "me_icp_lsq_sums",
     "me_nn1", "me_icp_p2p_sums", "me_render_distance", "me_render_entropy", "me_nn_stats", "me_nn_partial_sums", "me_nn_sigma_sums", "me_nn_finalize", "me_chamfer",
     "me_mme", "me_voxel_gaussians", "me_voxel_metrics", "me_awd_scs", "me_w2_batch", "me_scs_table", "me_run_suite", "me_run_suite_from", "me_mme_fetch",
@@ -120,6 +120,21 @@ class SuiteOut(C.Structure):
     ]
 
 
+class PerturbParams(C.Structure):
+    _fields_ = [
+        ("noise_std", C.c_double),
+        ("sparse_ratio", C.c_double),
+        ("dense_ratio", C.c_double),
+        ("region_size", C.c_double),
+        ("outlier_ratio", C.c_double),
+        ("outlier_range", C.c_double),
+        ("deform_radius", C.c_double),
+        ("deform_strength", C.c_double),
+        ("deform_center", C.c_double * 3),
+        ("seed", C.c_uint64),
+    ]
+
+
 _lib = None
 
 
@@ -181,6 +196,8 @@ def load():
     L.me_set_voxel_hint.restype = C.c_int
     L.me_voxel_downsample.argtypes = [vp, C.c_int, C.c_double, C.POINTER(C.c_int64)]
     L.me_transform_cloud.argtypes = [vp, C.c_int, dp]
+    L.me_perturb_cloud.argtypes = [vp, C.c_int, C.c_int, C.POINTER(PerturbParams), C.POINTER(C.c_int64)]
+    L.me_perturb_cloud.restype = C.c_int
     L.me_upload_cloud.argtypes = [vp, C.c_int, dp, C.c_int64, dp, C.c_double]
     L.me_upload_cloud_device.argtypes = [vp, C.c_int, dp, C.c_int64, dp, C.c_double]
     L.me_cloud_size.restype = C.c_int64

@@ -260,6 +260,14 @@ int me_voxel_downsample(me_ctx *ctx, int slot, double voxel_size, int64_t *n_out
     return rc;
 }
 
+int me_perturb_cloud(me_ctx *ctx, int dst_slot, int src_slot, const me_perturb_params *p, int64_t *n_out) {
+    if (!ctx) return ME_ERR_ARG;
+    long long n = 0;
+    const int rc = me::perturb_cloud(ctx, dst_slot, src_slot, p, &n);
+    if (n_out && rc == ME_OK) *n_out = n;
+    return rc;
+}
+
 int me_transform_cloud(me_ctx *ctx, int slot, const double *T) {
     if (!ctx) return ME_ERR_ARG;
     return me::cloud_transform(ctx, slot, T);

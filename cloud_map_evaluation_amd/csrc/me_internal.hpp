@@ -456,6 +456,9 @@ int cloud_finish(me_ctx *ctx, int slot, bool bbox_ready = false);
 int cloud_transform(me_ctx *ctx, int slot, const double *T);
 int voxel_downsample(me_ctx *ctx, int slot, double voxel_size, long long *n_out);
 
+// ---- me_perturb.hip ----
+int perturb_cloud(me_ctx *ctx, int dst_slot, int src_slot, const me_perturb_params *p, long long *n_out);
+
 // ---- me_nn.hip ----
 int nn_search(me_ctx *ctx, int qslot, int rslot);
 int nn_fetch(me_ctx *ctx, int qslot, int32_t *idx, double *d2);

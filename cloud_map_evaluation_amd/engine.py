@@ -173,6 +173,28 @@ class Engine:
         Tm = np.ascontiguousarray(T, dtype=np.float64).reshape(16)
         self._ck(self._L.me_transform_cloud(self._ctx, slot, _addr(Tm)))
 
+    def perturb(self, dst: int, src: int, *, noise_std: float = 0.0, sparse_ratio: float = 1.0, dense_ratio: float = 1.0,
+                region_size: float = 0.0, outlier_ratio: float = 0.0, outlier_range: float = 0.0, deform_radius: float = 0.0,
+                deform_strength: float = 0.0, deform_center=(0.0, 0.0, 0.0), seed: int = 0) -> int:
+        """me_perturb_cloud: slot dst = the reference's simulation-mode copy of slot src (addLocalDeformation, addNonUniformDensity,
+        addGaussianNoise, addSparseOutliers, map_eval.cpp:1745-1829, in that order; the defaults switch every stage off) with
+        Philox4x64-10 randomness keyed by seed.  dst == src works in place.  Returns dst's new point count."""
+        pp = _lib.PerturbParams()
+        pp.noise_std = float(noise_std)
+        pp.sparse_ratio = float(sparse_ratio)
+        pp.dense_ratio = float(dense_ratio)
+        pp.region_size = float(region_size)
+        pp.outlier_ratio = float(outlier_ratio)
+        pp.outlier_range = float(outlier_range)
+        pp.deform_radius = float(deform_radius)
+        pp.deform_strength = float(deform_strength)
+        for a in range(3):
+            pp.deform_center[a] = float(deform_center[a])
+        pp.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        n = C.c_int64(0)
+        self._ck(self._L.me_perturb_cloud(self._ctx, int(dst), int(src), C.byref(pp), C.byref(n)))
+        return n.value
+
     def size(self, slot: int) -> int:
         return int(self._L.me_cloud_size(self._ctx, slot))
 

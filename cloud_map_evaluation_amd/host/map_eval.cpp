@@ -136,6 +136,41 @@ Param loadParametersFromYAML(const std::string &yaml_file_path) {
     if (config.has("save_voxel_metrics")) param.save_voxel_metrics = config.as_bool("save_voxel_metrics");
     if (param.save_voxel_metrics && param.num_gpus > 1)
         throw std::runtime_error("save_voxel_metrics: single GPU only (num_gpus must be 1)");
+    // simulation mode (the reference reads evaluate_noised_gt and noise_std_dev only; the misspelt evaluate_noise_gt of its shipped
+    // configs is not read there either)
+    if (config.has("noise_seed")) {
+        const std::string &v = config.at("noise_seed").scalar;
+        size_t used = 0;
+        unsigned long long seed = 0;
+        try {
+            seed = std::stoull(v, &used, 0);
+        } catch (const std::exception &) {
+            used = 0;
+        }
+        if (v.empty() || v[0] == '-' || used != v.size()) throw std::runtime_error("noise_seed: expected an unsigned integer, got '" + v + "'");
+        param.noise_seed = seed;
+    }
+    if (config.has("noise_sparse_ratio")) param.noise_sparse_ratio = config.as_double("noise_sparse_ratio");
+    if (config.has("noise_dense_ratio")) param.noise_dense_ratio = config.as_double("noise_dense_ratio");
+    if (config.has("noise_region_size")) param.noise_region_size = config.as_double("noise_region_size");
+    if (config.has("noise_outlier_ratio")) param.noise_outlier_ratio = config.as_double("noise_outlier_ratio");
+    if (config.has("noise_outlier_range")) param.noise_outlier_range = config.as_double("noise_outlier_range");
+    if (config.has("noise_deform_radius")) param.noise_deform_radius = config.as_double("noise_deform_radius");
+    if (config.has("noise_deform_strength")) param.noise_deform_strength = config.as_double("noise_deform_strength");
+    if (config.has("noise_deform_center")) {
+        const auto &c = config.at("noise_deform_center").seq;
+        if (c.size() != 3) throw std::runtime_error("noise_deform_center: expected a flow list of three numbers");
+        for (int a = 0; a < 3; ++a) param.noise_deform_center[a] = yaml_lite::Document::to_double(c[a], "noise_deform_center");
+    }
+    if (config.has("noise_sweep")) {
+        const auto &c = config.at("noise_sweep").seq;
+        if (c.empty()) throw std::runtime_error("noise_sweep: expected a flow list of noise levels");
+        for (const auto &v : c) param.noise_sweep.push_back(yaml_lite::Document::to_double(v, "noise_sweep"));
+    }
+    if (param.evaluate_noised_gt_ && param.num_gpus > 1)
+        throw std::runtime_error("evaluate_noised_gt: single GPU only (num_gpus must be 1)");
+    if (!param.noise_sweep.empty() && !(param.evaluate_noised_gt_ && param.evaluate_using_initial_ && param.num_gpus == 1))
+        throw std::runtime_error("noise_sweep: needs evaluate_noised_gt: true, evaluate_using_initial: true and num_gpus: 1");
     return param;
 }
 
@@ -156,7 +191,15 @@ std::string paramToJson(const Param &p) {
       << p.pcd_file_name_ << "\", \"enable_debug\": " << b(p.enable_debug) << ", \"use_tbb_mme\": " << b(p.use_tbb_mme)
       << ", \"use_visualization\": " << b(p.use_visualization) << ", \"result_path\": \"" << p.result_path_
       << "\", \"gpu_device\": " << p.gpu_device << ", \"strict_reference\": " << b(p.strict_reference) << ", \"num_gpus\": " << p.num_gpus
-      << ", \"save_voxel_metrics\": " << b(p.save_voxel_metrics) << "}";
+      << ", \"save_voxel_metrics\": " << b(p.save_voxel_metrics) << ", \"evaluate_noised_gt\": " << b(p.evaluate_noised_gt_)
+      << ", \"noise_std_dev\": " << p.noise_std_dev_ << ", \"noise_seed\": " << p.noise_seed << ", \"noise_sparse_ratio\": " << p.noise_sparse_ratio
+      << ", \"noise_dense_ratio\": " << p.noise_dense_ratio << ", \"noise_region_size\": " << p.noise_region_size
+      << ", \"noise_outlier_ratio\": " << p.noise_outlier_ratio << ", \"noise_outlier_range\": " << p.noise_outlier_range
+      << ", \"noise_deform_radius\": " << p.noise_deform_radius << ", \"noise_deform_strength\": " << p.noise_deform_strength
+      << ", \"noise_deform_center\": [" << p.noise_deform_center[0] << ", " << p.noise_deform_center[1] << ", " << p.noise_deform_center[2]
+      << "], \"noise_sweep\": [";
+    for (size_t i = 0; i < p.noise_sweep.size(); ++i) o << (i ? ", " : "") << p.noise_sweep[i];
+    o << "]}";
     return o.str();
 }
 
@@ -210,11 +253,16 @@ int MapEval::process() {
     // the estimated map's own normal_x/y/z, if its PCD has them: Open3D's InitializePointCloudForGeneralizedICP uses a
     // cloud's normals when it carries them and estimates them (KNN 20) only otherwise
     std::vector<double> map_normals;
-    const bool success = pcio::read_pcd(param_.evaluation_map_pcd_path_ + param_.pcd_file_name_, map_3d_->points_, &err, &map_normals);
-    if (param_.enable_debug)
-        std::cout << "INFO: Loading map point cloud from: " << param_.evaluation_map_pcd_path_ + param_.pcd_file_name_ << std::endl;
-    if (!success) return fail("Failed to load point cloud from the specified path.");
-    if (map_3d_->IsEmpty() || gt_3d_->IsEmpty()) return fail("One or both point clouds are empty!");
+    // evaluate_noised_gt: "the system do not load the estimate map, instead the noise gt_map will be used" (config.yaml): the map is
+    // made from the resident ground truth below (me_perturb_cloud), so its file may be absent
+    const bool noised = param_.evaluate_noised_gt_;
+    if (!noised) {
+        const bool success = pcio::read_pcd(param_.evaluation_map_pcd_path_ + param_.pcd_file_name_, map_3d_->points_, &err, &map_normals);
+        if (param_.enable_debug)
+            std::cout << "INFO: Loading map point cloud from: " << param_.evaluation_map_pcd_path_ + param_.pcd_file_name_ << std::endl;
+        if (!success) return fail("Failed to load point cloud from the specified path.");
+    }
+    if ((!noised && map_3d_->IsEmpty()) || gt_3d_->IsEmpty()) return fail("One or both point clouds are empty!");
 
     // ---- the GPU engine: no CPU fallback ----
     ctx_ = me_create(param_.gpu_device, 0);
@@ -226,7 +274,8 @@ int MapEval::process() {
     // The initial-matrix evaluation on one GPU is ONE library call (processOneCall: me_run_suite_from): without down-sampling it
     // starts from the host clouds as they were read — the uploads are part of the call's two-lane schedule.
     const bool one_call = param_.evaluate_using_initial_ && !comm_;
-    if (one_call && !(param_.downsample_size > 0)) {
+    if (noised && comm_) return fail("evaluate_noised_gt: single GPU only (the multi-GPU path reads both maps from disk)");
+    if (one_call && !noised && !(param_.downsample_size > 0)) {
         file_result << std::fixed << std::setprecision(15) << "Estimated-Ground Truth point count: " << map_3d_->size() << " / "
                     << gt_3d_->size() << std::endl;
         if (param_.enable_debug)
@@ -235,7 +284,8 @@ int MapEval::process() {
         return processOneCall(true, tic_toc.toc());
     }
     if (me_upload_cloud(ctx_, ME_SLOT_GT, gt_3d_->points_.data(), (int64_t) gt_3d_->size(), nullptr, param_.nn_radius_) != ME_OK ||
-        me_upload_cloud(ctx_, ME_SLOT_EST, map_3d_->points_.data(), (int64_t) map_3d_->size(), nullptr, param_.nn_radius_) != ME_OK)
+        (!noised &&
+         me_upload_cloud(ctx_, ME_SLOT_EST, map_3d_->points_.data(), (int64_t) map_3d_->size(), nullptr, param_.nn_radius_) != ME_OK))
         return fail(me_last_error(ctx_));
     if (gt_normals.size() == gt_3d_->points_.size() && !gt_normals.empty() &&
         me_set_normals(ctx_, ME_SLOT_GT, gt_normals.data()) != ME_OK)
@@ -246,14 +296,21 @@ int MapEval::process() {
     // map_3d_ = map_3d_->VoxelDownSample(downsample_size) (:38-39), on the device (normals are averaged with the points)
     if (param_.downsample_size > 0) {
         int64_t ne = 0, ng = 0;
-        if (me_voxel_downsample(ctx_, ME_SLOT_EST, param_.downsample_size, &ne) != ME_OK ||
+        if ((!noised && me_voxel_downsample(ctx_, ME_SLOT_EST, param_.downsample_size, &ne) != ME_OK) ||
             me_voxel_downsample(ctx_, ME_SLOT_GT, param_.downsample_size, &ng) != ME_OK)
             return fail(me_last_error(ctx_));
         map_3d_->points_.resize((size_t) ne * 3);
         gt_3d_->points_.resize((size_t) ng * 3);
-        if (me_download_cloud(ctx_, ME_SLOT_EST, map_3d_->points_.data()) != ME_OK ||
+        if ((!noised && me_download_cloud(ctx_, ME_SLOT_EST, map_3d_->points_.data()) != ME_OK) ||
             me_download_cloud(ctx_, ME_SLOT_GT, gt_3d_->points_.data()) != ME_OK)
             return fail(me_last_error(ctx_));
+    }
+    if (noised) {  // map_3d_ = the perturbed ground truth (map_eval.cpp:1745-1829); the host copy is what the writers read
+        const me_perturb_params pp = perturbParams(param_.noise_std_dev_);
+        int64_t ne = 0;
+        if (me_perturb_cloud(ctx_, ME_SLOT_EST, ME_SLOT_GT, &pp, &ne) != ME_OK) return fail(me_last_error(ctx_));
+        map_3d_->points_.resize((size_t) ne * 3);
+        if (me_download_cloud(ctx_, ME_SLOT_EST, map_3d_->points_.data()) != ME_OK) return fail(me_last_error(ctx_));
     }
     file_result << std::fixed << std::setprecision(15) << "Estimated-Ground Truth point count: " << map_3d_->size() << " / "
                 << gt_3d_->size() << std::endl;
@@ -261,7 +318,11 @@ int MapEval::process() {
         std::cout << "INFO: Loaded point clouds: " << map_3d_->size() << " points (Map), " << gt_3d_->size()
                   << " points (Ground Truth)." << std::endl;
     if (comm_) return processDist(tic_toc.toc());  // num_gpus > 1 (map_eval_dist.cpp)
-    if (one_call) return processOneCall(false, tic_toc.toc());  // (the down-sampled clouds are resident)
+    if (one_call) {  // (the down-sampled or perturbed clouds are resident)
+        const int rc = processOneCall(false, tic_toc.toc());
+        if (rc != 0 || param_.noise_sweep.empty()) return rc;
+        return runNoiseSweep();
+    }
     t1 = tic_toc.toc();
     // The reference computes MME on the map as loaded (:56) and transforms it afterwards, inside
     // calculateMetricsWithInitialMatrix (:1206): same order here (me_transform_cloud below), skipped for an identity matrix.
@@ -1002,4 +1063,64 @@ void MapEval::saveRegistrationResults() {
             std::cout << "INFO: Saved raw / inlier distance error maps to " << results_subfolder << "{raw,inlier}_rendered_dis_map.pcd"
                       << std::endl;
     }
+    // the noised ground truth as evaluated, i.e. after the transform (:502-505)
+    if (param_.evaluate_noised_gt_) {
+        pcio::write_pcd(results_subfolder + "noise_gt_map.pcd", map_3d_->points_.data(), map_3d_->size());
+        if (param_.enable_debug) std::cout << "INFO: Saved noisy ground truth map to " << results_subfolder + "noise_gt_map.pcd" << std::endl;
+    }
+}
+
+me_perturb_params MapEval::perturbParams(double noise_std) const {
+    me_perturb_params pp{};
+    pp.noise_std = noise_std;
+    pp.sparse_ratio = param_.noise_sparse_ratio;
+    pp.dense_ratio = param_.noise_dense_ratio;
+    pp.region_size = param_.noise_region_size;
+    pp.outlier_ratio = param_.noise_outlier_ratio;
+    pp.outlier_range = param_.noise_outlier_range;
+    pp.deform_radius = param_.noise_deform_radius;
+    pp.deform_strength = param_.noise_deform_strength;
+    for (int a = 0; a < 3; ++a) pp.deform_center[a] = param_.noise_deform_center[a];
+    pp.seed = param_.noise_seed;
+    return pp;
+}
+
+// noise_sweep.txt (noise_sweep: [..]; no reference counterpart): the robustness sweep of the paper's noise-sensitivity experiment on
+// the resident ground truth — it was read, down-sampled and indexed once; each level regenerates the map from it (same seed and
+// stages, noise_std_dev = the level) and runs the whole suite on the two resident clouds.  One row per level:
+// noise_std_dev n_est ac[5] com[5] full_cd mme_est mme_gt awd scs  (ac = est -> gt rmse "RMSE/AC", com = fitness "Comp")
+int MapEval::runNoiseSweep() {
+    me_suite_params sp{};
+    sp.icp_max_distance = param_.icp_max_distance_;
+    sp.gate_mode = ME_GATE_LE_UNSQUARED;  // (:1219, as processOneCall)
+    for (int k = 0; k < 5; ++k) sp.trunc[k] = param_.trunc_dist_[k];
+    sp.nn_radius = param_.nn_radius_;
+    sp.vmd_voxel_size = param_.vmd_voxel_size_;
+    sp.evaluate_mme = param_.evaluate_mme_ ? 1 : 0;
+    sp.evaluate_gt_mme = param_.evaluate_gt_mme_ ? 1 : 0;
+    sp.min_pts = 100;
+    sp.scs_radius = 5;
+    std::ofstream f(results_subfolder + "noise_sweep.txt");
+    if (!f.is_open()) return fail("cannot write " + results_subfolder + "noise_sweep.txt");
+    f << "# noise_std_dev n_est ac0 ac1 ac2 ac3 ac4 com0 com1 com2 com3 com4 full_cd mme_est mme_gt awd scs\n";
+    f << std::setprecision(17);
+    for (const double sigma : param_.noise_sweep) {
+        TicToc clock;
+        const me_perturb_params pp = perturbParams(sigma);
+        int64_t ne = 0;
+        me_suite_out so;
+        if (me_perturb_cloud(ctx_, ME_SLOT_EST, ME_SLOT_GT, &pp, &ne) != ME_OK ||
+            me_run_suite_from(ctx_, nullptr, 0, nullptr, 0, param_.initial_matrix_.data(), &sp, ME_SUITE_OVERLAP, &so) != ME_OK)
+            return fail(me_last_error(ctx_));
+        const double cd = param_.strict_reference ? 0.0 : so.est_gt.mean_nn_dist + so.gt_est.mean_nn_dist;  // (as finishInitialMatrixMetrics)
+        f << sigma << " " << ne;
+        for (int k = 0; k < 5; ++k) f << " " << so.est_gt.rmse[k];
+        for (int k = 0; k < 5; ++k) f << " " << so.est_gt.fitness[k];
+        f << " " << cd << " " << (param_.evaluate_mme_ ? so.mme_est : 0.0) << " " << (param_.evaluate_mme_ ? so.mme_gt : 0.0) << " " << so.awd
+          << " " << so.scs << "\n";
+        std::cout << std::setprecision(6) << "INFO: noise sweep, noise_std_dev " << sigma << ": " << ne << " points, AC " << so.est_gt.rmse[0]
+                  << ", " << clock.toc() << " ms" << std::endl;
+    }
+    if (!f.good()) return fail("writing " + results_subfolder + "noise_sweep.txt failed");
+    return 0;
 }

@@ -52,6 +52,17 @@ struct Param {
                                     // clouds cut into N slabs, collectives over RCCL (map_eval_dist.cpp)
     bool save_voxel_metrics = false;  // `save_voxel_metrics:` true = also write map_results/voxel_metrics.txt, the per-voxel AC / COM / CD /
                                       // MME sums on the AWD lattice (single GPU only; saveVoxelMetrics)
+    // simulation mode (evaluate_noised_gt: true): the map evaluated is a perturbed copy of the ground truth, made on the device
+    // (me_perturb_cloud).  noise_std_dev_ above is the noise; these keys switch the reference's other three generators on
+    // (map_eval.cpp:1757-1829; the defaults leave them off) and fix the Philox seed
+    uint64_t noise_seed = 0;                                      // `noise_seed:`
+    double noise_sparse_ratio = 1.0, noise_dense_ratio = 1.0;     // `noise_sparse_ratio:`, `noise_dense_ratio:` keep probabilities
+    double noise_region_size = 0.0;                               // `noise_region_size:` (<= 0: no density stage)
+    double noise_outlier_ratio = 0.0, noise_outlier_range = 0.0;  // `noise_outlier_ratio:`, `noise_outlier_range:`
+    double noise_deform_radius = 0.0, noise_deform_strength = 0.0;  // `noise_deform_radius:`, `noise_deform_strength:`
+    std::array<double, 3> noise_deform_center{{0, 0, 0}};         // `noise_deform_center: [x, y, z]`
+    std::vector<double> noise_sweep;  // `noise_sweep: [s0, s1, ..]` after the run, one suite per noise level on the resident ground
+                                      // truth -> map_results/noise_sweep.txt (single GPU, initial-matrix path; runNoiseSweep)
     int dist_rank = 0;              // (set by the launcher, not a YAML key)
     void printParam() const;
 };
@@ -80,6 +91,8 @@ public:
     void saveMmeResults();                                 // map_eval.cpp:392-421
     void saveRegistrationResults();                        // map_eval.cpp:424-482 (text lines; renderers out of scope)
     void saveVoxelMetrics(int gate_mode);                  // voxel_metrics.txt (save_voxel_metrics; no reference counterpart)
+    me_perturb_params perturbParams(double noise_std) const;  // the noise_* keys as me_perturb_cloud's parameters
+    int runNoiseSweep();                                   // noise_sweep.txt (noise_sweep; no reference counterpart)
 
     // multi-GPU (map_eval_dist.cpp): the communicator of this rank; forced = take the distributed path with one rank too
     void setComm(medist::Comm *comm, bool forced) {

@@ -248,6 +248,40 @@ int me_voxel_downsample(me_ctx *ctx, int slot, double voxel_size, int64_t *n_out
 /* *cloud = cloud->Transform(T) (map_eval.cpp:1206, :1392) on the cloud already on the device (row-major 4x4); the index
  * is rebuilt.  Lets MME run on the map as loaded and AC/COM/CD/AWD on the transformed map, as the reference does. */
 int me_transform_cloud(me_ctx *ctx, int slot, const double *T_rowmajor4x4);
+
+/* ---- simulation mode: evaluate_noised_gt (map_eval_main.cpp:177-183, map_eval.h:79,87) -------------------------------------- */
+/* The estimated map as a perturbed copy of a resident cloud.  Stages, in this order, each switchable:
+ *   1. addLocalDeformation  (map_eval.cpp:1808-1829): d = |p - c| as Eigen's norm(); if d < R: p += (p - c) / d * s * w,
+ *      w = 0.5 (1 + cos(pi d / R)); a point at d == 0 stays (normalize() leaves a zero vector).  No randomness.
+ *   2. addNonUniformDensity (:1757-1784) on the deformed point: keep iff u < sparse_ratio where
+ *      sin(x / region_size pi) sin(y / region_size pi) > 0, u < dense_ratio elsewhere; survivors keep the source order.
+ *   3. addGaussianNoise     (:1745-1755): + N(0, noise_std^2) per coordinate of every survivor.
+ *   4. addSparseOutliers    (:1786-1806): m = (int64)(n_kept outlier_ratio) outliers appended after the survivors; outlier j =
+ *      point b = min(n_kept - 1, (int64)(u n_kept)) of the noised, compacted cloud + N(0, outlier_range^2) per axis (the clamp is
+ *      a guard: the reference reads one past the end if its draw rounds to 1.0; with u < 1 below the product stays < n_kept).
+ * Randomness: Philox4x64-10 (Random123) with key (seed, 0) — the reference's mt19937 is seeded from std::random_device, so no run of
+ * it can be reproduced; here every block is a pure function of (seed, counter):
+ *   density of source point i  counter (i, 1, 0, 0)  w0 -> u
+ *   noise of source point i    counter (i, 2, 0, 0)  Box-Muller (w0, w1) -> x, y; (w2, w3) -> z (its second normal unused)
+ *   outlier j                  counter (j, 3, 0, 0)  w0 -> u of the base index; Box-Muller (w1, w2) -> x, y
+ *                              counter (j, 3, 1, 0)  Box-Muller (w0, w1) -> z
+ * u = (w >> 11) 2^-53 in [0, 1); Box-Muller (a, b): u1 = ((a >> 11) + 1) 2^-53 in (0, 1], u2 = u(b),
+ * n = sqrt(-2 ln u1) cos(2 pi u2), and sin(2 pi u2) for the pair's second.  i is the index in the source's order: a surviving
+ * point gets the same noise whatever the density stage dropped, and nothing depends on the launch shape.
+ * dst gets the upload-time reset (index rebuilt on the source's cell size; NN, MME, voxel state invalidated; normals and
+ * covariances dropped; the other slot's NN result invalidated); src is left untouched unless dst == src (in place works).
+ * *n_out = points in dst.  ME_ERR_ARG: p NULL, slab or shard mode, noise_std < 0, a ratio outside [0, 1], outlier_range < 0, an
+ * output of 2^31 points or more, or no survivor.  Device timer "perturb". */
+typedef struct me_perturb_params {
+    double noise_std;                    /* addGaussianNoise noise_std_dev (map_eval.cpp:1746)            (0 = off)    */
+    double sparse_ratio, dense_ratio;    /* addNonUniformDensity keep probabilities (:1758-1759)                       */
+    double region_size;                  /*   its region_size (:1760)                                       (<= 0 = off) */
+    double outlier_ratio, outlier_range; /* addSparseOutliers (:1787-1788)                                  (ratio 0 = off) */
+    double deform_radius, deform_strength, deform_center[3]; /* addLocalDeformation (:1809-1811)    (radius <= 0 or strength 0 = off) */
+    uint64_t seed;                       /* Philox key word 0 (no reference counterpart: std::random_device)            */
+} me_perturb_params;
+int me_perturb_cloud(me_ctx *ctx, int dst_slot, int src_slot, const me_perturb_params *p, int64_t *n_out);
+
 int64_t me_cloud_size(me_ctx *ctx, int slot);
 /* transformed points back to the host (N x 3), original order — what map_3d_->points_ holds after :1206 */
 int me_download_cloud(me_ctx *ctx, int slot, double *xyz_host);
