@@ -29,7 +29,7 @@ SYMBOLS = [
     "me_nn_unresolved", "me_nn_points", "me_nn_points_bounded", "me_nn_points_covered", "me_nn_cross_message", "me_nn_cross_answer", "me_nn_cross_patch", "me_nn_patch", "me_nn_fetch", "me_slab_points", "me_set_mme_result", "me_set_nn_result", "me_voxel_partials",
     "me_transform_points_device", "me_upload_slab_device", "me_halo_pack_device", "me_halo_pack_tagged_device", "me_lattice_histograms_device", "me_lattice_messages_device", "me_lattice_plan_device", "me_voxel_partial_rows_device", "me_voxel_merge_device",
     "me_upload_cloud", "me_upload_cloud_device", "me_cloud_size", "me_download_cloud", "me_voxel_downsample",
-    "me_transform_cloud", "me_perturb_cloud",
+    "me_transform_cloud", "me_perturb_cloud", "me_voxel_downsample_into", "me_fpfh", "me_fpfh_match", "me_global_register",
     "me_set_normals", "me_get_normals", "me_estimate_normals", "me_gicp_covariances", "me_get_covariances", "me_icp_lsq_sums",
     "me_nn1", "me_icp_p2p_sums", "me_render_distance", "me_render_entropy", "me_nn_stats", "me_nn_partial_sums", "me_nn_sigma_sums", "me_nn_finalize", "me_chamfer",
     "me_mme", "me_voxel_gaussians", "me_voxel_metrics", "me_awd_scs", "me_w2_batch", "me_scs_table", "me_run_suite", "me_run_suite_from", "me_mme_fetch",
@@ -135,6 +135,34 @@ class PerturbParams(C.Structure):
     ]
 
 
+
+class FpfhParams(C.Structure):
+    _fields_ = [("radius", C.c_double), ("max_nn", C.c_int), ("normal_knn", C.c_int)]
+
+
+class GlobRegParams(C.Structure):
+    _fields_ = [
+        ("fpfh", FpfhParams),
+        ("max_corr_dist", C.c_double),
+        ("edge_ratio", C.c_double),
+        ("max_iterations", C.c_int64),
+        ("validate_top", C.c_int),
+        ("mutual", C.c_int),
+        ("seed", C.c_uint64),
+    ]
+
+
+class GlobRegInfo(C.Structure):
+    _fields_ = [
+        ("n_corr", C.c_int64),
+        ("n_valid_hypotheses", C.c_int64),
+        ("best_hypothesis", C.c_int64),
+        ("best_corr_inliers", C.c_int64),
+        ("fitness", C.c_double),
+        ("inlier_rmse", C.c_double),
+    ]
+
+
 _lib = None
 
 
@@ -198,6 +226,12 @@ def load():
     L.me_transform_cloud.argtypes = [vp, C.c_int, dp]
     L.me_perturb_cloud.argtypes = [vp, C.c_int, C.c_int, C.POINTER(PerturbParams), C.POINTER(C.c_int64)]
     L.me_perturb_cloud.restype = C.c_int
+    L.me_voxel_downsample_into.argtypes = [vp, C.c_int, vp, C.c_int, C.c_double, C.POINTER(C.c_int64)]
+    L.me_fpfh.argtypes = [vp, C.c_int, C.POINTER(FpfhParams), dp]
+    L.me_fpfh_match.argtypes = [vp, C.c_int, C.c_int, C.c_int, ip, C.POINTER(C.c_int64)]
+    L.me_global_register.argtypes = [vp, C.c_int, C.c_int, C.POINTER(GlobRegParams), dp, C.POINTER(GlobRegInfo), vp]
+    for f in ("me_voxel_downsample_into", "me_fpfh", "me_fpfh_match", "me_global_register"):
+        getattr(L, f).restype = C.c_int
     L.me_upload_cloud.argtypes = [vp, C.c_int, dp, C.c_int64, dp, C.c_double]
     L.me_upload_cloud_device.argtypes = [vp, C.c_int, dp, C.c_int64, dp, C.c_double]
     L.me_cloud_size.restype = C.c_int64

@@ -268,6 +268,33 @@ int me_perturb_cloud(me_ctx *ctx, int dst_slot, int src_slot, const me_perturb_p
     return rc;
 }
 
+int me_voxel_downsample_into(me_ctx *src_ctx, int src_slot, me_ctx *dst_ctx, int dst_slot, double voxel_size, int64_t *n_out) {
+    if (!src_ctx || !dst_ctx) return ME_ERR_ARG;
+    long long n = 0;
+    const int rc = me::voxel_downsample_into(src_ctx, src_slot, dst_ctx, dst_slot, voxel_size, &n);
+    if (n_out && rc == ME_OK) *n_out = n;
+    return rc;
+}
+
+int me_fpfh(me_ctx *ctx, int slot, const me_fpfh_params *p, double *features) {
+    if (!ctx) return ME_ERR_ARG;
+    return me::fpfh(ctx, slot, p, features);
+}
+
+int me_fpfh_match(me_ctx *ctx, int src_slot, int ref_slot, int mutual, int32_t *corr, int64_t *n_corr) {
+    if (!ctx) return ME_ERR_ARG;
+    long long n = 0;
+    const int rc = me::fpfh_match(ctx, src_slot, ref_slot, mutual, corr, &n);
+    if (n_corr && rc == ME_OK) *n_corr = n;
+    return rc;
+}
+
+int me_global_register(me_ctx *ctx, int src_slot, int ref_slot, const me_globreg_params *p, double T_out[16], me_globreg_info *info,
+                       int64_t *scores) {
+    if (!ctx) return ME_ERR_ARG;
+    return me::global_register(ctx, src_slot, ref_slot, p, T_out, info, scores);
+}
+
 int me_transform_cloud(me_ctx *ctx, int slot, const double *T) {
     if (!ctx) return ME_ERR_ARG;
     return me::cloud_transform(ctx, slot, T);

@@ -752,6 +752,7 @@ int cloud_finish(me_ctx *ctx, int slot, bool bbox_ready) {
     c.vox_valid = false;
     c.vox_merged = false;
     c.n_vox = 0;
+    c.fpfh_valid = false;
     ctx->cloud[1 - slot].nn_ref_slot = -1;
     // bbox
     const unsigned int nb = (unsigned int) std::min<long long>(1024, (n + 255) / 256);

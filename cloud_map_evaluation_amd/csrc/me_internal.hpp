@@ -221,6 +221,9 @@ struct Cloud {
     DevBuf normals;  // double[n][3]
     DevBuf cov;      // double[n][9] generalized-ICP covariances
     bool have_normals = false, have_cov = false;
+    // FPFH features of the cloud, ORIGINAL point order, double[n][33] (me_globreg.hip); dropped with the points (cloud_finish) and normals
+    DevBuf fpfh;
+    bool fpfh_valid = false;
 };
 
 struct TimerRec {
@@ -455,9 +458,15 @@ int cloud_finish_octree(me_ctx *ctx, int slot);
 int cloud_finish(me_ctx *ctx, int slot, bool bbox_ready = false);
 int cloud_transform(me_ctx *ctx, int slot, const double *T);
 int voxel_downsample(me_ctx *ctx, int slot, double voxel_size, long long *n_out);
+int voxel_downsample_into(me_ctx *src_ctx, int src_slot, me_ctx *dst_ctx, int dst_slot, double voxel_size, long long *n_out);
 
 // ---- me_perturb.hip ----
 int perturb_cloud(me_ctx *ctx, int dst_slot, int src_slot, const me_perturb_params *p, long long *n_out);
+// ---- me_globreg.hip ----
+int fpfh(me_ctx *ctx, int slot, const me_fpfh_params *p, double *features_host);
+int fpfh_match(me_ctx *ctx, int src_slot, int ref_slot, int mutual, int32_t *corr_host, long long *n_corr);
+int global_register(me_ctx *ctx, int src_slot, int ref_slot, const me_globreg_params *p, double T_out[16], me_globreg_info *info,
+                    int64_t *scores);
 
 // ---- me_nn.hip ----
 int nn_search(me_ctx *ctx, int qslot, int rslot);
@@ -482,6 +491,10 @@ int gicp_covariances(me_ctx *ctx, int slot, double epsilon, double *cov_host);
 int get_covariances(me_ctx *ctx, int slot, double *cov_host);
 int rotate_attributes(me_ctx *ctx, int slot, const double *T);
 int icp_lsq_sums(me_ctx *ctx, int qslot, int mode, double max_distance, me_icp_lsq *out);
+// the k nearest neighbours of every point of a slot in that slot (the walk of me_estimate_normals; normals untouched): idx / d2 [n][k],
+// original order, ascending by (d2, index), -1 / inf past the end.  Device buffers; queued on ctx->stream.
+constexpr int kKnnMax = 40;
+int knn_lists(me_ctx *ctx, int slot, int k, int *idx_device, double *d2_device);
 
 #ifdef ME_AB  // ---- profiles/ab/me_mme7.hip (round 4's matrix-pipe MME kernel: measurement build only) ----
 int mme7_prepare(me_ctx *ctx, Cloud &c, double radius, bool *usable);

@@ -19,12 +19,11 @@
 #include <utility>
 
 #include "me_internal.hpp"
+#include "me_philox.hpp"
 
 namespace me {
 
 namespace {
-
-typedef unsigned long long u64;
 
 struct PerturbK {
     double cx, cy, cz, radius, strength;  // deform (radius <= 0 or strength == 0: off)
@@ -34,37 +33,6 @@ struct PerturbK {
     u64 seed;
     int deform, density, noise;
 };
-
-// Philox4x64-10 (Salmon et al., SC'11; Random123 philox4x64_R with R = 10)
-__device__ __forceinline__ void philox4x64_10(u64 c[4], u64 k0, u64 k1) {
-    const u64 M0 = 0xD2E7470EE14C6C93ull, M1 = 0xCA5A826395121157ull;
-    const u64 W0 = 0x9E3779B97F4A7C15ull, W1 = 0xBB67AE8584CAA73Bull;
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        if (r > 0) {
-            k0 += W0;
-            k1 += W1;
-        }
-        const u64 hi0 = __umul64hi(M0, c[0]), lo0 = M0 * c[0];
-        const u64 hi1 = __umul64hi(M1, c[2]), lo1 = M1 * c[2];
-        const u64 n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
-        c[0] = n0;
-        c[1] = lo1;
-        c[2] = n2;
-        c[3] = lo0;
-    }
-}
-
-__device__ __forceinline__ void philox_block(u64 seed, u64 c0, u64 c1, u64 c2, u64 w[4]) {
-    w[0] = c0;
-    w[1] = c1;
-    w[2] = c2;
-    w[3] = 0;
-    philox4x64_10(w, seed, 0);
-}
-
-__device__ __forceinline__ double u01(u64 w) { return (double) (w >> 11) * 0x1p-53; }          // [0, 1)
-__device__ __forceinline__ double u01_open0(u64 w) { return (double) ((w >> 11) + 1) * 0x1p-53; }  // (0, 1]
 
 // Box-Muller: two N(0, 1) from the words (a, b); a gives the radius, b the angle
 __device__ __forceinline__ void box_muller(u64 a, u64 b, double &n0, double &n1) {

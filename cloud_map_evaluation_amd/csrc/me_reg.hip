@@ -204,7 +204,7 @@ __device__ __forceinline__ double box_lb(const ONode *__restrict__ nd, double qx
 }
 
 constexpr int kKnnBlock = 128;
-constexpr int kKnnMax = 40;  // k * 128 lanes * 12 B of LDS <= 60 KB
+static_assert(kKnnMax == 40, "k * 128 lanes * 12 B of LDS <= 60 KB");
 
 // ---- k nearest neighbours of every point of a cloud IN that cloud + the normal of their raw-moment covariance ----
 // One lane per query (sorted order, so a wave walks neighbouring paths); the k best so far live in LDS, sorted
@@ -304,6 +304,7 @@ k_knn_normals(const SPoint *__restrict__ sp, long long n, OctView oct, const dou
             knn_d2[qi * k + j] = j < cnt ? s_d[j * kKnnBlock + tid] : INFINITY;
         }
     }
+    if (!normals) return;  // (knn_lists: the neighbour lists only)
     // utility::ComputeCovariance over the neighbours (ascending distance): raw moments / count
     double cov[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
     if (cnt >= 3) {
@@ -505,6 +506,7 @@ int set_normals(me_ctx *ctx, int slot, const double *normals_host) {
     ME_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     c.have_normals = true;
     c.have_cov = false;
+    c.fpfh_valid = false;
     return ME_OK;
 }
 
@@ -553,6 +555,18 @@ int estimate_normals(me_ctx *ctx, int slot, int knn, double *normals_host, int32
     ME_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     c.have_normals = true;
     c.have_cov = false;
+    c.fpfh_valid = false;
+    return ME_OK;
+}
+
+int knn_lists(me_ctx *ctx, int slot, int k, int *idx_device, double *d2_device) {
+    ME_TRY(need_plain_cloud(ctx, slot, "knn_lists", true));
+    if (k < 1 || k > kKnnMax) return ctx->fail(ME_ERR_ARG, "knn_lists: k must be in [1, 40]");
+    Cloud &c = ctx->cloud[slot];
+    const size_t lds = (size_t) k * kKnnBlock * 12;
+    hipLaunchKernelGGL(k_knn_normals, dim3(grid_for(c.n, kKnnBlock)), dim3(kKnnBlock), lds, ctx->stream, c.sp.as<SPoint>(), c.n,
+                       c.oct, c.xyz.as<double>(), k, (double *) nullptr, idx_device, d2_device);
+    ME_CHECK(ctx, hipGetLastError());
     return ME_OK;
 }
 

@@ -13,6 +13,8 @@
 // voxel over the (2r+1)^3 stencil with hash probes.
 #include <cmath>
 
+#include <utility>
+
 #include "me_internal.hpp"
 #include "me_vox_rows.hpp"
 #include "me_stat.hpp"
@@ -1144,14 +1146,9 @@ int awd_scs(me_ctx *ctx, double voxel_size, int min_pts, int scs_radius, double 
     return ME_OK;
 }
 
-int voxel_downsample(me_ctx *ctx, int slot, double voxel_size, long long *n_out) {
-    if (slot < 0 || slot > 1) return ctx->fail(ME_ERR_ARG, "bad slot");
-    if (!(voxel_size > 0)) return ctx->fail(ME_ERR_ARG, "me_voxel_downsample: voxel_size must be > 0");
-    Cloud &c = ctx->cloud[slot];
-    if (!c.uploaded) return ctx->fail(ME_ERR_STATE, "me_voxel_downsample: cloud not uploaded");
-    if (c.slab.axis >= 0) return ctx->fail(ME_ERR_STATE, "me_voxel_downsample: not available in slab mode (down-sample before sharding)");
-    ME_CHECK(ctx, hipSetDevice(ctx->device));
-    const long long n = c.n;
+// the down-sample of n points at `xyz` (bounding-box minimum `lo`) on ctx's stream and scratch: the means, ascending voxel index, in `out`
+// (V x 3); the sorted permutation stays in ctx->tmp[3] and the segment starts in ctx->tmp[0] for a second attribute (the normals)
+static int vds_run(me_ctx *ctx, const double *xyz, long long n, const double lo[3], double voxel_size, DevBuf &out, long long *V_out) {
     DevBuf &keys_in = ctx->tmp[0], &iota = ctx->tmp[1], &keys = ctx->tmp[2], &perm = ctx->tmp[3], &flags = ctx->tmp[4];
     ME_CHECK(ctx, keys_in.ensure((size_t) n * 8));
     ME_CHECK(ctx, iota.ensure((size_t) n * 4));
@@ -1162,10 +1159,11 @@ int voxel_downsample(me_ctx *ctx, int slot, double voxel_size, long long *n_out)
     int *d_err = ctx->red.as<int>();
     ME_CHECK(ctx, hipMemsetAsync(d_err, 0, 4, ctx->stream));
     // voxel_min_bound = GetMinBound() - voxel_size / 2  [Open3D, upstream]
-    const double mx = c.bbox_lo[0] - voxel_size * 0.5, my = c.bbox_lo[1] - voxel_size * 0.5, mz = c.bbox_lo[2] - voxel_size * 0.5;
-    TimerScope ts(ctx, "downsample");
-    hipLaunchKernelGGL(k_vds_keys, dim3(grid_for(n)), dim3(256), 0, ctx->stream, c.xyz.as<double>(), n, voxel_size, mx, my, mz,
+    const double mx = lo[0] - voxel_size * 0.5, my = lo[1] - voxel_size * 0.5, mz = lo[2] - voxel_size * 0.5;
+    TimerScope ts(ctx, "downsample");  // (ended before the sort, which has its own scope: scopes do not nest)
+    hipLaunchKernelGGL(k_vds_keys, dim3(grid_for(n)), dim3(256), 0, ctx->stream, xyz, n, voxel_size, mx, my, mz,
                        keys_in.as<unsigned long long>(), iota.as<unsigned int>(), d_err);
+    ts.end();
     ME_TRY(sort_pairs_u64_u32(ctx, keys_in.as<unsigned long long>(), keys.as<unsigned long long>(), iota.as<unsigned int>(),
                               perm.as<unsigned int>(), n, 0, 63));
     DevBuf &pos = ctx->tmp[1];
@@ -1184,7 +1182,8 @@ int voxel_downsample(me_ctx *ctx, int slot, double voxel_size, long long *n_out)
     ME_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     if (h_err) return ctx->fail(ME_ERR_ARG, "voxel_size is too small for the cloud extent (more than 2^21 voxels per axis)");
     const long long V = (long long) last_pos + last_flag;
-    DevBuf &seg_start = ctx->tmp[0], seg_key, out;
+    DevBuf &seg_start = ctx->tmp[0], seg_key;
+    TimerScope ts2(ctx, "downsample");
     ME_CHECK(ctx, seg_start.ensure((size_t) (V + 1) * 4));
     ME_CHECK(ctx, seg_key.ensure((size_t) V * 8));
     ME_CHECK(ctx, out.ensure((size_t) V * 24));
@@ -1192,13 +1191,27 @@ int voxel_downsample(me_ctx *ctx, int slot, double voxel_size, long long *n_out)
                        flags.as<unsigned int>(), pos.as<unsigned int>(), n, seg_key.as<unsigned long long>(),
                        seg_start.as<unsigned int>());
     hipLaunchKernelGGL(k_set_u32v, dim3(1), dim3(1), 0, ctx->stream, seg_start.as<unsigned int>(), V, (unsigned int) n);
-    hipLaunchKernelGGL(k_vds_mean, dim3(grid_for(V)), dim3(256), 0, ctx->stream, c.xyz.as<double>(), perm.as<unsigned int>(),
+    hipLaunchKernelGGL(k_vds_mean, dim3(grid_for(V)), dim3(256), 0, ctx->stream, xyz, perm.as<unsigned int>(),
                        seg_start.as<unsigned int>(), V, out.as<double>());
+    *V_out = V;
+    return ME_OK;
+}
+
+int voxel_downsample(me_ctx *ctx, int slot, double voxel_size, long long *n_out) {
+    if (slot < 0 || slot > 1) return ctx->fail(ME_ERR_ARG, "bad slot");
+    if (!(voxel_size > 0)) return ctx->fail(ME_ERR_ARG, "me_voxel_downsample: voxel_size must be > 0");
+    Cloud &c = ctx->cloud[slot];
+    if (!c.uploaded) return ctx->fail(ME_ERR_STATE, "me_voxel_downsample: cloud not uploaded");
+    if (c.slab.axis >= 0) return ctx->fail(ME_ERR_STATE, "me_voxel_downsample: not available in slab mode (down-sample before sharding)");
+    ME_CHECK(ctx, hipSetDevice(ctx->device));
+    DevBuf out;
+    long long V = 0;
+    ME_TRY(vds_run(ctx, c.xyz.as<double>(), c.n, c.bbox_lo, voxel_size, out, &V));
     if (!c.xyz.owned) ME_CHECK(ctx, c.xyz.ensure((size_t) V * 24));  // (a borrowed input buffer is the caller's: the result gets its own)
     ME_CHECK(ctx, hipMemcpyAsync(c.xyz.p, out.p, (size_t) V * 24, hipMemcpyDeviceToDevice, ctx->stream));
     if (c.have_normals) {  // Open3D averages the normals of a voxel as well (sum / count, not re-normalised)
-        hipLaunchKernelGGL(k_vds_mean, dim3(grid_for(V)), dim3(256), 0, ctx->stream, c.normals.as<double>(), perm.as<unsigned int>(),
-                           seg_start.as<unsigned int>(), V, out.as<double>());
+        hipLaunchKernelGGL(k_vds_mean, dim3(grid_for(V)), dim3(256), 0, ctx->stream, c.normals.as<double>(), ctx->tmp[3].as<unsigned int>(),
+                           ctx->tmp[0].as<unsigned int>(), V, out.as<double>());
         ME_CHECK(ctx, hipMemcpyAsync(c.normals.p, out.p, (size_t) V * 24, hipMemcpyDeviceToDevice, ctx->stream));
     }
     c.have_cov = false;
@@ -1208,6 +1221,66 @@ int voxel_downsample(me_ctx *ctx, int slot, double voxel_size, long long *n_out)
     c.n_total = V;
     if (n_out) *n_out = V;
     return cloud_finish(ctx, slot);  // output order: ascending voxel index (Open3D: hash-map iteration order)
+}
+
+// me_voxel_downsample of a resident cloud into a slot of another context (or another slot of the same one), src untouched: the same
+// passes on the same points and bounding box (a cloud's bbox is always that of its current points: cloud_finish), so the result is
+// what an upload of src's points into dst followed by me_voxel_downsample would hold.  The work runs on dst's stream and scratch.
+int voxel_downsample_into(me_ctx *sctx, int src_slot, me_ctx *dctx, int dst_slot, double voxel_size, long long *n_out) {
+    if (src_slot < 0 || src_slot > 1 || dst_slot < 0 || dst_slot > 1) return dctx->fail(ME_ERR_ARG, "me_voxel_downsample_into: bad slot");
+    if (!(voxel_size > 0)) return dctx->fail(ME_ERR_ARG, "me_voxel_downsample_into: voxel_size must be > 0");
+    if (sctx->device != dctx->device) return dctx->fail(ME_ERR_ARG, "me_voxel_downsample_into: the contexts are on different devices");
+    Cloud &S = sctx->cloud[src_slot];
+    Cloud &D = dctx->cloud[dst_slot];
+    if (&S == &D) return dctx->fail(ME_ERR_ARG, "me_voxel_downsample_into: dst is src (use me_voxel_downsample)");
+    if (sctx->shard_world != 1 || dctx->shard_world != 1 || sctx->slab.axis >= 0 || dctx->slab.axis >= 0 || S.slab.axis >= 0)
+        return dctx->fail(ME_ERR_ARG, "me_voxel_downsample_into: single GPU only (no slab or shard mode)");
+    if (!S.uploaded) return dctx->fail(ME_ERR_STATE, "me_voxel_downsample_into: source cloud not uploaded");
+    ME_CHECK(dctx, hipSetDevice(dctx->device));
+    struct EventGuard {  // destroyed only once dst's stream has passed its wait (below) or on an early return
+        hipEvent_t ev = nullptr;
+        hipStream_t s = nullptr;
+        ~EventGuard() {
+            if (!ev) return;
+            (void) hipStreamSynchronize(s);
+            (void) hipEventDestroy(ev);
+        }
+    } eg;
+    if (sctx->stream != dctx->stream) {  // dst's work is ordered after whatever src's stream still has queued
+        ME_CHECK(dctx, hipEventCreateWithFlags(&eg.ev, hipEventDisableTiming));
+        eg.s = dctx->stream;
+        ME_CHECK(dctx, hipEventRecord(eg.ev, sctx->stream));
+        ME_CHECK(dctx, hipStreamWaitEvent(dctx->stream, eg.ev, 0));
+    }
+    DevBuf out;
+    long long V = 0;
+    ME_TRY(vds_run(dctx, S.xyz.as<double>(), S.n, S.bbox_lo, voxel_size, out, &V));
+    ME_CHECK(dctx, hipStreamSynchronize(dctx->stream));  // (src is read; from here on only dst changes)
+    ME_CHECK(dctx, hipGetLastError());
+    std::swap(D.xyz.p, out.p);
+    std::swap(D.xyz.bytes, out.bytes);
+    std::swap(D.xyz.owned, out.owned);
+    // the upload-time reset of dst (cloud_upload)
+    D.uploaded = false;
+    D.index_valid = false;
+    D.nn_ref_slot = -1;
+    D.n_vox = 0;
+    D.vox_size = 0;
+    D.vox_valid = false;
+    D.vox_merged = false;
+    D.vox_rec_valid = false;
+    D.mme_have = false;
+    dctx->cloud[1 - dst_slot].nn_ref_slot = -1;
+    D.n = V;
+    D.n_total = V;
+    D.have_normals = D.have_cov = false;
+    D.fpfh_valid = false;
+    D.slab = dctx->slab;
+    D.n_unres = 0;
+    D.slab_identity = true;
+    D.cell_size_req = S.cell_size_req;
+    if (n_out) *n_out = V;
+    return cloud_finish(dctx, dst_slot);
 }
 
 // ------------------------------------------------------------------------------------------------------------

@@ -195,6 +195,72 @@ class Engine:
         self._ck(self._L.me_perturb_cloud(self._ctx, int(dst), int(src), C.byref(pp), C.byref(n)))
         return n.value
 
+    # ---- coarse global registration (FPFH + RANSAC, me_globreg.hip) ----
+    def downsample_into(self, src_slot: int, dst: "Engine", dst_slot: int, voxel_size: float) -> int:
+        """me_voxel_downsample_into: dst's slot = the voxel down-sample of this engine's src_slot (src untouched; dst may be self, another
+        slot).  Returns the point count."""
+        n = C.c_int64(0)
+        rc = self._L.me_voxel_downsample_into(self._ctx, int(src_slot), dst._ctx, int(dst_slot), float(voxel_size), C.byref(n))
+        dst._ck(rc)  # (the library reports on dst_ctx)
+        dst._held.pop(int(dst_slot), None)
+        return n.value
+
+    @staticmethod
+    def _fpfh_params(radius: float, max_nn: int, normal_knn: int) -> _lib.FpfhParams:
+        fp = _lib.FpfhParams()
+        fp.radius, fp.max_nn, fp.normal_knn = float(radius), int(max_nn), int(normal_knn)
+        return fp
+
+    def fpfh(self, slot: int, radius: float, max_nn: int = 40, normal_knn: int = 30, fetch: bool = True):
+        """me_fpfh: Open3D ComputeFPFHFeature with KDTreeSearchParamHybrid(radius, max_nn <= 40) on the resident cloud (normals estimated
+        with normal_knn when the slot has none).  Returns the (N, 33) features (fetch) or None; they also stay on the device."""
+        fp = self._fpfh_params(radius, max_nn, normal_knn)
+        out = np.empty((self.size(slot), 33), np.float64) if fetch else None
+        self._ck(self._L.me_fpfh(self._ctx, int(slot), C.byref(fp), _addr(out)))
+        return out
+
+    def fpfh_match(self, src_slot: int, ref_slot: int, mutual: bool = True):
+        """me_fpfh_match: exact 1-NN in feature space.  Returns (corr, n_corr): corr[i] = matched ref point of src point i, or -1."""
+        corr = np.empty(self.size(src_slot), np.int32)
+        n = C.c_int64(0)
+        self._ck(self._L.me_fpfh_match(self._ctx, int(src_slot), int(ref_slot), int(bool(mutual)), _addr(corr), C.byref(n)))
+        return corr, n.value
+
+    def global_register(self, src_slot: int, ref_slot: int, *, max_corr_dist: float, radius: float = 0.0, max_nn: int = 40,
+                        normal_knn: int = 30, edge_ratio: float = 0.9, max_iterations: int = 1_000_000, validate_top: int = 64,
+                        mutual: bool = True, seed: int = 0, scores: bool = False):
+        """me_global_register: FPFH feature matching + RANSAC on the device.  Returns (T, info) — T (4x4) maps src's current
+        coordinates to ref's frame, info a dict of me_globreg_info — and, with scores=True, the per-hypothesis correspondence inliers
+        (-1 = invalid) as a third item."""
+        gp = _lib.GlobRegParams()
+        gp.fpfh = self._fpfh_params(radius, max_nn, normal_knn)
+        gp.max_corr_dist = float(max_corr_dist)
+        gp.edge_ratio = float(edge_ratio)
+        gp.max_iterations = int(max_iterations)
+        gp.validate_top = int(validate_top)
+        gp.mutual = int(bool(mutual))
+        gp.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        T = np.zeros(16, np.float64)
+        info = _lib.GlobRegInfo()
+        sc = np.empty(int(max_iterations), np.int64) if scores else None
+        self._ck(self._L.me_global_register(self._ctx, int(src_slot), int(ref_slot), C.byref(gp), _addr(T), C.byref(info), _addr(sc)))
+        d = {k: getattr(info, k) for k, _ in _lib.GlobRegInfo._fields_}
+        return (T.reshape(4, 4), d, sc) if scores else (T.reshape(4, 4), d)
+
+    def coarse_align(self, voxel_size: float, *, src_slot: int = 0, ref_slot: int = 1, radius: float | None = None,
+                     max_corr_dist: float | None = None, **params):
+        """The initial pose: voxel_size down-samples of both resident slots in a private second context on the same device, FPFH
+        (radius 5 voxel_size by default), matching and RANSAC (max_corr_dist 1.5 voxel_size by default); returns T (4x4, src -> ref).
+        The resident clouds are not changed: apply T with transform_cloud and run performICPRegistration as usual."""
+        radius = 5.0 * voxel_size if radius is None else radius
+        max_corr_dist = 1.5 * voxel_size if max_corr_dist is None else max_corr_dist
+        with Engine(self.device) as co:
+            self.downsample_into(src_slot, co, 0, voxel_size)
+            self.downsample_into(ref_slot, co, 1, voxel_size)
+            T, info = co.global_register(0, 1, radius=radius, max_corr_dist=max_corr_dist, **params)[:2]
+        self.last_coarse_info = info
+        return T
+
     def size(self, slot: int) -> int:
         return int(self._L.me_cloud_size(self._ctx, slot))
 

@@ -14,6 +14,7 @@
 #include <numeric>
 #include <sstream>
 
+#include "../csrc/me_horn.hpp"
 #include "pcd_io.hpp"
 #include "yaml_lite.hpp"
 
@@ -138,8 +139,8 @@ Param loadParametersFromYAML(const std::string &yaml_file_path) {
         throw std::runtime_error("save_voxel_metrics: single GPU only (num_gpus must be 1)");
     // simulation mode (the reference reads evaluate_noised_gt and noise_std_dev only; the misspelt evaluate_noise_gt of its shipped
     // configs is not read there either)
-    if (config.has("noise_seed")) {
-        const std::string &v = config.at("noise_seed").scalar;
+    auto as_seed = [&config](const char *key) -> uint64_t {
+        const std::string &v = config.at(key).scalar;
         size_t used = 0;
         unsigned long long seed = 0;
         try {
@@ -147,9 +148,11 @@ Param loadParametersFromYAML(const std::string &yaml_file_path) {
         } catch (const std::exception &) {
             used = 0;
         }
-        if (v.empty() || v[0] == '-' || used != v.size()) throw std::runtime_error("noise_seed: expected an unsigned integer, got '" + v + "'");
-        param.noise_seed = seed;
-    }
+        if (v.empty() || v[0] == '-' || used != v.size())
+            throw std::runtime_error(std::string(key) + ": expected an unsigned integer, got '" + v + "'");
+        return seed;
+    };
+    if (config.has("noise_seed")) param.noise_seed = as_seed("noise_seed");
     if (config.has("noise_sparse_ratio")) param.noise_sparse_ratio = config.as_double("noise_sparse_ratio");
     if (config.has("noise_dense_ratio")) param.noise_dense_ratio = config.as_double("noise_dense_ratio");
     if (config.has("noise_region_size")) param.noise_region_size = config.as_double("noise_region_size");
@@ -171,6 +174,32 @@ Param loadParametersFromYAML(const std::string &yaml_file_path) {
         throw std::runtime_error("evaluate_noised_gt: single GPU only (num_gpus must be 1)");
     if (!param.noise_sweep.empty() && !(param.evaluate_noised_gt_ && param.evaluate_using_initial_ && param.num_gpus == 1))
         throw std::runtime_error("noise_sweep: needs evaluate_noised_gt: true, evaluate_using_initial: true and num_gpus: 1");
+    // coarse global registration (no reference counterpart)
+    if (config.has("global_registration")) param.global_registration = config.as_bool("global_registration");
+    if (config.has("global_voxel_size")) param.global_voxel_size = config.as_double("global_voxel_size");
+    if (config.has("global_feature_radius")) param.global_feature_radius = config.as_double("global_feature_radius");
+    else param.global_feature_radius = 5.0 * param.global_voxel_size;
+    if (config.has("global_max_nn")) param.global_max_nn = config.as_int("global_max_nn");
+    if (config.has("global_normal_knn")) param.global_normal_knn = config.as_int("global_normal_knn");
+    if (config.has("global_max_corr_dist")) param.global_max_corr_dist = config.as_double("global_max_corr_dist");
+    else param.global_max_corr_dist = 1.5 * param.global_voxel_size;
+    if (config.has("global_max_iterations")) param.global_max_iterations = (int64_t) config.as_double("global_max_iterations");
+    if (config.has("global_edge_ratio")) param.global_edge_ratio = config.as_double("global_edge_ratio");
+    if (config.has("global_mutual_filter")) param.global_mutual_filter = config.as_bool("global_mutual_filter");
+    if (config.has("global_seed")) param.global_seed = as_seed("global_seed");
+    if (config.has("global_min_fitness")) param.global_min_fitness = config.as_double("global_min_fitness");
+    if (param.global_registration) {
+        if (param.evaluate_using_initial_)
+            throw std::runtime_error("global_registration: needs the registration path (evaluate_using_initial: false): there is no ICP to start");
+        if (param.num_gpus > 1) throw std::runtime_error("global_registration: single GPU only (num_gpus must be 1)");
+    }
+    if (!(param.global_voxel_size > 0)) throw std::runtime_error("global_voxel_size: must be > 0");
+    if (!(param.global_feature_radius > 0)) throw std::runtime_error("global_feature_radius: must be > 0");
+    if (!(param.global_max_corr_dist > 0)) throw std::runtime_error("global_max_corr_dist: must be > 0");
+    if (param.global_max_iterations < 1) throw std::runtime_error("global_max_iterations: must be >= 1");
+    if (!(param.global_edge_ratio > 0 && param.global_edge_ratio <= 1)) throw std::runtime_error("global_edge_ratio: must lie in (0, 1]");
+    if (param.global_max_nn < 1 || param.global_max_nn > 40) throw std::runtime_error("global_max_nn: must lie in 1..40");
+    if (param.global_normal_knn < 1 || param.global_normal_knn > 40) throw std::runtime_error("global_normal_knn: must lie in 1..40");
     return param;
 }
 
@@ -199,7 +228,12 @@ std::string paramToJson(const Param &p) {
       << ", \"noise_deform_center\": [" << p.noise_deform_center[0] << ", " << p.noise_deform_center[1] << ", " << p.noise_deform_center[2]
       << "], \"noise_sweep\": [";
     for (size_t i = 0; i < p.noise_sweep.size(); ++i) o << (i ? ", " : "") << p.noise_sweep[i];
-    o << "]}";
+    o << "], \"global_registration\": " << b(p.global_registration) << ", \"global_voxel_size\": " << p.global_voxel_size
+      << ", \"global_feature_radius\": " << p.global_feature_radius << ", \"global_max_nn\": " << p.global_max_nn
+      << ", \"global_normal_knn\": " << p.global_normal_knn << ", \"global_max_corr_dist\": " << p.global_max_corr_dist
+      << ", \"global_max_iterations\": " << p.global_max_iterations << ", \"global_edge_ratio\": " << p.global_edge_ratio
+      << ", \"global_mutual_filter\": " << b(p.global_mutual_filter) << ", \"global_seed\": " << p.global_seed
+      << ", \"global_min_fitness\": " << p.global_min_fitness << "}";
     return o.str();
 }
 
@@ -381,42 +415,6 @@ int MapEval::process() {
 
 namespace {
 
-// symmetric n x n Jacobi eigen-decomposition (n <= 4): eigenvalues in d, eigenvectors in the columns of V
-void jacobi_sym(int n, double *a, double *d, double *V) {
-    for (int i = 0; i < n; ++i)
-        for (int j = 0; j < n; ++j) V[n * i + j] = (i == j) ? 1.0 : 0.0;
-    for (int sweep = 0; sweep < 100; ++sweep) {
-        double off = 0;
-        for (int p = 0; p < n; ++p)
-            for (int q = p + 1; q < n; ++q) off += a[n * p + q] * a[n * p + q];
-        if (off < 1e-300) break;
-        for (int p = 0; p < n; ++p)
-            for (int q = p + 1; q < n; ++q) {
-                const double apq = a[n * p + q];
-                if (apq == 0.0) continue;
-                const double theta = (a[n * q + q] - a[n * p + p]) / (2.0 * apq);
-                const double t = (theta >= 0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
-                const double c = 1.0 / std::sqrt(t * t + 1.0), sn = t * c;
-                for (int k = 0; k < n; ++k) {
-                    const double akp = a[n * k + p], akq = a[n * k + q];
-                    a[n * k + p] = c * akp - sn * akq;
-                    a[n * k + q] = sn * akp + c * akq;
-                }
-                for (int k = 0; k < n; ++k) {
-                    const double apk = a[n * p + k], aqk = a[n * q + k];
-                    a[n * p + k] = c * apk - sn * aqk;
-                    a[n * q + k] = sn * apk + c * aqk;
-                }
-                for (int k = 0; k < n; ++k) {
-                    const double vkp = V[n * k + p], vkq = V[n * k + q];
-                    V[n * k + p] = c * vkp - sn * vkq;
-                    V[n * k + q] = sn * vkp + c * vkq;
-                }
-            }
-    }
-    for (int i = 0; i < n; ++i) d[i] = a[n * i + i];
-}
-
 // Optimal rigid update (row-major 4x4, absolute coordinates) from the me_icp_sums block: Horn's closed form, which gives
 // the same rotation as Eigen::umeyama without scaling (TransformationEstimationPointToPoint [Open3D, upstream]).
 void kabsch_from_sums(const me_icp_sums &s, double T[16]) {
@@ -428,19 +426,8 @@ void kabsch_from_sums(const me_icp_sums &s, double T[16]) {
     }
     for (int r = 0; r < 3; ++r)
         for (int c = 0; c < 3; ++c) S[3 * r + c] = s.sum_pq[3 * r + c] - n * pb[r] * qb[c];  // sum (p-pb)(q-qb)^T
-    double N[16] = {S[0] + S[4] + S[8], S[5] - S[7],        S[6] - S[2],         S[1] - S[3],
-                    S[5] - S[7],        S[0] - S[4] - S[8], S[1] + S[3],         S[6] + S[2],
-                    S[6] - S[2],        S[1] + S[3],        -S[0] + S[4] - S[8], S[5] + S[7],
-                    S[1] - S[3],        S[6] + S[2],        S[5] + S[7],         -S[0] - S[4] + S[8]};
-    double d[4], V[16];
-    jacobi_sym(4, N, d, V);
-    int best = 0;
-    for (int i = 1; i < 4; ++i)
-        if (d[i] > d[best]) best = i;
-    const double w = V[best], x = V[4 + best], y = V[8 + best], z = V[12 + best];
-    const double R[9] = {w * w + x * x - y * y - z * z, 2 * (x * y - w * z),           2 * (x * z + w * y),
-                         2 * (x * y + w * z),           w * w - x * x + y * y - z * z, 2 * (y * z - w * x),
-                         2 * (x * z - w * y),           2 * (y * z + w * x),           w * w - x * x - y * y + z * z};
+    double R[9];
+    me::horn_rotation(S, R);  // csrc/me_horn.hpp (shared with the device RANSAC fit)
     // x -> o + R (x - o - pb) + qb
     for (int i = 0; i < 16; ++i) T[i] = (i == 15) ? 1.0 : 0.0;
     for (int r = 0; r < 3; ++r) {
@@ -523,6 +510,16 @@ int MapEval::performRegistration(bool metrics) {
     const bool root = param_.dist_rank == 0;
     if (comm_ && me_set_shard(ctx_, comm_->rank, comm_->world) != ME_OK) return fail(me_last_error(ctx_));
     for (int i = 0; i < 16; ++i) trans[i] = param_.initial_matrix_[i];
+    if (param_.global_registration && !comm_) {  // ICP starts from T_c * initial_matrix (the map as loaded, moved by both)
+        double Tc[16];
+        if (globalRegistration(Tc) != 0) return -1;
+        std::array<double, 16> M{};
+        for (int r = 0; r < 4; ++r)
+            for (int c = 0; c < 4; ++c)
+                M[4 * r + c] = ((Tc[4 * r] * param_.initial_matrix_[c] + Tc[4 * r + 1] * param_.initial_matrix_[4 + c]) +
+                                Tc[4 * r + 2] * param_.initial_matrix_[8 + c]) + Tc[4 * r + 3] * param_.initial_matrix_[12 + c];
+        for (int i = 0; i < 16; ++i) trans[i] = M[i];
+    }
     bool identity = true;
     for (int i = 0; i < 16; ++i) identity = identity && (trans[i] == ((i % 5 == 0) ? 1.0 : 0.0));
     const int method = param_.evaluation_method_;
@@ -1083,6 +1080,56 @@ me_perturb_params MapEval::perturbParams(double noise_std) const {
     for (int a = 0; a < 3; ++a) pp.deform_center[a] = param_.noise_deform_center[a];
     pp.seed = param_.noise_seed;
     return pp;
+}
+
+// global_registration.txt (global_registration: true; no reference counterpart): the initial pose found on the device.  Coarse copies of
+// the map as loaded and of the ground truth are made in a second context (me_voxel_downsample_into), the coarse map is moved by
+// initial_matrix, and me_global_register gives T_c (coarse map -> ground truth).  The file holds T_c (four rows, %.17g), then fitness,
+// inlier RMSE, the correspondence count, the valid hypothesis count and the seed, one "name value" per line.
+int MapEval::globalRegistration(double T_c[16]) {
+    me_ctx *co = me_create(param_.gpu_device, 0);
+    if (!co) return fail(std::string("global_registration: ") + me_last_error(nullptr));
+    struct Destroy {
+        me_ctx *c;
+        ~Destroy() { me_destroy(c); }
+    } d{co};
+    int64_t n = 0;
+    if (me_voxel_downsample_into(ctx_, ME_SLOT_EST, co, ME_SLOT_EST, param_.global_voxel_size, &n) != ME_OK ||
+        me_voxel_downsample_into(ctx_, ME_SLOT_GT, co, ME_SLOT_GT, param_.global_voxel_size, &n) != ME_OK)
+        return fail(std::string("global_registration: ") + me_last_error(co));
+    bool identity = true;
+    for (int i = 0; i < 16; ++i) identity = identity && (param_.initial_matrix_[i] == ((i % 5 == 0) ? 1.0 : 0.0));
+    if (!identity && me_transform_cloud(co, ME_SLOT_EST, param_.initial_matrix_.data()) != ME_OK)
+        return fail(std::string("global_registration: ") + me_last_error(co));
+    me_globreg_params gp{};
+    gp.fpfh.radius = param_.global_feature_radius > 0 ? param_.global_feature_radius : 5.0 * param_.global_voxel_size;
+    gp.fpfh.max_nn = param_.global_max_nn;
+    gp.fpfh.normal_knn = param_.global_normal_knn;
+    gp.max_corr_dist = param_.global_max_corr_dist > 0 ? param_.global_max_corr_dist : 1.5 * param_.global_voxel_size;
+    gp.edge_ratio = param_.global_edge_ratio;
+    gp.max_iterations = param_.global_max_iterations;
+    gp.validate_top = 64;
+    gp.mutual = param_.global_mutual_filter ? 1 : 0;
+    gp.seed = param_.global_seed;
+    me_globreg_info info{};
+    if (me_global_register(co, ME_SLOT_EST, ME_SLOT_GT, &gp, T_c, &info, nullptr) != ME_OK)
+        return fail(std::string("global_registration: ") + me_last_error(co));
+    std::filesystem::create_directories(results_subfolder);
+    const std::string path = results_subfolder + "global_registration.txt";
+    FILE *f = std::fopen(path.c_str(), "w");
+    if (!f) return fail("cannot write " + path);
+    for (int r = 0; r < 4; ++r)
+        std::fprintf(f, "%.17g %.17g %.17g %.17g\n", T_c[4 * r], T_c[4 * r + 1], T_c[4 * r + 2], T_c[4 * r + 3]);
+    std::fprintf(f, "fitness %.17g\ninlier_rmse %.17g\ncorrespondences %lld\nvalid_hypotheses %lld\nseed %llu\n", info.fitness,
+                 info.inlier_rmse, (long long) info.n_corr, (long long) info.n_valid_hypotheses, (unsigned long long) param_.global_seed);
+    if (std::fclose(f) != 0) return fail("writing " + path + " failed");
+    if (info.fitness < param_.global_min_fitness) {
+        std::ostringstream m;
+        m << "global_registration: fitness " << info.fitness << " of the coarse alignment is below global_min_fitness "
+          << param_.global_min_fitness << "; not evaluating a map that may be misaligned";
+        return fail(m.str());
+    }
+    return 0;
 }
 
 // noise_sweep.txt (noise_sweep: [..]; no reference counterpart): the robustness sweep of the paper's noise-sensitivity experiment on

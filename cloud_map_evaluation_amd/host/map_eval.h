@@ -63,6 +63,19 @@ struct Param {
     std::array<double, 3> noise_deform_center{{0, 0, 0}};         // `noise_deform_center: [x, y, z]`
     std::vector<double> noise_sweep;  // `noise_sweep: [s0, s1, ..]` after the run, one suite per noise level on the resident ground
                                       // truth -> map_results/noise_sweep.txt (single GPU, initial-matrix path; runNoiseSweep)
+    // coarse global registration (global_registration: true; no reference counterpart): on the registration path, FPFH + RANSAC on
+    // down-sampled copies finds T_c, and ICP starts from T_c * initial_matrix (me_global_register)
+    bool global_registration = false;      // `global_registration:`
+    double global_voxel_size = 1.0;        // `global_voxel_size:` coarse voxel
+    double global_feature_radius = 0.0;    // `global_feature_radius:` FPFH radius (<= 0 in the struct: 5 x voxel)
+    int global_max_nn = 40;                // `global_max_nn:` FPFH neighbour cap, 1..40
+    int global_normal_knn = 30;            // `global_normal_knn:` k of the normal estimation
+    double global_max_corr_dist = 0.0;     // `global_max_corr_dist:` inlier distance (<= 0 in the struct: 1.5 x voxel)
+    int64_t global_max_iterations = 1000000;  // `global_max_iterations:` hypotheses drawn
+    double global_edge_ratio = 0.9;        // `global_edge_ratio:`
+    bool global_mutual_filter = true;      // `global_mutual_filter:`
+    uint64_t global_seed = 0;              // `global_seed:` Philox seed
+    double global_min_fitness = 0.0;       // `global_min_fitness:` below this fitness of T_c the run fails
     int dist_rank = 0;              // (set by the launcher, not a YAML key)
     void printParam() const;
 };
@@ -92,7 +105,8 @@ public:
     void saveRegistrationResults();                        // map_eval.cpp:424-482 (text lines; renderers out of scope)
     void saveVoxelMetrics(int gate_mode);                  // voxel_metrics.txt (save_voxel_metrics; no reference counterpart)
     me_perturb_params perturbParams(double noise_std) const;  // the noise_* keys as me_perturb_cloud's parameters
-    int runNoiseSweep();                                   // noise_sweep.txt (noise_sweep; no reference counterpart)
+    int runNoiseSweep();
+    int globalRegistration(double T_c[16]);                 // global_registration.txt (global_registration; no reference counterpart)                                   // noise_sweep.txt (noise_sweep; no reference counterpart)
 
     // multi-GPU (map_eval_dist.cpp): the communicator of this rank; forced = take the distributed path with one rank too
     void setComm(medist::Comm *comm, bool forced) {

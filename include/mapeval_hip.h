@@ -282,6 +282,78 @@ typedef struct me_perturb_params {
 } me_perturb_params;
 int me_perturb_cloud(me_ctx *ctx, int dst_slot, int src_slot, const me_perturb_params *p, int64_t *n_out);
 
+/* ---- coarse global registration: the initial pose (the reference's FAQ "How to obtain initial pose?": by hand in CloudCompare) --- */
+/* Open3D's compute_fpfh_feature + registration_ransac_based_on_feature_matching, on the device.
+ *
+ * me_voxel_downsample_into: me_voxel_downsample of src_ctx's src_slot written into dst_ctx's dst_slot; src is untouched.  The
+ * result (points, order, index) is bit-identical to uploading src's points into dst with src's cell size and calling
+ * me_voxel_downsample there.  dst gets the upload-time reset (no normals, features, NN, MME or voxel state).  dst_ctx may be
+ * src_ctx (another slot); its stream waits for src_ctx's pending work.  ME_ERR_ARG: different devices, the same (context, slot),
+ * slab or shard mode, voxel_size <= 0.  Device timer "downsample" of dst_ctx.
+ *
+ * me_fpfh: Fast Point Feature Histograms (Open3D ComputeFPFHFeature) of a resident cloud, N x 33.
+ *   normals: those of the slot (me_set_normals / me_estimate_normals / averaged by a down-sample) are used as they are; a slot
+ *            without normals gets me_estimate_normals(normal_knn) first (1..40).
+ *   neighbours: Open3D's KDTreeSearchParamHybrid(radius, max_nn) — the max_nn nearest points (the exact k-NN walk of
+ *            me_estimate_normals, ascending by (d2, index)) with d2 < radius^2, the query itself removed by index.  1 <= max_nn <= 40:
+ *            Open3D's tutorial value of 100 is clipped to 40 (the k-NN walk keeps its list in LDS).
+ *   pair feature of (p1, n1, p2, n2): d = p2 - p1, L = sqrt((dx dx + dy dy) + dz dz), L == 0 -> (0, 0, 0); a1 = n1.d / L,
+ *            a2 = n2.d / L; if |a1| < |a2| the roles swap (n2, n1, -d) and f2 = -a2, else f2 = a1 (Open3D's acos(|a1|) > acos(|a2|)
+ *            without the library call); v = d x n1', |v| == 0 -> (0, 0, 0), v /= |v|; w = n1' x v; f1 = v.n2';
+ *            f0 = atan2(w.n2', n1'.n2').  Dots are (x x' + y y') + z z'.
+ *   SPFH of a point with m >= 1 neighbours: each adds 100 / m to the bins floor(11 (f0 + pi) / (2 pi)), 11 + floor(11 (f1 + 1) / 2),
+ *            22 + floor(11 (f2 + 1) / 2), each index clamped to [0, 10]; m = 0: all zeros.
+ *   FPFH: sum over the neighbours in list order of SPFH(j) / d2 (d2 == 0 skipped: Open3D weighs by the SQUARED distance), each
+ *            11-bin block scaled by 100 / block sum when that sum is nonzero, then + SPFH(i).
+ * The features stay on the device with the slot; an upload, down-sample, perturbation, transform or new normals drops them.
+ * features: N x 33 host array in the caller's (cloud) order, nullable.  Device timer "fpfh" (its normal estimation: "normals").
+ *
+ * me_fpfh_match: exact 1-NN in the 33-dimensional feature space, both directions: squared distance = a sequential fp64 sum over the
+ * dimensions in index order (no contraction), ties to the smallest index.  corr[i] (n_src entries, host, nullable) = the reference
+ * point matched to source point i, or -1; mutual = 1 keeps i -> j only when j -> i (Open3D's mutual_filter).  *n_corr = entries
+ * != -1.  Both slots need me_fpfh features (ME_ERR_STATE).  Device timer "fpfh_match".
+ *
+ * me_global_register: RANSAC over the correspondences (i, corr[i]) in ascending i, on the device.  Hypothesis h < max_iterations
+ * is a pure function of (seed, h): Philox4x64-10 counter (h, 4, 0, 0), key (seed, 0) -> w0, w1, w2; sample k_j = mulhi64(w_j,
+ * n_corr) (the high word of w_j n_corr).  It is INVALID when two samples coincide; when an edge fails the two-sided length check
+ * (|s_a - s_b| < edge_ratio |t_a - t_b| or |t_a - t_b| < edge_ratio |s_a - s_b|, Open3D's CorrespondenceCheckerBasedOnEdgeLength);
+ * when the source triangle is degenerate: |e01 x e02|^2 <= 1e-12 |e01|^2 |e02|^2 (sine of its angle at s0 <= 1e-6); or when, after
+ * the fit, a sampled pair is farther than max_corr_dist (d2 > eps^2, CorrespondenceCheckerBasedOnDistance).  The fit is Horn's
+ * method of csrc/me_horn.hpp on the three pairs.  The valid hypotheses are scored (in batches, hypothesis order kept): the count of
+ * correspondences with |R s + t - q|^2 < eps^2, fp64, ((R_r0 x + R_r1 y) + R_r2 z) + t_r, ((dx dx + dy dy) + dz dz).  The top
+ * validate_top by (score desc, h asc) are re-scored on the whole source cloud (every point moved, 1-NN in ref_slot as me_nn_points,
+ * inlier iff d2 < eps^2): fitness = inliers / N_src, inlier_rmse = sqrt(sum d2 / inliers) (0 without inliers), as Open3D evaluates
+ * a RANSAC hypothesis.  The winner is the best by (fitness desc, rmse asc, h asc); T_out (row-major 4x4) maps the source's current
+ * coordinates to ref_slot's frame; the source slot is not moved.  No confidence early stop: every hypothesis is drawn.
+ * Features are computed with p->fpfh on a slot that has none.  scores (max_iterations entries, host, nullable): the correspondence
+ * inliers of hypothesis h, -1 = invalid.  ME_ERR_STATE: fewer than 3 correspondences, or no valid hypothesis (with a message).
+ * ME_ERR_ARG: bad parameters (max_corr_dist <= 0, edge_ratio outside (0, 1], max_iterations < 1, validate_top < 1), src == ref,
+ * slab or shard mode.  Device timers "ransac" (sampling, fit, scoring), "ransac_validate" (the re-scoring without its 1-NN search,
+ * which counts to "nn1"), and "fpfh" / "fpfh_match" of its own feature work. */
+int me_voxel_downsample_into(me_ctx *src_ctx, int src_slot, me_ctx *dst_ctx, int dst_slot, double voxel_size, int64_t *n_out);
+typedef struct me_fpfh_params {
+    double radius;   /* KDTreeSearchParamHybrid radius                                       */
+    int max_nn;      /*   its max_nn, 1..40                                                   */
+    int normal_knn;  /* k of the normal estimation of a slot without normals, 1..40          */
+} me_fpfh_params;
+int me_fpfh(me_ctx *ctx, int slot, const me_fpfh_params *p, double *features);
+int me_fpfh_match(me_ctx *ctx, int src_slot, int ref_slot, int mutual, int32_t *corr, int64_t *n_corr);
+typedef struct me_globreg_params {
+    me_fpfh_params fpfh;        /* computed on both slots when absent                                    */
+    double max_corr_dist;       /* epsilon: inlier iff d2 < epsilon^2 (strict, the library's convention)  */
+    double edge_ratio;          /* 0.9, CorrespondenceCheckerBasedOnEdgeLength                           */
+    int64_t max_iterations;     /* hypotheses drawn; no confidence early stop                            */
+    int validate_top;           /* K hypotheses re-scored on the whole cloud (default 64)                */
+    int mutual;                 /* feature-match mutual filter                                           */
+    uint64_t seed;              /* Philox key word 0                                                     */
+} me_globreg_params;
+typedef struct me_globreg_info {
+    int64_t n_corr, n_valid_hypotheses, best_hypothesis, best_corr_inliers;
+    double fitness, inlier_rmse; /* of the chosen T against ref_slot, 1-NN, gate d2 < epsilon^2              */
+} me_globreg_info;
+int me_global_register(me_ctx *ctx, int src_slot, int ref_slot, const me_globreg_params *p, double T_out[16], me_globreg_info *info,
+                       int64_t *scores);
+
 int64_t me_cloud_size(me_ctx *ctx, int slot);
 /* transformed points back to the host (N x 3), original order — what map_3d_->points_ holds after :1206 */
 int me_download_cloud(me_ctx *ctx, int slot, double *xyz_host);
@@ -488,7 +560,7 @@ int me_run_suite_from(me_ctx *ctx, const double *est, int64_t n_est, const doubl
 
 /* ---- instrumentation (bench.py roofline leg) ------------------------------------------------------------- */
 /* Average device time (ms, HIP events on the context's stream) and launch count of a named kernel family since
- * the last me_timers_reset: "nn_grid", "nn1", "mme", "sort", "morton", "gather", "cells" (the cell tables), "octree", "nn_stats", "voxel", "voxel_metrics", "w2", "scs", "slab_filter", "halo_pack".  Enabled by me_timers_enable(1).
+ * the last me_timers_reset: "nn_grid", "nn1", "mme", "sort", "morton", "gather", "cells" (the cell tables), "octree", "nn_stats", "voxel", "voxel_metrics", "w2", "scs", "slab_filter", "halo_pack", "perturb", "fpfh", "fpfh_match", "ransac", "ransac_validate".  Enabled by me_timers_enable(1).
  * Counters (total_ms = 0, value in *launches): "mme_pairs" (accepted (query, neighbour) pairs of the MME launches: the useful work of
  * the VALU-bound kernel, bench.py's roofline.valu), "mme_refined" (queries whose thin neighbourhood — smallest covariance eigenvalue below ~1.8e-6 cell^2 — the MME pass
  * recomputed two-pass about the query itself; counted whether or not timers are on), "nn_queries" / "nn_fallback_queries" (1-NN queries, and those that needed the
