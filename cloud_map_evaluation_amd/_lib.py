@@ -30,6 +30,7 @@ SYMBOLS = [
     "me_transform_points_device", "me_upload_slab_device", "me_halo_pack_device", "me_halo_pack_tagged_device", "me_lattice_histograms_device", "me_lattice_messages_device", "me_lattice_plan_device", "me_voxel_partial_rows_device", "me_voxel_merge_device",
     "me_upload_cloud", "me_upload_cloud_device", "me_cloud_size", "me_download_cloud", "me_voxel_downsample",
     "me_transform_cloud", "me_perturb_cloud", "me_voxel_downsample_into", "me_fpfh", "me_fpfh_match", "me_global_register",
+    "me_statistical_outlier", "me_radius_outlier", "me_outlier_select_into",
     "me_set_normals", "me_get_normals", "me_estimate_normals", "me_gicp_covariances", "me_get_covariances", "me_icp_lsq_sums",
     "me_nn1", "me_icp_p2p_sums", "me_render_distance", "me_render_entropy", "me_nn_stats", "me_nn_partial_sums", "me_nn_sigma_sums", "me_nn_finalize", "me_chamfer",
     "me_mme", "me_voxel_gaussians", "me_voxel_metrics", "me_awd_scs", "me_w2_batch", "me_scs_table", "me_run_suite", "me_run_suite_from", "me_mme_fetch",
@@ -163,6 +164,17 @@ class GlobRegInfo(C.Structure):
     ]
 
 
+class OutlierInfo(C.Structure):
+    _fields_ = [
+        ("n_in", C.c_int64),
+        ("n_kept", C.c_int64),
+        ("n_fallback", C.c_int64),
+        ("mean", C.c_double),
+        ("std_dev", C.c_double),
+        ("threshold", C.c_double),
+    ]
+
+
 _lib = None
 
 
@@ -231,6 +243,11 @@ def load():
     L.me_fpfh_match.argtypes = [vp, C.c_int, C.c_int, C.c_int, ip, C.POINTER(C.c_int64)]
     L.me_global_register.argtypes = [vp, C.c_int, C.c_int, C.POINTER(GlobRegParams), dp, C.POINTER(GlobRegInfo), vp]
     for f in ("me_voxel_downsample_into", "me_fpfh", "me_fpfh_match", "me_global_register"):
+        getattr(L, f).restype = C.c_int
+    L.me_statistical_outlier.argtypes = [vp, C.c_int, C.c_int, C.c_double, dp, vp, C.POINTER(OutlierInfo)]
+    L.me_radius_outlier.argtypes = [vp, C.c_int, C.c_int, C.c_double, ip, vp, C.POINTER(OutlierInfo)]
+    L.me_outlier_select_into.argtypes = [vp, C.c_int, vp, C.c_int, C.POINTER(C.c_int64)]
+    for f in ("me_statistical_outlier", "me_radius_outlier", "me_outlier_select_into"):
         getattr(L, f).restype = C.c_int
     L.me_upload_cloud.argtypes = [vp, C.c_int, dp, C.c_int64, dp, C.c_double]
     L.me_upload_cloud_device.argtypes = [vp, C.c_int, dp, C.c_int64, dp, C.c_double]

@@ -295,6 +295,25 @@ int me_global_register(me_ctx *ctx, int src_slot, int ref_slot, const me_globreg
     return me::global_register(ctx, src_slot, ref_slot, p, T_out, info, scores);
 }
 
+int me_statistical_outlier(me_ctx *ctx, int slot, int nb_neighbors, double std_ratio, double *avg_dist, uint8_t *keep,
+                           me_outlier_info *info) {
+    if (!ctx) return ME_ERR_ARG;
+    return me::statistical_outlier(ctx, slot, nb_neighbors, std_ratio, avg_dist, keep, info);
+}
+
+int me_radius_outlier(me_ctx *ctx, int slot, int nb_points, double radius, int32_t *counts, uint8_t *keep, me_outlier_info *info) {
+    if (!ctx) return ME_ERR_ARG;
+    return me::radius_outlier(ctx, slot, nb_points, radius, counts, keep, info);
+}
+
+int me_outlier_select_into(me_ctx *src_ctx, int src_slot, me_ctx *dst_ctx, int dst_slot, int64_t *n_out) {
+    if (!src_ctx || !dst_ctx) return ME_ERR_ARG;
+    long long n = 0;
+    const int rc = me::outlier_select_into(src_ctx, src_slot, dst_ctx, dst_slot, &n);
+    if (n_out && rc == ME_OK) *n_out = n;
+    return rc;
+}
+
 int me_transform_cloud(me_ctx *ctx, int slot, const double *T) {
     if (!ctx) return ME_ERR_ARG;
     return me::cloud_transform(ctx, slot, T);

@@ -649,6 +649,7 @@ int cloud_upload(me_ctx *ctx, int slot, const double *src, bool src_on_device, l
         e.nn_ref_slot = -1;
         e.vox_valid = e.vox_merged = false;
         e.have_normals = e.have_cov = false;
+        e.outlier_keep_valid = false;
         ctx->cloud[1 - slot].nn_ref_slot = -1;
         return ME_OK;
     }
@@ -753,6 +754,7 @@ int cloud_finish(me_ctx *ctx, int slot, bool bbox_ready) {
     c.vox_merged = false;
     c.n_vox = 0;
     c.fpfh_valid = false;
+    c.outlier_keep_valid = false;  // (the mask belongs to the points it was computed on)
     ctx->cloud[1 - slot].nn_ref_slot = -1;
     // bbox
     const unsigned int nb = (unsigned int) std::min<long long>(1024, (n + 255) / 256);
@@ -783,6 +785,29 @@ int cloud_finish(me_ctx *ctx, int slot, bool bbox_ready) {
         return ctx->fail(ME_ERR_ARG, "slab upload: points outside [lo - halo, hi + halo) of me_set_slab along the slab axis");
     c.uploaded = true;
     return cloud_build_index(ctx, slot, c.cell_size_req);
+}
+
+void cloud_reset_replaced(me_ctx *ctx, int slot, long long n, double cell_size_req) {
+    Cloud &D = ctx->cloud[slot];
+    D.uploaded = false;
+    D.index_valid = false;
+    D.nn_ref_slot = -1;
+    D.n_vox = 0;
+    D.vox_size = 0;
+    D.vox_valid = false;
+    D.vox_merged = false;
+    D.vox_rec_valid = false;
+    D.mme_have = false;
+    ctx->cloud[1 - slot].nn_ref_slot = -1;
+    D.n = n;
+    D.n_total = n;
+    D.have_normals = D.have_cov = false;
+    D.fpfh_valid = false;
+    D.outlier_keep_valid = false;
+    D.slab = ctx->slab;
+    D.n_unres = 0;
+    D.slab_identity = true;
+    D.cell_size_req = cell_size_req;
 }
 
 // *map_3d_ = map_3d_->Transform(T) (map_eval.cpp:1206) on the cloud already on the device

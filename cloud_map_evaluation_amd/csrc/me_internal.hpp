@@ -224,6 +224,9 @@ struct Cloud {
     // FPFH features of the cloud, ORIGINAL point order, double[n][33] (me_globreg.hip); dropped with the points (cloud_finish) and normals
     DevBuf fpfh;
     bool fpfh_valid = false;
+    // keep-mask of the last me_statistical_outlier / me_radius_outlier, uint8[n] in cloud order (me_outlier.hip); dropped with the points
+    DevBuf outlier_keep;
+    bool outlier_keep_valid = false;
 };
 
 struct TimerRec {
@@ -297,6 +300,7 @@ struct me_ctx {
     me::DevBuf nn_flags, nn_list_a, nn_list_b;   // 1-NN cascade: unresolved flags of the fine-grid pass, their ordered list, ping-pong
     me::DevBuf mme_keep_e, mme_keep_v;           // me_run_suite_from: the map's per-point MME result across its transform (mme_carry_*)
     long long mme_keep_n = -1;
+    me::DevBuf outlier_tmp[2];                   // me_outlier.hip: per-point avg_dist / counts and the fallback list, kept for repeated calls
     me::DevBuf nn1_dbg_buf;                      // octree-walk counters (nodes opened, leaves scanned, points, max per query)
     unsigned long long *nn1_dbg() {
         if (!nn1_dbg_buf.p) {
@@ -456,6 +460,8 @@ int cloud_upload(me_ctx *ctx, int slot, const double *src, bool src_on_device, l
 int cloud_build_index(me_ctx *ctx, int slot, double cell_size);
 int cloud_finish_octree(me_ctx *ctx, int slot);
 int cloud_finish(me_ctx *ctx, int slot, bool bbox_ready = false);
+// the upload-time reset of a slot whose points a device-side producer has just replaced (n points, no normals), before its cloud_finish
+void cloud_reset_replaced(me_ctx *ctx, int slot, long long n, double cell_size_req);
 int cloud_transform(me_ctx *ctx, int slot, const double *T);
 int voxel_downsample(me_ctx *ctx, int slot, double voxel_size, long long *n_out);
 int voxel_downsample_into(me_ctx *src_ctx, int src_slot, me_ctx *dst_ctx, int dst_slot, double voxel_size, long long *n_out);
@@ -467,6 +473,11 @@ int fpfh(me_ctx *ctx, int slot, const me_fpfh_params *p, double *features_host);
 int fpfh_match(me_ctx *ctx, int src_slot, int ref_slot, int mutual, int32_t *corr_host, long long *n_corr);
 int global_register(me_ctx *ctx, int src_slot, int ref_slot, const me_globreg_params *p, double T_out[16], me_globreg_info *info,
                     int64_t *scores);
+// ---- me_outlier.hip ----
+int statistical_outlier(me_ctx *ctx, int slot, int nb_neighbors, double std_ratio, double *avg_host, uint8_t *keep_host,
+                        me_outlier_info *info);
+int radius_outlier(me_ctx *ctx, int slot, int nb_points, double radius, int32_t *counts_host, uint8_t *keep_host, me_outlier_info *info);
+int outlier_select_into(me_ctx *src_ctx, int src_slot, me_ctx *dst_ctx, int dst_slot, long long *n_out);
 
 // ---- me_nn.hip ----
 int nn_search(me_ctx *ctx, int qslot, int rslot);

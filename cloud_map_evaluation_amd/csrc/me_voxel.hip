@@ -1260,25 +1260,7 @@ int voxel_downsample_into(me_ctx *sctx, int src_slot, me_ctx *dctx, int dst_slot
     std::swap(D.xyz.p, out.p);
     std::swap(D.xyz.bytes, out.bytes);
     std::swap(D.xyz.owned, out.owned);
-    // the upload-time reset of dst (cloud_upload)
-    D.uploaded = false;
-    D.index_valid = false;
-    D.nn_ref_slot = -1;
-    D.n_vox = 0;
-    D.vox_size = 0;
-    D.vox_valid = false;
-    D.vox_merged = false;
-    D.vox_rec_valid = false;
-    D.mme_have = false;
-    dctx->cloud[1 - dst_slot].nn_ref_slot = -1;
-    D.n = V;
-    D.n_total = V;
-    D.have_normals = D.have_cov = false;
-    D.fpfh_valid = false;
-    D.slab = dctx->slab;
-    D.n_unres = 0;
-    D.slab_identity = true;
-    D.cell_size_req = S.cell_size_req;
+    cloud_reset_replaced(dctx, dst_slot, V, S.cell_size_req);  // the upload-time reset of dst (cloud_upload)
     if (n_out) *n_out = V;
     return cloud_finish(dctx, dst_slot);
 }

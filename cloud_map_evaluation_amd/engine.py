@@ -248,18 +248,81 @@ class Engine:
         return (T.reshape(4, 4), d, sc) if scores else (T.reshape(4, 4), d)
 
     def coarse_align(self, voxel_size: float, *, src_slot: int = 0, ref_slot: int = 1, radius: float | None = None,
-                     max_corr_dist: float | None = None, **params):
+                     max_corr_dist: float | None = None, outlier_nb_neighbors: int = 0, outlier_std_ratio: float = 2.0, **params):
         """The initial pose: voxel_size down-samples of both resident slots in a private second context on the same device, FPFH
         (radius 5 voxel_size by default), matching and RANSAC (max_corr_dist 1.5 voxel_size by default); returns T (4x4, src -> ref).
-        The resident clouds are not changed: apply T with transform_cloud and run performICPRegistration as usual."""
+        outlier_nb_neighbors > 0: statistical outlier removal (that k, outlier_std_ratio) on the full-resolution clouds first — the
+        kept points are copied into the private context and down-sampled there in place (self.last_coarse_outliers: both infos; None
+        when the filter is off).  The resident POINTS are not changed: apply T with transform_cloud and run performICPRegistration as
+        usual.  With the filter on, the filter's mask replaces any outlier mask the two slots held, and their octrees are built if
+        they were not yet."""
         radius = 5.0 * voxel_size if radius is None else radius
         max_corr_dist = 1.5 * voxel_size if max_corr_dist is None else max_corr_dist
+        self.last_coarse_outliers = None
         with Engine(self.device) as co:
-            self.downsample_into(src_slot, co, 0, voxel_size)
-            self.downsample_into(ref_slot, co, 1, voxel_size)
+            if outlier_nb_neighbors > 0:
+                outl = []
+                for s, d in ((src_slot, 0), (ref_slot, 1)):
+                    outl.append(self.statistical_outlier(s, outlier_nb_neighbors, outlier_std_ratio))
+                    self.select_kept_into(s, co, d)
+                    co.voxel_downsample(d, voxel_size)
+                self.last_coarse_outliers = outl
+            else:
+                self.downsample_into(src_slot, co, 0, voxel_size)
+                self.downsample_into(ref_slot, co, 1, voxel_size)
             T, info = co.global_register(0, 1, radius=radius, max_corr_dist=max_corr_dist, **params)[:2]
         self.last_coarse_info = info
         return T
+
+    # ---- outlier removal (Open3D remove_statistical_outlier / remove_radius_outlier) ----
+    @staticmethod
+    def _outlier_dict(o: _lib.OutlierInfo) -> dict:
+        return {f: getattr(o, f) for f, _ in o._fields_}
+
+    def statistical_outlier(self, slot: int, nb_neighbors: int = 20, std_ratio: float = 2.0, fetch: bool = False):
+        """The statistical filter's mask on the slot (kept until the cloud changes); returns the info dict, and with fetch=True also
+        (avg_dist, keep) in cloud order."""
+        o = _lib.OutlierInfo()
+        if not fetch:
+            self._ck(self._L.me_statistical_outlier(self._ctx, slot, int(nb_neighbors), float(std_ratio), 0, 0, C.byref(o)))
+            return self._outlier_dict(o)
+        n = self.size(slot)
+        avg = np.empty(n, np.float64)
+        keep = np.empty(n, np.uint8)
+        self._ck(self._L.me_statistical_outlier(self._ctx, slot, int(nb_neighbors), float(std_ratio), _addr(avg), _addr(keep), C.byref(o)))
+        return self._outlier_dict(o), avg, keep
+
+    def radius_outlier(self, slot: int, nb_points: int, radius: float, fetch: bool = False):
+        """The radius filter's mask on the slot; returns the info dict, and with fetch=True also (counts, keep) in cloud order."""
+        o = _lib.OutlierInfo()
+        if not fetch:
+            self._ck(self._L.me_radius_outlier(self._ctx, slot, int(nb_points), float(radius), 0, 0, C.byref(o)))
+            return self._outlier_dict(o)
+        n = self.size(slot)
+        counts = np.empty(n, np.int32)
+        keep = np.empty(n, np.uint8)
+        self._ck(self._L.me_radius_outlier(self._ctx, slot, int(nb_points), float(radius), _addr(counts), _addr(keep), C.byref(o)))
+        return self._outlier_dict(o), counts, keep
+
+    def select_kept_into(self, src_slot: int, dst: "Engine | None" = None, dst_slot: int | None = None) -> int:
+        """The kept points of the slot's last mask into dst's dst_slot (default: this engine, the same slot — in place)."""
+        dst = self if dst is None else dst
+        dst_slot = src_slot if dst_slot is None else dst_slot
+        n = C.c_int64(0)
+        rc = self._L.me_outlier_select_into(self._ctx, int(src_slot), dst._ctx, int(dst_slot), C.byref(n))
+        dst._ck(rc)  # (the library reports on dst_ctx)
+        dst._held.pop(int(dst_slot), None)
+        return int(n.value)
+
+    def remove_statistical_outlier(self, slot: int, nb_neighbors: int = 20, std_ratio: float = 2.0):
+        """Open3D's remove_statistical_outlier, in place: returns (n_kept, info)."""
+        info = self.statistical_outlier(slot, nb_neighbors, std_ratio)
+        return self.select_kept_into(slot), info
+
+    def remove_radius_outlier(self, slot: int, nb_points: int, radius: float):
+        """Open3D's remove_radius_outlier, in place: returns (n_kept, info)."""
+        info = self.radius_outlier(slot, nb_points, radius)
+        return self.select_kept_into(slot), info
 
     def size(self, slot: int) -> int:
         return int(self._L.me_cloud_size(self._ctx, slot))

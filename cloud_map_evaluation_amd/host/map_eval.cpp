@@ -200,6 +200,34 @@ Param loadParametersFromYAML(const std::string &yaml_file_path) {
     if (!(param.global_edge_ratio > 0 && param.global_edge_ratio <= 1)) throw std::runtime_error("global_edge_ratio: must lie in (0, 1]");
     if (param.global_max_nn < 1 || param.global_max_nn > 40) throw std::runtime_error("global_max_nn: must lie in 1..40");
     if (param.global_normal_knn < 1 || param.global_normal_knn > 40) throw std::runtime_error("global_normal_knn: must lie in 1..40");
+    if (config.has("global_outlier_nb_neighbors")) param.global_outlier_nb_neighbors = config.as_int("global_outlier_nb_neighbors");
+    if (config.has("global_outlier_std_ratio")) param.global_outlier_std_ratio = config.as_double("global_outlier_std_ratio");
+    if (param.global_outlier_nb_neighbors < 0 || param.global_outlier_nb_neighbors > 40)
+        throw std::runtime_error("global_outlier_nb_neighbors: must lie in 0..40 (0 = off)");
+    if (!(param.global_outlier_std_ratio > 0)) throw std::runtime_error("global_outlier_std_ratio: must be > 0");
+    // outlier removal in front of the evaluation (no reference counterpart)
+    if (config.has("remove_outliers")) param.remove_outliers = config.as_string("remove_outliers");
+    if (param.remove_outliers != "none" && param.remove_outliers != "statistical" && param.remove_outliers != "radius")
+        throw std::runtime_error("remove_outliers: expected none, statistical or radius, got '" + param.remove_outliers + "'");
+    if (config.has("outlier_nb_neighbors")) param.outlier_nb_neighbors = config.as_int("outlier_nb_neighbors");
+    if (config.has("outlier_std_ratio")) param.outlier_std_ratio = config.as_double("outlier_std_ratio");
+    if (config.has("outlier_nb_points")) param.outlier_nb_points = config.as_int("outlier_nb_points");
+    if (config.has("outlier_radius")) param.outlier_radius = config.as_double("outlier_radius");
+    if (config.has("outlier_filter_gt")) param.outlier_filter_gt = config.as_bool("outlier_filter_gt");
+    if (param.outlier_nb_neighbors < 1 || param.outlier_nb_neighbors > 40) throw std::runtime_error("outlier_nb_neighbors: must lie in 1..40");
+    if (!(param.outlier_std_ratio > 0)) throw std::runtime_error("outlier_std_ratio: must be > 0");
+    if (param.remove_outliers == "radius") {
+        if (!config.has("outlier_nb_points") || param.outlier_nb_points < 0)
+            throw std::runtime_error("outlier_nb_points: remove_outliers: radius needs it, >= 0");
+        if (!config.has("outlier_radius") || !(param.outlier_radius > 0))
+            throw std::runtime_error("outlier_radius: remove_outliers: radius needs it, > 0");
+    }
+    if (param.remove_outliers != "none") {
+        if (param.num_gpus > 1)
+            throw std::runtime_error("remove_outliers: single GPU only for now (num_gpus must be 1; the multi-GPU path is out of scope)");
+        if (param.evaluate_noised_gt_)
+            throw std::runtime_error("remove_outliers: not with evaluate_noised_gt for now (the simulated map is out of scope)");
+    }
     return param;
 }
 
@@ -233,7 +261,11 @@ std::string paramToJson(const Param &p) {
       << ", \"global_normal_knn\": " << p.global_normal_knn << ", \"global_max_corr_dist\": " << p.global_max_corr_dist
       << ", \"global_max_iterations\": " << p.global_max_iterations << ", \"global_edge_ratio\": " << p.global_edge_ratio
       << ", \"global_mutual_filter\": " << b(p.global_mutual_filter) << ", \"global_seed\": " << p.global_seed
-      << ", \"global_min_fitness\": " << p.global_min_fitness << "}";
+      << ", \"global_min_fitness\": " << p.global_min_fitness << ", \"global_outlier_nb_neighbors\": " << p.global_outlier_nb_neighbors
+      << ", \"global_outlier_std_ratio\": " << p.global_outlier_std_ratio << ", \"remove_outliers\": \"" << p.remove_outliers
+      << "\", \"outlier_nb_neighbors\": " << p.outlier_nb_neighbors << ", \"outlier_std_ratio\": " << p.outlier_std_ratio
+      << ", \"outlier_nb_points\": " << p.outlier_nb_points << ", \"outlier_radius\": " << p.outlier_radius
+      << ", \"outlier_filter_gt\": " << b(p.outlier_filter_gt) << "}";
     return o.str();
 }
 
@@ -309,7 +341,9 @@ int MapEval::process() {
     // starts from the host clouds as they were read — the uploads are part of the call's two-lane schedule.
     const bool one_call = param_.evaluate_using_initial_ && !comm_;
     if (noised && comm_) return fail("evaluate_noised_gt: single GPU only (the multi-GPU path reads both maps from disk)");
-    if (one_call && !noised && !(param_.downsample_size > 0)) {
+    const bool filter = param_.remove_outliers != "none";  // (the filter runs on resident clouds: the uploads below, not the one call's)
+    if (filter && (noised || comm_)) return fail("remove_outliers: single GPU only, and not with evaluate_noised_gt, for now");
+    if (one_call && !noised && !filter && !(param_.downsample_size > 0)) {
         file_result << std::fixed << std::setprecision(15) << "Estimated-Ground Truth point count: " << map_3d_->size() << " / "
                     << gt_3d_->size() << std::endl;
         if (param_.enable_debug)
@@ -339,6 +373,7 @@ int MapEval::process() {
             me_download_cloud(ctx_, ME_SLOT_GT, gt_3d_->points_.data()) != ME_OK)
             return fail(me_last_error(ctx_));
     }
+    if (filter && removeOutliers() != 0) return -1;  // (right after the down-sample, before everything else)
     if (noised) {  // map_3d_ = the perturbed ground truth (map_eval.cpp:1745-1829); the host copy is what the writers read
         const me_perturb_params pp = perturbParams(param_.noise_std_dev_);
         int64_t ne = 0;
@@ -1082,6 +1117,43 @@ me_perturb_params MapEval::perturbParams(double noise_std) const {
     return pp;
 }
 
+// outlier_removal.txt (remove_outliers: statistical | radius; no reference counterpart): the map, and with outlier_filter_gt the ground
+// truth, filtered in place on the device (me_statistical_outlier / me_radius_outlier + me_outlier_select_into); the host copies take the
+// kept points, so every writer sees the filtered clouds.  The file: the method, its parameters ("name value"), then per filtered cloud
+// "<est|gt> n_in n_kept mean std_dev threshold" (radius: mean = std_dev = 0, threshold = nb_points).
+int MapEval::removeOutliers() {
+    const bool sor = param_.remove_outliers == "statistical";
+    std::filesystem::create_directories(results_subfolder);
+    const std::string path = results_subfolder + "outlier_removal.txt";
+    FILE *f = std::fopen(path.c_str(), "w");
+    if (!f) return fail("cannot write " + path);
+    std::fprintf(f, "method %s\n", param_.remove_outliers.c_str());
+    if (sor) std::fprintf(f, "nb_neighbors %d\nstd_ratio %.17g\n", param_.outlier_nb_neighbors, param_.outlier_std_ratio);
+    else std::fprintf(f, "nb_points %d\nradius %.17g\n", param_.outlier_nb_points, param_.outlier_radius);
+    std::fprintf(f, "filter_gt %s\n", param_.outlier_filter_gt ? "true" : "false");
+    for (int s : {ME_SLOT_EST, ME_SLOT_GT}) {
+        if (s == ME_SLOT_GT && !param_.outlier_filter_gt) break;
+        me_outlier_info info{};
+        const int rc = sor ? me_statistical_outlier(ctx_, s, param_.outlier_nb_neighbors, param_.outlier_std_ratio, nullptr, nullptr, &info)
+                           : me_radius_outlier(ctx_, s, param_.outlier_nb_points, param_.outlier_radius, nullptr, nullptr, &info);
+        int64_t n = 0;
+        if (rc != ME_OK || me_outlier_select_into(ctx_, s, ctx_, s, &n) != ME_OK) {
+            std::fclose(f);
+            return fail(std::string("remove_outliers: ") + me_last_error(ctx_));
+        }
+        PointCloud &pc = s == ME_SLOT_EST ? *map_3d_ : *gt_3d_;
+        pc.points_.resize((size_t) n * 3);
+        if (me_download_cloud(ctx_, s, pc.points_.data()) != ME_OK) {
+            std::fclose(f);
+            return fail(me_last_error(ctx_));
+        }
+        std::fprintf(f, "%s %lld %lld %.17g %.17g %.17g\n", s == ME_SLOT_EST ? "est" : "gt", (long long) info.n_in, (long long) info.n_kept,
+                     info.mean, info.std_dev, info.threshold);
+    }
+    if (std::fclose(f) != 0) return fail("writing " + path + " failed");
+    return 0;
+}
+
 // global_registration.txt (global_registration: true; no reference counterpart): the initial pose found on the device.  Coarse copies of
 // the map as loaded and of the ground truth are made in a second context (me_voxel_downsample_into), the coarse map is moved by
 // initial_matrix, and me_global_register gives T_c (coarse map -> ground truth).  The file holds T_c (four rows, %.17g), then fitness,
@@ -1094,9 +1166,19 @@ int MapEval::globalRegistration(double T_c[16]) {
         ~Destroy() { me_destroy(c); }
     } d{co};
     int64_t n = 0;
-    if (me_voxel_downsample_into(ctx_, ME_SLOT_EST, co, ME_SLOT_EST, param_.global_voxel_size, &n) != ME_OK ||
-        me_voxel_downsample_into(ctx_, ME_SLOT_GT, co, ME_SLOT_GT, param_.global_voxel_size, &n) != ME_OK)
+    me_outlier_info oinfo[2]{};
+    const int k_out = param_.global_outlier_nb_neighbors;
+    if (k_out > 0) {  // SOR on the full-resolution clouds; the kept points go to the second context, which down-samples them in place
+        for (int s : {ME_SLOT_EST, ME_SLOT_GT}) {
+            if (me_statistical_outlier(ctx_, s, k_out, param_.global_outlier_std_ratio, nullptr, nullptr, &oinfo[s]) != ME_OK)
+                return fail(std::string("global_registration: ") + me_last_error(ctx_));
+            if (me_outlier_select_into(ctx_, s, co, s, &n) != ME_OK || me_voxel_downsample(co, s, param_.global_voxel_size, &n) != ME_OK)
+                return fail(std::string("global_registration: ") + me_last_error(co));
+        }
+    } else if (me_voxel_downsample_into(ctx_, ME_SLOT_EST, co, ME_SLOT_EST, param_.global_voxel_size, &n) != ME_OK ||
+               me_voxel_downsample_into(ctx_, ME_SLOT_GT, co, ME_SLOT_GT, param_.global_voxel_size, &n) != ME_OK) {
         return fail(std::string("global_registration: ") + me_last_error(co));
+    }
     bool identity = true;
     for (int i = 0; i < 16; ++i) identity = identity && (param_.initial_matrix_[i] == ((i % 5 == 0) ? 1.0 : 0.0));
     if (!identity && me_transform_cloud(co, ME_SLOT_EST, param_.initial_matrix_.data()) != ME_OK)
@@ -1122,6 +1204,13 @@ int MapEval::globalRegistration(double T_c[16]) {
         std::fprintf(f, "%.17g %.17g %.17g %.17g\n", T_c[4 * r], T_c[4 * r + 1], T_c[4 * r + 2], T_c[4 * r + 3]);
     std::fprintf(f, "fitness %.17g\ninlier_rmse %.17g\ncorrespondences %lld\nvalid_hypotheses %lld\nseed %llu\n", info.fitness,
                  info.inlier_rmse, (long long) info.n_corr, (long long) info.n_valid_hypotheses, (unsigned long long) param_.global_seed);
+    if (k_out > 0) {  // the filter's lines: only when it ran
+        std::fprintf(f, "outlier_nb_neighbors %d\noutlier_std_ratio %.17g\n", k_out, param_.global_outlier_std_ratio);
+        const char *name[2] = {"outlier_est", "outlier_gt"};
+        for (int s = 0; s < 2; ++s)
+            std::fprintf(f, "%s %lld %lld %.17g %.17g %.17g\n", name[s], (long long) oinfo[s].n_in, (long long) oinfo[s].n_kept,
+                         oinfo[s].mean, oinfo[s].std_dev, oinfo[s].threshold);
+    }
     if (std::fclose(f) != 0) return fail("writing " + path + " failed");
     if (info.fitness < param_.global_min_fitness) {
         std::ostringstream m;

@@ -76,6 +76,17 @@ struct Param {
     bool global_mutual_filter = true;      // `global_mutual_filter:`
     uint64_t global_seed = 0;              // `global_seed:` Philox seed
     double global_min_fitness = 0.0;       // `global_min_fitness:` below this fitness of T_c the run fails
+    int global_outlier_nb_neighbors = 0;   // `global_outlier_nb_neighbors:` > 0: statistical outlier removal (this k) on full-resolution
+                                           // copies of both clouds before global_voxel_size (me_statistical_outlier)
+    double global_outlier_std_ratio = 2.0; // `global_outlier_std_ratio:`
+    // outlier removal in front of the evaluation (remove_outliers: statistical | radius; no reference counterpart): the map, and with
+    // outlier_filter_gt the ground truth, filtered in place on the device after downsample_size -> map_results/outlier_removal.txt
+    std::string remove_outliers = "none";  // `remove_outliers:` none | statistical | radius
+    int outlier_nb_neighbors = 20;         // `outlier_nb_neighbors:` statistical: k, 1..40
+    double outlier_std_ratio = 2.0;        // `outlier_std_ratio:`
+    int outlier_nb_points = -1;            // `outlier_nb_points:` radius: keep points with more than this many within the radius (required)
+    double outlier_radius = 0.0;           // `outlier_radius:` radius (required)
+    bool outlier_filter_gt = false;        // `outlier_filter_gt:` filter the ground truth as well
     int dist_rank = 0;              // (set by the launcher, not a YAML key)
     void printParam() const;
 };
@@ -106,6 +117,7 @@ public:
     void saveVoxelMetrics(int gate_mode);                  // voxel_metrics.txt (save_voxel_metrics; no reference counterpart)
     me_perturb_params perturbParams(double noise_std) const;  // the noise_* keys as me_perturb_cloud's parameters
     int runNoiseSweep();
+    int removeOutliers();                                   // outlier_removal.txt (remove_outliers; no reference counterpart)
     int globalRegistration(double T_c[16]);                 // global_registration.txt (global_registration; no reference counterpart)                                   // noise_sweep.txt (noise_sweep; no reference counterpart)
 
     // multi-GPU (map_eval_dist.cpp): the communicator of this rank; forced = take the distributed path with one rank too

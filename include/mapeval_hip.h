@@ -354,6 +354,38 @@ typedef struct me_globreg_info {
 int me_global_register(me_ctx *ctx, int src_slot, int ref_slot, const me_globreg_params *p, double T_out[16], me_globreg_info *info,
                        int64_t *scores);
 
+/* ---- outlier removal: Open3D 0.15's PointCloud::RemoveStatisticalOutlier / RemoveRadiusOutlier on a resident cloud -------------- */
+/* (DESIGN.md section 4.8).  Single GPU only: slab or shard mode is ME_ERR_ARG.  Every per-point host output (N entries, nullable)
+ * is in the slot's cloud order, the order of me_download_cloud.  Each call leaves a uint8 keep-mask on the slot, held until the
+ * cloud changes (upload, down-sample, transform, perturbation, selection); me_outlier_select_into applies it.
+ *
+ * me_statistical_outlier (k = nb_neighbors in [1, 40], std_ratio > 0, else ME_ERR_ARG): the neighbours of point i are its k nearest
+ * points of the same cloud, itself included (at d2 = 0), all n points when n < k; d2 = ((dx*dx + dy*dy) + dz*dz) in fp64.  Ties at
+ * the k-th distance need no rule: only the multiset of the k smallest d2 is used.  avg_dist[i] = the sum of sqrt(d2_j) in ascending d2
+ * order, starting from 0, divided by the neighbour count.  mean = (sum of avg_i > 0) / n — Open3D divides by every point —,
+ * std_dev = sqrt(sum over avg_i > 0 of (avg_i - mean)^2 / (n - 1)), threshold = mean + std_ratio std_dev; both sums in a fixed
+ * order (bit-identical from run to run).  keep[i] = avg_i > 0 && avg_i < threshold.  So k = 1 keeps nothing, nor does n = 1 (the
+ * threshold is NaN), and a point whose neighbours all coincide with it is dropped.  info->n_fallback = the points the exact
+ * octree walk settled (the grid pass could not).  Device timer "outlier".
+ *
+ * me_radius_outlier (nb_points >= 0, radius > 0): counts[i] = the points j with d2 < radius^2 (strict, the library's radius
+ * convention), i itself included; keep[i] = counts[i] > nb_points.  The slot's radius grid is rebuilt at the radius when its cell
+ * differs, as me_mme does.  info: mean = std_dev = 0, threshold = nb_points, n_fallback = 0.  Device timer "outlier".
+ *
+ * me_outlier_select_into: the points of src_slot whose mask entry is 1, in cloud order, written into dst_ctx's dst_slot — in place
+ * when (dst_ctx, dst_slot) is (src_ctx, src_slot); otherwise src is untouched and dst_ctx (same device) waits for src_ctx's pending
+ * work.  Normals travel with their points; covariances, FPFH features, NN and MME results of dst are dropped and its index is
+ * rebuilt (src's cell size), as after me_voxel_downsample.  ME_ERR_STATE: src has no mask, or the mask keeps no point.  *n_out = the
+ * points kept.  Device timer "outlier_select" of dst_ctx. */
+typedef struct me_outlier_info {
+    int64_t n_in, n_kept, n_fallback;
+    double mean, std_dev, threshold; /* statistical as defined above; radius: 0, 0, nb_points */
+} me_outlier_info;
+int me_statistical_outlier(me_ctx *ctx, int slot, int nb_neighbors, double std_ratio, double *avg_dist, uint8_t *keep,
+                           me_outlier_info *info);
+int me_radius_outlier(me_ctx *ctx, int slot, int nb_points, double radius, int32_t *counts, uint8_t *keep, me_outlier_info *info);
+int me_outlier_select_into(me_ctx *src_ctx, int src_slot, me_ctx *dst_ctx, int dst_slot, int64_t *n_out);
+
 int64_t me_cloud_size(me_ctx *ctx, int slot);
 /* transformed points back to the host (N x 3), original order — what map_3d_->points_ holds after :1206 */
 int me_download_cloud(me_ctx *ctx, int slot, double *xyz_host);
