@@ -367,8 +367,9 @@ def hypothesis(cs: np.ndarray, cq: np.ndarray, k, eps: float, edge_ratio: float)
     return True, T
 
 
-def ransac_scores(cs, cq, seed: int, n_hyp: int, eps: float, edge_ratio: float = 0.9):
-    """scores [n_hyp] (-1 = invalid) and the fitted T of every valid hypothesis (dict h -> [3, 4])."""
+def ransac_scores_scalar(cs, cq, seed: int, n_hyp: int, eps: float, edge_ratio: float = 0.9):
+    """scores [n_hyp] (-1 = invalid) and the fitted T of every valid hypothesis (dict h -> [3, 4]): hypothesis() on every h in turn
+    (the check of ransac_scores() below)."""
     cs, cq = np.asarray(cs, np.float64), np.asarray(cq, np.float64)
     ks = samples(seed, np.arange(n_hyp), len(cs))
     scores = np.full(n_hyp, -1, np.int64)
@@ -379,3 +380,108 @@ def ransac_scores(cs, cq, seed: int, n_hyp: int, eps: float, edge_ratio: float =
             scores[h] = int(np.count_nonzero(moved_d2(T, cs, cq) < eps * eps))
             fits[h] = T
     return scores, fits
+
+
+def _edge_len(a, b):
+    dx, dy, dz = a[..., 0] - b[..., 0], a[..., 1] - b[..., 1], a[..., 2] - b[..., 2]
+    return np.sqrt((dx * dx + dy * dy) + dz * dz)
+
+
+def sample_checks(cs, cq, ks, edge_ratio: float):
+    """The checks of hypotheses with samples ks [m, 3] that come before the fit, for all of them at once (the same operations as
+    hypothesis(), element by element): (coincide [m], passes [m]) — two samples coincide; distinct samples, every edge inside the
+    two-sided length check and a non-degenerate source triangle."""
+    cs, cq, ks = np.asarray(cs, np.float64), np.asarray(cq, np.float64), np.asarray(ks, np.int64).reshape(-1, 3)
+    coincide = (ks[:, 0] == ks[:, 1]) | (ks[:, 0] == ks[:, 2]) | (ks[:, 1] == ks[:, 2])
+    p, q = cs[ks], cq[ks]  # [m, 3 samples, 3]
+    ok = ~coincide
+    for a in range(3):
+        for b in range(a + 1, 3):
+            ds, dt = _edge_len(p[:, a], p[:, b]), _edge_len(q[:, a], q[:, b])
+            ok &= ~((ds < dt * edge_ratio) | (dt < ds * edge_ratio))
+    e1, e2 = p[:, 1] - p[:, 0], p[:, 2] - p[:, 0]
+    cr = _cross(e1, e2)
+    ok &= ~(_dot(cr, cr) <= (1e-12 * _dot(e1, e1)) * _dot(e2, e2))
+    return coincide, ok
+
+
+def ransac_scores(cs, cq, seed: int, n_hyp: int, eps: float, edge_ratio: float = 0.9, hyps=None, score: bool = True):
+    """scores (-1 = invalid) and the fitted T of every valid hypothesis (dict h -> [3, 4]).  Without hyps: hypotheses 0 .. n_hyp - 1,
+    scores[h].  With hyps (any hypothesis numbers, each a pure function of (seed, h)): scores[t] belongs to hyps[t]; n_hyp is not
+    used.  The checks before the fit run on all hypotheses at once (sample_checks) and only those that pass are fitted, one by one,
+    by horn_fit3.  score = False: the validity alone, 0 in place of the inlier count."""
+    cs, cq = np.asarray(cs, np.float64), np.asarray(cq, np.float64)
+    hyps = np.arange(n_hyp, dtype=np.int64) if hyps is None else np.asarray(hyps, np.int64).reshape(-1)
+    ks = samples(seed, hyps, len(cs)).reshape(-1, 3)
+    _, passes = sample_checks(cs, cq, ks, edge_ratio)
+    scores = np.full(len(hyps), -1, np.int64)
+    fits = {}
+    for t in np.flatnonzero(passes):
+        p, q = cs[ks[t]], cq[ks[t]]
+        T = horn_fit3(p, q)
+        if np.any(moved_d2(T, p, q) > eps * eps):
+            continue
+        scores[t] = int(np.count_nonzero(moved_d2(T, cs, cq) < eps * eps)) if score else 0
+        fits[int(hyps[t])] = T
+    return scores, fits
+
+
+# ---- inputs of the edge tests (test_gpu_globreg_edges.py; what they are meant to exercise is checked on the model in test_globreg_cpu.py)
+def unit_normals(n: int, seed: int) -> np.ndarray:
+    """n random unit vectors."""
+    v = np.random.default_rng(seed).normal(size=(n, 3))
+    return v / np.linalg.norm(v, axis=1)[:, None]
+
+
+def three_planes(n_per: int = 1000, side: float = 17.0, seed: int = 1, noise: float = 0.02) -> np.ndarray:
+    """Three noisy orthogonal planes (x = 0, y = 0, z = 0), n_per points on side x side each, coordinates rounded to 2^-8: sums and
+    differences of such coordinates (and of shifts by integers) are exact in fp64.  About 3.5 points / m^2 by default."""
+    rng = np.random.default_rng(seed)
+    parts = []
+    for axis in range(3):
+        p = rng.uniform(0.0, side, (n_per, 3))
+        p[:, axis] = rng.normal(scale=noise, size=n_per)
+        parts.append(p)
+    return np.round(np.concatenate(parts) * 256.0) / 256.0
+
+
+def tripled_cloud(n: int = 200, seed: int = 2):
+    """n points on a noisy 4 m x 4 m patch, each three times in a row (np.repeat: copies are adjacent in index), and unit normals that
+    are the same for the copies of a point."""
+    rng = np.random.default_rng(seed)
+    p = np.column_stack([rng.uniform(0, 4, n), rng.uniform(0, 4, n), rng.normal(scale=0.05, size=n)])
+    return np.repeat(p, 3, axis=0), np.repeat(unit_normals(n, seed + 1), 3, axis=0)
+
+
+def lattice_cloud(nx: int = 12, ny: int = 12, nz: int = 2) -> np.ndarray:
+    """The integer lattice nx x ny x nz: squared distances are small integers, so d2 == radius^2 occurs exactly."""
+    g = np.stack(np.meshgrid(np.arange(nx), np.arange(ny), np.arange(nz), indexing="ij"), axis=-1)
+    return g.reshape(-1, 3).astype(np.float64)
+
+
+def rotation(yaw: float, roll: float = 0.0, pitch: float = 0.0) -> np.ndarray:
+    cz, sz, cx, sx, cy, sy = math.cos(yaw), math.sin(yaw), math.cos(roll), math.sin(roll), math.cos(pitch), math.sin(pitch)
+    Rz = np.array([[cz, -sz, 0], [sz, cz, 0], [0, 0, 1]])
+    Rx = np.array([[1, 0, 0], [0, cx, -sx], [0, sx, cx]])
+    Ry = np.array([[cy, 0, sy], [0, 1, 0], [-sy, 0, cy]])
+    return Rz @ Ry @ Rx
+
+
+def moved_points(T, s) -> np.ndarray:
+    """The points s [n, 3] moved by T ([3, 4] or [4, 4]) in the library's order: ((T_r0 x + T_r1 y) + T_r2 z) + T_r3."""
+    return np.stack([((T[r, 0] * s[:, 0] + T[r, 1] * s[:, 1]) + T[r, 2] * s[:, 2]) + T[r, 3] for r in range(3)], axis=1)
+
+
+def ransac_pair(n_extra: int = 3000, noise: float = 0.06, seed: int = 11):
+    """(src, src normals, ref, ref normals, R0, t0): the reference is three planes plus an unrelated cluster 100 m away; the source is
+    a noisy copy of the three planes plus another unrelated cluster, moved by (R0, t0).  The clusters only yield wrong feature matches,
+    so that most RANSAC samples fail one of the checks."""
+    rng = np.random.default_rng(seed + 2)
+    a, na = three_planes(seed=seed), unit_normals(3000, seed + 1)
+    side, shift = 17.0 * math.sqrt(n_extra / 1000.0), np.array([100.0, 0.0, 0.0])
+    ref = np.concatenate([a, three_planes(n_extra, side, seed + 3) + shift])
+    nr = np.concatenate([na, unit_normals(3 * n_extra, seed + 4)])
+    base = np.concatenate([a + rng.normal(scale=noise, size=a.shape), three_planes(n_extra, side, seed + 5) + shift])
+    nb = np.concatenate([na, unit_normals(3 * n_extra, seed + 6)])
+    R0, t0 = rotation(1.9, 0.03, 0.02), np.array([25.0, 14.0, -2.0])
+    return base @ R0.T + t0, nb @ R0.T, ref, nr, R0, t0

@@ -160,6 +160,7 @@ def test_ransac_scores_and_winner_match_the_model(coarse):
         if best is None or key < best[0]:
             best = (key, h, Th)
     assert info["best_hypothesis"] == best[1]
+    assert info["best_corr_inliers"] == ref_sc[best[1]]
     np.testing.assert_allclose(T[:3, :], best[2], atol=1e-12, rtol=0)
     assert info["fitness"] == pytest.approx(-best[0][0], abs=2.0 / len(src))
 
