@@ -314,6 +314,24 @@ int me_outlier_select_into(me_ctx *src_ctx, int src_slot, me_ctx *dst_ctx, int d
     return rc;
 }
 
+int me_cluster_dbscan(me_ctx *ctx, int slot, double eps, int min_points, int32_t *labels, int32_t *counts, me_cluster_info *info) {
+    if (!ctx) return ME_ERR_ARG;
+    return me::cluster_dbscan(ctx, slot, eps, min_points, labels, counts, info);
+}
+
+int me_cluster_sizes(me_ctx *ctx, int slot, int64_t *sizes, int64_t capacity, int64_t *n_clusters) {
+    if (!ctx) return ME_ERR_ARG;
+    long long m = 0;
+    const int rc = me::cluster_sizes(ctx, slot, sizes, capacity, &m);
+    if (n_clusters && (rc == ME_OK || rc == ME_ERR_CAPACITY)) *n_clusters = m;
+    return rc;
+}
+
+int me_cluster_keep(me_ctx *ctx, int slot, int64_t min_cluster_size, int64_t keep_largest, uint8_t *keep, me_outlier_info *info) {
+    if (!ctx) return ME_ERR_ARG;
+    return me::cluster_keep(ctx, slot, min_cluster_size, keep_largest, keep, info);
+}
+
 int me_transform_cloud(me_ctx *ctx, int slot, const double *T) {
     if (!ctx) return ME_ERR_ARG;
     return me::cloud_transform(ctx, slot, T);

@@ -650,6 +650,7 @@ int cloud_upload(me_ctx *ctx, int slot, const double *src, bool src_on_device, l
         e.vox_valid = e.vox_merged = false;
         e.have_normals = e.have_cov = false;
         e.outlier_keep_valid = false;
+        e.cluster_valid = false;
         ctx->cloud[1 - slot].nn_ref_slot = -1;
         return ME_OK;
     }
@@ -755,6 +756,7 @@ int cloud_finish(me_ctx *ctx, int slot, bool bbox_ready) {
     c.n_vox = 0;
     c.fpfh_valid = false;
     c.outlier_keep_valid = false;  // (the mask belongs to the points it was computed on)
+    c.cluster_valid = false;
     ctx->cloud[1 - slot].nn_ref_slot = -1;
     // bbox
     const unsigned int nb = (unsigned int) std::min<long long>(1024, (n + 255) / 256);
@@ -804,6 +806,7 @@ void cloud_reset_replaced(me_ctx *ctx, int slot, long long n, double cell_size_r
     D.have_normals = D.have_cov = false;
     D.fpfh_valid = false;
     D.outlier_keep_valid = false;
+    D.cluster_valid = false;
     D.slab = ctx->slab;
     D.n_unres = 0;
     D.slab_identity = true;

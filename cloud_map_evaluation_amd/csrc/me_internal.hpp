@@ -227,6 +227,10 @@ struct Cloud {
     // keep-mask of the last me_statistical_outlier / me_radius_outlier, uint8[n] in cloud order (me_outlier.hip); dropped with the points
     DevBuf outlier_keep;
     bool outlier_keep_valid = false;
+    // labels (int32[n], cloud order) and cluster sizes (uint64[cluster_n]) of the last me_cluster_dbscan (me_cluster.hip); dropped with the points
+    DevBuf cluster_labels, cluster_sizes;
+    long long cluster_n = 0;
+    bool cluster_valid = false;
 };
 
 struct TimerRec {
@@ -301,6 +305,7 @@ struct me_ctx {
     me::DevBuf mme_keep_e, mme_keep_v;           // me_run_suite_from: the map's per-point MME result across its transform (mme_carry_*)
     long long mme_keep_n = -1;
     me::DevBuf outlier_tmp[2];                   // me_outlier.hip: per-point avg_dist / counts and the fallback list, kept for repeated calls
+    me::DevBuf cluster_tmp[5];                   // me_cluster.hip: parent, smallest index per root, the two flag arrays, the border list
     me::DevBuf nn1_dbg_buf;                      // octree-walk counters (nodes opened, leaves scanned, points, max per query)
     unsigned long long *nn1_dbg() {
         if (!nn1_dbg_buf.p) {
@@ -478,6 +483,11 @@ int statistical_outlier(me_ctx *ctx, int slot, int nb_neighbors, double std_rati
                         me_outlier_info *info);
 int radius_outlier(me_ctx *ctx, int slot, int nb_points, double radius, int32_t *counts_host, uint8_t *keep_host, me_outlier_info *info);
 int outlier_select_into(me_ctx *src_ctx, int src_slot, me_ctx *dst_ctx, int dst_slot, long long *n_out);
+int need_outlier_slot(me_ctx *ctx, int slot, const char *who);  // slot in range, single GPU (no slab or shard mode), uploaded
+// ---- me_cluster.hip ----
+int cluster_dbscan(me_ctx *ctx, int slot, double eps, int min_points, int32_t *labels_host, int32_t *counts_host, me_cluster_info *info);
+int cluster_sizes(me_ctx *ctx, int slot, int64_t *sizes_host, long long capacity, long long *n_clusters);
+int cluster_keep(me_ctx *ctx, int slot, long long min_cluster_size, long long keep_largest, uint8_t *keep_host, me_outlier_info *info);
 
 // ---- me_nn.hip ----
 int nn_search(me_ctx *ctx, int qslot, int rslot);

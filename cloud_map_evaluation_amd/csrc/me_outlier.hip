@@ -16,6 +16,7 @@
 #include <utility>
 
 #include "me_internal.hpp"
+#include "me_wave_stream.hpp"
 
 #ifndef ME_TUNE_KNN_MEAN_OCC
 #define ME_TUNE_KNN_MEAN_OCC 1.5  // k_knn_mean: points per occupied cell of the grid level, per neighbour asked for
@@ -73,49 +74,6 @@ struct TopK {
     }
 };
 
-// One wave's sorted queries [i0, i0 + 64) against the cell table g: groups of lanes (wave_group_table, Chebyshev 2 around a leader)
-// stream every run of their box through a wave-private LDS tile ONCE; every lane of the round's group calls f(px, py, pz) on each
-// candidate.  The box of a group holds every lane's own 3x3x3 block.
-struct WaveTile {
-    double x[64], y[64], z[64];
-};
-template <class F>
-__device__ __forceinline__ void wave_stream(bool pending, int cx, int cy, int cz, const SPoint *__restrict__ sp, const GridView &g,
-                                            int lane, int2 *tab, WaveTile *tile, F &&f) {
-    const int cell_lim = 1 << (kMortonBits - g.shift);
-    bool done = !pending;
-    while (__ballot(!done)) {
-        GroupBox bx;
-        int nk = 0;
-        const bool in = wave_group_table<1>(!done, cx, cy, cz, g, cell_lim, lane, tab, bx, &nk);
-        wave_for_each_run<true>(tab, nk, lane, [&](int b, int e, int) {
-            for (int base = b; base < e; base += 64) {
-                const int m = min(64, e - base);  // wave-uniform
-                if (lane < m) {
-                    const SPoint p = sp[base + lane];
-                    tile->x[lane] = p.x;
-                    tile->y[lane] = p.y;
-                    tile->z[lane] = p.z;
-                }
-                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                if (in)
-                    for (int j = 0; j < m; ++j) f(tile->x[j], tile->y[j], tile->z[j]);
-                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                __builtin_amdgcn_wave_barrier();  // the tile is overwritten by the next chunk
-            }
-        });
-        if (in) done = true;
-    }
-}
-
-__device__ __forceinline__ void cell_of(unsigned long long code, int shift, int &cx, int &cy, int &cz) {
-    const unsigned long long c = code >> (3 * shift);
-    cx = (int) compact21(c);
-    cy = (int) compact21(c >> 1);
-    cz = (int) compact21(c >> 2);
-}
-
 // ---- statistical: grid pass ----
 // Settled when the k-th smallest d2 is below the squared distance from the query to the faces of its own 3x3x3 block, less 2^-20
 // of a cell edge (a point outside the block is at least that far: its cell index came from a floor of the same coordinates).
@@ -140,7 +98,7 @@ k_knn_mean(const SPoint *__restrict__ sp, const unsigned long long *__restrict__
     }
     TopK<KC> t;
     t.init(k);
-    wave_stream(active, cx, cy, cz, sp, g, lane, s_tab[w], &s_tile[w], [&](double px, double py, double pz) {
+    wave_stream(active, cx, cy, cz, sp, g, lane, s_tab[w], &s_tile[w], [&](double px, double py, double pz, int, int) {
         const double d = dist2_exact(qx, qy, qz, px, py, pz);
         if (d < t.worst()) t.push(d);
     });
@@ -314,7 +272,7 @@ k_radius_count(const SPoint *__restrict__ sp, const unsigned long long *__restri
         cell_of(codes[i], g.shift, cx, cy, cz);
     }
     int cnt = 0;
-    wave_stream(active, cx, cy, cz, sp, g, lane, s_tab[w], &s_tile[w], [&](double px, double py, double pz) {
+    wave_stream(active, cx, cy, cz, sp, g, lane, s_tab[w], &s_tile[w], [&](double px, double py, double pz, int, int) {
         cnt += dist2_exact(qx, qy, qz, px, py, pz) < r2 ? 1 : 0;
     });
     bool k = false;
@@ -343,15 +301,6 @@ k_keep_gather(const unsigned int *__restrict__ idx, long long m, const double *_
     }
 }
 
-int need_outlier_slot(me_ctx *ctx, int slot, const char *who) {
-    if (slot < 0 || slot > 1) return ctx->fail(ME_ERR_ARG, std::string(who) + ": bad slot");
-    Cloud &c = ctx->cloud[slot];
-    if (ctx->shard_world != 1 || ctx->slab.axis >= 0 || c.slab.axis >= 0)
-        return ctx->fail(ME_ERR_ARG, std::string(who) + ": single GPU only (no slab or shard mode)");
-    if (!c.uploaded) return ctx->fail(ME_ERR_STATE, std::string(who) + ": cloud not uploaded");
-    return ME_OK;
-}
-
 // the finest cell table of the index whose occupied cells hold >= ME_TUNE_KNN_MEAN_OCC x k points on average (the radius grid when
 // none does): its 3x3x3 block then usually holds the k nearest points of a surface point
 const GridView &knn_mean_grid(const Cloud &c, int k) {
@@ -378,6 +327,15 @@ void launch_knn_mean(me_ctx *ctx, const Cloud &c, const GridView &g, int k, doub
 constexpr size_t kAuxHead = 64;
 
 }  // namespace
+
+int need_outlier_slot(me_ctx *ctx, int slot, const char *who) {
+    if (slot < 0 || slot > 1) return ctx->fail(ME_ERR_ARG, std::string(who) + ": bad slot");
+    Cloud &c = ctx->cloud[slot];
+    if (ctx->shard_world != 1 || ctx->slab.axis >= 0 || c.slab.axis >= 0)
+        return ctx->fail(ME_ERR_ARG, std::string(who) + ": single GPU only (no slab or shard mode)");
+    if (!c.uploaded) return ctx->fail(ME_ERR_STATE, std::string(who) + ": cloud not uploaded");
+    return ME_OK;
+}
 
 int statistical_outlier(me_ctx *ctx, int slot, int nb_neighbors, double std_ratio, double *avg_host, uint8_t *keep_host,
                         me_outlier_info *info) {

@@ -248,25 +248,43 @@ class Engine:
         return (T.reshape(4, 4), d, sc) if scores else (T.reshape(4, 4), d)
 
     def coarse_align(self, voxel_size: float, *, src_slot: int = 0, ref_slot: int = 1, radius: float | None = None,
-                     max_corr_dist: float | None = None, outlier_nb_neighbors: int = 0, outlier_std_ratio: float = 2.0, **params):
+                     max_corr_dist: float | None = None, outlier_nb_neighbors: int = 0, outlier_std_ratio: float = 2.0,
+                     cluster_eps: float = 0.0, cluster_min_points: int = 10, cluster_min_size: int = 1, **params):
         """The initial pose: voxel_size down-samples of both resident slots in a private second context on the same device, FPFH
         (radius 5 voxel_size by default), matching and RANSAC (max_corr_dist 1.5 voxel_size by default); returns T (4x4, src -> ref).
         outlier_nb_neighbors > 0: statistical outlier removal (that k, outlier_std_ratio) on the full-resolution clouds first — the
         kept points are copied into the private context and down-sampled there in place (self.last_coarse_outliers: both infos; None
         when the filter is off).  The resident POINTS are not changed: apply T with transform_cloud and run performICPRegistration as
         usual.  With the filter on, the filter's mask replaces any outlier mask the two slots held, and their octrees are built if
-        they were not yet."""
+        they were not yet.
+        cluster_eps > 0: the DBSCAN cluster filter (cluster_eps, cluster_min_points; clusters below cluster_min_size and noise dropped)
+        on the full-resolution copies as well, after the statistical filter when both are on (self.last_coarse_clusters: per cloud the
+        cluster info with n_kept; None when off).  With the cluster filter alone the slots' radius grids are rebuilt at cluster_eps
+        when their cell differs."""
         radius = 5.0 * voxel_size if radius is None else radius
         max_corr_dist = 1.5 * voxel_size if max_corr_dist is None else max_corr_dist
         self.last_coarse_outliers = None
+        self.last_coarse_clusters = None
         with Engine(self.device) as co:
-            if outlier_nb_neighbors > 0:
-                outl = []
+            if outlier_nb_neighbors > 0 or cluster_eps > 0:
+                outl, clus = [], []
                 for s, d in ((src_slot, 0), (ref_slot, 1)):
-                    outl.append(self.statistical_outlier(s, outlier_nb_neighbors, outlier_std_ratio))
-                    self.select_kept_into(s, co, d)
+                    if outlier_nb_neighbors > 0:
+                        outl.append(self.statistical_outlier(s, outlier_nb_neighbors, outlier_std_ratio))
+                        self.select_kept_into(s, co, d)
+                        if cluster_eps > 0:  # (on the private copy: the statistical filter's survivors)
+                            ci = co.cluster_dbscan(d, cluster_eps, cluster_min_points)
+                            ci["n_kept"] = co.cluster_keep(d, cluster_min_size)["n_kept"]
+                            co.select_kept_into(d)
+                            clus.append(ci)
+                    else:
+                        ci = self.cluster_dbscan(s, cluster_eps, cluster_min_points)
+                        ci["n_kept"] = self.cluster_keep(s, cluster_min_size)["n_kept"]
+                        self.select_kept_into(s, co, d)
+                        clus.append(ci)
                     co.voxel_downsample(d, voxel_size)
-                self.last_coarse_outliers = outl
+                self.last_coarse_outliers = outl or None
+                self.last_coarse_clusters = clus or None
             else:
                 self.downsample_into(src_slot, co, 0, voxel_size)
                 self.downsample_into(ref_slot, co, 1, voxel_size)
@@ -322,6 +340,43 @@ class Engine:
     def remove_radius_outlier(self, slot: int, nb_points: int, radius: float):
         """Open3D's remove_radius_outlier, in place: returns (n_kept, info)."""
         info = self.radius_outlier(slot, nb_points, radius)
+        return self.select_kept_into(slot), info
+
+    # ---- clustering (Open3D cluster_dbscan) and the cluster-size filter (me_cluster.hip) ----
+    def cluster_dbscan(self, slot: int, eps: float, min_points: int, fetch: bool = False):
+        """me_cluster_dbscan: labels and cluster sizes stay on the slot until the cloud changes; returns the info dict, and with
+        fetch=True also (labels, counts) in cloud order (-1 = noise; counts include the point itself)."""
+        o = _lib.ClusterInfo()
+        if not fetch:
+            self._ck(self._L.me_cluster_dbscan(self._ctx, int(slot), float(eps), int(min_points), 0, 0, C.byref(o)))
+            return {f: getattr(o, f) for f, _ in o._fields_}
+        n = self.size(slot)
+        labels = np.empty(n, np.int32)
+        counts = np.empty(n, np.int32)
+        self._ck(self._L.me_cluster_dbscan(self._ctx, int(slot), float(eps), int(min_points), _addr(labels), _addr(counts), C.byref(o)))
+        return {f: getattr(o, f) for f, _ in o._fields_}, labels, counts
+
+    def cluster_sizes(self, slot: int) -> np.ndarray:
+        """me_cluster_sizes: points per cluster id (core and border) of the slot's last cluster_dbscan, int64."""
+        m = C.c_int64(0)
+        self._ck(self._L.me_cluster_sizes(self._ctx, int(slot), 0, 0, C.byref(m)))
+        sizes = np.empty(m.value, np.int64)
+        if m.value:
+            self._ck(self._L.me_cluster_sizes(self._ctx, int(slot), _addr(sizes), int(m.value), C.byref(m)))
+        return sizes
+
+    def cluster_keep(self, slot: int, min_cluster_size: int = 1, keep_largest: int = 0, fetch: bool = False):
+        """me_cluster_keep: the slot's keep-mask = the points of clusters with at least min_cluster_size points (and, keep_largest > 0,
+        among the keep_largest largest); noise is dropped.  Returns the info dict, and with fetch=True also the mask (cloud order)."""
+        o = _lib.OutlierInfo()
+        keep = np.empty(self.size(slot), np.uint8) if fetch else None
+        self._ck(self._L.me_cluster_keep(self._ctx, int(slot), int(min_cluster_size), int(keep_largest), _addr(keep), C.byref(o)))
+        return (self._outlier_dict(o), keep) if fetch else self._outlier_dict(o)
+
+    def remove_small_clusters(self, slot: int, eps: float, min_points: int, min_cluster_size: int = 1, keep_largest: int = 0):
+        """DBSCAN + the cluster-size filter, in place: returns (n_kept, info) — info = the cluster info with the filter's n_kept."""
+        info = self.cluster_dbscan(slot, eps, min_points)
+        info["n_kept"] = self.cluster_keep(slot, min_cluster_size, keep_largest)["n_kept"]
         return self.select_kept_into(slot), info
 
     def size(self, slot: int) -> int:

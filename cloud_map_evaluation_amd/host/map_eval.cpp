@@ -207,8 +207,9 @@ Param loadParametersFromYAML(const std::string &yaml_file_path) {
     if (!(param.global_outlier_std_ratio > 0)) throw std::runtime_error("global_outlier_std_ratio: must be > 0");
     // outlier removal in front of the evaluation (no reference counterpart)
     if (config.has("remove_outliers")) param.remove_outliers = config.as_string("remove_outliers");
-    if (param.remove_outliers != "none" && param.remove_outliers != "statistical" && param.remove_outliers != "radius")
-        throw std::runtime_error("remove_outliers: expected none, statistical or radius, got '" + param.remove_outliers + "'");
+    if (param.remove_outliers != "none" && param.remove_outliers != "statistical" && param.remove_outliers != "radius" &&
+        param.remove_outliers != "cluster")
+        throw std::runtime_error("remove_outliers: expected none, statistical, radius or cluster, got '" + param.remove_outliers + "'");
     if (config.has("outlier_nb_neighbors")) param.outlier_nb_neighbors = config.as_int("outlier_nb_neighbors");
     if (config.has("outlier_std_ratio")) param.outlier_std_ratio = config.as_double("outlier_std_ratio");
     if (config.has("outlier_nb_points")) param.outlier_nb_points = config.as_int("outlier_nb_points");
@@ -221,6 +222,17 @@ Param loadParametersFromYAML(const std::string &yaml_file_path) {
             throw std::runtime_error("outlier_nb_points: remove_outliers: radius needs it, >= 0");
         if (!config.has("outlier_radius") || !(param.outlier_radius > 0))
             throw std::runtime_error("outlier_radius: remove_outliers: radius needs it, > 0");
+    }
+    if (config.has("outlier_eps")) param.outlier_eps = config.as_double("outlier_eps");
+    if (config.has("outlier_min_points")) param.outlier_min_points = config.as_int("outlier_min_points");
+    if (config.has("outlier_min_cluster_size")) param.outlier_min_cluster_size = config.as_int("outlier_min_cluster_size");
+    if (config.has("outlier_keep_largest")) param.outlier_keep_largest = config.as_int("outlier_keep_largest");
+    if (param.outlier_min_points < 1) throw std::runtime_error("outlier_min_points: must be >= 1");
+    if (param.outlier_min_cluster_size < 1) throw std::runtime_error("outlier_min_cluster_size: must be >= 1");
+    if (param.outlier_keep_largest < 0) throw std::runtime_error("outlier_keep_largest: must be >= 0 (0 = no limit)");
+    if (param.remove_outliers == "cluster") {
+        if (!config.has("outlier_eps") || !(param.outlier_eps > 0) || !std::isfinite(param.outlier_eps))
+            throw std::runtime_error("outlier_eps: remove_outliers: cluster needs it, > 0");
     }
     if (param.remove_outliers != "none") {
         if (param.num_gpus > 1)
@@ -265,7 +277,9 @@ std::string paramToJson(const Param &p) {
       << ", \"global_outlier_std_ratio\": " << p.global_outlier_std_ratio << ", \"remove_outliers\": \"" << p.remove_outliers
       << "\", \"outlier_nb_neighbors\": " << p.outlier_nb_neighbors << ", \"outlier_std_ratio\": " << p.outlier_std_ratio
       << ", \"outlier_nb_points\": " << p.outlier_nb_points << ", \"outlier_radius\": " << p.outlier_radius
-      << ", \"outlier_filter_gt\": " << b(p.outlier_filter_gt) << "}";
+      << ", \"outlier_filter_gt\": " << b(p.outlier_filter_gt) << ", \"outlier_eps\": " << p.outlier_eps
+      << ", \"outlier_min_points\": " << p.outlier_min_points << ", \"outlier_min_cluster_size\": " << p.outlier_min_cluster_size
+      << ", \"outlier_keep_largest\": " << p.outlier_keep_largest << "}";
     return o.str();
 }
 
@@ -1121,7 +1135,10 @@ me_perturb_params MapEval::perturbParams(double noise_std) const {
 // truth, filtered in place on the device (me_statistical_outlier / me_radius_outlier + me_outlier_select_into); the host copies take the
 // kept points, so every writer sees the filtered clouds.  The file: the method, its parameters ("name value"), then per filtered cloud
 // "<est|gt> n_in n_kept mean std_dev threshold" (radius: mean = std_dev = 0, threshold = nb_points).
+// remove_outliers: cluster (me_cluster_dbscan + me_cluster_keep): "eps", "min_points", "min_cluster_size", "keep_largest", then per
+// filtered cloud "<est|gt> n_in n_clusters n_core n_border n_noise largest kept".
 int MapEval::removeOutliers() {
+    if (param_.remove_outliers == "cluster") return removeSmallClusters();
     const bool sor = param_.remove_outliers == "statistical";
     std::filesystem::create_directories(results_subfolder);
     const std::string path = results_subfolder + "outlier_removal.txt";
@@ -1149,6 +1166,38 @@ int MapEval::removeOutliers() {
         }
         std::fprintf(f, "%s %lld %lld %.17g %.17g %.17g\n", s == ME_SLOT_EST ? "est" : "gt", (long long) info.n_in, (long long) info.n_kept,
                      info.mean, info.std_dev, info.threshold);
+    }
+    if (std::fclose(f) != 0) return fail("writing " + path + " failed");
+    return 0;
+}
+
+int MapEval::removeSmallClusters() {
+    std::filesystem::create_directories(results_subfolder);
+    const std::string path = results_subfolder + "outlier_removal.txt";
+    FILE *f = std::fopen(path.c_str(), "w");
+    if (!f) return fail("cannot write " + path);
+    std::fprintf(f, "method cluster\neps %.17g\nmin_points %d\nmin_cluster_size %d\nkeep_largest %d\n", param_.outlier_eps,
+                 param_.outlier_min_points, param_.outlier_min_cluster_size, param_.outlier_keep_largest);
+    std::fprintf(f, "filter_gt %s\n", param_.outlier_filter_gt ? "true" : "false");
+    for (int s : {ME_SLOT_EST, ME_SLOT_GT}) {
+        if (s == ME_SLOT_GT && !param_.outlier_filter_gt) break;
+        me_cluster_info ci{};
+        me_outlier_info info{};
+        int64_t n = 0;
+        if (me_cluster_dbscan(ctx_, s, param_.outlier_eps, param_.outlier_min_points, nullptr, nullptr, &ci) != ME_OK ||
+            me_cluster_keep(ctx_, s, param_.outlier_min_cluster_size, param_.outlier_keep_largest, nullptr, &info) != ME_OK ||
+            me_outlier_select_into(ctx_, s, ctx_, s, &n) != ME_OK) {
+            std::fclose(f);
+            return fail(std::string("remove_outliers: ") + me_last_error(ctx_));
+        }
+        PointCloud &pc = s == ME_SLOT_EST ? *map_3d_ : *gt_3d_;
+        pc.points_.resize((size_t) n * 3);
+        if (me_download_cloud(ctx_, s, pc.points_.data()) != ME_OK) {
+            std::fclose(f);
+            return fail(me_last_error(ctx_));
+        }
+        std::fprintf(f, "%s %lld %lld %lld %lld %lld %lld %lld\n", s == ME_SLOT_EST ? "est" : "gt", (long long) ci.n_in, (long long) ci.n_clusters,
+                     (long long) ci.n_core, (long long) ci.n_border, (long long) ci.n_noise, (long long) ci.largest, (long long) info.n_kept);
     }
     if (std::fclose(f) != 0) return fail("writing " + path + " failed");
     return 0;

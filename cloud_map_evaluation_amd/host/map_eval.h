@@ -81,12 +81,16 @@ struct Param {
     double global_outlier_std_ratio = 2.0; // `global_outlier_std_ratio:`
     // outlier removal in front of the evaluation (remove_outliers: statistical | radius; no reference counterpart): the map, and with
     // outlier_filter_gt the ground truth, filtered in place on the device after downsample_size -> map_results/outlier_removal.txt
-    std::string remove_outliers = "none";  // `remove_outliers:` none | statistical | radius
+    std::string remove_outliers = "none";  // `remove_outliers:` none | statistical | radius | cluster
     int outlier_nb_neighbors = 20;         // `outlier_nb_neighbors:` statistical: k, 1..40
     double outlier_std_ratio = 2.0;        // `outlier_std_ratio:`
     int outlier_nb_points = -1;            // `outlier_nb_points:` radius: keep points with more than this many within the radius (required)
     double outlier_radius = 0.0;           // `outlier_radius:` radius (required)
     bool outlier_filter_gt = false;        // `outlier_filter_gt:` filter the ground truth as well
+    double outlier_eps = 0.0;              // `outlier_eps:` cluster: DBSCAN eps (required, > 0)
+    int outlier_min_points = 10;           // `outlier_min_points:` cluster: DBSCAN min_points, >= 1
+    int outlier_min_cluster_size = 1;      // `outlier_min_cluster_size:` cluster: clusters below this size are dropped (noise always is)
+    int outlier_keep_largest = 0;          // `outlier_keep_largest:` cluster: > 0 keeps only that many of the largest clusters
     int dist_rank = 0;              // (set by the launcher, not a YAML key)
     void printParam() const;
 };
@@ -118,6 +122,7 @@ public:
     me_perturb_params perturbParams(double noise_std) const;  // the noise_* keys as me_perturb_cloud's parameters
     int runNoiseSweep();
     int removeOutliers();                                   // outlier_removal.txt (remove_outliers; no reference counterpart)
+    int removeSmallClusters();                              // ... remove_outliers: cluster
     int globalRegistration(double T_c[16]);                 // global_registration.txt (global_registration; no reference counterpart)                                   // noise_sweep.txt (noise_sweep; no reference counterpart)
 
     // multi-GPU (map_eval_dist.cpp): the communicator of this rank; forced = take the distributed path with one rank too

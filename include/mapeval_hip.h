@@ -386,6 +386,37 @@ int me_statistical_outlier(me_ctx *ctx, int slot, int nb_neighbors, double std_r
 int me_radius_outlier(me_ctx *ctx, int slot, int nb_points, double radius, int32_t *counts, uint8_t *keep, me_outlier_info *info);
 int me_outlier_select_into(me_ctx *src_ctx, int src_slot, me_ctx *dst_ctx, int dst_slot, int64_t *n_out);
 
+/* ---- clustering: Open3D 0.15's PointCloud::ClusterDBSCAN on a resident cloud, and a cluster-size filter ------------------------ */
+/* (DESIGN.md section 4.9).  Single GPU only: slab or shard mode is ME_ERR_ARG.  Every per-point host output (N entries, nullable)
+ * is in the slot's cloud order, the order of me_download_cloud.  Labels and sizes stay with the slot until the cloud changes (upload,
+ * down-sample, transform, perturbation, selection).  The slot's radius grid is rebuilt at eps when its cell differs, as
+ * me_radius_outlier does.  Device timer "cluster".
+ *
+ * me_cluster_dbscan (eps > 0 finite, min_points >= 1, else ME_ERR_ARG).  The result is a function of the cloud alone:
+ *   1. d2 = ((dx*dx + dy*dy) + dz*dz) in fp64, no FMA.  j is a neighbour of i iff d2 < eps*eps (strict, the library's radius
+ *      convention).  counts[i] = the number of neighbours of i, i itself included.
+ *   2. i is a core point iff counts[i] >= min_points.
+ *   3. Two core points are in the same cluster iff a chain of core points connects them, consecutive ones being neighbours.
+ *   4. Clusters are numbered 0 .. n_clusters - 1 in ascending order of their smallest core point index (cloud order).
+ *   5. A non-core point with at least one core neighbour is a border point; its label is the smallest cluster id among its core
+ *      neighbours' clusters.
+ *   6. Every other point is noise, label -1.
+ * info: n_core + n_border + n_noise = n_in; largest = the largest cluster's size (0 without clusters).
+ *
+ * me_cluster_sizes: sizes[c] = the points labelled c (core and border), c < *n_clusters.  sizes NULL: only the count.
+ * ME_ERR_CAPACITY: capacity < *n_clusters (the count is still written).  ME_ERR_STATE: no current labels.
+ *
+ * me_cluster_keep (min_cluster_size >= 1, keep_largest >= 0, else ME_ERR_ARG; ME_ERR_STATE without current labels):
+ * keep[i] = label[i] >= 0 && size[label[i]] >= min_cluster_size && (keep_largest == 0 || rank[label[i]] < keep_largest), where rank
+ * orders the clusters by descending size, ties by ascending id.  It writes the slot's outlier keep-mask: me_outlier_select_into
+ * applies it.  info: n_in, n_kept, threshold = min_cluster_size, the other fields 0. */
+typedef struct me_cluster_info {
+    int64_t n_in, n_clusters, n_core, n_border, n_noise, largest;
+} me_cluster_info;
+int me_cluster_dbscan(me_ctx *ctx, int slot, double eps, int min_points, int32_t *labels, int32_t *counts, me_cluster_info *info);
+int me_cluster_sizes(me_ctx *ctx, int slot, int64_t *sizes, int64_t capacity, int64_t *n_clusters);
+int me_cluster_keep(me_ctx *ctx, int slot, int64_t min_cluster_size, int64_t keep_largest, uint8_t *keep, me_outlier_info *info);
+
 int64_t me_cloud_size(me_ctx *ctx, int slot);
 /* transformed points back to the host (N x 3), original order — what map_3d_->points_ holds after :1206 */
 int me_download_cloud(me_ctx *ctx, int slot, double *xyz_host);
