@@ -284,6 +284,26 @@ def test_host_point_to_plane_and_generalized_icp(tmp_path, method):
     np.testing.assert_allclose(vals["FULL CD"][0], oracle.chamfer(ref["cloud"], gt), atol=6e-6)
 
 
+def test_host_point_to_plane_on_a_rank_deficient_plane(tmp_path):
+    """One horizontal plane against itself shifted in-plane, point-to-plane: rows rz, tx, ty of J^T J are exact zeros.  The host's own
+    6x6 solve (Gaussian elimination, a zero pivot leaves the identity) must take the same way out as icp.lsq_update (LAPACK reports
+    the singular factor): the run succeeds, the transformation is the identity, every point is a correspondence."""
+    import _reg_ref as R
+
+    plane = R.plane_lattice(2, 60, 60, 0.25, 0.5)
+    est_dir = tmp_path / "est"
+    est_dir.mkdir()
+    _write_pcd(est_dir / "map.pcd", plane + np.array([0.0625, 0.03125, 0.0]))
+    _write_pcd_normals(tmp_path / "gt.pcd", plane, np.tile([0.0, 0, 1], (len(plane), 1)))
+    r = subprocess.run([EXE, str(_host_cfg(tmp_path, est_dir, 1, 0.5))], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    txt = open(est_dir / "map_results" / "map_results.txt").read()
+    m = re.search(r"Aligned cloud:\s+((?:[-\d.e+]+\s+){16})", txt)
+    Th = np.array([float(v) for v in m.group(1).split()]).reshape(4, 4)
+    assert np.array_equal(Th, np.eye(4))
+    assert int(re.search(r"Aligned results: ([\d.]+) (\d+)", txt).group(2)) == len(plane)
+
+
 def test_host_point_to_plane_needs_target_normals(tmp_path):
     """Open3D refuses point-to-plane ICP on a target without normals; so does the host (no silent estimate)."""
     est_dir = tmp_path / "est"
