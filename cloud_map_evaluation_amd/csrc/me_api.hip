@@ -107,6 +107,15 @@ void mail_drop(me_ctx *ctx) {
     ctx->mail_pending.clear();
     ctx->mail_used = 0;
 }
+
+int need_single_gpu_cloud(me_ctx *ctx, int slot, const char *who) {
+    if (slot < 0 || slot > 1) return ctx->fail(ME_ERR_ARG, std::string(who) + ": bad slot");
+    Cloud &c = ctx->cloud[slot];
+    if (ctx->shard_world != 1 || ctx->slab.axis >= 0 || c.slab.axis >= 0)
+        return ctx->fail(ME_ERR_ARG, std::string(who) + ": single GPU only (no slab or shard mode)");
+    if (!c.uploaded) return ctx->fail(ME_ERR_STATE, std::string(who) + ": cloud not uploaded");
+    return ME_OK;
+}
 }  // namespace me
 
 extern "C" {

@@ -23,8 +23,6 @@ namespace me {
 
 namespace {
 
-inline unsigned int blocks_of(long long n, int block = 256) { return (unsigned int) std::max<long long>(1, (n + block - 1) / block); }
-
 // parent[] is read while other workgroups change it.  A value read late is still a member of the same set with a smaller position (a
 // pointer only ever moves towards the root), so no load needs to be ordered with anything; the agent-scope load only keeps it from
 // being served by this CU's L1 for the rest of the kernel.
@@ -104,26 +102,15 @@ k_cluster_count(const SPoint *__restrict__ sp, const unsigned long long *__restr
     __shared__ int2 s_tab[4][kGroupTab + 1];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const long long i = (long long) blockIdx.x * 256 + threadIdx.x;
-    const bool active = i < n;
-    double qx = 0, qy = 0, qz = 0;
-    int cx = 0, cy = 0, cz = 0;
-    long long qi = 0;
-    if (active) {
-        const SPoint q = sp[i];
-        qx = q.x;
-        qy = q.y;
-        qz = q.z;
-        qi = q.idx;
-        cell_of(codes[i], g.shift, cx, cy, cz);
-    }
+    const StreamQuery q = stream_query(sp, codes, i, n, g.shift);
     int cnt = 0;
-    wave_stream(active, cx, cy, cz, sp, g, lane, s_tab[w], &s_tile[w], [&](double px, double py, double pz, int, int) {
-        cnt += dist2_exact(qx, qy, qz, px, py, pz) < r2 ? 1 : 0;
+    wave_stream(q.active, q.cx, q.cy, q.cz, sp, g, lane, s_tab[w], &s_tile[w], [&](double px, double py, double pz, int, int) {
+        cnt += dist2_exact(q.qx, q.qy, q.qz, px, py, pz) < r2 ? 1 : 0;
     });
     bool core = false;
-    if (active) {
+    if (q.active) {
         core = cnt >= min_points;
-        counts[qi] = cnt;
+        counts[q.idx] = cnt;
         parent[i] = core ? (int) i : -1;
         min_idx[i] = 0xffffffffu;
         bflag[i] = (!core && cnt >= 2) ? 1 : 0;  // (a border point has a core neighbour besides itself)
@@ -314,7 +301,7 @@ constexpr size_t kAuxBytes = 64;
 }  // namespace
 
 int cluster_dbscan(me_ctx *ctx, int slot, double eps, int min_points, int32_t *labels_host, int32_t *counts_host, me_cluster_info *info) {
-    ME_TRY(need_outlier_slot(ctx, slot, "me_cluster_dbscan"));
+    ME_TRY(need_single_gpu_cloud(ctx, slot, "me_cluster_dbscan"));
     if (!(eps > 0) || !std::isfinite(eps)) return ctx->fail(ME_ERR_ARG, "me_cluster_dbscan: eps must be finite and > 0");
     if (min_points < 1) return ctx->fail(ME_ERR_ARG, "me_cluster_dbscan: min_points must be >= 1");
     Cloud &c = ctx->cloud[slot];
@@ -421,7 +408,7 @@ int cluster_dbscan(me_ctx *ctx, int slot, double eps, int min_points, int32_t *l
 }
 
 int cluster_sizes(me_ctx *ctx, int slot, int64_t *sizes_host, long long capacity, long long *n_clusters) {
-    ME_TRY(need_outlier_slot(ctx, slot, "me_cluster_sizes"));
+    ME_TRY(need_single_gpu_cloud(ctx, slot, "me_cluster_sizes"));
     Cloud &c = ctx->cloud[slot];
     if (!c.cluster_valid) return ctx->fail(ME_ERR_STATE, "me_cluster_sizes: the slot has no cluster labels (me_cluster_dbscan)");
     if (n_clusters) *n_clusters = c.cluster_n;
@@ -435,7 +422,7 @@ int cluster_sizes(me_ctx *ctx, int slot, int64_t *sizes_host, long long capacity
 }
 
 int cluster_keep(me_ctx *ctx, int slot, long long min_cluster_size, long long keep_largest, uint8_t *keep_host, me_outlier_info *info) {
-    ME_TRY(need_outlier_slot(ctx, slot, "me_cluster_keep"));
+    ME_TRY(need_single_gpu_cloud(ctx, slot, "me_cluster_keep"));
     if (min_cluster_size < 1) return ctx->fail(ME_ERR_ARG, "me_cluster_keep: min_cluster_size must be >= 1");
     if (keep_largest < 0) return ctx->fail(ME_ERR_ARG, "me_cluster_keep: keep_largest must be >= 0");
     Cloud &c = ctx->cloud[slot];

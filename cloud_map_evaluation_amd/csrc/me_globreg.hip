@@ -26,22 +26,13 @@ namespace {
 
 constexpr int kFeat = 33;
 
-inline unsigned int blocks_of(long long n, int block = 256) { return (unsigned int) std::max<long long>(1, (n + block - 1) / block); }
-
-__device__ __forceinline__ double dot3g(const double *a, const double *b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
-__device__ __forceinline__ void cross3g(const double *a, const double *b, double *o) {
-    o[0] = a[1] * b[2] - a[2] * b[1];
-    o[1] = a[2] * b[0] - a[0] * b[2];
-    o[2] = a[0] * b[1] - a[1] * b[0];
-}
-
 // ComputePairFeatures [Open3D] of (p1, n1, p2, n2) -> (f0, f1, f2); the swap test |a1| < |a2| stands for acos(|a1|) > acos(|a2|)
 __device__ __forceinline__ void pair_feature(const double *p1, const double *n1, const double *p2, const double *n2, double f[3]) {
     f[0] = f[1] = f[2] = 0.0;
     double d[3] = {p2[0] - p1[0], p2[1] - p1[1], p2[2] - p1[2]};
     const double L = sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
     if (L == 0.0) return;
-    const double a1 = dot3g(n1, d) / L, a2 = dot3g(n2, d) / L;
+    const double a1 = dot3(n1, d) / L, a2 = dot3(n2, d) / L;
     const double *m1 = n1, *m2 = n2;
     double f2 = a1;
     if (fabs(a1) < fabs(a2)) {
@@ -53,15 +44,15 @@ __device__ __forceinline__ void pair_feature(const double *p1, const double *n1,
         f2 = -a2;
     }
     double v[3], w[3];
-    cross3g(d, m1, v);
+    cross3(d, m1, v);
     const double vn = sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
     if (vn == 0.0) return;
     v[0] /= vn;
     v[1] /= vn;
     v[2] /= vn;
-    cross3g(m1, v, w);
-    f[0] = atan2(dot3g(w, m2), dot3g(m1, m2));
-    f[1] = dot3g(v, m2);
+    cross3(m1, v, w);
+    f[0] = atan2(dot3(w, m2), dot3(m1, m2));
+    f[1] = dot3(v, m2);
     f[2] = f2;
 }
 
@@ -259,8 +250,8 @@ __global__ void __launch_bounds__(256) k_ransac_hyp(long long h0, long long nh, 
         // degenerate source triangle: |e01 x e02|^2 <= 1e-12 |e01|^2 |e02|^2
         const double e1[3] = {p[3] - p[0], p[4] - p[1], p[5] - p[2]}, e2[3] = {p[6] - p[0], p[7] - p[1], p[8] - p[2]};
         double cr[3];
-        cross3g(e1, e2, cr);
-        if (dot3g(cr, cr) <= (1e-12 * dot3g(e1, e1)) * dot3g(e2, e2)) ok = false;
+        cross3(e1, e2, cr);
+        if (dot3(cr, cr) <= (1e-12 * dot3(e1, e1)) * dot3(e2, e2)) ok = false;
         if (ok) {
             horn_fit3(p, q, T);
 #pragma unroll
@@ -337,15 +328,6 @@ __global__ void __launch_bounds__(256) k_fit_reduce(const double *__restrict__ d
     }
 }
 
-int need_single(me_ctx *ctx, int slot, const char *who) {
-    if (slot < 0 || slot > 1) return ctx->fail(ME_ERR_ARG, std::string(who) + ": bad slot");
-    Cloud &c = ctx->cloud[slot];
-    if (ctx->shard_world != 1 || ctx->slab.axis >= 0 || c.slab.axis >= 0)
-        return ctx->fail(ME_ERR_ARG, std::string(who) + ": single GPU only (no slab or shard mode)");
-    if (!c.uploaded) return ctx->fail(ME_ERR_STATE, std::string(who) + ": cloud not uploaded");
-    return ME_OK;
-}
-
 bool fpfh_params_ok(const me_fpfh_params *p) {
     return p && p->radius > 0 && std::isfinite(p->radius) && p->max_nn >= 1 && p->max_nn <= kKnnMax && p->normal_knn >= 1 &&
            p->normal_knn <= kKnnMax;
@@ -398,7 +380,7 @@ int match_device(me_ctx *ctx, int s_slot, int r_slot, int mutual, DevBuf &corr, 
 }  // namespace
 
 int fpfh(me_ctx *ctx, int slot, const me_fpfh_params *p, double *features_host) {
-    ME_TRY(need_single(ctx, slot, "me_fpfh"));
+    ME_TRY(need_single_gpu_cloud(ctx, slot, "me_fpfh"));
     if (!fpfh_params_ok(p))
         return ctx->fail(ME_ERR_ARG, "me_fpfh: radius must be finite and > 0, max_nn and normal_knn in [1, 40]");
     Cloud &c = ctx->cloud[slot];
@@ -431,8 +413,8 @@ int fpfh(me_ctx *ctx, int slot, const me_fpfh_params *p, double *features_host) 
 }
 
 int fpfh_match(me_ctx *ctx, int src_slot, int ref_slot, int mutual, int32_t *corr_host, long long *n_corr) {
-    ME_TRY(need_single(ctx, src_slot, "me_fpfh_match"));
-    ME_TRY(need_single(ctx, ref_slot, "me_fpfh_match"));
+    ME_TRY(need_single_gpu_cloud(ctx, src_slot, "me_fpfh_match"));
+    ME_TRY(need_single_gpu_cloud(ctx, ref_slot, "me_fpfh_match"));
     if (src_slot == ref_slot) return ctx->fail(ME_ERR_ARG, "me_fpfh_match: src_slot == ref_slot");
     ME_CHECK(ctx, hipSetDevice(ctx->device));
     DevBuf corr, list;
@@ -446,8 +428,8 @@ int fpfh_match(me_ctx *ctx, int src_slot, int ref_slot, int mutual, int32_t *cor
 
 int global_register(me_ctx *ctx, int src_slot, int ref_slot, const me_globreg_params *p, double T_out[16], me_globreg_info *info,
                     int64_t *scores) {
-    ME_TRY(need_single(ctx, src_slot, "me_global_register"));
-    ME_TRY(need_single(ctx, ref_slot, "me_global_register"));
+    ME_TRY(need_single_gpu_cloud(ctx, src_slot, "me_global_register"));
+    ME_TRY(need_single_gpu_cloud(ctx, ref_slot, "me_global_register"));
     if (src_slot == ref_slot) return ctx->fail(ME_ERR_ARG, "me_global_register: src_slot == ref_slot");
     if (!p || !T_out) return ctx->fail(ME_ERR_ARG, "me_global_register: params or T_out is NULL");
     if (!(p->max_corr_dist > 0) || !std::isfinite(p->max_corr_dist) || !(p->edge_ratio > 0 && p->edge_ratio <= 1) ||

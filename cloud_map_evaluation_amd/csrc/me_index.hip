@@ -595,7 +595,6 @@ k_cell_fill(const unsigned long long *__restrict__ codes, long long n, int shift
     if (blockIdx.x == 0 && threadIdx.x == 0) cell_start[n_cells] = (unsigned int) n;
 }
 
-static inline unsigned int grid_for(long long n, int block = 256) { return (unsigned int) ((n + block - 1) / block); }
 
 // occupied cells of Morton level `shift` (unique code >> 3*shift, run starts) + open-addressing hash:
 // a cell table of the sorted points from the blocks' histogram rows (see the kernels above); `offsets_ready`: block_off already holds this
@@ -605,7 +604,7 @@ static int build_grid_table_counted(me_ctx *ctx, Cloud &c, int shift, GridTable 
     const long long n = c.n;
     if (!offsets_ready) {
         unsigned int *cnt = block_off + (nblk + 2);
-        hipLaunchKernelGGL(k_block_counts<false>, dim3(grid_for(nblk + 1)), dim3(256), 0, ctx->stream, block_hist, nblk, shift, cnt,
+        hipLaunchKernelGGL(k_block_counts<false>, dim3(blocks_of(nblk + 1)), dim3(256), 0, ctx->stream, block_hist, nblk, shift, cnt,
                            (unsigned long long *) nullptr);
         ME_TRY(exclusive_scan_u32(ctx, cnt, block_off, nblk + 1));
     }
@@ -702,7 +701,7 @@ int cloud_upload(me_ctx *ctx, int slot, const double *src, bool src_on_device, l
         if (T) {
             Mat4 m;
             std::memcpy(m.m, T, sizeof(m.m));
-            hipLaunchKernelGGL(k_transform, dim3(grid_for(n)), dim3(256), 0, ctx->stream, c.xyz.as_mut<double>(), n, m);
+            hipLaunchKernelGGL(k_transform, dim3(blocks_of(n)), dim3(256), 0, ctx->stream, c.xyz.as_mut<double>(), n, m);
         }
     } else {
         // slab mode: keep only [reg_lo, reg_hi) along the slab axis of the (transformed) cloud, stable order.  A device
@@ -719,7 +718,7 @@ int cloud_upload(me_ctx *ctx, int slot, const double *src, bool src_on_device, l
         Mat4 m{};
         if (T) std::memcpy(m.m, T, sizeof(m.m));
         TimerScope ts(ctx, "slab_filter");
-        hipLaunchKernelGGL(k_slab_flags, dim3(grid_for(n)), dim3(256), 0, ctx->stream, in, n, T ? 1 : 0, m, c.slab,
+        hipLaunchKernelGGL(k_slab_flags, dim3(blocks_of(n)), dim3(256), 0, ctx->stream, in, n, T ? 1 : 0, m, c.slab,
                            flags.as<unsigned int>());
         ME_TRY(exclusive_scan_u32(ctx, flags.as<unsigned int>(), pos.as<unsigned int>(), n));
         unsigned int last_pos = 0, last_flag = 0;
@@ -730,7 +729,7 @@ int cloud_upload(me_ctx *ctx, int slot, const double *src, bool src_on_device, l
         ME_CHECK(ctx, c.xyz.ensure((size_t) std::max<long long>(kept, 1) * 3 * sizeof(double)));
         ME_CHECK(ctx, c.slab_orig.ensure((size_t) std::max<long long>(kept, 1) * 4));
         c.slab_identity = false;
-        hipLaunchKernelGGL(k_slab_compact, dim3(grid_for(n)), dim3(256), 0, ctx->stream, in, n, T ? 1 : 0, m,
+        hipLaunchKernelGGL(k_slab_compact, dim3(blocks_of(n)), dim3(256), 0, ctx->stream, in, n, T ? 1 : 0, m,
                            flags.as<unsigned int>(), pos.as<unsigned int>(), c.xyz.as_mut<double>(), c.slab_orig.as<int>());
         c.n = kept;
         if (kept == 0) {  // this rank's slab (+halo) holds nothing of this cloud: every pass returns empty partials
@@ -829,7 +828,7 @@ int cloud_transform(me_ctx *ctx, int slot, const double *T) {
     Mat4 m;
     std::memcpy(m.m, T, sizeof(m.m));
     ME_CHECK(ctx, c.xyz.make_owned(ctx->stream));  // (a borrowed input buffer is the caller's: transform a private copy)
-    hipLaunchKernelGGL(k_transform, dim3(grid_for(c.n)), dim3(256), 0, ctx->stream, c.xyz.as_mut<double>(), c.n, m);
+    hipLaunchKernelGGL(k_transform, dim3(blocks_of(c.n)), dim3(256), 0, ctx->stream, c.xyz.as_mut<double>(), c.n, m);
     ME_TRY(rotate_attributes(ctx, slot, T));  // normals / covariances follow the points (Open3D PointCloud::Transform)
     return cloud_finish(ctx, slot);
 }
@@ -842,7 +841,7 @@ int transform_points_device(me_ctx *ctx, double *xyz_device, long long n, const 
     ME_CHECK(ctx, hipSetDevice(ctx->device));
     Mat4 m;
     std::memcpy(m.m, T, sizeof(m.m));
-    hipLaunchKernelGGL(k_transform, dim3(grid_for(n)), dim3(256), 0, ctx->stream, xyz_device, n, m);
+    hipLaunchKernelGGL(k_transform, dim3(blocks_of(n)), dim3(256), 0, ctx->stream, xyz_device, n, m);
     ME_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     ME_CHECK(ctx, hipGetLastError());
     return ME_OK;
@@ -873,7 +872,7 @@ static int build_octree(me_ctx *ctx, Cloud &c, int nn_shift, bool small_top) {
     v.pbegin = c.oct_pbegin.as<unsigned int>();
     ONode *nodes = c.oct_nodes.as<ONode>();
     unsigned int *pbeg = c.oct_pbegin.as<unsigned int>();
-    hipLaunchKernelGGL(k_oct_leaves, dim3(grid_for((v.count[0] + 1) * 8)), dim3(256), 0, ctx->stream, c.sp.as<SPoint>(),
+    hipLaunchKernelGGL(k_oct_leaves, dim3(blocks_of((v.count[0] + 1) * 8)), dim3(256), 0, ctx->stream, c.sp.as<SPoint>(),
                        c.nn_grid.cell_start, v.count[0], n, nodes, pbeg);
     // prefix codes of the current level (level 0: the cell codes of the 1-NN grid), ping-pong
     DevBuf &ca = ctx->tmp[2], &cb = ctx->tmp[3], &pos = ctx->tmp[1], &begin = ctx->tmp[4];
@@ -902,9 +901,9 @@ static int build_octree(me_ctx *ctx, Cloud &c, int nn_shift, bool small_top) {
         DevBuf &nxt = (l % 2 == 0) ? ca : cb;
         ME_CHECK(ctx, nxt.ensure((size_t) np * 8));
         ME_TRY(cell_start_ranks(ctx, cur, nc, 3, pos.as<unsigned int>()));
-        hipLaunchKernelGGL(k_cell_scatter, dim3(grid_for(nc)), dim3(256), 0, ctx->stream, cur, pos.as<unsigned int>(), nc, 3,
+        hipLaunchKernelGGL(k_cell_scatter, dim3(blocks_of(nc)), dim3(256), 0, ctx->stream, cur, pos.as<unsigned int>(), nc, 3,
                            nxt.as<unsigned long long>(), begin.as<unsigned int>());
-        hipLaunchKernelGGL(k_oct_up, dim3(grid_for(np + 1)), dim3(256), 0, ctx->stream, nodes + v.off[l], nc,
+        hipLaunchKernelGGL(k_oct_up, dim3(blocks_of(np + 1)), dim3(256), 0, ctx->stream, nodes + v.off[l], nc,
                            begin.as<unsigned int>(), np, nodes + v.off[l + 1], pbeg + v.off[l], pbeg + v.off[l + 1]);
         cur = nxt.as<unsigned long long>();
     }
@@ -988,7 +987,7 @@ int cloud_build_index(me_ctx *ctx, int slot, double cell_size) {
     if (pack_bits > 0) ME_CHECK(ctx, perm.ensure((size_t) n * 8));  // (the sorted words)
     {
         TimerScope ts(ctx, "morton");
-        hipLaunchKernelGGL(k_morton, dim3(grid_for(n)), dim3(256), 0, ctx->stream, c.xyz.as<double>(), n, c.origin[0],
+        hipLaunchKernelGGL(k_morton, dim3(blocks_of(n)), dim3(256), 0, ctx->stream, c.xyz.as<double>(), n, c.origin[0],
                            c.origin[1], c.origin[2], c.fine_h, sort_min_level, hilbert, pack_bits, codes_in.as<unsigned long long>(),
                            iota.as<unsigned int>());
     }
@@ -1020,7 +1019,7 @@ int cloud_build_index(me_ctx *ctx, int slot, double cell_size) {
     {
         TimerScope ts(ctx, "gather");
 #define ME_LAUNCH_GATHER(VOX_, PER_)                                                                                                     \
-    hipLaunchKernelGGL((k_gather<VOX_, PER_>), dim3(grid_for(n, 256 * PER_)), dim3(256), 0, ctx->stream, c.xyz.as<double>(),            \
+    hipLaunchKernelGGL((k_gather<VOX_, PER_>), dim3(blocks_of(n, 256 * PER_)), dim3(256), 0, ctx->stream, c.xyz.as<double>(),            \
                        pack_bits > 0 ? (const unsigned int *) nullptr : perm.as<unsigned int>(),                                       \
                        pack_bits > 0 ? perm.as<unsigned long long>() : (const unsigned long long *) nullptr,                           \
                        pack_bits > 0 ? ((1ULL << pack_bits) - 1ULL) : 0ULL, n, c.origin[0], c.origin[1], c.origin[2], c.fine_h,        \
@@ -1047,7 +1046,7 @@ int cloud_build_index(me_ctx *ctx, int slot, double cell_size) {
         unsigned int *d_boff = reinterpret_cast<unsigned int *>(d_hist + 64), *d_bcnt = d_boff + (nblk + 2), *d_bhist = d_bcnt + (nblk + 2);
         ME_CHECK(ctx, hipMemsetAsync(d_hist, 0, 32 * 8, ctx->stream));
         hipLaunchKernelGGL(k_level_hist_rows, dim3((unsigned int) nblk), dim3(256), 0, ctx->stream, c.codes.as<unsigned long long>(), n, d_bhist);
-        hipLaunchKernelGGL(k_block_counts<true>, dim3(grid_for(nblk + 1)), dim3(256), 0, ctx->stream, d_bhist, nblk, c.shift, d_bcnt, d_hist);
+        hipLaunchKernelGGL(k_block_counts<true>, dim3(blocks_of(nblk + 1)), dim3(256), 0, ctx->stream, d_bhist, nblk, c.shift, d_bcnt, d_hist);
         ME_TRY(exclusive_scan_u32(ctx, d_bcnt, d_boff, nblk + 1));
         unsigned long long h_hist[32];
         {
@@ -1153,7 +1152,7 @@ int slab_points(me_ctx *ctx, int slot, int64_t *orig_index, uint8_t *owned, long
     DevBuf &oi = ctx->tmp[0], &ow = ctx->tmp[1];
     ME_CHECK(ctx, oi.ensure((size_t) c.n * 8));
     ME_CHECK(ctx, ow.ensure((size_t) c.n));
-    hipLaunchKernelGGL(k_slab_points, dim3(grid_for(c.n)), dim3(256), 0, ctx->stream, c.xyz.as<double>(), c.n, c.slab,
+    hipLaunchKernelGGL(k_slab_points, dim3(blocks_of(c.n)), dim3(256), 0, ctx->stream, c.xyz.as<double>(), c.n, c.slab,
                        c.slab_identity ? (const int *) nullptr : c.slab_orig.as<int>(), orig_index ? oi.as<long long>() : nullptr,
                        owned ? ow.as<unsigned char>() : nullptr);
     if (orig_index) ME_TRY(copy_d2h(ctx, orig_index, oi.p, (size_t) c.n * 8));

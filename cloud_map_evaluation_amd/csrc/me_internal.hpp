@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <cstdlib>
 #include <cstdio>
@@ -422,6 +423,8 @@ struct TimerScope {  // (scopes do not nest: a scope that calls into another tim
 #define ME_TUNE_SUITE_NN_FIRST 1  // me_run_suite_from, second lane: the reverse 1-NN search before the voxel tables (0: round 5's order)
 #endif
 inline unsigned int xcd_chunk_setting() { return (unsigned int) ME_TUNE_XCD_CHUNK; }
+// blocks of `block` threads for n items, at least one: a kernel launched for n == 0 bounds-checks its index, a zero-sized grid is a launch error
+inline unsigned int blocks_of(long long n, int block = 256) { return (unsigned int) std::max<long long>(1, (n + block - 1) / block); }
 
 // ---- me_api.hip: copies between caller (host) memory and the device ----
 int copy_h2d(me_ctx *ctx, void *dst_device, const void *src_host, size_t bytes);  // ordered on ctx->stream
@@ -431,6 +434,8 @@ constexpr size_t kMailBytes = 128 * 1024;
 int mail_post(me_ctx *ctx, void *host_dst, const void *dev_src, size_t bytes);  // asynchronous on ctx->stream
 int mail_sync(me_ctx *ctx);                                                     // hipStreamSynchronize + delivery of what was posted
 void mail_drop(me_ctx *ctx);                                                    // forget what was posted (nothing is delivered)
+// ---- me_api.hip: the check of the single-GPU features: slot in range, no slab or shard mode, uploaded ----
+int need_single_gpu_cloud(me_ctx *ctx, int slot, const char *who);
 // The host destinations of mail_post are usually LOCALS of the posting function: if it returns before its mail_sync (a failed
 // allocation or launch in between), the queued entries must not survive it — the next mail_sync on the context would copy into a
 // dead stack frame.  A MailGuard in scope between the first mail_post and the mail_sync drops them on every early return.
@@ -483,7 +488,6 @@ int statistical_outlier(me_ctx *ctx, int slot, int nb_neighbors, double std_rati
                         me_outlier_info *info);
 int radius_outlier(me_ctx *ctx, int slot, int nb_points, double radius, int32_t *counts_host, uint8_t *keep_host, me_outlier_info *info);
 int outlier_select_into(me_ctx *src_ctx, int src_slot, me_ctx *dst_ctx, int dst_slot, long long *n_out);
-int need_outlier_slot(me_ctx *ctx, int slot, const char *who);  // slot in range, single GPU (no slab or shard mode), uploaded
 // ---- me_cluster.hip ----
 int cluster_dbscan(me_ctx *ctx, int slot, double eps, int min_points, int32_t *labels_host, int32_t *counts_host, me_cluster_info *info);
 int cluster_sizes(me_ctx *ctx, int slot, int64_t *sizes_host, long long capacity, long long *n_clusters);
@@ -581,6 +585,13 @@ __device__ __forceinline__ double dist2_exact(double ax, double ay, double az, d
     // this expression must be bit-identical to the CPU path (nanoflann L2 adaptor order).
     const double dx = ax - bx, dy = ay - by, dz = az - bz;
     return (dx * dx + dy * dy) + dz * dz;
+}
+// 3-vectors, the same association: tests/_reg_ref.py and tests/_globreg_ref.py restate it
+__device__ __forceinline__ double dot3(const double *a, const double *b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
+__device__ __forceinline__ void cross3(const double *a, const double *b, double *o) {
+    o[0] = a[1] * b[2] - a[2] * b[1];
+    o[1] = a[2] * b[0] - a[0] * b[2];
+    o[2] = a[0] * b[1] - a[1] * b[0];
 }
 
 __device__ __forceinline__ double wave_sum(double v) {

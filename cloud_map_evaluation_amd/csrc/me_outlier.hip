@@ -3,8 +3,8 @@
 //                  streams the runs of its group's cell box (wave_group_table) through LDS, every lane keeps its k smallest d2 in
 //                  registers; a lane is settled when its k-th d2 lies inside its own 3x3x3 block.  The grid level is the finest
 //                  table of the index whose occupied cells hold >= ME_TUNE_KNN_MEAN_OCC x k points      (me_statistical_outlier, "outlier")
-//   k_knn_mean_walk  what the grid pass leaves (isolated points, n < k): the exact nearest-first octree walk of k_knn_normals,
-//                  distances only                                                                                           ("outlier")
+//   k_knn_mean_walk  what the grid pass leaves (isolated points, n < k): the exact nearest-first octree walk of me_oct_walk.hpp
+//                  (the one k_knn_normals uses), distances only                                                             ("outlier")
 //   k_sor_partials / k_sor_final  mean and std in fp64: block partials in point order, then one block — no float atomics
 //   k_radius_count per point: the points with d2 < r^2 in the 27-cell stencil of the radius grid (cell >= r), exact fp64
 //                                                                                                  (me_radius_outlier, "outlier")
@@ -16,6 +16,7 @@
 #include <utility>
 
 #include "me_internal.hpp"
+#include "me_oct_walk.hpp"
 #include "me_wave_stream.hpp"
 
 #ifndef ME_TUNE_KNN_MEAN_OCC
@@ -25,8 +26,6 @@
 namespace me {
 
 namespace {
-
-inline unsigned int blocks_of(long long n, int block = 256) { return (unsigned int) std::max<long long>(1, (n + block - 1) / block); }
 
 // v_min_f64 / v_max_f64 without the NaN canonicalisation fmin() / fmax() carry (squared distances are never NaN)
 __device__ __forceinline__ double min_raw(double a, double b) {
@@ -86,27 +85,18 @@ k_knn_mean(const SPoint *__restrict__ sp, const unsigned long long *__restrict__
     __shared__ int2 s_tab[4][kGroupTab + 1];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const long long i = (long long) blockIdx.x * 256 + threadIdx.x;
-    const bool active = i < n;
-    double qx = 0, qy = 0, qz = 0;
-    int cx = 0, cy = 0, cz = 0;
-    if (active) {
-        const SPoint q = sp[i];
-        qx = q.x;
-        qy = q.y;
-        qz = q.z;
-        cell_of(codes[i], g.shift, cx, cy, cz);
-    }
+    const StreamQuery q = stream_query(sp, codes, i, n, g.shift);
     TopK<KC> t;
     t.init(k);
-    wave_stream(active, cx, cy, cz, sp, g, lane, s_tab[w], &s_tile[w], [&](double px, double py, double pz, int, int) {
-        const double d = dist2_exact(qx, qy, qz, px, py, pz);
+    wave_stream(q.active, q.cx, q.cy, q.cz, sp, g, lane, s_tab[w], &s_tile[w], [&](double px, double py, double pz, int, int) {
+        const double d = dist2_exact(q.qx, q.qy, q.qz, px, py, pz);
         if (d < t.worst()) t.push(d);
     });
-    if (!active) return;
+    if (!q.active) return;
     const double hs = ldexp(fr.fine_h, g.shift);
-    const double bx = fmin(qx - (fr.ox + (double) (cx - 1) * hs), (fr.ox + (double) (cx + 2) * hs) - qx);
-    const double by = fmin(qy - (fr.oy + (double) (cy - 1) * hs), (fr.oy + (double) (cy + 2) * hs) - qy);
-    const double bz = fmin(qz - (fr.oz + (double) (cz - 1) * hs), (fr.oz + (double) (cz + 2) * hs) - qz);
+    const double bx = fmin(q.qx - (fr.ox + (double) (q.cx - 1) * hs), (fr.ox + (double) (q.cx + 2) * hs) - q.qx);
+    const double by = fmin(q.qy - (fr.oy + (double) (q.cy - 1) * hs), (fr.oy + (double) (q.cy + 2) * hs) - q.qy);
+    const double bz = fmin(q.qz - (fr.oz + (double) (q.cz - 1) * hs), (fr.oz + (double) (q.cz + 2) * hs) - q.qz);
     const double bd = fmin(fmin(bx, by), bz) - hs * 0x1p-20;
     if (bd > 0.0 && t.worst() < bd * bd) {
         avg[sp[i].idx] = t.mean();
@@ -116,15 +106,8 @@ k_knn_mean(const SPoint *__restrict__ sp, const unsigned long long *__restrict__
     }
 }
 
-__device__ __forceinline__ double box_lb(const ONode *__restrict__ nd, double qx, double qy, double qz) {
-    const double dx = fmax(fmax((double) nd->lo[0] - qx, qx - (double) nd->hi[0]), 0.0);
-    const double dy = fmax(fmax((double) nd->lo[1] - qy, qy - (double) nd->hi[1]), 0.0);
-    const double dz = fmax(fmax((double) nd->lo[2] - qz, qz - (double) nd->hi[2]), 0.0);
-    return (dx * dx + dy * dy) + dz * dz;  // never exceeds the computed d2 of a point inside (boxes rounded outward)
-}
-
-// ---- statistical: the exact walk for the listed queries (the stackless nearest-first walk of k_knn_normals; a box whose bound
-// is not below the k-th d2 cannot change the k smallest distances, so ties need no index rule) ----
+// ---- statistical: the exact walk for the listed queries (oct_walk_nearest, me_oct_walk.hpp; a box whose bound is not below the
+// k-th d2 cannot change the k smallest distances, so ties need no index rule: < where k_knn_normals admits with <=) ----
 constexpr int kWalkBlock = 128;
 template <int KC>
 __global__ void __launch_bounds__(kWalkBlock)
@@ -149,48 +132,7 @@ k_knn_mean_walk(const SPoint *__restrict__ sp, OctView oct, int k, const unsigne
                 if (d < top.worst()) top.push(d);
             }
         };
-        if (L == 0) {
-            scan_leaf(0);
-        } else {
-            int l = L;
-            long long nd = 0;
-            unsigned long long taken_lo = 0, taken_hi = 0;  // one byte of "children already entered" per level 1..8 / 9..16
-            for (;;) {
-                const ONode *__restrict__ me = nodes + s_off[l] + nd;
-                const long long cb = me[0].begin;
-                const int cc = (int) (me[1].begin - cb);
-                const unsigned int tk = (l <= 8) ? (unsigned int) (taken_lo >> (8 * (l - 1))) & 0xffu
-                                                 : (unsigned int) (taken_hi >> (8 * (l - 9))) & 0xffu;
-                double kd = INFINITY;
-                int kc = 8;
-                const ONode *__restrict__ ch = nodes + s_off[l - 1] + cb;
-                const double worst = top.worst();
-                for (int c = 0; c < cc; ++c) {
-                    if ((tk >> c) & 1u) continue;
-                    const double lb = box_lb(ch + c, qx, qy, qz);
-                    if (lb < worst && lb < kd) {
-                        kd = lb;
-                        kc = c;
-                    }
-                }
-                if (kc >= 8) {
-                    if (l == L) break;
-                    nd = me[0].parent;
-                    ++l;
-                } else {
-                    if (l <= 8) taken_lo |= 1ULL << (8 * (l - 1) + kc);
-                    else taken_hi |= 1ULL << (8 * (l - 9) + kc);
-                    if (l == 1) {
-                        scan_leaf(s_off[0] + cb + kc);
-                    } else {
-                        --l;
-                        nd = cb + kc;
-                        if (l <= 8) taken_lo &= ~(0xffULL << (8 * (l - 1)));
-                        else taken_hi &= ~(0xffULL << (8 * (l - 9)));
-                    }
-                }
-            }
-        }
+        oct_walk_nearest(nodes, s_off, L, qx, qy, qz, [&](double lb) { return lb < top.worst(); }, scan_leaf);
         avg[q.idx] = top.mean();
     }
 }
@@ -261,22 +203,13 @@ k_radius_count(const SPoint *__restrict__ sp, const unsigned long long *__restri
     __shared__ int2 s_tab[4][kGroupTab + 1];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const long long i = (long long) blockIdx.x * 256 + threadIdx.x;
-    const bool active = i < n;
-    double qx = 0, qy = 0, qz = 0;
-    int cx = 0, cy = 0, cz = 0;
-    if (active) {
-        const SPoint q = sp[i];
-        qx = q.x;
-        qy = q.y;
-        qz = q.z;
-        cell_of(codes[i], g.shift, cx, cy, cz);
-    }
+    const StreamQuery q = stream_query(sp, codes, i, n, g.shift);
     int cnt = 0;
-    wave_stream(active, cx, cy, cz, sp, g, lane, s_tab[w], &s_tile[w], [&](double px, double py, double pz, int, int) {
-        cnt += dist2_exact(qx, qy, qz, px, py, pz) < r2 ? 1 : 0;
+    wave_stream(q.active, q.cx, q.cy, q.cz, sp, g, lane, s_tab[w], &s_tile[w], [&](double px, double py, double pz, int, int) {
+        cnt += dist2_exact(q.qx, q.qy, q.qz, px, py, pz) < r2 ? 1 : 0;
     });
     bool k = false;
-    if (active) {
+    if (q.active) {
         const long long qi = sp[i].idx;
         counts[qi] = cnt;
         k = cnt > nb_points;
@@ -328,18 +261,9 @@ constexpr size_t kAuxHead = 64;
 
 }  // namespace
 
-int need_outlier_slot(me_ctx *ctx, int slot, const char *who) {
-    if (slot < 0 || slot > 1) return ctx->fail(ME_ERR_ARG, std::string(who) + ": bad slot");
-    Cloud &c = ctx->cloud[slot];
-    if (ctx->shard_world != 1 || ctx->slab.axis >= 0 || c.slab.axis >= 0)
-        return ctx->fail(ME_ERR_ARG, std::string(who) + ": single GPU only (no slab or shard mode)");
-    if (!c.uploaded) return ctx->fail(ME_ERR_STATE, std::string(who) + ": cloud not uploaded");
-    return ME_OK;
-}
-
 int statistical_outlier(me_ctx *ctx, int slot, int nb_neighbors, double std_ratio, double *avg_host, uint8_t *keep_host,
                         me_outlier_info *info) {
-    ME_TRY(need_outlier_slot(ctx, slot, "me_statistical_outlier"));
+    ME_TRY(need_single_gpu_cloud(ctx, slot, "me_statistical_outlier"));
     if (nb_neighbors < 1 || nb_neighbors > kKnnMax) return ctx->fail(ME_ERR_ARG, "me_statistical_outlier: nb_neighbors must be in [1, 40]");
     if (!(std_ratio > 0) || !std::isfinite(std_ratio)) return ctx->fail(ME_ERR_ARG, "me_statistical_outlier: std_ratio must be > 0");
     Cloud &c = ctx->cloud[slot];
@@ -403,7 +327,7 @@ int statistical_outlier(me_ctx *ctx, int slot, int nb_neighbors, double std_rati
 }
 
 int radius_outlier(me_ctx *ctx, int slot, int nb_points, double radius, int32_t *counts_host, uint8_t *keep_host, me_outlier_info *info) {
-    ME_TRY(need_outlier_slot(ctx, slot, "me_radius_outlier"));
+    ME_TRY(need_single_gpu_cloud(ctx, slot, "me_radius_outlier"));
     if (nb_points < 0) return ctx->fail(ME_ERR_ARG, "me_radius_outlier: nb_points must be >= 0");
     if (!(radius > 0) || !std::isfinite(radius)) return ctx->fail(ME_ERR_ARG, "me_radius_outlier: radius must be > 0");
     Cloud &c = ctx->cloud[slot];

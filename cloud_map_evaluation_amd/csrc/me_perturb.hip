@@ -120,7 +120,6 @@ __global__ void __launch_bounds__(256) k_perturb_outliers(double *__restrict__ p
     pts[3 * (n_kept + j) + 2] = z;
 }
 
-inline unsigned int blocks_for(long long n) { return (unsigned int) ((n + 255) / 256); }
 
 inline bool unit_interval(double v) { return v >= 0.0 && v <= 1.0; }
 
@@ -162,7 +161,7 @@ int perturb_cloud(me_ctx *ctx, int dst_slot, int src_slot, const me_perturb_para
     if (k.density) {
         ME_CHECK(ctx, flags.ensure((size_t) n * 4));
         ME_CHECK(ctx, pos.ensure((size_t) n * 4));
-        hipLaunchKernelGGL(k_perturb_keep, dim3(blocks_for(n)), dim3(256), 0, ctx->stream, S.xyz.as<double>(), n, k,
+        hipLaunchKernelGGL(k_perturb_keep, dim3(blocks_of(n)), dim3(256), 0, ctx->stream, S.xyz.as<double>(), n, k,
                            flags.as<unsigned int>());
         ME_TRY(exclusive_scan_u32(ctx, flags.as<unsigned int>(), pos.as<unsigned int>(), n));
         unsigned int last_pos = 0, last_flag = 0;
@@ -184,11 +183,11 @@ int perturb_cloud(me_ctx *ctx, int dst_slot, int src_slot, const me_perturb_para
     DevBuf scratch;
     DevBuf &out = in_place ? scratch : D.xyz;
     ME_CHECK(ctx, out.ensure((size_t) total * 24));  // (a borrowed dst buffer is the caller's: ensure() replaces it by an own one)
-    hipLaunchKernelGGL(k_perturb_scatter, dim3(blocks_for(n)), dim3(256), 0, ctx->stream, S.xyz.as<double>(), n, k,
+    hipLaunchKernelGGL(k_perturb_scatter, dim3(blocks_of(n)), dim3(256), 0, ctx->stream, S.xyz.as<double>(), n, k,
                        k.density ? flags.as<unsigned int>() : nullptr, k.density ? pos.as<unsigned int>() : nullptr,
                        out.as_mut<double>());
     if (m > 0)
-        hipLaunchKernelGGL(k_perturb_outliers, dim3(blocks_for(m)), dim3(256), 0, ctx->stream, out.as_mut<double>(), n_kept, m, k);
+        hipLaunchKernelGGL(k_perturb_outliers, dim3(blocks_of(m)), dim3(256), 0, ctx->stream, out.as_mut<double>(), n_kept, m, k);
     ME_CHECK(ctx, hipGetLastError());
     ts.end();
     if (in_place) {

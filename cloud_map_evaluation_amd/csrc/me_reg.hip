@@ -3,6 +3,8 @@
 //   reference tree; stated Open3D 0.15.1].  What runs here, per cloud or per iteration:
 //     * PointCloud::EstimateNormals(KDTreeSearchParamKNN(k)): exact k-NN (one lane per query, nearest-first walk of the
 //       sparse octree, the k best kept sorted in LDS) + utility::ComputeCovariance + FastEigen3x3          (k_knn_normals)
+//       The walk is written out here; box_lb and the taken masks come from me_oct_walk.hpp, whose oct_walk_nearest is the
+//       same loop as a function (me_outlier.hip uses it): with it this kernel measured 3 % slower (profiles/EXPERIMENTS.md)
 //     * InitializePointCloudForGeneralizedICP(epsilon): covariance = Rx diag(eps,1,1) Rx^T                (k_gicp_cov)
 //     * PointCloud::Transform on the attributes: n <- R n, C <- R C R^T                                   (k_rotate_attr)
 //     * the correspondence + reduction step of one iteration: J^T J, J^T r, sum r^2 over the 1-NN pairs with
@@ -14,6 +16,7 @@
 #include <cstring>
 
 #include "me_internal.hpp"
+#include "me_oct_walk.hpp"
 
 namespace me {
 
@@ -32,13 +35,6 @@ __device__ __forceinline__ void mat3_mul_bt(const double *a, const double *b, do
         for (int j = 0; j < 3; ++j)
             o[3 * i + j] = (a[3 * i] * b[3 * j] + a[3 * i + 1] * b[3 * j + 1]) + a[3 * i + 2] * b[3 * j + 2];
 }
-__device__ __forceinline__ void cross3(const double *a, const double *b, double *o) {
-    o[0] = a[1] * b[2] - a[2] * b[1];
-    o[1] = a[2] * b[0] - a[0] * b[2];
-    o[2] = a[0] * b[1] - a[1] * b[0];
-}
-__device__ __forceinline__ double dot3(const double *a, const double *b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
-
 // Eigen Matrix3d::inverse(): cofactors, determinant along column 0
 __device__ __forceinline__ void inv3(const double *m, double *o) {
     const double c00 = m[4] * m[8] - m[5] * m[7], c01 = m[5] * m[6] - m[3] * m[8], c02 = m[3] * m[7] - m[4] * m[6];
@@ -196,20 +192,13 @@ __device__ void fast_eigen3x3(const double *cov, double *out) {
     }
 }
 
-__device__ __forceinline__ double box_lb(const ONode *__restrict__ nd, double qx, double qy, double qz) {
-    const double dx = fmax(fmax((double) nd->lo[0] - qx, qx - (double) nd->hi[0]), 0.0);
-    const double dy = fmax(fmax((double) nd->lo[1] - qy, qy - (double) nd->hi[1]), 0.0);
-    const double dz = fmax(fmax((double) nd->lo[2] - qz, qz - (double) nd->hi[2]), 0.0);
-    return (dx * dx + dy * dy) + dz * dz;  // never exceeds the computed d2 of a point inside (boxes rounded outward)
-}
-
 constexpr int kKnnBlock = 128;
 static_assert(kKnnMax == 40, "k * 128 lanes * 12 B of LDS <= 60 KB");
 
 // ---- k nearest neighbours of every point of a cloud IN that cloud + the normal of their raw-moment covariance ----
 // One lane per query (sorted order, so a wave walks neighbouring paths); the k best so far live in LDS, sorted
 // ascending by (d2, original index), element j of lane t at [j * blockDim + t] (conflict-free).  The walk is the
-// stackless nearest-first one of k_nn1 with the k-th best as the bound (<=: a tie may hold a smaller index).
+// stackless nearest-first one of oct_walk_nearest with the k-th best as the bound (<=: a tie may hold a smaller index).
 __global__ void __launch_bounds__(kKnnBlock)
 k_knn_normals(const SPoint *__restrict__ sp, long long n, OctView oct, const double *__restrict__ xyz, int k,
               double *__restrict__ normals, int *__restrict__ knn_idx, double *__restrict__ knn_d2) {
@@ -261,13 +250,12 @@ k_knn_normals(const SPoint *__restrict__ sp, long long n, OctView oct, const dou
     } else {
         int l = L;
         long long nd = 0;
-        unsigned long long taken_lo = 0, taken_hi = 0;  // one byte of "children already entered" per level 1..8 / 9..16
+        OctTaken taken;
         for (;;) {
             const ONode *__restrict__ me = nodes + s_off[l] + nd;
             const long long cb = me[0].begin;
             const int cc = (int) (me[1].begin - cb);
-            const unsigned int tk = (l <= 8) ? (unsigned int) (taken_lo >> (8 * (l - 1))) & 0xffu
-                                             : (unsigned int) (taken_hi >> (8 * (l - 9))) & 0xffu;
+            const unsigned int tk = taken_get(taken, l);
             double kd = INFINITY;
             int kc = 8;
             const ONode *__restrict__ ch = nodes + s_off[l - 1] + cb;
@@ -284,15 +272,13 @@ k_knn_normals(const SPoint *__restrict__ sp, long long n, OctView oct, const dou
                 nd = me[0].parent;
                 ++l;
             } else {
-                if (l <= 8) taken_lo |= 1ULL << (8 * (l - 1) + kc);
-                else taken_hi |= 1ULL << (8 * (l - 9) + kc);
+                taken_set(taken, l, kc);
                 if (l == 1) {
                     scan_leaf(s_off[0] + cb + kc);
                 } else {
                     --l;
                     nd = cb + kc;
-                    if (l <= 8) taken_lo &= ~(0xffULL << (8 * (l - 1)));
-                    else taken_hi &= ~(0xffULL << (8 * (l - 9)));
+                    taken_clear(taken, l);
                 }
             }
         }
@@ -482,8 +468,6 @@ k_lsq_final(const double *__restrict__ pd, const long long *__restrict__ pc, int
     }
 }
 
-inline unsigned int grid_for(long long n, int block = 256) { return (unsigned int) ((n + block - 1) / block); }
-
 int need_plain_cloud(me_ctx *ctx, int slot, const char *who, bool need_index) {
     if (slot < 0 || slot > 1) return ctx->fail(ME_ERR_ARG, std::string(who) + ": bad slot");
     Cloud &c = ctx->cloud[slot];
@@ -542,7 +526,7 @@ int estimate_normals(me_ctx *ctx, int slot, int knn, double *normals_host, int32
     {
         TimerScope ts(ctx, "normals");
         const size_t lds = (size_t) knn * kKnnBlock * 12;
-        hipLaunchKernelGGL(k_knn_normals, dim3(grid_for(n, kKnnBlock)), dim3(kKnnBlock), lds, ctx->stream, c.sp.as<SPoint>(), n,
+        hipLaunchKernelGGL(k_knn_normals, dim3(blocks_of(n, kKnnBlock)), dim3(kKnnBlock), lds, ctx->stream, c.sp.as<SPoint>(), n,
                            c.oct, c.xyz.as<double>(), knn, c.normals.as<double>(), d_idx, d_d2);
     }
     ME_CHECK(ctx, hipGetLastError());
@@ -564,7 +548,7 @@ int knn_lists(me_ctx *ctx, int slot, int k, int *idx_device, double *d2_device) 
     if (k < 1 || k > kKnnMax) return ctx->fail(ME_ERR_ARG, "knn_lists: k must be in [1, 40]");
     Cloud &c = ctx->cloud[slot];
     const size_t lds = (size_t) k * kKnnBlock * 12;
-    hipLaunchKernelGGL(k_knn_normals, dim3(grid_for(c.n, kKnnBlock)), dim3(kKnnBlock), lds, ctx->stream, c.sp.as<SPoint>(), c.n,
+    hipLaunchKernelGGL(k_knn_normals, dim3(blocks_of(c.n, kKnnBlock)), dim3(kKnnBlock), lds, ctx->stream, c.sp.as<SPoint>(), c.n,
                        c.oct, c.xyz.as<double>(), k, (double *) nullptr, idx_device, d2_device);
     ME_CHECK(ctx, hipGetLastError());
     return ME_OK;
@@ -581,7 +565,7 @@ int gicp_covariances(me_ctx *ctx, int slot, double epsilon, double *cov_host) {
     ME_CHECK(ctx, c.cov.ensure((size_t) n * 72));
     {
         TimerScope ts(ctx, "normals");
-        hipLaunchKernelGGL(k_gicp_cov, dim3(grid_for(n)), dim3(256), 0, ctx->stream, c.normals.as<double>(), n, epsilon,
+        hipLaunchKernelGGL(k_gicp_cov, dim3(blocks_of(n)), dim3(256), 0, ctx->stream, c.normals.as<double>(), n, epsilon,
                            c.cov.as<double>());
     }
     if (cov_host) ME_TRY(copy_d2h(ctx, cov_host, c.cov.p, (size_t) n * 72));
@@ -609,7 +593,7 @@ int rotate_attributes(me_ctx *ctx, int slot, const double *T) {
     Rot3 R;
     for (int r = 0; r < 3; ++r)
         for (int k = 0; k < 3; ++k) R.r[3 * r + k] = T[4 * r + k];
-    hipLaunchKernelGGL(k_rotate_attr, dim3(grid_for(c.n)), dim3(256), 0, ctx->stream,
+    hipLaunchKernelGGL(k_rotate_attr, dim3(blocks_of(c.n)), dim3(256), 0, ctx->stream,
                        c.have_normals ? c.normals.as<double>() : nullptr, c.have_cov ? c.cov.as<double>() : nullptr, c.n, R);
     return ME_OK;
 }

@@ -101,7 +101,6 @@ __global__ void k_render_entropy(const double *__restrict__ xyz, const double *_
     xyz_out[3 * m + 2] = xyz[3 * o + 2];
 }
 
-static inline unsigned int blocks_for(long long n) { return (unsigned int) ((n + 255) / 256); }
 
 int render_distance(me_ctx *ctx, int qslot, double dis, double gate, int gate_mode, double *rgb, uint8_t *inlier) {
     if (qslot < 0 || qslot > 1 || !rgb || !(dis > 0)) return ctx->fail(ME_ERR_ARG, "me_render_distance: bad argument");
@@ -116,7 +115,7 @@ int render_distance(me_ctx *ctx, int qslot, double dis, double gate, int gate_mo
     ME_CHECK(ctx, col.ensure((size_t) n * 24));
     ME_CHECK(ctx, inl.ensure((size_t) n));
     const double g = (gate < 0) ? -1.0 : (gate_mode == ME_GATE_LT_SQUARED ? gate * gate : gate);
-    hipLaunchKernelGGL(k_render_distance, dim3(blocks_for(n)), dim3(256), 0, ctx->stream, q.sp.as<SPoint>(), q.nn_d2.as<double>(), n,
+    hipLaunchKernelGGL(k_render_distance, dim3(blocks_of(n)), dim3(256), 0, ctx->stream, q.sp.as<SPoint>(), q.nn_d2.as<double>(), n,
                        dis, g, gate_mode == ME_GATE_LT_SQUARED ? 1 : 0, col.as<double>(), inlier ? inl.as<unsigned char>() : nullptr);
     ME_TRY(copy_d2h(ctx, rgb, col.p, (size_t) n * 24));
     if (inlier) ME_TRY(copy_d2h(ctx, inlier, inl.p, (size_t) n));
@@ -147,7 +146,7 @@ int render_entropy(me_ctx *ctx, int slot, double *xyz_out, double *rgb_out, long
     ME_CHECK(ctx, eo.ensure((size_t) n * 8));
     ME_CHECK(ctx, fl.ensure((size_t) n * 4));
     ME_CHECK(ctx, ps.ensure((size_t) n * 4));
-    hipLaunchKernelGGL(k_entropy_unpermute, dim3(blocks_for(n)), dim3(256), 0, ctx->stream, c.sp.as<SPoint>(), c.mme_ent.as<double>(),
+    hipLaunchKernelGGL(k_entropy_unpermute, dim3(blocks_of(n)), dim3(256), 0, ctx->stream, c.sp.as<SPoint>(), c.mme_ent.as<double>(),
                        c.mme_val.as<unsigned char>(), n, eo.as<double>(), fl.as<unsigned int>());
     ME_TRY(exclusive_scan_u32(ctx, fl.as<unsigned int>(), ps.as<unsigned int>(), n));
     unsigned int last_pos = 0, last_flag = 0;
@@ -171,7 +170,7 @@ int render_entropy(me_ctx *ctx, int slot, double *xyz_out, double *rgb_out, long
     DevBuf &xo = ctx->tmp[3], &co = ctx->tmp[4];
     ME_CHECK(ctx, xo.ensure((size_t) m * 24));
     ME_CHECK(ctx, co.ensure((size_t) m * 24));
-    hipLaunchKernelGGL(k_render_entropy, dim3(blocks_for(n)), dim3(256), 0, ctx->stream, c.xyz.as<double>(), eo.as<double>(),
+    hipLaunchKernelGGL(k_render_entropy, dim3(blocks_of(n)), dim3(256), 0, ctx->stream, c.xyz.as<double>(), eo.as<double>(),
                        fl.as<unsigned int>(), ps.as<unsigned int>(), n, min_abs, max_abs, xo.as<double>(), co.as<double>());
     ME_TRY(copy_d2h(ctx, xyz_out, xo.p, (size_t) m * 24));
     ME_TRY(copy_d2h(ctx, rgb_out, co.p, (size_t) m * 24));

@@ -686,7 +686,6 @@ __global__ void k_vds_mean(const double *__restrict__ xyz, const unsigned int *_
     out[3 * v + 2] = sz / cnt;
 }
 
-static inline unsigned int grid_for(long long n, int block = 256) { return (unsigned int) std::max<long long>(1, (n + block - 1) / block); }
 
 // SCS over a device-resident sparse W table: writes sum(scs_i) and #voxels-with-neighbours to d_sum / d_count
 static int scs_device(me_ctx *ctx, const unsigned long long *mkey, const double *mw, long long M, int scs_radius,
@@ -699,7 +698,7 @@ static int scs_device(me_ctx *ctx, const unsigned long long *mkey, const double 
     ME_CHECK(ctx, scs_d.ensure((size_t) M * 8));
     ME_CHECK(ctx, has_d.ensure((size_t) M * 4));
     ME_CHECK(ctx, hipMemsetAsync(hk.p, 0xFF, (size_t) hsize * 8, ctx->stream));
-    hipLaunchKernelGGL(k_hash_insert_keys, dim3(grid_for(M)), dim3(256), 0, ctx->stream, mkey, M, hk.as<unsigned long long>(),
+    hipLaunchKernelGGL(k_hash_insert_keys, dim3(blocks_of(M)), dim3(256), 0, ctx->stream, mkey, M, hk.as<unsigned long long>(),
                        hv.as<unsigned int>(), (unsigned int) (hsize - 1));
     const int side = 2 * scs_radius + 1;
     const size_t lds = (size_t) side * side * side * 8;
@@ -745,7 +744,7 @@ int w2_batch(me_ctx *ctx, const double *mu1, const double *sigma1, const int32_t
     for (int k = 0; k < 6; ++k) ME_TRY(copy_h2d(ctx, b[k].p, src[k], sz[k]));
     {
         TimerScope ts(ctx, "w2");
-        hipLaunchKernelGGL(k_w2_batch, dim3(grid_for(count)), dim3(256), 0, ctx->stream, b[0].as<double>(), b[1].as<double>(),
+        hipLaunchKernelGGL(k_w2_batch, dim3(blocks_of(count)), dim3(256), 0, ctx->stream, b[0].as<double>(), b[1].as<double>(),
                            b[2].as<int>(), b[3].as<double>(), b[4].as<double>(), b[5].as<int>(), count, b[6].as<double>());
     }
     ME_TRY(copy_d2h(ctx, w, b[6].p, sz[6]));
@@ -774,7 +773,7 @@ int scs_table(me_ctx *ctx, const int32_t *keys, const double *w, long long n, in
     ME_CHECK(ctx, hipMemsetAsync(d_err, 0, 4, ctx->stream));
     ME_TRY(copy_h2d(ctx, k3.p, keys, (size_t) n * 12));
     ME_TRY(copy_h2d(ctx, ww.p, w, (size_t) n * 8));
-    hipLaunchKernelGGL(k_pack_keys, dim3(grid_for(n)), dim3(256), 0, ctx->stream, k3.as<int>(), n, kk.as<unsigned long long>(), d_err);
+    hipLaunchKernelGGL(k_pack_keys, dim3(blocks_of(n)), dim3(256), 0, ctx->stream, k3.as<int>(), n, kk.as<unsigned long long>(), d_err);
     ME_TRY(scs_device(ctx, kk.as<unsigned long long>(), ww.as<double>(), n, scs_radius, d_sum, d_cnt));
     int h_err = 0;
     double h_s = 0;
@@ -824,7 +823,7 @@ static int voxel_build_onepass(me_ctx *ctx, Cloud &c, double voxel_size, bool ra
         ME_CHECK(ctx, hipMemsetAsync(cnt, 0, kVoxCounterBytes, ctx->stream));
         ME_CHECK(ctx, ibuf.ensure((size_t) cap * 12));      // rec_n | compacted slot indices | sorted slot indices
         TimerScope ts(ctx, "voxel");
-        hipLaunchKernelGGL(k_vox_records, dim3(grid_for(n)), dim3(256), 0, ctx->stream, sp, n, vp, c.slab, kbuf.as<unsigned long long>(),
+        hipLaunchKernelGGL(k_vox_records, dim3(blocks_of(n)), dim3(256), 0, ctx->stream, sp, n, vp, c.slab, kbuf.as<unsigned long long>(),
                            ibuf.as<int>(), sbuf.as<double>(), cnt + 2, (unsigned int) nw, (unsigned int) rsize, reinterpret_cast<int *>(cnt));
         slot_key_src = kbuf.as<unsigned long long>();
         rec_n_src = ibuf.as<int>();
@@ -848,7 +847,7 @@ static int voxel_build_onepass(me_ctx *ctx, Cloud &c, double voxel_size, bool ra
     unsigned int *cidx = ibuf.as<unsigned int>() + cap, *perm_r = cidx + cap;
     unsigned int *flags = mbuf.as<unsigned int>(), *pos = flags + cap;
     // the used slots, compacted in slot order
-    hipLaunchKernelGGL(k_used_flags, dim3(grid_for(S)), dim3(256), 0, ctx->stream, slot_key, S, flags);
+    hipLaunchKernelGGL(k_used_flags, dim3(blocks_of(S)), dim3(256), 0, ctx->stream, slot_key, S, flags);
     ME_TRY(exclusive_scan_u32_plain(ctx, flags, pos, S));
     unsigned int last_pos = 0, last_flag = 0;
     {
@@ -858,10 +857,10 @@ static int voxel_build_onepass(me_ctx *ctx, Cloud &c, double voxel_size, bool ra
         ME_TRY(mg.sync());
     }
     const long long R = (long long) last_pos + last_flag;  // run records
-    hipLaunchKernelGGL(k_compact_used, dim3(grid_for(S)), dim3(256), 0, ctx->stream, slot_key, (const unsigned int *) flags,
+    hipLaunchKernelGGL(k_compact_used, dim3(blocks_of(S)), dim3(256), 0, ctx->stream, slot_key, (const unsigned int *) flags,
                        (const unsigned int *) pos, S, ckey, cidx);
     ME_TRY(sort_pairs_merge_u64_u32(ctx, ckey, skey, cidx, perm_r, R));
-    hipLaunchKernelGGL(k_head_flags_shifted, dim3(grid_for(R)), dim3(256), 0, ctx->stream, (const unsigned long long *) skey, R, vp.pos_bits, flags);
+    hipLaunchKernelGGL(k_head_flags_shifted, dim3(blocks_of(R)), dim3(256), 0, ctx->stream, (const unsigned long long *) skey, R, vp.pos_bits, flags);
     ME_TRY(exclusive_scan_u32_plain(ctx, flags, pos, R));
     unsigned long long last_key = 0;
     {
@@ -882,7 +881,7 @@ static int voxel_build_onepass(me_ctx *ctx, Cloud &c, double voxel_size, bool ra
     ME_CHECK(ctx, c.vox_sigma.ensure((size_t) std::max<long long>(V, 1) * 72));
     ME_CHECK(ctx, c.vox_entropy.ensure((size_t) std::max<long long>(V, 1) * 8));
     // (k_seg_scatter also writes the heads' keys: into ckey, dead since the sort)
-    hipLaunchKernelGGL(k_seg_scatter, dim3(grid_for(R)), dim3(256), 0, ctx->stream, (const unsigned long long *) skey, (const unsigned int *) flags,
+    hipLaunchKernelGGL(k_seg_scatter, dim3(blocks_of(R)), dim3(256), 0, ctx->stream, (const unsigned long long *) skey, (const unsigned int *) flags,
                        (const unsigned int *) pos, R, ckey, seg_start);
     if (!has_sentinel) hipLaunchKernelGGL(k_set_u32v, dim3(1), dim3(1), 0, ctx->stream, seg_start, V, (unsigned int) R);
     if (V > 0) {
@@ -942,7 +941,7 @@ int voxel_build(me_ctx *ctx, int slot, double voxel_size, bool raw) {
     unsigned int *wave_runs = wbuf.as<unsigned int>(), *wave_off = wave_runs + nw;
     {
         TimerScope ts(ctx, "voxel");
-        hipLaunchKernelGGL(k_vox_count_runs, dim3(grid_for(n)), dim3(256), 0, ctx->stream, sp, n, voxel_size, c.slab, wave_runs, d_err);
+        hipLaunchKernelGGL(k_vox_count_runs, dim3(blocks_of(n)), dim3(256), 0, ctx->stream, sp, n, voxel_size, c.slab, wave_runs, d_err);
     }
     ME_TRY(exclusive_scan_u32_plain(ctx, wave_runs, wave_off, nw));  // (plain kernels: this build runs beside the other lane's full-chip kernels)
     unsigned int last_off = 0, last_runs = 0;
@@ -972,7 +971,7 @@ int voxel_build(me_ctx *ctx, int slot, double voxel_size, bool raw) {
     unsigned int *flags = mbuf.as<unsigned int>(), *pos = flags + R;
     {
         TimerScope ts(ctx, "voxel");
-        hipLaunchKernelGGL(k_vox_pass1, dim3(grid_for(n)), dim3(256), 0, ctx->stream, sp, n, voxel_size, c.slab, wave_off, rec_key,
+        hipLaunchKernelGGL(k_vox_pass1, dim3(blocks_of(n)), dim3(256), 0, ctx->stream, sp, n, voxel_size, c.slab, wave_off, rec_key,
                            iota, rec_n, rec_sum, d_err);
     }
     // radix sort is stable: the sorted order is preserved inside every voxel (fixed summation order)
@@ -981,7 +980,7 @@ int voxel_build(me_ctx *ctx, int slot, double voxel_size, bool raw) {
 #else
     ME_TRY(sort_pairs_u64_u32(ctx, rec_key, skey, iota, perm_r, R, 0, 63));
 #endif
-    hipLaunchKernelGGL(k_head_flags, dim3(grid_for(R)), dim3(256), 0, ctx->stream, skey, R, flags);
+    hipLaunchKernelGGL(k_head_flags, dim3(blocks_of(R)), dim3(256), 0, ctx->stream, skey, R, flags);
     ME_TRY(exclusive_scan_u32_plain(ctx, flags, pos, R));
     unsigned int last_pos = 0, last_flag = 0;
     unsigned long long last_key = 0;
@@ -1009,7 +1008,7 @@ int voxel_build(me_ctx *ctx, int slot, double voxel_size, bool raw) {
     ME_CHECK(ctx, c.vox_mu.ensure((size_t) std::max<long long>(V, 1) * 24));
     ME_CHECK(ctx, c.vox_sigma.ensure((size_t) std::max<long long>(V, 1) * 72));
     ME_CHECK(ctx, c.vox_entropy.ensure((size_t) std::max<long long>(V, 1) * 8));
-    hipLaunchKernelGGL(k_seg_scatter, dim3(grid_for(R)), dim3(256), 0, ctx->stream, skey, flags, pos, R,
+    hipLaunchKernelGGL(k_seg_scatter, dim3(blocks_of(R)), dim3(256), 0, ctx->stream, skey, flags, pos, R,
                        c.vox_key.as<unsigned long long>(), seg_start);
     if (!has_sentinel)  // (with a sentinel segment, entry V is its start, written by the scatter)
         hipLaunchKernelGGL(k_set_u32v, dim3(1), dim3(1), 0, ctx->stream, seg_start, V, (unsigned int) R);
@@ -1018,7 +1017,7 @@ int voxel_build(me_ctx *ctx, int slot, double voxel_size, bool raw) {
         const dim3 gv((unsigned int) ((V + 3) / 4));
         hipLaunchKernelGGL(k_vox_mean, gv, dim3(256), 0, ctx->stream, perm_r, seg_start, V, rec_n, rec_sum, rec_vox, c.vox_n.as<int>(),
                            c.vox_mu.as<double>());
-        hipLaunchKernelGGL(k_vox_pass2, dim3(grid_for(n)), dim3(256), 0, ctx->stream, sp, n, voxel_size, c.slab, wave_off, rec_vox,
+        hipLaunchKernelGGL(k_vox_pass2, dim3(blocks_of(n)), dim3(256), 0, ctx->stream, sp, n, voxel_size, c.slab, wave_off, rec_vox,
                            c.vox_mu.as<double>(), rec_m2, d_err);
         hipLaunchKernelGGL(k_vox_final, gv, dim3(256), 0, ctx->stream, perm_r, seg_start, V, rec_m2, c.vox_n.as<int>(), raw ? 1 : 0,
                            c.vox_sigma.as<double>(), c.vox_entropy.as<double>());
@@ -1043,7 +1042,7 @@ int voxel_export(me_ctx *ctx, int slot, int32_t *keys, int32_t *npts, double *mu
     if (cap < V) return ctx->fail(ME_ERR_CAPACITY, "me_voxel_gaussians: capacity too small");
     if (keys) {
         ME_CHECK(ctx, ctx->tmp[0].ensure((size_t) V * 12));
-        hipLaunchKernelGGL(k_unpack_keys, dim3(grid_for(V)), dim3(256), 0, ctx->stream, c.vox_key.as<unsigned long long>(), V,
+        hipLaunchKernelGGL(k_unpack_keys, dim3(blocks_of(V)), dim3(256), 0, ctx->stream, c.vox_key.as<unsigned long long>(), V,
                            ctx->tmp[0].as<int>());
         ME_TRY(copy_d2h(ctx, keys, ctx->tmp[0].p, (size_t) V * 12));
     }
@@ -1075,7 +1074,7 @@ int awd_scs(me_ctx *ctx, double voxel_size, int min_pts, int scs_radius, double 
     ME_CHECK(ctx, mpos.ensure((size_t) Ve * 4));
     ME_CHECK(ctx, ctx->red.ensure(256));
     long long *d_cnt = ctx->red.as<long long>();  // [0] active, [1] matched, [2..] scratch
-    hipLaunchKernelGGL(k_join, dim3(grid_for(Ve)), dim3(256), 0, ctx->stream, E.vox_key.as<unsigned long long>(),
+    hipLaunchKernelGGL(k_join, dim3(blocks_of(Ve)), dim3(256), 0, ctx->stream, E.vox_key.as<unsigned long long>(),
                        E.vox_n.as<int>(), Ve, G.vox_key.as<unsigned long long>(), G.vox_n.as<int>(), Vg, min_pts, gi.as<int>(),
                        match.as<unsigned int>(), active.as<unsigned int>());
     hipLaunchKernelGGL(k_count_u32, dim3(1), dim3(256), 0, ctx->stream, active.as<unsigned int>(), Ve, d_cnt);
@@ -1113,7 +1112,7 @@ int awd_scs(me_ctx *ctx, double voxel_size, int min_pts, int scs_radius, double 
     if (rows) ME_CHECK(ctx, rows_d.ensure((size_t) M * 27 * 8));
     {
         TimerScope ts(ctx, "w2");
-        hipLaunchKernelGGL(k_w2, dim3(grid_for(Ve)), dim3(256), 0, ctx->stream, match.as<unsigned int>(), mpos.as<unsigned int>(),
+        hipLaunchKernelGGL(k_w2, dim3(blocks_of(Ve)), dim3(256), 0, ctx->stream, match.as<unsigned int>(), mpos.as<unsigned int>(),
                            gi.as<int>(), Ve, E.vox_key.as<unsigned long long>(), E.vox_n.as<int>(), E.vox_mu.as<double>(),
                            E.vox_sigma.as<double>(), G.vox_n.as<int>(), G.vox_mu.as<double>(), G.vox_sigma.as<double>(),
                            voxel_size, mkey.as<unsigned long long>(), mw_own.as<double>(), rows ? rows_d.as<double>() : nullptr);
@@ -1161,13 +1160,13 @@ static int vds_run(me_ctx *ctx, const double *xyz, long long n, const double lo[
     // voxel_min_bound = GetMinBound() - voxel_size / 2  [Open3D, upstream]
     const double mx = lo[0] - voxel_size * 0.5, my = lo[1] - voxel_size * 0.5, mz = lo[2] - voxel_size * 0.5;
     TimerScope ts(ctx, "downsample");  // (ended before the sort, which has its own scope: scopes do not nest)
-    hipLaunchKernelGGL(k_vds_keys, dim3(grid_for(n)), dim3(256), 0, ctx->stream, xyz, n, voxel_size, mx, my, mz,
+    hipLaunchKernelGGL(k_vds_keys, dim3(blocks_of(n)), dim3(256), 0, ctx->stream, xyz, n, voxel_size, mx, my, mz,
                        keys_in.as<unsigned long long>(), iota.as<unsigned int>(), d_err);
     ts.end();
     ME_TRY(sort_pairs_u64_u32(ctx, keys_in.as<unsigned long long>(), keys.as<unsigned long long>(), iota.as<unsigned int>(),
                               perm.as<unsigned int>(), n, 0, 63));
     DevBuf &pos = ctx->tmp[1];
-    hipLaunchKernelGGL(k_head_flags, dim3(grid_for(n)), dim3(256), 0, ctx->stream, keys.as<unsigned long long>(), n,
+    hipLaunchKernelGGL(k_head_flags, dim3(blocks_of(n)), dim3(256), 0, ctx->stream, keys.as<unsigned long long>(), n,
                        flags.as<unsigned int>());
     ME_TRY(exclusive_scan_u32(ctx, flags.as<unsigned int>(), pos.as<unsigned int>(), n));
     unsigned int last_pos = 0, last_flag = 0;
@@ -1187,11 +1186,11 @@ static int vds_run(me_ctx *ctx, const double *xyz, long long n, const double lo[
     ME_CHECK(ctx, seg_start.ensure((size_t) (V + 1) * 4));
     ME_CHECK(ctx, seg_key.ensure((size_t) V * 8));
     ME_CHECK(ctx, out.ensure((size_t) V * 24));
-    hipLaunchKernelGGL(k_seg_scatter, dim3(grid_for(n)), dim3(256), 0, ctx->stream, keys.as<unsigned long long>(),
+    hipLaunchKernelGGL(k_seg_scatter, dim3(blocks_of(n)), dim3(256), 0, ctx->stream, keys.as<unsigned long long>(),
                        flags.as<unsigned int>(), pos.as<unsigned int>(), n, seg_key.as<unsigned long long>(),
                        seg_start.as<unsigned int>());
     hipLaunchKernelGGL(k_set_u32v, dim3(1), dim3(1), 0, ctx->stream, seg_start.as<unsigned int>(), V, (unsigned int) n);
-    hipLaunchKernelGGL(k_vds_mean, dim3(grid_for(V)), dim3(256), 0, ctx->stream, xyz, perm.as<unsigned int>(),
+    hipLaunchKernelGGL(k_vds_mean, dim3(blocks_of(V)), dim3(256), 0, ctx->stream, xyz, perm.as<unsigned int>(),
                        seg_start.as<unsigned int>(), V, out.as<double>());
     *V_out = V;
     return ME_OK;
@@ -1210,7 +1209,7 @@ int voxel_downsample(me_ctx *ctx, int slot, double voxel_size, long long *n_out)
     if (!c.xyz.owned) ME_CHECK(ctx, c.xyz.ensure((size_t) V * 24));  // (a borrowed input buffer is the caller's: the result gets its own)
     ME_CHECK(ctx, hipMemcpyAsync(c.xyz.p, out.p, (size_t) V * 24, hipMemcpyDeviceToDevice, ctx->stream));
     if (c.have_normals) {  // Open3D averages the normals of a voxel as well (sum / count, not re-normalised)
-        hipLaunchKernelGGL(k_vds_mean, dim3(grid_for(V)), dim3(256), 0, ctx->stream, c.normals.as<double>(), ctx->tmp[3].as<unsigned int>(),
+        hipLaunchKernelGGL(k_vds_mean, dim3(blocks_of(V)), dim3(256), 0, ctx->stream, c.normals.as<double>(), ctx->tmp[3].as<unsigned int>(),
                            ctx->tmp[0].as<unsigned int>(), V, out.as<double>());
         ME_CHECK(ctx, hipMemcpyAsync(c.normals.p, out.p, (size_t) V * 24, hipMemcpyDeviceToDevice, ctx->stream));
     }
@@ -1444,7 +1443,7 @@ int voxel_metrics(me_ctx *ctx, int slot, double voxel_size, double gate, int gat
         ME_CHECK(ctx, hipMemsetAsync(cnt, 0, kVoxCounterBytes, ctx->stream));
         {
             TimerScope ts(ctx, "voxel_metrics");
-            hipLaunchKernelGGL(k_voxm_records, dim3(grid_for(n)), dim3(256), 0, ctx->stream, c.sp.as<SPoint>(), c.nn_d2.as<double>(),
+            hipLaunchKernelGGL(k_voxm_records, dim3(blocks_of(n)), dim3(256), 0, ctx->stream, c.sp.as<SPoint>(), c.nn_d2.as<double>(),
                                mme ? c.mme_ent.as<double>() : nullptr, mme ? c.mme_val.as<unsigned char>() : nullptr, n, voxel_size, c.slab,
                                st, pbuf.as<unsigned long long>(), pbuf.as<unsigned long long>() + cap, cbuf.as<uint2>(), dbuf.as<double>(),
                                cnt + 2, (unsigned int) n_rows, (unsigned int) rsize, reinterpret_cast<int *>(cnt));
@@ -1468,7 +1467,7 @@ int voxel_metrics(me_ctx *ctx, int slot, double voxel_size, double gate, int gat
     unsigned long long *ka = kbuf.as<unsigned long long>(), *kb = ka + cap;
     unsigned int *flags = ibuf.as<unsigned int>(), *pos = flags + cap, *cidx = pos + cap, *perm1 = cidx + cap, *perm2 = perm1 + cap;
     // the used slots, compacted in slot order
-    hipLaunchKernelGGL(k_used_flags, dim3(grid_for(S)), dim3(256), 0, ctx->stream, rec_pos, S, flags);
+    hipLaunchKernelGGL(k_used_flags, dim3(blocks_of(S)), dim3(256), 0, ctx->stream, rec_pos, S, flags);
     ME_TRY(exclusive_scan_u32_plain(ctx, flags, pos, S));
     unsigned int last_pos = 0, last_flag = 0;
     {
@@ -1478,13 +1477,13 @@ int voxel_metrics(me_ctx *ctx, int slot, double voxel_size, double gate, int gat
         ME_TRY(mg.sync());
     }
     const long long R = (long long) last_pos + last_flag;  // run records (>= 1: the cloud is not empty)
-    hipLaunchKernelGGL(k_compact_used, dim3(grid_for(S)), dim3(256), 0, ctx->stream, rec_pos, (const unsigned int *) flags,
+    hipLaunchKernelGGL(k_compact_used, dim3(blocks_of(S)), dim3(256), 0, ctx->stream, rec_pos, (const unsigned int *) flags,
                        (const unsigned int *) pos, S, ka, cidx);
     // records in cloud order (row, run), then stably by voxel: a fixed order inside every voxel
     ME_TRY(sort_pairs_merge_u64_u32(ctx, ka, kb, cidx, perm1, R));
-    hipLaunchKernelGGL(k_voxm_gather_keys, dim3(grid_for(R)), dim3(256), 0, ctx->stream, (const unsigned int *) perm1, rec_vkey, R, ka);
+    hipLaunchKernelGGL(k_voxm_gather_keys, dim3(blocks_of(R)), dim3(256), 0, ctx->stream, (const unsigned int *) perm1, rec_vkey, R, ka);
     ME_TRY(sort_pairs_merge_u64_u32(ctx, ka, kb, perm1, perm2, R));
-    hipLaunchKernelGGL(k_head_flags, dim3(grid_for(R)), dim3(256), 0, ctx->stream, (const unsigned long long *) kb, R, flags);
+    hipLaunchKernelGGL(k_head_flags, dim3(blocks_of(R)), dim3(256), 0, ctx->stream, (const unsigned long long *) kb, R, flags);
     ME_TRY(exclusive_scan_u32_plain(ctx, flags, pos, R));
     {
         MailGuard mg(ctx);
@@ -1500,7 +1499,7 @@ int voxel_metrics(me_ctx *ctx, int slot, double voxel_size, double gate, int gat
     ME_CHECK(ctx, nn_d.ensure((size_t) V * sizeof(me_nn_partial)));
     ME_CHECK(ctx, sh_d.ensure((size_t) V * 8));
     ME_CHECK(ctx, nh_d.ensure((size_t) V * 8));
-    hipLaunchKernelGGL(k_seg_scatter, dim3(grid_for(R)), dim3(256), 0, ctx->stream, (const unsigned long long *) kb, (const unsigned int *) flags,
+    hipLaunchKernelGGL(k_seg_scatter, dim3(blocks_of(R)), dim3(256), 0, ctx->stream, (const unsigned long long *) kb, (const unsigned int *) flags,
                        (const unsigned int *) pos, R, vkey_d.as<unsigned long long>(), seg_d.as<unsigned int>());
     hipLaunchKernelGGL(k_set_u32v, dim3(1), dim3(1), 0, ctx->stream, seg_d.as<unsigned int>(), V, (unsigned int) R);
     {

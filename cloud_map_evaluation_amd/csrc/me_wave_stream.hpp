@@ -57,5 +57,27 @@ __device__ __forceinline__ void cell_of(unsigned long long code, int shift, int 
     cz = (int) compact21(c >> 2);
 }
 
+// The query of one lane of a wave_stream kernel: the sorted point i (inactive past the end: zeros, and the stream skips the lane), its
+// original index and its cell at the grid's shift.
+struct StreamQuery {
+    bool active;
+    double qx, qy, qz;
+    long long idx;
+    int cx, cy, cz;
+};
+__device__ __forceinline__ StreamQuery stream_query(const SPoint *__restrict__ sp, const unsigned long long *__restrict__ codes, long long i,
+                                                    long long n, int shift) {
+    StreamQuery q{i < n, 0, 0, 0, 0, 0, 0, 0};
+    if (q.active) {
+        const SPoint p = sp[i];
+        q.qx = p.x;
+        q.qy = p.y;
+        q.qz = p.z;
+        q.idx = p.idx;
+        cell_of(codes[i], shift, q.cx, q.cy, q.cz);
+    }
+    return q;
+}
+
 }  // namespace me
 #endif
