@@ -32,6 +32,7 @@ SYMBOLS = [
     "me_transform_cloud", "me_perturb_cloud", "me_voxel_downsample_into", "me_fpfh", "me_fpfh_match", "me_global_register",
     "me_statistical_outlier", "me_radius_outlier", "me_outlier_select_into",
     "me_cluster_dbscan", "me_cluster_sizes", "me_cluster_keep",
+    "me_local_geometry", "me_local_geometry_fetch",
     "me_set_normals", "me_get_normals", "me_estimate_normals", "me_gicp_covariances", "me_get_covariances", "me_icp_lsq_sums",
     "me_nn1", "me_icp_p2p_sums", "me_render_distance", "me_render_entropy", "me_nn_stats", "me_nn_partial_sums", "me_nn_sigma_sums", "me_nn_finalize", "me_chamfer",
     "me_mme", "me_voxel_gaussians", "me_voxel_metrics", "me_awd_scs", "me_w2_batch", "me_scs_table", "me_run_suite", "me_run_suite_from", "me_mme_fetch",
@@ -187,6 +188,19 @@ class ClusterInfo(C.Structure):
     ]
 
 
+class LocalGeomOut(C.Structure):
+    _fields_ = [
+        ("n", C.c_int64),
+        ("n_valid", C.c_int64),
+        ("sum_l3", C.c_double),
+        ("sum_linearity", C.c_double),
+        ("sum_planarity", C.c_double),
+        ("sum_sphericity", C.c_double),
+        ("sum_surface_variation", C.c_double),
+        ("sum_k", C.c_int64),
+    ]
+
+
 _lib = None
 
 
@@ -265,6 +279,10 @@ def load():
     L.me_cluster_sizes.argtypes = [vp, C.c_int, vp, C.c_int64, C.POINTER(C.c_int64)]
     L.me_cluster_keep.argtypes = [vp, C.c_int, C.c_int64, C.c_int64, vp, C.POINTER(OutlierInfo)]
     for f in ("me_cluster_dbscan", "me_cluster_sizes", "me_cluster_keep"):
+        getattr(L, f).restype = C.c_int
+    L.me_local_geometry.argtypes = [vp, C.c_int, C.c_double, C.c_int, C.POINTER(LocalGeomOut)]
+    L.me_local_geometry_fetch.argtypes = [vp, C.c_int, dp, ip, vp]
+    for f in ("me_local_geometry", "me_local_geometry_fetch"):
         getattr(L, f).restype = C.c_int
     L.me_upload_cloud.argtypes = [vp, C.c_int, dp, C.c_int64, dp, C.c_double]
     L.me_upload_cloud_device.argtypes = [vp, C.c_int, dp, C.c_int64, dp, C.c_double]

@@ -341,6 +341,16 @@ int me_cluster_keep(me_ctx *ctx, int slot, int64_t min_cluster_size, int64_t kee
     return me::cluster_keep(ctx, slot, min_cluster_size, keep_largest, keep, info);
 }
 
+int me_local_geometry(me_ctx *ctx, int slot, double radius, int min_k, me_local_geom_out *out) {
+    if (!ctx) return ME_ERR_ARG;
+    return me::local_geometry(ctx, slot, radius, min_k, out);
+}
+
+int me_local_geometry_fetch(me_ctx *ctx, int slot, double *eig, int32_t *k, uint8_t *valid) {
+    if (!ctx) return ME_ERR_ARG;
+    return me::local_geometry_fetch(ctx, slot, eig, k, valid);
+}
+
 int me_transform_cloud(me_ctx *ctx, int slot, const double *T) {
     if (!ctx) return ME_ERR_ARG;
     return me::cloud_transform(ctx, slot, T);

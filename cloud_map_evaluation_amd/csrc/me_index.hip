@@ -650,6 +650,7 @@ int cloud_upload(me_ctx *ctx, int slot, const double *src, bool src_on_device, l
         e.have_normals = e.have_cov = false;
         e.outlier_keep_valid = false;
         e.cluster_valid = false;
+        e.lg_have = false;
         ctx->cloud[1 - slot].nn_ref_slot = -1;
         return ME_OK;
     }
@@ -806,6 +807,7 @@ void cloud_reset_replaced(me_ctx *ctx, int slot, long long n, double cell_size_r
     D.fpfh_valid = false;
     D.outlier_keep_valid = false;
     D.cluster_valid = false;
+    D.lg_have = false;
     D.slab = ctx->slab;
     D.n_unres = 0;
     D.slab_identity = true;
@@ -938,6 +940,7 @@ int cloud_build_index(me_ctx *ctx, int slot, double cell_size) {
     c.fine_h = std::ldexp(cell_h, -c.shift);
     c.index_valid = false;
     c.mme_have = false;  // (the sorted order changes)
+    c.lg_have = false;
 #ifdef ME_AB
     c.mme_feat_valid = false;
 #endif

@@ -232,6 +232,10 @@ struct Cloud {
     DevBuf cluster_labels, cluster_sizes;
     long long cluster_n = 0;
     bool cluster_valid = false;
+    // last me_local_geometry of this cloud, SORTED order (me_localgeom.hip): eigenvalues double[n][3] (l1 >= l2 >= l3, zeros where
+    // invalid), neighbour count int32[n], validity byte; dropped with the points and with the sorted order (cloud_build_index)
+    DevBuf lg_eig, lg_k, lg_val;
+    bool lg_have = false;
 };
 
 struct TimerRec {
@@ -488,6 +492,9 @@ int statistical_outlier(me_ctx *ctx, int slot, int nb_neighbors, double std_rati
                         me_outlier_info *info);
 int radius_outlier(me_ctx *ctx, int slot, int nb_points, double radius, int32_t *counts_host, uint8_t *keep_host, me_outlier_info *info);
 int outlier_select_into(me_ctx *src_ctx, int src_slot, me_ctx *dst_ctx, int dst_slot, long long *n_out);
+// ---- me_localgeom.hip ----
+int local_geometry(me_ctx *ctx, int slot, double radius, int min_k, me_local_geom_out *out);
+int local_geometry_fetch(me_ctx *ctx, int slot, double *eig_host, int32_t *k_host, uint8_t *valid_host);
 // ---- me_cluster.hip ----
 int cluster_dbscan(me_ctx *ctx, int slot, double eps, int min_points, int32_t *labels_host, int32_t *counts_host, me_cluster_info *info);
 int cluster_sizes(me_ctx *ctx, int slot, int64_t *sizes_host, long long capacity, long long *n_clusters);

@@ -1,0 +1,233 @@
+// me_localgeom.hip — mean plane variance (MPV) and the eigenvalue shape features of every point's radius neighbourhood, on a resident
+// single-GPU cloud.  DESIGN.md section 4.10.
+//   k_local_geom   per point: the neighbours j with d2 < r^2 (strict, the library's radius convention, the query itself removed once)
+//                  streamed through the wave's LDS tile (me_wave_stream.hpp) over the radius grid (cell >= r); k, sum(d) and
+//                  sum(d d^T) with d = p_j - q in fp64 — moments about the QUERY, so that no term exceeds r^2 and the smallest
+//                  eigenvalue keeps its digits on every point (k_mme3 takes them about the round leader's point: me_mme.hip) —
+//                  then C = (sum(d d^T) - sum(d) sum(d)^T / k) / (k - 1), its eigenvalues by jacobi_sym (me_horn.hpp), clamped at 0
+//                  and ordered l1 >= l2 >= l3.  The point is valid iff k >= min_k and l1 > 0; an invalid point stores zeros.
+//                  Per block: the partial sums of l3, linearity, planarity, sphericity, surface variation, k and the valid count.
+//   k_lg_final     the block partials in block order (256 chunks, then one block): a fixed order, bit-identical from run to run, no
+//                  floating-point atomics                                                             (me_local_geometry, "local_geom")
+//   k_lg_unpermute the per-point results, kept in SORTED order on the cloud, back in cloud order           (me_local_geometry_fetch)
+// The file is compiled with -ffp-contract=off: tests/_localgeom_ref.py restates the neighbour test.
+#include <algorithm>
+#include <cmath>
+
+#include "me_horn.hpp"
+#include "me_internal.hpp"
+#include "me_wave_stream.hpp"
+
+namespace me {
+
+namespace {
+
+constexpr int kLgSums = 8;  // l3, linearity, planarity, sphericity, surface variation (double); k, valid points (int64); one spare
+constexpr int kLgStage = 256;
+
+union LgWord {
+    double d;
+    long long i;
+};
+
+// One kernel: the streaming loop alone needs 76 VGPRs (the 9 fp64 sums, the query, d and its products next to the stream's own
+// state), the eigen-solve epilogue brings the kernel to 78 — 6 waves per SIMD either way, no scratch — so a second launch for the
+// epilogue would only add 152 bytes of traffic per point (measured at compile time both ways: DESIGN.md section 4.10).
+__global__ void __launch_bounds__(256)
+k_local_geom(const SPoint *__restrict__ sp, const unsigned long long *__restrict__ codes, long long n, GridView g, double r2, int min_k,
+             double *__restrict__ eig_s, int *__restrict__ k_s, unsigned char *__restrict__ valid_s, LgWord *__restrict__ part,
+             unsigned int nb) {
+    __shared__ WaveTile s_tile[4];
+    __shared__ int2 s_tab[4][kGroupTab + 1];
+    __shared__ double smd[4];
+    __shared__ long long smi[4];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const long long i = (long long) blockIdx.x * 256 + threadIdx.x;
+    const StreamQuery q = stream_query(sp, codes, i, n, g.shift);
+    int cnt = 0;
+    double sx = 0, sy = 0, sz = 0, sxx = 0, sxy = 0, sxz = 0, syy = 0, syz = 0, szz = 0;
+    wave_stream(q.active, q.cx, q.cy, q.cz, sp, g, lane, s_tab[w], &s_tile[w], [&](double px, double py, double pz, int, int) {
+        // d2 is dist2_exact(q, p) up to the sign of d, which the squares drop: the set is the library's
+        const double dx = px - q.qx, dy = py - q.qy, dz = pz - q.qz;
+        if ((dx * dx + dy * dy) + dz * dz < r2) {
+            ++cnt;
+            sx += dx;
+            sy += dy;
+            sz += dz;
+            sxx += dx * dx;
+            sxy += dx * dy;
+            sxz += dx * dz;
+            syy += dy * dy;
+            syz += dy * dz;
+            szz += dz * dz;
+        }
+    });
+    // the query itself (d = 0: it added nothing to the sums) is removed once; its coincident duplicates stay
+    const int k = q.active ? cnt - 1 : 0;
+    double l1 = 0, l2 = 0, l3 = 0;
+    bool ok = false;
+    if (q.active && k >= min_k) {
+        const double kd = (double) k, km = (double) (k - 1);
+        double a[9], d[3], V[9];
+        a[0] = (sxx - sx * sx / kd) / km;
+        a[4] = (syy - sy * sy / kd) / km;
+        a[8] = (szz - sz * sz / kd) / km;
+        a[1] = a[3] = (sxy - sx * sy / kd) / km;
+        a[2] = a[6] = (sxz - sx * sz / kd) / km;
+        a[5] = a[7] = (syz - sy * sz / kd) / km;
+        jacobi_sym(3, a, d, V);
+        double e0 = fmax(d[0], 0.0), e1 = fmax(d[1], 0.0), e2 = fmax(d[2], 0.0);
+        double t;
+        if (e0 < e1) t = e0, e0 = e1, e1 = t;
+        if (e1 < e2) t = e1, e1 = e2, e2 = t;
+        if (e0 < e1) t = e0, e0 = e1, e1 = t;
+        ok = e0 > 0.0;
+        if (ok) l1 = e0, l2 = e1, l3 = e2;
+    }
+    if (q.active) {
+        eig_s[3 * i] = l1;
+        eig_s[3 * i + 1] = l2;
+        eig_s[3 * i + 2] = l3;
+        k_s[i] = k;
+        valid_s[i] = ok ? 1 : 0;
+    }
+    // (the denominators are > 0 on a valid point; every other lane adds zeros)
+    const double lin = ok ? (l1 - l2) / l1 : 0.0, pla = ok ? (l2 - l3) / l1 : 0.0, sph = ok ? l3 / l1 : 0.0;
+    const double sv = ok ? l3 / ((l1 + l2) + l3) : 0.0;
+    const double b0 = block_sum_256(l3, smd);
+    const double b1 = block_sum_256(lin, smd);
+    const double b2 = block_sum_256(pla, smd);
+    const double b3 = block_sum_256(sph, smd);
+    const double b4 = block_sum_256(sv, smd);
+    const long long b5 = block_sum_256_ll(ok ? (long long) k : 0, smi);
+    const long long b6 = block_sum_256_ll(ok ? 1 : 0, smi);
+    if (threadIdx.x == 0) {
+        part[0 * (size_t) nb + blockIdx.x].d = b0;
+        part[1 * (size_t) nb + blockIdx.x].d = b1;
+        part[2 * (size_t) nb + blockIdx.x].d = b2;
+        part[3 * (size_t) nb + blockIdx.x].d = b3;
+        part[4 * (size_t) nb + blockIdx.x].d = b4;
+        part[5 * (size_t) nb + blockIdx.x].i = b5;
+        part[6 * (size_t) nb + blockIdx.x].i = b6;
+    }
+}
+
+// row v of `in` ([kLgSums][nb]) -> out[v * gridDim.x + block]: block b sums the chunk [b chunk, (b + 1) chunk) of the row, thread t
+// taking t, t + 256, ... in order.  Rows 0 - 4 are doubles, 5 - 6 int64.
+__global__ void __launch_bounds__(256)
+k_lg_final(const LgWord *__restrict__ in, long long nb, long long chunk, LgWord *__restrict__ out) {
+    __shared__ double smd[4];
+    __shared__ long long smi[4];
+    const long long b0 = (long long) blockIdx.x * chunk, b1 = b0 + chunk < nb ? b0 + chunk : nb;
+    for (int v = 0; v < 7; ++v) {
+        const LgWord *row = in + (size_t) v * nb;
+        LgWord r;
+        if (v < 5) {
+            double s = 0.0;
+            for (long long b = b0 + threadIdx.x; b < b1; b += 256) s += row[b].d;
+            r.d = block_sum_256(s, smd);
+        } else {
+            long long s = 0;
+            for (long long b = b0 + threadIdx.x; b < b1; b += 256) s += row[b].i;
+            r.i = block_sum_256_ll(s, smi);
+        }
+        if (threadIdx.x == 0) out[(size_t) v * gridDim.x + blockIdx.x] = r;
+    }
+}
+
+__global__ void __launch_bounds__(256)
+k_lg_unpermute(const SPoint *__restrict__ sp, long long n, const double *__restrict__ eig_s, const int *__restrict__ k_s,
+               const unsigned char *__restrict__ valid_s, double *__restrict__ eig_o, int *__restrict__ k_o,
+               unsigned char *__restrict__ valid_o) {
+    const long long i = (long long) blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const long long o = sp[i].idx;
+    if (eig_o) {
+        eig_o[3 * o] = eig_s[3 * i];
+        eig_o[3 * o + 1] = eig_s[3 * i + 1];
+        eig_o[3 * o + 2] = eig_s[3 * i + 2];
+    }
+    if (k_o) k_o[o] = k_s[i];
+    if (valid_o) valid_o[o] = valid_s[i];
+}
+
+}  // namespace
+
+int local_geometry(me_ctx *ctx, int slot, double radius, int min_k, me_local_geom_out *out) {
+    ME_TRY(need_single_gpu_cloud(ctx, slot, "me_local_geometry"));
+    if (!(radius > 0) || !std::isfinite(radius)) return ctx->fail(ME_ERR_ARG, "me_local_geometry: radius must be finite and > 0");
+    if (min_k < 2) return ctx->fail(ME_ERR_ARG, "me_local_geometry: min_k must be >= 2 (the covariance divides by k - 1)");
+    Cloud &c = ctx->cloud[slot];
+    ME_CHECK(ctx, hipSetDevice(ctx->device));
+    // the radius grid, rebuilt as me_mme / me_radius_outlier do: the 27-cell stencil is exact when the cell edge is >= r
+    const double want_h = radius * (1.0 + 0x1p-20);
+    if (!c.index_valid || c.cell_h < want_h || c.cell_h > 1.5 * want_h) {
+        const double req = c.cell_size_req;
+        ME_TRY(cloud_build_index(ctx, slot, radius));
+        c.cell_size_req = req;
+    }
+    const long long n = c.n;
+    c.lg_have = false;
+    ME_CHECK(ctx, c.lg_eig.ensure((size_t) n * 24));
+    ME_CHECK(ctx, c.lg_k.ensure((size_t) n * 4));
+    ME_CHECK(ctx, c.lg_val.ensure((size_t) n));
+    const unsigned int nb = blocks_of(n);
+    // [kLgSums][nb] block partials | [kLgSums][kLgStage] | [kLgSums] totals
+    ME_CHECK(ctx, ctx->red.ensure(((size_t) nb + kLgStage + 1) * kLgSums * 8));
+    LgWord *part = ctx->red.as<LgWord>();
+    LgWord *part2 = part + (size_t) nb * kLgSums;
+    LgWord *tot = part2 + (size_t) kLgStage * kLgSums;
+    {
+        TimerScope ts(ctx, "local_geom");
+        hipLaunchKernelGGL(k_local_geom, dim3(nb), dim3(256), 0, ctx->stream, c.sp.as<SPoint>(), c.codes.as<unsigned long long>(), n, c.grid,
+                           radius * radius, min_k, c.lg_eig.as<double>(), c.lg_k.as<int>(), c.lg_val.as<unsigned char>(), part, nb);
+        const long long chunk = ((long long) nb + kLgStage - 1) / kLgStage;
+        hipLaunchKernelGGL(k_lg_final, dim3(kLgStage), dim3(256), 0, ctx->stream, (const LgWord *) part, (long long) nb, chunk, part2);
+        hipLaunchKernelGGL(k_lg_final, dim3(1), dim3(256), 0, ctx->stream, (const LgWord *) part2, (long long) kLgStage, (long long) kLgStage,
+                           tot);
+    }
+    ME_CHECK(ctx, hipGetLastError());
+    LgWord h[7];
+    {
+        MailGuard mg(ctx);
+        ME_TRY(mail_post(ctx, h, tot, sizeof(h)));
+        ME_TRY(mg.sync());
+    }
+    c.lg_have = true;
+    if (out) {
+        out->n = n;
+        out->n_valid = h[6].i;
+        out->sum_l3 = h[0].d;
+        out->sum_linearity = h[1].d;
+        out->sum_planarity = h[2].d;
+        out->sum_sphericity = h[3].d;
+        out->sum_surface_variation = h[4].d;
+        out->sum_k = h[5].i;
+    }
+    return ME_OK;
+}
+
+int local_geometry_fetch(me_ctx *ctx, int slot, double *eig, int32_t *k, uint8_t *valid) {
+    ME_TRY(need_single_gpu_cloud(ctx, slot, "me_local_geometry_fetch"));
+    Cloud &c = ctx->cloud[slot];
+    if (!c.lg_have || !c.index_valid)
+        return ctx->fail(ME_ERR_STATE, "me_local_geometry_fetch: no result for this slot (run me_local_geometry; a changed cloud or a new index discards it)");
+    if (!eig && !k && !valid) return ME_OK;
+    ME_CHECK(ctx, hipSetDevice(ctx->device));
+    const long long n = c.n;
+    DevBuf &eo = ctx->tmp[2], &ko = ctx->tmp[3], &vo = ctx->tmp[4];
+    if (eig) ME_CHECK(ctx, eo.ensure((size_t) n * 24));
+    if (k) ME_CHECK(ctx, ko.ensure((size_t) n * 4));
+    if (valid) ME_CHECK(ctx, vo.ensure((size_t) n));
+    hipLaunchKernelGGL(k_lg_unpermute, dim3(blocks_of(n)), dim3(256), 0, ctx->stream, c.sp.as<SPoint>(), n, c.lg_eig.as<double>(),
+                       c.lg_k.as<int>(), c.lg_val.as<unsigned char>(), eig ? eo.as<double>() : nullptr, k ? ko.as<int>() : nullptr,
+                       valid ? vo.as<unsigned char>() : nullptr);
+    ME_CHECK(ctx, hipGetLastError());
+    if (eig) ME_TRY(copy_d2h(ctx, eig, eo.p, (size_t) n * 24));
+    if (k) ME_TRY(copy_d2h(ctx, k, ko.p, (size_t) n * 4));
+    if (valid) ME_TRY(copy_d2h(ctx, valid, vo.p, (size_t) n));
+    ME_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    return ME_OK;
+}
+
+}  // namespace me

@@ -206,6 +206,7 @@ int perturb_cloud(me_ctx *ctx, int dst_slot, int src_slot, const me_perturb_para
     D.vox_merged = false;
     D.vox_rec_valid = false;
     D.mme_have = false;
+    D.lg_have = false;
     ctx->cloud[1 - dst_slot].nn_ref_slot = -1;
     D.n = total;
     D.n_total = total;

@@ -528,6 +528,34 @@ class Engine:
         mme_gt = self.mme(ME_SLOT_GT, p.nn_radius_, 5, per_point=False)[0] if p.evaluate_gt_mme_ else 0.0
         return mme_est, mme_gt
 
+    # ---- MPV and the eigenvalue shape features (me_localgeom.hip) ----
+    def local_geometry(self, slot: int, radius: float, min_k: int = 5, fetch: bool = False):
+        """me_local_geometry: the eigenvalues l1 >= l2 >= l3 of every point's radius-neighbourhood covariance.  Returns the info dict
+        (n, n_valid, sum_k and the means over the valid points: mpv = mean l3, linearity, planarity, sphericity, surface_variation,
+        mean_k; 0.0 when no point is valid, as MME's mean), and with fetch=True also (eig[N, 3], k[N], valid[N]) in cloud order."""
+        o = _lib.LocalGeomOut()
+        self._ck(self._L.me_local_geometry(self._ctx, int(slot), float(radius), int(min_k), C.byref(o)))
+        nv = o.n_valid
+
+        def mean(s):
+            return s / nv if nv > 0 else 0.0
+
+        info = {"n": o.n, "n_valid": nv, "sum_k": o.sum_k, "mpv": mean(o.sum_l3), "linearity": mean(o.sum_linearity),
+                "planarity": mean(o.sum_planarity), "sphericity": mean(o.sum_sphericity),
+                "surface_variation": mean(o.sum_surface_variation), "mean_k": mean(o.sum_k)}
+        if not fetch:
+            return info
+        n = self.size(slot)
+        eig = np.empty((n, 3), np.float64)
+        k = np.empty(n, np.int32)
+        valid = np.empty(n, np.uint8)
+        self._ck(self._L.me_local_geometry_fetch(self._ctx, int(slot), _addr(eig), _addr(k), _addr(valid)))
+        return info, eig, k, valid
+
+    def mpv(self, slot: int, radius: float, min_k: int = 5) -> float:
+        """Mean plane variance: the mean smallest covariance eigenvalue over the valid points (0.0 without one)."""
+        return self.local_geometry(slot, radius, min_k)["mpv"]
+
     # ---- voxels ----
     def voxel_build(self, slot: int, voxel_size: float) -> int:
         """Builds (and caches on the cloud) the voxel-Gaussian table without exporting it; returns the voxel count."""

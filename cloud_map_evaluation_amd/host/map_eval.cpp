@@ -240,6 +240,16 @@ Param loadParametersFromYAML(const std::string &yaml_file_path) {
         if (param.evaluate_noised_gt_)
             throw std::runtime_error("remove_outliers: not with evaluate_noised_gt for now (the simulated map is out of scope)");
     }
+    // mean plane variance and the eigenvalue shape features (no reference counterpart)
+    if (config.has("evaluate_mpv")) param.evaluate_mpv = config.as_bool("evaluate_mpv");
+    param.mpv_radius = config.has("mpv_radius") ? config.as_double("mpv_radius") : param.nn_radius_;
+    if (config.has("mpv_min_points")) param.mpv_min_points = config.as_int("mpv_min_points");
+    param.evaluate_gt_mpv = config.has("evaluate_gt_mpv") ? config.as_bool("evaluate_gt_mpv") : param.evaluate_gt_mme_;
+    if (param.evaluate_mpv) {
+        if (!(param.mpv_radius > 0) || !std::isfinite(param.mpv_radius)) throw std::runtime_error("mpv_radius: must be > 0");
+        if (param.mpv_min_points < 2) throw std::runtime_error("mpv_min_points: must be >= 2 (the covariance divides by k - 1)");
+        if (param.num_gpus > 1) throw std::runtime_error("evaluate_mpv: single GPU only (num_gpus must be 1)");
+    }
     return param;
 }
 
@@ -279,7 +289,9 @@ std::string paramToJson(const Param &p) {
       << ", \"outlier_nb_points\": " << p.outlier_nb_points << ", \"outlier_radius\": " << p.outlier_radius
       << ", \"outlier_filter_gt\": " << b(p.outlier_filter_gt) << ", \"outlier_eps\": " << p.outlier_eps
       << ", \"outlier_min_points\": " << p.outlier_min_points << ", \"outlier_min_cluster_size\": " << p.outlier_min_cluster_size
-      << ", \"outlier_keep_largest\": " << p.outlier_keep_largest << "}";
+      << ", \"outlier_keep_largest\": " << p.outlier_keep_largest << ", \"evaluate_mpv\": " << b(p.evaluate_mpv)
+      << ", \"mpv_radius\": " << p.mpv_radius << ", \"mpv_min_points\": " << p.mpv_min_points << ", \"evaluate_gt_mpv\": " << b(p.evaluate_gt_mpv)
+      << "}";
     return o.str();
 }
 
@@ -357,7 +369,9 @@ int MapEval::process() {
     if (noised && comm_) return fail("evaluate_noised_gt: single GPU only (the multi-GPU path reads both maps from disk)");
     const bool filter = param_.remove_outliers != "none";  // (the filter runs on resident clouds: the uploads below, not the one call's)
     if (filter && (noised || comm_)) return fail("remove_outliers: single GPU only, and not with evaluate_noised_gt, for now");
-    if (one_call && !noised && !filter && !(param_.downsample_size > 0)) {
+    const bool mpv = param_.evaluate_mpv;  // (on resident clouds too, before the one call transforms the map)
+    if (mpv && comm_) return fail("evaluate_mpv: single GPU only (num_gpus must be 1)");
+    if (one_call && !noised && !filter && !mpv && !(param_.downsample_size > 0)) {
         file_result << std::fixed << std::setprecision(15) << "Estimated-Ground Truth point count: " << map_3d_->size() << " / "
                     << gt_3d_->size() << std::endl;
         if (param_.enable_debug)
@@ -400,6 +414,7 @@ int MapEval::process() {
     if (param_.enable_debug)
         std::cout << "INFO: Loaded point clouds: " << map_3d_->size() << " points (Map), " << gt_3d_->size()
                   << " points (Ground Truth)." << std::endl;
+    if (mpv && computeMPV() != 0) return -1;  // (the clouds as loaded, where computeMME runs: before the transform)
     if (comm_) return processDist(tic_toc.toc());  // num_gpus > 1 (map_eval_dist.cpp)
     if (one_call) {  // (the down-sampled or perturbed clouds are resident)
         const int rc = processOneCall(false, tic_toc.toc());
@@ -423,6 +438,7 @@ int MapEval::process() {
     } else {
         t2 = t1;
     }
+    if (mpv && param_.save_immediate_result_) saveMpvResults();
 
     if (param_.evaluate_using_initial_) {
         if (param_.enable_debug) std::cout << "INFO: Using initial matrix without registration." << std::endl;
@@ -781,6 +797,7 @@ int MapEval::processOneCall(bool from_host, double t_loaded) {
         }
         if (param_.save_immediate_result_) saveMmeResults();
     }
+    if (param_.evaluate_mpv && param_.save_immediate_result_) saveMpvResults();
     t2 = t1 + so.stage_ms[0] + so.stage_ms[4] + so.stage_ms[5];
     // ---- calculateMetricsWithInitialMatrix's members (:1204-1260) ----
     if (param_.enable_debug) std::cout << "INFO: Using initial matrix without registration." << std::endl;
@@ -1061,6 +1078,56 @@ void MapEval::saveMmeResults() {
     // (extra) the raw per-point entropies, so that nothing is lost to the colour map
     std::ofstream e(results_subfolder + "map_entropy.txt");
     for (size_t i = 0; i < est_entropies.size(); ++i) e << est_entropies[i] << " " << (int) valid_entropy_points[i] << "\n";
+}
+
+// the means of a me_local_geom_out: [0] MPV (mean l3), [1..4] linearity, planarity, sphericity, surface variation, [5] mean k; zeros
+// when no point is valid (MME's convention)
+static std::array<double, 6> local_geom_means(const me_local_geom_out &o) {
+    std::array<double, 6> m{};
+    if (o.n_valid > 0) {
+        const double nv = (double) o.n_valid;
+        m = {o.sum_l3 / nv, o.sum_linearity / nv, o.sum_planarity / nv, o.sum_sphericity / nv, o.sum_surface_variation / nv,
+             (double) o.sum_k / nv};
+    }
+    return m;
+}
+
+int MapEval::computeMPV() {
+    for (int s : {ME_SLOT_EST, ME_SLOT_GT}) {
+        if (s == ME_SLOT_GT && !param_.evaluate_gt_mpv) break;
+        if (me_local_geometry(ctx_, s, param_.mpv_radius, param_.mpv_min_points, &mpv_out[s]) != ME_OK)
+            return fail(std::string("evaluate_mpv: ") + me_last_error(ctx_));
+    }
+    const auto e = local_geom_means(mpv_out[ME_SLOT_EST]), g = local_geom_means(mpv_out[ME_SLOT_GT]);
+    if (param_.evaluate_gt_mpv) std::cout << "MPV EST-GT: " << e[0] << " " << g[0] << std::endl;
+    else std::cout << "MPV EST: " << e[0] << std::endl;
+    return 0;
+}
+
+void MapEval::saveMpvResults() {
+    const bool gt = param_.evaluate_gt_mpv;
+    const auto e = local_geom_means(mpv_out[ME_SLOT_EST]), g = local_geom_means(mpv_out[ME_SLOT_GT]);
+    file_result << std::fixed << std::setprecision(5) << "MPV: " << e[0];
+    if (gt) file_result << " " << g[0];
+    file_result << std::endl;
+    file_result << std::fixed << std::setprecision(5) << "LocalGeometry lin-plan-sph-sv: " << e[1] << " " << e[2] << " " << e[3] << " " << e[4];
+    if (gt) file_result << " " << g[1] << " " << g[2] << " " << g[3] << " " << g[4];
+    file_result << std::endl;
+    // local_geometry.txt: radius and min_points, then per cloud n, n_valid, mean_k, MPV, linearity, planarity, sphericity, surface variation
+    const std::string path = results_subfolder + "local_geometry.txt";
+    FILE *f = std::fopen(path.c_str(), "w");
+    if (!f) {
+        fail("cannot write " + path);
+        return;
+    }
+    std::fprintf(f, "radius %.17g\nmin_points %d\n", param_.mpv_radius, param_.mpv_min_points);
+    for (int s : {ME_SLOT_EST, ME_SLOT_GT}) {
+        if (s == ME_SLOT_GT && !gt) break;
+        const auto &m = s == ME_SLOT_EST ? e : g;
+        std::fprintf(f, "%s %lld %lld %.17g %.17g %.17g %.17g %.17g %.17g\n", s == ME_SLOT_EST ? "est" : "gt", (long long) mpv_out[s].n,
+                     (long long) mpv_out[s].n_valid, m[5], m[0], m[1], m[2], m[3], m[4]);
+    }
+    if (std::fclose(f) != 0) fail("writing " + path + " failed");
 }
 
 void MapEval::saveRegistrationResults() {

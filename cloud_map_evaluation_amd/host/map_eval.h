@@ -91,6 +91,12 @@ struct Param {
     int outlier_min_points = 10;           // `outlier_min_points:` cluster: DBSCAN min_points, >= 1
     int outlier_min_cluster_size = 1;      // `outlier_min_cluster_size:` cluster: clusters below this size are dropped (noise always is)
     int outlier_keep_largest = 0;          // `outlier_keep_largest:` cluster: > 0 keeps only that many of the largest clusters
+    // mean plane variance and the eigenvalue shape features (optional keys; no reference counterpart): me_local_geometry on the clouds
+    // as loaded, where computeMME runs; an `MPV:` and a `LocalGeometry` line after `MME:`, and local_geometry.txt
+    bool evaluate_mpv = false;             // `evaluate_mpv:`
+    double mpv_radius = 0.0;               // `mpv_radius:` neighbourhood radius, > 0 (default: nn_radius)
+    int mpv_min_points = 5;                // `mpv_min_points:` neighbours a point needs to count, >= 2
+    bool evaluate_gt_mpv = false;          // `evaluate_gt_mpv:` also on the ground truth (default: evaluate_gt_mme)
     int dist_rank = 0;              // (set by the launcher, not a YAML key)
     void printParam() const;
 };
@@ -121,6 +127,8 @@ public:
     void saveVoxelMetrics(int gate_mode);                  // voxel_metrics.txt (save_voxel_metrics; no reference counterpart)
     me_perturb_params perturbParams(double noise_std) const;  // the noise_* keys as me_perturb_cloud's parameters
     int runNoiseSweep();
+    int computeMPV();                                       // evaluate_mpv: me_local_geometry on both clouds (no reference counterpart)
+    void saveMpvResults();                                  // its result lines and local_geometry.txt
     int removeOutliers();                                   // outlier_removal.txt (remove_outliers; no reference counterpart)
     int removeSmallClusters();                              // ... remove_outliers: cluster
     int globalRegistration(double T_c[16]);                 // global_registration.txt (global_registration; no reference counterpart)                                   // noise_sweep.txt (noise_sweep; no reference counterpart)
@@ -139,6 +147,7 @@ public:
     std::array<double, 16> trans{{1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1}};  // ICP result (row-major), map_eval.h:332
     double vmd = 0.0, full_chamfer_dist = 0.0, scs_overall = 0.0;
     double mme_est = 0.0, mme_gt = 0.0, max_abs_entropy = 0.0, min_abs_entropy = 0.0;
+    me_local_geom_out mpv_out[2] = {};  // evaluate_mpv: [ME_SLOT_EST], [ME_SLOT_GT] (the latter with evaluate_gt_mpv)
     std::vector<double> est_entropies, gt_entropies;
     std::vector<uint8_t> valid_entropy_points, gt_valid_entropy_points;
     std::vector<double> map_entropy_xyz, map_entropy_rgb, gt_entropy_xyz, gt_entropy_rgb;  // map_3d_entropy / gt_3d_entropy (:330)

@@ -417,6 +417,33 @@ int me_cluster_dbscan(me_ctx *ctx, int slot, double eps, int min_points, int32_t
 int me_cluster_sizes(me_ctx *ctx, int slot, int64_t *sizes, int64_t capacity, int64_t *n_clusters);
 int me_cluster_keep(me_ctx *ctx, int slot, int64_t min_cluster_size, int64_t keep_largest, uint8_t *keep, me_outlier_info *info);
 
+/* ---- local geometry: mean plane variance (MPV) and the eigenvalue shape features of every radius neighbourhood --------------- */
+/* (DESIGN.md section 4.10).  MPV is MME's no-reference companion (Razlaw et al. 2015; Kornilova and Ferrer 2021): the mean, over the
+ * valid points, of the smallest eigenvalue of the neighbourhood covariance.  Single GPU only: slab or shard mode is ME_ERR_ARG.
+ * The slot's radius grid is rebuilt at `radius` when its cell differs, as me_mme does.  Device timer "local_geom".
+ *
+ * me_local_geometry (radius finite and > 0, min_k >= 2, else ME_ERR_ARG).  Per point i:
+ *   1. j is a neighbour iff d2 = ((dx*dx + dy*dy) + dz*dz) < radius*radius (fp64, no FMA, strict: the set me_mme uses); the query
+ *      itself is removed once, its coincident duplicates stay.  k_i = the neighbours left.
+ *   2. k_i >= min_k: C = (sum(d d^T) - sum(d) sum(d)^T / k) / (k - 1) with d = p_j - p_i (moments about the query: no term
+ *      exceeds radius^2, so each eigenvalue is within 8 k 2^-53 radius^2 of the exact one), eigenvalues by cyclic Jacobi, clamped at
+ *      0 from below, ordered l1 >= l2 >= l3.
+ *   3. The point is valid iff k_i >= min_k and l1 > 0; an invalid point stores l1 = l2 = l3 = 0.
+ * out: n, n_valid and, over the valid points, the sums of l3 (MPV = sum_l3 / n_valid), linearity (l1 - l2) / l1, planarity
+ * (l2 - l3) / l1, sphericity l3 / l1, surface variation l3 / (l1 + l2 + l3), and k.  The sums are formed from per-block partials in
+ * block order: bit-identical from run to run.
+ *
+ * me_local_geometry_fetch: the per-point arrays of the slot's last me_local_geometry in cloud order (N entries each, nullable):
+ * eig = N x 3 (l1, l2, l3), k, valid.  ME_ERR_STATE: no current result — the cloud changed (upload, down-sample, transform,
+ * perturbation, selection) or another stage rebuilt the slot's grid at a different cell. */
+typedef struct me_local_geom_out {
+    int64_t n, n_valid;
+    double sum_l3, sum_linearity, sum_planarity, sum_sphericity, sum_surface_variation;
+    int64_t sum_k;
+} me_local_geom_out;
+int me_local_geometry(me_ctx *ctx, int slot, double radius, int min_k, me_local_geom_out *out);
+int me_local_geometry_fetch(me_ctx *ctx, int slot, double *eig, int32_t *k, uint8_t *valid);
+
 int64_t me_cloud_size(me_ctx *ctx, int slot);
 /* transformed points back to the host (N x 3), original order — what map_3d_->points_ holds after :1206 */
 int me_download_cloud(me_ctx *ctx, int slot, double *xyz_host);
