@@ -1100,7 +1100,11 @@ int cloud_build_index(me_ctx *ctx, int slot, double cell_size) {
         c.oct_deferred = false;
         c.oct_nn_shift = nn_shift;
         ts.end();  // ("cells": the tables the radius search and the 1-NN grid pass use; the octree has its own timer since round 6)
-        if (ctx->defer_octree) {
+        // An octree deeper than its level table (two dense patches 2^17 1-NN cells apart) is no reason to refuse the INDEX: the radius
+        // passes need the cell tables only.  It stays deferred, and whoever asks for it (cloud_finish_octree) gets build_octree's error.
+        int oct_levels = 1;
+        for (int k = nn_shift; k < kMortonBits && c.level_unique[k] != 1; ++k) ++oct_levels;
+        if (ctx->defer_octree || oct_levels > kMaxLevels) {
             c.oct_deferred = true;
         } else {
             TimerScope to(ctx, "octree");

@@ -235,7 +235,11 @@ int me_voxel_merge_device(me_ctx *ctx, int slot, double voxel_size, const double
 /* Replaces: *map_3d_ = map_3d_->Transform(initial_matrix) (map_eval.cpp:1206) + every KDTreeFlann::SetGeometry
  * (map_eval.cpp:1214,1227,1401-1402,1449,1551,1619): uploads the cloud, applies T (row-major 4x4, NULL = none;
  * homogeneous divide as Open3D), sorts it along a space-filling curve and builds the search index ONCE.
- * cell_size: edge of the radius-search grid cell (pass nn_radius; <= 0 = automatic, rebuilt lazily by me_mme). */
+ * cell_size: edge of the radius-search grid cell (pass nn_radius; <= 0 = automatic, rebuilt lazily by me_mme).
+ * Limits: more than 2^21 cells per axis -> ME_ERR_ARG "cell size too small for the cloud extent".  A cloud whose 1-NN octree
+ * would need more than 17 levels (dense patches more than ~2^17 1-NN cells apart) is indexed WITHOUT the octree: the radius passes
+ * (me_mme, me_local_geometry, ...) work; the calls that walk the octree — me_nn1, me_nn_points*, me_estimate_normals, me_fpfh,
+ * me_statistical_outlier — return ME_ERR_ARG "octree deeper than the level table". */
 int me_upload_cloud(me_ctx *ctx, int slot, const double *xyz_host, int64_t n, const double *T_rowmajor4x4,
                     double cell_size);
 int me_upload_cloud_device(me_ctx *ctx, int slot, const double *xyz_device, int64_t n,
@@ -451,7 +455,8 @@ int me_download_cloud(me_ctx *ctx, int slot, double *xyz_host);
 /* ---- 1-NN: KDTreeFlann::SearchKNN(q, 1, idx, d2) over a whole cloud (map_eval.cpp:1218,1231,1415,1424,579) --- */
 /* Searches every point of query_slot in ref_slot; results stay on the device for the me_nn_* calls below.
  * idx / d2 (query-cloud order, length N_query; nullable) receive the neighbour index in ref cloud order and the
- * SQUARED distance ((dx*dx + dy*dy) + dz*dz), bit-identical to the CPU path.  Ties -> smallest ref index. */
+ * SQUARED distance ((dx*dx + dy*dy) + dz*dz), bit-identical to the CPU path.  Ties -> smallest ref index, between coincident
+ * and between equidistant reference points alike.  ME_ERR_ARG "octree deeper than the level table": see me_upload_cloud. */
 int me_nn1(me_ctx *ctx, int query_slot, int ref_slot, int32_t *idx, double *d2);
 
 /* getDiffRegResultWithCorrespondence / getDiffRegResult (map_eval.cpp:1069-1145, 828-897, 990-1067) on the
