@@ -33,6 +33,7 @@ SYMBOLS = [
     "me_statistical_outlier", "me_radius_outlier", "me_outlier_select_into",
     "me_cluster_dbscan", "me_cluster_sizes", "me_cluster_keep",
     "me_local_geometry", "me_local_geometry_fetch",
+    "me_segment_planes", "me_plane_fetch", "me_plane_keep",
     "me_set_normals", "me_get_normals", "me_estimate_normals", "me_gicp_covariances", "me_get_covariances", "me_icp_lsq_sums",
     "me_nn1", "me_icp_p2p_sums", "me_render_distance", "me_render_entropy", "me_nn_stats", "me_nn_partial_sums", "me_nn_sigma_sums", "me_nn_finalize", "me_chamfer",
     "me_mme", "me_voxel_gaussians", "me_voxel_metrics", "me_awd_scs", "me_w2_batch", "me_scs_table", "me_run_suite", "me_run_suite_from", "me_mme_fetch",
@@ -201,6 +202,41 @@ class LocalGeomOut(C.Structure):
     ]
 
 
+class PlaneParams(C.Structure):
+    _fields_ = [
+        ("distance_threshold", C.c_double),
+        ("num_iterations", C.c_int64),
+        ("max_planes", C.c_int32),
+        ("refit", C.c_int32),
+        ("min_inliers", C.c_int64),
+        ("seed", C.c_uint64),
+    ]
+
+
+class PlaneRecord(C.Structure):
+    _fields_ = [
+        ("count", C.c_int64),
+        ("h", C.c_int64),
+        ("score", C.c_int64),
+        ("plane", C.c_double * 4),
+        ("rms", C.c_double),
+        ("mean_abs", C.c_double),
+        ("max_abs", C.c_double),
+        ("refit_degenerate", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+
+class PlaneInfo(C.Structure):
+    _fields_ = [
+        ("n_in", C.c_int64),
+        ("n_planes", C.c_int64),
+        ("n_labelled", C.c_int64),
+        ("n_valid_hypotheses", C.c_int64),
+        ("rounds", C.c_int64),
+    ]
+
+
 _lib = None
 
 
@@ -283,6 +319,11 @@ def load():
     L.me_local_geometry.argtypes = [vp, C.c_int, C.c_double, C.c_int, C.POINTER(LocalGeomOut)]
     L.me_local_geometry_fetch.argtypes = [vp, C.c_int, dp, ip, vp]
     for f in ("me_local_geometry", "me_local_geometry_fetch"):
+        getattr(L, f).restype = C.c_int
+    L.me_segment_planes.argtypes = [vp, C.c_int, C.POINTER(PlaneParams), vp, ip, vp, C.POINTER(PlaneInfo)]
+    L.me_plane_fetch.argtypes = [vp, C.c_int, vp, C.c_int64, C.POINTER(C.c_int64), ip]
+    L.me_plane_keep.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.POINTER(OutlierInfo)]
+    for f in ("me_segment_planes", "me_plane_fetch", "me_plane_keep"):
         getattr(L, f).restype = C.c_int
     L.me_upload_cloud.argtypes = [vp, C.c_int, dp, C.c_int64, dp, C.c_double]
     L.me_upload_cloud_device.argtypes = [vp, C.c_int, dp, C.c_int64, dp, C.c_double]

@@ -351,6 +351,25 @@ int me_local_geometry_fetch(me_ctx *ctx, int slot, double *eig, int32_t *k, uint
     return me::local_geometry_fetch(ctx, slot, eig, k, valid);
 }
 
+int me_segment_planes(me_ctx *ctx, int slot, const me_plane_params *p, me_plane_record *planes, int32_t *labels, int64_t *scores,
+                      me_plane_info *info) {
+    if (!ctx) return ME_ERR_ARG;
+    return me::segment_planes(ctx, slot, p, planes, labels, scores, info);
+}
+
+int me_plane_fetch(me_ctx *ctx, int slot, me_plane_record *planes, int64_t capacity, int64_t *n_planes, int32_t *labels) {
+    if (!ctx) return ME_ERR_ARG;
+    long long m = 0;
+    const int rc = me::plane_fetch(ctx, slot, planes, capacity, &m, labels);
+    if (n_planes && (rc == ME_OK || rc == ME_ERR_CAPACITY)) *n_planes = m;
+    return rc;
+}
+
+int me_plane_keep(me_ctx *ctx, int slot, int plane, int invert, uint8_t *keep, me_outlier_info *info) {
+    if (!ctx) return ME_ERR_ARG;
+    return me::plane_keep(ctx, slot, plane, invert, keep, info);
+}
+
 int me_transform_cloud(me_ctx *ctx, int slot, const double *T) {
     if (!ctx) return ME_ERR_ARG;
     return me::cloud_transform(ctx, slot, T);

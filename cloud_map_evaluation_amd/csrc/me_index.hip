@@ -650,6 +650,7 @@ int cloud_upload(me_ctx *ctx, int slot, const double *src, bool src_on_device, l
         e.have_normals = e.have_cov = false;
         e.outlier_keep_valid = false;
         e.cluster_valid = false;
+        e.plane_valid = false;
         e.lg_have = false;
         ctx->cloud[1 - slot].nn_ref_slot = -1;
         return ME_OK;
@@ -757,6 +758,7 @@ int cloud_finish(me_ctx *ctx, int slot, bool bbox_ready) {
     c.fpfh_valid = false;
     c.outlier_keep_valid = false;  // (the mask belongs to the points it was computed on)
     c.cluster_valid = false;
+    c.plane_valid = false;
     ctx->cloud[1 - slot].nn_ref_slot = -1;
     // bbox
     const unsigned int nb = (unsigned int) std::min<long long>(1024, (n + 255) / 256);
@@ -807,6 +809,7 @@ void cloud_reset_replaced(me_ctx *ctx, int slot, long long n, double cell_size_r
     D.fpfh_valid = false;
     D.outlier_keep_valid = false;
     D.cluster_valid = false;
+    D.plane_valid = false;
     D.lg_have = false;
     D.slab = ctx->slab;
     D.n_unres = 0;

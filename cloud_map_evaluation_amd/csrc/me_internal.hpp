@@ -236,6 +236,10 @@ struct Cloud {
     // invalid), neighbour count int32[n], validity byte; dropped with the points and with the sorted order (cloud_build_index)
     DevBuf lg_eig, lg_k, lg_val;
     bool lg_have = false;
+    // labels (int32[n], cloud order, -1 = no plane) and per-plane records of the last me_segment_planes (me_plane.hip); dropped with the points
+    DevBuf plane_labels;
+    std::vector<me_plane_record> plane_rec;
+    bool plane_valid = false;
 };
 
 struct TimerRec {
@@ -311,6 +315,7 @@ struct me_ctx {
     long long mme_keep_n = -1;
     me::DevBuf outlier_tmp[2];                   // me_outlier.hip: per-point avg_dist / counts and the fallback list, kept for repeated calls
     me::DevBuf cluster_tmp[5];                   // me_cluster.hip: parent, smallest index per root, the two flag arrays, the border list
+    me::DevBuf plane_tmp[7];                     // me_plane.hip: remaining flags and list, the compacted coordinates, hypotheses, scores, scalars
     me::DevBuf nn1_dbg_buf;                      // octree-walk counters (nodes opened, leaves scanned, points, max per query)
     unsigned long long *nn1_dbg() {
         if (!nn1_dbg_buf.p) {
@@ -495,6 +500,11 @@ int outlier_select_into(me_ctx *src_ctx, int src_slot, me_ctx *dst_ctx, int dst_
 // ---- me_localgeom.hip ----
 int local_geometry(me_ctx *ctx, int slot, double radius, int min_k, me_local_geom_out *out);
 int local_geometry_fetch(me_ctx *ctx, int slot, double *eig_host, int32_t *k_host, uint8_t *valid_host);
+// ---- me_plane.hip ----
+int segment_planes(me_ctx *ctx, int slot, const me_plane_params *p, me_plane_record *planes_host, int32_t *labels_host, int64_t *scores_host,
+                   me_plane_info *info);
+int plane_fetch(me_ctx *ctx, int slot, me_plane_record *planes_host, long long capacity, long long *n_planes, int32_t *labels_host);
+int plane_keep(me_ctx *ctx, int slot, int plane, int invert, uint8_t *keep_host, me_outlier_info *info);
 // ---- me_cluster.hip ----
 int cluster_dbscan(me_ctx *ctx, int slot, double eps, int min_points, int32_t *labels_host, int32_t *counts_host, me_cluster_info *info);
 int cluster_sizes(me_ctx *ctx, int slot, int64_t *sizes_host, long long capacity, long long *n_clusters);

@@ -379,6 +379,69 @@ class Engine:
         info["n_kept"] = self.cluster_keep(slot, min_cluster_size, keep_largest)["n_kept"]
         return self.select_kept_into(slot), info
 
+    # ---- plane segmentation (Open3D segment_plane) and multi-plane extraction (me_plane.hip) ----
+    @staticmethod
+    def _plane_dict(r: _lib.PlaneRecord) -> dict:
+        return {"count": int(r.count), "h": int(r.h), "score": int(r.score), "plane": np.array(list(r.plane), np.float64), "rms": r.rms,
+                "mean_abs": r.mean_abs, "max_abs": r.max_abs, "refit_degenerate": int(r.refit_degenerate)}
+
+    def segment_planes(self, slot: int, distance_threshold: float, num_iterations: int = 1000, max_planes: int = 1, min_inliers: int = 3,
+                       refit: bool = True, seed: int = 0, fetch: bool = False):
+        """me_segment_planes: up to max_planes RANSAC planes, each on what the earlier ones left; labels and records stay on the slot
+        until the cloud changes.  Returns (info, planes) — planes = one dict per plane (count, h, score, plane = (a, b, c, d), rms,
+        mean_abs, max_abs, refit_degenerate) — and with fetch=True also (labels [N] int32 in cloud order, -1 = no plane; scores
+        [max_planes, num_iterations] int64, -1 = invalid hypothesis or round not reached)."""
+        prm = _lib.PlaneParams(float(distance_threshold), int(num_iterations), int(max_planes), int(bool(refit)), int(min_inliers),
+                               int(seed) & 0xFFFFFFFFFFFFFFFF)
+        o = _lib.PlaneInfo()
+        cap = max(1, min(int(max_planes), 64))
+        recs = (_lib.PlaneRecord * cap)()
+        labels = scores = None
+        if fetch:
+            labels = np.empty(self.size(slot), np.int32)
+            if 1 <= int(max_planes) <= 64 and 1 <= int(num_iterations) <= 1 << 24:
+                scores = np.empty((int(max_planes), int(num_iterations)), np.int64)
+        self._ck(self._L.me_segment_planes(self._ctx, int(slot), C.byref(prm), C.addressof(recs), _addr(labels), _addr(scores), C.byref(o)))
+        info = {f: getattr(o, f) for f, _ in o._fields_}
+        planes = [self._plane_dict(recs[k]) for k in range(int(o.n_planes))]
+        return (info, planes, labels, scores) if fetch else (info, planes)
+
+    def segment_plane(self, slot: int, distance_threshold: float, num_iterations: int = 1000, min_inliers: int = 3, refit: bool = True,
+                      seed: int = 0):
+        """Open3D's segment_plane(distance_threshold, 3, num_iterations): (plane (a, b, c, d), inlier indices in cloud order); without a
+        plane (None, an empty index array)."""
+        _, planes, labels, _ = self.segment_planes(slot, distance_threshold, num_iterations, 1, min_inliers, refit, seed, fetch=True)
+        if not planes:
+            return None, np.empty(0, np.int64)
+        return planes[0]["plane"], np.flatnonzero(labels == 0)
+
+    def plane_fetch(self, slot: int):
+        """me_plane_fetch: (planes, labels) of the slot's last segment_planes."""
+        m = C.c_int64(0)
+        self._ck(self._L.me_plane_fetch(self._ctx, int(slot), 0, 0, C.byref(m), 0))
+        recs = (_lib.PlaneRecord * max(1, m.value))()
+        labels = np.empty(self.size(slot), np.int32)
+        self._ck(self._L.me_plane_fetch(self._ctx, int(slot), C.addressof(recs), int(m.value), C.byref(m), _addr(labels)))
+        return [self._plane_dict(recs[k]) for k in range(m.value)], labels
+
+    def plane_keep(self, slot: int, plane: int = -1, invert: bool = False, fetch: bool = False):
+        """me_plane_keep: the slot's keep-mask = the points of that plane (plane = -1: of any plane), or with invert the others.
+        Returns the info dict, and with fetch=True also the mask (cloud order)."""
+        o = _lib.OutlierInfo()
+        keep = np.empty(self.size(slot), np.uint8) if fetch else None
+        self._ck(self._L.me_plane_keep(self._ctx, int(slot), int(plane), int(bool(invert)), _addr(keep), C.byref(o)))
+        return (self._outlier_dict(o), keep) if fetch else self._outlier_dict(o)
+
+    def remove_plane(self, slot: int, distance_threshold: float, num_iterations: int = 1000, min_inliers: int = 3, refit: bool = True,
+                     seed: int = 0):
+        """Segment the largest plane and remove its points, in place (ground removal): returns (n_kept, info, planes); without a plane
+        the cloud stays as it is."""
+        info, planes = self.segment_planes(slot, distance_threshold, num_iterations, 1, min_inliers, refit, seed)
+        if not planes:
+            return self.size(slot), info, planes
+        info["n_kept"] = self.plane_keep(slot, 0, invert=True)["n_kept"]
+        return self.select_kept_into(slot), info, planes
+
     def size(self, slot: int) -> int:
         return int(self._L.me_cloud_size(self._ctx, slot))
 

@@ -208,8 +208,8 @@ Param loadParametersFromYAML(const std::string &yaml_file_path) {
     // outlier removal in front of the evaluation (no reference counterpart)
     if (config.has("remove_outliers")) param.remove_outliers = config.as_string("remove_outliers");
     if (param.remove_outliers != "none" && param.remove_outliers != "statistical" && param.remove_outliers != "radius" &&
-        param.remove_outliers != "cluster")
-        throw std::runtime_error("remove_outliers: expected none, statistical, radius or cluster, got '" + param.remove_outliers + "'");
+        param.remove_outliers != "cluster" && param.remove_outliers != "plane")
+        throw std::runtime_error("remove_outliers: expected none, statistical, radius, cluster or plane, got '" + param.remove_outliers + "'");
     if (config.has("outlier_nb_neighbors")) param.outlier_nb_neighbors = config.as_int("outlier_nb_neighbors");
     if (config.has("outlier_std_ratio")) param.outlier_std_ratio = config.as_double("outlier_std_ratio");
     if (config.has("outlier_nb_points")) param.outlier_nb_points = config.as_int("outlier_nb_points");
@@ -249,6 +249,24 @@ Param loadParametersFromYAML(const std::string &yaml_file_path) {
         if (!(param.mpv_radius > 0) || !std::isfinite(param.mpv_radius)) throw std::runtime_error("mpv_radius: must be > 0");
         if (param.mpv_min_points < 2) throw std::runtime_error("mpv_min_points: must be >= 2 (the covariance divides by k - 1)");
         if (param.num_gpus > 1) throw std::runtime_error("evaluate_mpv: single GPU only (num_gpus must be 1)");
+    }
+    // RANSAC plane segmentation (no reference counterpart); remove_outliers: plane takes the same plane_* keys
+    if (config.has("segment_planes")) param.segment_planes = config.as_bool("segment_planes");
+    if (config.has("plane_distance_threshold")) param.plane_distance_threshold = config.as_double("plane_distance_threshold");
+    if (config.has("plane_num_iterations")) param.plane_num_iterations = (int64_t) config.as_double("plane_num_iterations");
+    if (config.has("plane_max_planes")) param.plane_max_planes = config.as_int("plane_max_planes");
+    if (config.has("plane_min_inliers")) param.plane_min_inliers = (int64_t) config.as_double("plane_min_inliers");
+    if (config.has("plane_seed")) param.plane_seed = as_seed("plane_seed");
+    if (config.has("plane_refit")) param.plane_refit = config.as_bool("plane_refit");
+    param.segment_gt_planes = config.has("segment_gt_planes") ? config.as_bool("segment_gt_planes") : param.evaluate_gt_mme_;
+    if (param.segment_planes || param.remove_outliers == "plane") {
+        if (!(param.plane_distance_threshold > 0) || !std::isfinite(param.plane_distance_threshold))
+            throw std::runtime_error("plane_distance_threshold: must be > 0");
+        if (param.plane_num_iterations < 1 || param.plane_num_iterations > (1 << 24))
+            throw std::runtime_error("plane_num_iterations: must lie in 1..2^24");
+        if (param.plane_max_planes < 1 || param.plane_max_planes > 64) throw std::runtime_error("plane_max_planes: must lie in 1..64");
+        if (param.plane_min_inliers < 3) throw std::runtime_error("plane_min_inliers: must be >= 3");
+        if (param.segment_planes && param.num_gpus > 1) throw std::runtime_error("segment_planes: single GPU only (num_gpus must be 1)");
     }
     return param;
 }
@@ -291,7 +309,10 @@ std::string paramToJson(const Param &p) {
       << ", \"outlier_min_points\": " << p.outlier_min_points << ", \"outlier_min_cluster_size\": " << p.outlier_min_cluster_size
       << ", \"outlier_keep_largest\": " << p.outlier_keep_largest << ", \"evaluate_mpv\": " << b(p.evaluate_mpv)
       << ", \"mpv_radius\": " << p.mpv_radius << ", \"mpv_min_points\": " << p.mpv_min_points << ", \"evaluate_gt_mpv\": " << b(p.evaluate_gt_mpv)
-      << "}";
+      << ", \"segment_planes\": " << b(p.segment_planes) << ", \"plane_distance_threshold\": " << p.plane_distance_threshold
+      << ", \"plane_num_iterations\": " << p.plane_num_iterations << ", \"plane_max_planes\": " << p.plane_max_planes
+      << ", \"plane_min_inliers\": " << p.plane_min_inliers << ", \"plane_seed\": " << p.plane_seed << ", \"plane_refit\": " << b(p.plane_refit)
+      << ", \"segment_gt_planes\": " << b(p.segment_gt_planes) << "}";
     return o.str();
 }
 
@@ -371,7 +392,9 @@ int MapEval::process() {
     if (filter && (noised || comm_)) return fail("remove_outliers: single GPU only, and not with evaluate_noised_gt, for now");
     const bool mpv = param_.evaluate_mpv;  // (on resident clouds too, before the one call transforms the map)
     if (mpv && comm_) return fail("evaluate_mpv: single GPU only (num_gpus must be 1)");
-    if (one_call && !noised && !filter && !mpv && !(param_.downsample_size > 0)) {
+    const bool planes = param_.segment_planes;  // (likewise)
+    if (planes && comm_) return fail("segment_planes: single GPU only (num_gpus must be 1)");
+    if (one_call && !noised && !filter && !mpv && !planes && !(param_.downsample_size > 0)) {
         file_result << std::fixed << std::setprecision(15) << "Estimated-Ground Truth point count: " << map_3d_->size() << " / "
                     << gt_3d_->size() << std::endl;
         if (param_.enable_debug)
@@ -415,6 +438,7 @@ int MapEval::process() {
         std::cout << "INFO: Loaded point clouds: " << map_3d_->size() << " points (Map), " << gt_3d_->size()
                   << " points (Ground Truth)." << std::endl;
     if (mpv && computeMPV() != 0) return -1;  // (the clouds as loaded, where computeMME runs: before the transform)
+    if (planes && segmentPlanes() != 0) return -1;  // (likewise)
     if (comm_) return processDist(tic_toc.toc());  // num_gpus > 1 (map_eval_dist.cpp)
     if (one_call) {  // (the down-sampled or perturbed clouds are resident)
         const int rc = processOneCall(false, tic_toc.toc());
@@ -439,6 +463,7 @@ int MapEval::process() {
         t2 = t1;
     }
     if (mpv && param_.save_immediate_result_) saveMpvResults();
+    if (planes && param_.save_immediate_result_) savePlaneResults();
 
     if (param_.evaluate_using_initial_) {
         if (param_.enable_debug) std::cout << "INFO: Using initial matrix without registration." << std::endl;
@@ -798,6 +823,7 @@ int MapEval::processOneCall(bool from_host, double t_loaded) {
         if (param_.save_immediate_result_) saveMmeResults();
     }
     if (param_.evaluate_mpv && param_.save_immediate_result_) saveMpvResults();
+    if (param_.segment_planes && param_.save_immediate_result_) savePlaneResults();
     t2 = t1 + so.stage_ms[0] + so.stage_ms[4] + so.stage_ms[5];
     // ---- calculateMetricsWithInitialMatrix's members (:1204-1260) ----
     if (param_.enable_debug) std::cout << "INFO: Using initial matrix without registration." << std::endl;
@@ -1130,6 +1156,74 @@ void MapEval::saveMpvResults() {
     if (std::fclose(f) != 0) fail("writing " + path + " failed");
 }
 
+me_plane_params MapEval::planeParams(int max_planes) const {
+    me_plane_params pp{};
+    pp.distance_threshold = param_.plane_distance_threshold;
+    pp.num_iterations = param_.plane_num_iterations;
+    pp.max_planes = max_planes;
+    pp.refit = param_.plane_refit ? 1 : 0;
+    pp.min_inliers = param_.plane_min_inliers;
+    pp.seed = param_.plane_seed;
+    return pp;
+}
+
+// the count-weighted mean rms of a cloud's planes (0 without planes)
+static double planes_mean_rms(const std::vector<me_plane_record> &r) {
+    double num = 0.0, den = 0.0;
+    for (const auto &p : r) {
+        num += (double) p.count * p.rms;
+        den += (double) p.count;
+    }
+    return den > 0 ? num / den : 0.0;
+}
+
+int MapEval::segmentPlanes() {
+    const me_plane_params pp = planeParams(param_.plane_max_planes);
+    for (int s : {ME_SLOT_EST, ME_SLOT_GT}) {
+        if (s == ME_SLOT_GT && !param_.segment_gt_planes) break;
+        plane_rec[s].assign((size_t) pp.max_planes, me_plane_record{});
+        me_plane_info info{};
+        if (me_segment_planes(ctx_, s, &pp, plane_rec[s].data(), nullptr, nullptr, &info) != ME_OK)
+            return fail(std::string("segment_planes: ") + me_last_error(ctx_));
+        plane_rec[s].resize((size_t) info.n_planes);
+    }
+    if (param_.segment_gt_planes)
+        std::cout << "Planes EST-GT: " << plane_rec[ME_SLOT_EST].size() << " " << plane_rec[ME_SLOT_GT].size() << std::endl;
+    else std::cout << "Planes EST: " << plane_rec[ME_SLOT_EST].size() << std::endl;
+    return 0;
+}
+
+void MapEval::savePlaneResults() {
+    const bool gt = param_.segment_gt_planes;
+    // plane counts, then the count-weighted mean rms per cloud
+    file_result << std::fixed << std::setprecision(5) << "Planes est-gt: " << plane_rec[ME_SLOT_EST].size();
+    if (gt) file_result << " " << plane_rec[ME_SLOT_GT].size();
+    file_result << " rms " << planes_mean_rms(plane_rec[ME_SLOT_EST]);
+    if (gt) file_result << " " << planes_mean_rms(plane_rec[ME_SLOT_GT]);
+    file_result << std::endl;
+    // plane_segmentation.txt: the parameters ("name value"), then per cloud one row per plane:
+    // cloud index count h a b c d rms mean_abs max_abs refit_degenerate
+    const std::string path = results_subfolder + "plane_segmentation.txt";
+    FILE *f = std::fopen(path.c_str(), "w");
+    if (!f) {
+        fail("cannot write " + path);
+        return;
+    }
+    std::fprintf(f, "distance_threshold %.17g\nnum_iterations %lld\nmax_planes %d\nmin_inliers %lld\nseed %llu\nrefit %s\n",
+                 param_.plane_distance_threshold, (long long) param_.plane_num_iterations, param_.plane_max_planes,
+                 (long long) param_.plane_min_inliers, (unsigned long long) param_.plane_seed, param_.plane_refit ? "true" : "false");
+    for (int s : {ME_SLOT_EST, ME_SLOT_GT}) {
+        if (s == ME_SLOT_GT && !gt) break;
+        for (size_t i = 0; i < plane_rec[s].size(); ++i) {
+            const me_plane_record &r = plane_rec[s][i];
+            std::fprintf(f, "%s %zu %lld %lld %.17g %.17g %.17g %.17g %.17g %.17g %.17g %d\n", s == ME_SLOT_EST ? "est" : "gt", i,
+                         (long long) r.count, (long long) r.h, r.plane[0], r.plane[1], r.plane[2], r.plane[3], r.rms, r.mean_abs, r.max_abs,
+                         (int) r.refit_degenerate);
+        }
+    }
+    if (std::fclose(f) != 0) fail("writing " + path + " failed");
+}
+
 void MapEval::saveRegistrationResults() {
     // identical lines and precisions to map_eval.cpp:439-476
     file_result << std::fixed << std::setprecision(15) << "RMSE/AC: " << eigen_row(est_gt_results.at(1), 15) << std::endl;
@@ -1206,6 +1300,7 @@ me_perturb_params MapEval::perturbParams(double noise_std) const {
 // filtered cloud "<est|gt> n_in n_clusters n_core n_border n_noise largest kept".
 int MapEval::removeOutliers() {
     if (param_.remove_outliers == "cluster") return removeSmallClusters();
+    if (param_.remove_outliers == "plane") return removeLargestPlane();
     const bool sor = param_.remove_outliers == "statistical";
     std::filesystem::create_directories(results_subfolder);
     const std::string path = results_subfolder + "outlier_removal.txt";
@@ -1233,6 +1328,46 @@ int MapEval::removeOutliers() {
         }
         std::fprintf(f, "%s %lld %lld %.17g %.17g %.17g\n", s == ME_SLOT_EST ? "est" : "gt", (long long) info.n_in, (long long) info.n_kept,
                      info.mean, info.std_dev, info.threshold);
+    }
+    if (std::fclose(f) != 0) return fail("writing " + path + " failed");
+    return 0;
+}
+
+// remove_outliers: plane (me_segment_planes with one plane + me_plane_keep(0, inverted)): the plane_* parameters, then per filtered
+// cloud "<est|gt> n_in n_kept count h a b c d rms"; a cloud without a plane of plane_min_inliers points stays as it is (count 0).
+int MapEval::removeLargestPlane() {
+    std::filesystem::create_directories(results_subfolder);
+    const std::string path = results_subfolder + "outlier_removal.txt";
+    FILE *f = std::fopen(path.c_str(), "w");
+    if (!f) return fail("cannot write " + path);
+    std::fprintf(f, "method plane\ndistance_threshold %.17g\nnum_iterations %lld\nmin_inliers %lld\nseed %llu\nrefit %s\n",
+                 param_.plane_distance_threshold, (long long) param_.plane_num_iterations, (long long) param_.plane_min_inliers,
+                 (unsigned long long) param_.plane_seed, param_.plane_refit ? "true" : "false");
+    std::fprintf(f, "filter_gt %s\n", param_.outlier_filter_gt ? "true" : "false");
+    const me_plane_params pp = planeParams(1);
+    for (int s : {ME_SLOT_EST, ME_SLOT_GT}) {
+        if (s == ME_SLOT_GT && !param_.outlier_filter_gt) break;
+        me_plane_record rec{};
+        me_plane_info pi{};
+        me_outlier_info info{};
+        int64_t n = 0;
+        bool ok = me_segment_planes(ctx_, s, &pp, &rec, nullptr, nullptr, &pi) == ME_OK;
+        n = pi.n_in;
+        if (ok && pi.n_planes > 0)
+            ok = me_plane_keep(ctx_, s, 0, 1, nullptr, &info) == ME_OK && me_outlier_select_into(ctx_, s, ctx_, s, &n) == ME_OK;
+        if (!ok) {
+            std::fclose(f);
+            return fail(std::string("remove_outliers: ") + me_last_error(ctx_));
+        }
+        PointCloud &pc = s == ME_SLOT_EST ? *map_3d_ : *gt_3d_;
+        pc.points_.resize((size_t) n * 3);
+        if (me_download_cloud(ctx_, s, pc.points_.data()) != ME_OK) {
+            std::fclose(f);
+            return fail(me_last_error(ctx_));
+        }
+        std::fprintf(f, "%s %lld %lld %lld %lld %.17g %.17g %.17g %.17g %.17g\n", s == ME_SLOT_EST ? "est" : "gt", (long long) pi.n_in,
+                     (long long) n, (long long) rec.count, (long long) (pi.n_planes > 0 ? rec.h : -1), rec.plane[0], rec.plane[1], rec.plane[2],
+                     rec.plane[3], rec.rms);
     }
     if (std::fclose(f) != 0) return fail("writing " + path + " failed");
     return 0;

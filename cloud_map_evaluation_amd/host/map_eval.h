@@ -81,7 +81,7 @@ struct Param {
     double global_outlier_std_ratio = 2.0; // `global_outlier_std_ratio:`
     // outlier removal in front of the evaluation (remove_outliers: statistical | radius; no reference counterpart): the map, and with
     // outlier_filter_gt the ground truth, filtered in place on the device after downsample_size -> map_results/outlier_removal.txt
-    std::string remove_outliers = "none";  // `remove_outliers:` none | statistical | radius | cluster
+    std::string remove_outliers = "none";  // `remove_outliers:` none | statistical | radius | cluster | plane (the largest plane: plane_* keys)
     int outlier_nb_neighbors = 20;         // `outlier_nb_neighbors:` statistical: k, 1..40
     double outlier_std_ratio = 2.0;        // `outlier_std_ratio:`
     int outlier_nb_points = -1;            // `outlier_nb_points:` radius: keep points with more than this many within the radius (required)
@@ -97,6 +97,16 @@ struct Param {
     double mpv_radius = 0.0;               // `mpv_radius:` neighbourhood radius, > 0 (default: nn_radius)
     int mpv_min_points = 5;                // `mpv_min_points:` neighbours a point needs to count, >= 2
     bool evaluate_gt_mpv = false;          // `evaluate_gt_mpv:` also on the ground truth (default: evaluate_gt_mme)
+    // RANSAC plane segmentation (optional keys; no reference counterpart): me_segment_planes on the clouds as loaded, where
+    // computeMME runs; a `Planes est-gt:` line after the MPV lines, and plane_segmentation.txt
+    bool segment_planes = false;             // `segment_planes:`
+    double plane_distance_threshold = 0.05;  // `plane_distance_threshold:` > 0
+    int64_t plane_num_iterations = 1000;     // `plane_num_iterations:` hypotheses per round, >= 1
+    int plane_max_planes = 8;                // `plane_max_planes:` 1..64
+    int64_t plane_min_inliers = 1000;        // `plane_min_inliers:` >= 3
+    uint64_t plane_seed = 0;                 // `plane_seed:` Philox seed
+    bool plane_refit = true;                 // `plane_refit:` least-squares plane of the inliers
+    bool segment_gt_planes = false;          // `segment_gt_planes:` also on the ground truth (default: evaluate_gt_mme)
     int dist_rank = 0;              // (set by the launcher, not a YAML key)
     void printParam() const;
 };
@@ -131,6 +141,10 @@ public:
     void saveMpvResults();                                  // its result lines and local_geometry.txt
     int removeOutliers();                                   // outlier_removal.txt (remove_outliers; no reference counterpart)
     int removeSmallClusters();                              // ... remove_outliers: cluster
+    int removeLargestPlane();                               // ... remove_outliers: plane
+    me_plane_params planeParams(int max_planes) const;      // the plane_* keys as me_segment_planes' parameters
+    int segmentPlanes();                                    // segment_planes: me_segment_planes on both clouds (no reference counterpart)
+    void savePlaneResults();                                // its result line and plane_segmentation.txt
     int globalRegistration(double T_c[16]);                 // global_registration.txt (global_registration; no reference counterpart)                                   // noise_sweep.txt (noise_sweep; no reference counterpart)
 
     // multi-GPU (map_eval_dist.cpp): the communicator of this rank; forced = take the distributed path with one rank too
@@ -147,6 +161,7 @@ public:
     std::array<double, 16> trans{{1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1}};  // ICP result (row-major), map_eval.h:332
     double vmd = 0.0, full_chamfer_dist = 0.0, scs_overall = 0.0;
     double mme_est = 0.0, mme_gt = 0.0, max_abs_entropy = 0.0, min_abs_entropy = 0.0;
+    std::vector<me_plane_record> plane_rec[2];  // segment_planes: [ME_SLOT_EST], [ME_SLOT_GT] (the latter with segment_gt_planes)
     me_local_geom_out mpv_out[2] = {};  // evaluate_mpv: [ME_SLOT_EST], [ME_SLOT_GT] (the latter with evaluate_gt_mpv)
     std::vector<double> est_entropies, gt_entropies;
     std::vector<uint8_t> valid_entropy_points, gt_valid_entropy_points;

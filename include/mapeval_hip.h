@@ -448,6 +448,70 @@ typedef struct me_local_geom_out {
 int me_local_geometry(me_ctx *ctx, int slot, double radius, int min_k, me_local_geom_out *out);
 int me_local_geometry_fetch(me_ctx *ctx, int slot, double *eig, int32_t *k, uint8_t *valid);
 
+/* ---- plane segmentation: RANSAC plane fit and multi-plane extraction on a resident cloud ---------------------------------------- */
+/* (DESIGN.md section 4.11).  The model is Open3D's PointCloud::SegmentPlane(distance_threshold, 3, num_iterations), applied
+ * repeatedly to what is left; the deviations are listed in DESIGN.md section 5.  Single GPU only: slab or shard mode is ME_ERR_ARG.
+ * No index is needed.  Device timers "plane_score" (the scoring kernel) and "plane" (everything else).
+ *
+ * me_segment_planes.  Parameters: distance_threshold t finite and > 0, 1 <= num_iterations H <= 2^24, 1 <= max_planes P <= 64,
+ * min_inliers >= 3, refit 0 or 1, else ME_ERR_ARG.  The result is a pure function of (cloud, parameters, seed).  Round r = 0, 1, ...
+ * works on the REMAINING points — those without a label yet, m of them, in ascending cloud index (the order of me_download_cloud):
+ *   1. Hypothesis h < H of round r: Philox4x64-10 counter (h, 5, r, 0), key (seed, 0) -> w0, w1, w2 (counter word 1 = 5 names this
+ *      call); k_j = mulhi64(w_j, m); the sample p_j is the k_j-th remaining point.  The hypothesis is INVALID when two k_j coincide
+ *      or when |e01 x e02|^2 <= 1e-12 |e01|^2 |e02|^2, e01 = p1 - p0, e02 = p2 - p0 (cross / dot as in me_global_register:
+ *      dot(u, v) = (u0 v0 + u1 v1) + u2 v2, the test is dot(cr, cr) <= (1e-12 * dot(e01, e01)) * dot(e02, e02)).
+ *   2. Plane of a valid hypothesis: cr = e01 x e02, L = sqrt(dot(cr, cr)), n = cr / L component by component; n is negated when
+ *      c < 0, or c == 0 && b < 0, or c == b == 0 && a < 0; d = -((a x0 + b y0) + c z0).  fp64, no contraction.
+ *   3. Score: s_i = ((a x_i + b y_i) + c z_i) + d for every remaining point; i is an inlier iff |s_i| < t (strict, the library's
+ *      convention); score[h] = the number of inliers, an exact integer; -1 for an invalid hypothesis.
+ *   4. Winner: the largest score, ties to the smallest h.  The round ENDS the extraction, producing no plane, when m < 3 (nothing is
+ *      drawn: every score of the round is -1), when no hypothesis is valid, or when the best score is < min_inliers.
+ *   5. The winner's inliers get label r and leave the remaining set.
+ *   6. Returned plane.  refit = 0: the winner's (a, b, c, d).  refit = 1: the least-squares plane of the inliers — moments about
+ *      o = the winner's p0, M1 = sum(p - o), M2 = sum (p - o)(p - o)^T (per-block partials combined in block order: bit-identical
+ *      from run to run), C = (M2 - M1 M1^T / k) / k, the normal = the eigenvector of the smallest eigenvalue by cyclic Jacobi, the
+ *      sign rule of step 2, d = -dot(n, o + M1 / k).  When the two smallest eigenvalues are equal to working precision,
+ *      l2 - l3 <= 8 k 2^-53 D^2 with D = the largest |p - o|, the hypothesis plane is returned and refit_degenerate is set.
+ *      The labels are NOT recomputed after the refit (upstream's order).
+ *   7. Record of plane r: count, the winning h and its score (= count), the plane, rms = sqrt(sum s^2 / count), mean_abs and max_abs
+ *      of the inliers' residuals against the RETURNED plane (sums in fixed block order), refit_degenerate.
+ *   8. The extraction stops after P planes or at the first round that ends it.  n_planes >= 0 is a result, not an error: a cloud of
+ *      collinear points returns ME_OK with n_planes = 0.
+ * Host outputs (nullable): planes[max_planes] (the first n_planes are written), labels[N] in cloud order (-1 = no plane),
+ * scores[max_planes x num_iterations] (row r = the scores of round r; rows of rounds that were never started hold -1).
+ * info: n_in, n_planes, n_labelled, n_valid_hypotheses (summed over the rounds), rounds = the rounds started (the one that ended the
+ * extraction included).  Labels and records stay on the slot until the cloud changes (upload, down-sample, transform, perturbation,
+ * selection), as the cluster labels do.
+ *
+ * me_plane_fetch: the records and labels of the slot's last me_segment_planes (both nullable; *n_planes is always written).
+ * ME_ERR_STATE: no current labels.  ME_ERR_CAPACITY: capacity < *n_planes (the count is still written).
+ *
+ * me_plane_keep (plane = -1 or 0 <= plane < n_planes, invert 0 or 1, else ME_ERR_ARG; ME_ERR_STATE without current labels):
+ * keep[i] = (plane >= 0 ? label[i] == plane : label[i] >= 0) != invert.  It writes the slot's outlier keep-mask:
+ * me_outlier_select_into applies it.  Ground removal is (plane 0, invert 1), keeping only planar structure (-1, 0).
+ * info: n_in, n_kept, threshold = plane, the other fields 0. */
+typedef struct me_plane_params {
+    double distance_threshold;
+    int64_t num_iterations;
+    int32_t max_planes;
+    int32_t refit;
+    int64_t min_inliers;
+    uint64_t seed; /* Philox key word 0 */
+} me_plane_params;
+typedef struct me_plane_record {
+    int64_t count, h, score;
+    double plane[4]; /* a, b, c, d: a x + b y + c z + d = 0, |(a, b, c)| = 1 */
+    double rms, mean_abs, max_abs;
+    int32_t refit_degenerate, reserved;
+} me_plane_record;
+typedef struct me_plane_info {
+    int64_t n_in, n_planes, n_labelled, n_valid_hypotheses, rounds;
+} me_plane_info;
+int me_segment_planes(me_ctx *ctx, int slot, const me_plane_params *p, me_plane_record *planes, int32_t *labels, int64_t *scores,
+                      me_plane_info *info);
+int me_plane_fetch(me_ctx *ctx, int slot, me_plane_record *planes, int64_t capacity, int64_t *n_planes, int32_t *labels);
+int me_plane_keep(me_ctx *ctx, int slot, int plane, int invert, uint8_t *keep, me_outlier_info *info);
+
 int64_t me_cloud_size(me_ctx *ctx, int slot);
 /* transformed points back to the host (N x 3), original order — what map_3d_->points_ holds after :1206 */
 int me_download_cloud(me_ctx *ctx, int slot, double *xyz_host);
@@ -655,7 +719,7 @@ int me_run_suite_from(me_ctx *ctx, const double *est, int64_t n_est, const doubl
 
 /* ---- instrumentation (bench.py roofline leg) ------------------------------------------------------------- */
 /* Average device time (ms, HIP events on the context's stream) and launch count of a named kernel family since
- * the last me_timers_reset: "nn_grid", "nn1", "mme", "sort", "morton", "gather", "cells" (the cell tables), "octree", "nn_stats", "voxel", "voxel_metrics", "w2", "scs", "slab_filter", "halo_pack", "perturb", "fpfh", "fpfh_match", "ransac", "ransac_validate".  Enabled by me_timers_enable(1).
+ * the last me_timers_reset: "nn_grid", "nn1", "mme", "sort", "morton", "gather", "cells" (the cell tables), "octree", "nn_stats", "voxel", "voxel_metrics", "w2", "scs", "slab_filter", "halo_pack", "perturb", "fpfh", "fpfh_match", "ransac", "ransac_validate", "plane", "plane_score".  Enabled by me_timers_enable(1).
  * Counters (total_ms = 0, value in *launches): "mme_pairs" (accepted (query, neighbour) pairs of the MME launches: the useful work of
  * the VALU-bound kernel, bench.py's roofline.valu), "mme_refined" (queries whose thin neighbourhood — smallest covariance eigenvalue below ~1.8e-6 cell^2 — the MME pass
  * recomputed two-pass about the query itself; counted whether or not timers are on), "nn_queries" / "nn_fallback_queries" (1-NN queries, and those that needed the
