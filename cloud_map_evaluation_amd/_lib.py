@@ -11,6 +11,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MAPEVAL_HIP_LIB") or os.path.join(_HERE, "libmapeval_hip.so")
 
 ME_OK = 0
+ME_ERR_ARG = -1
+ME_ERR_STATE = -3
 ME_ERR_CAPACITY = -4
 ME_SLOT_EST = 0
 ME_SLOT_GT = 1
@@ -34,6 +36,7 @@ SYMBOLS = [
     "me_cluster_dbscan", "me_cluster_sizes", "me_cluster_keep",
     "me_local_geometry", "me_local_geometry_fetch",
     "me_segment_planes", "me_plane_fetch", "me_plane_keep",
+    "me_group_order_stats", "me_mom_select_axes", "me_mom", "me_mom_fetch",
     "me_set_normals", "me_get_normals", "me_estimate_normals", "me_gicp_covariances", "me_get_covariances", "me_icp_lsq_sums",
     "me_nn1", "me_icp_p2p_sums", "me_render_distance", "me_render_entropy", "me_nn_stats", "me_nn_partial_sums", "me_nn_sigma_sums", "me_nn_finalize", "me_chamfer",
     "me_mme", "me_voxel_gaussians", "me_voxel_metrics", "me_awd_scs", "me_w2_batch", "me_scs_table", "me_run_suite", "me_run_suite_from", "me_mme_fetch",
@@ -237,6 +240,50 @@ class PlaneInfo(C.Structure):
     ]
 
 
+class GroupStats(C.Structure):
+    _fields_ = [
+        ("count", C.c_int64),
+        ("sum", C.c_double),
+        ("min", C.c_double),
+        ("max", C.c_double),
+        ("lower", C.c_double),
+        ("upper", C.c_double),
+    ]
+
+
+class MomParams(C.Structure):
+    _fields_ = [("cos_parallel", C.c_double), ("cos_orthogonal", C.c_double), ("min_axis_points", C.c_int64)]
+
+
+class MomAxisChoice(C.Structure):
+    _fields_ = [("direction", C.c_int32), ("n_planes", C.c_int32), ("weight", C.c_int64), ("rep", C.c_double * 3)]
+
+
+class MomAxes(C.Structure):
+    _fields_ = [("n_axes", C.c_int32), ("n_directions", C.c_int32), ("axis", MomAxisChoice * 3)]
+
+
+class MomAxis(C.Structure):
+    _fields_ = [
+        ("direction", C.c_int32),
+        ("n_planes", C.c_int32),
+        ("rep", C.c_double * 3),
+        ("n_points", C.c_int64),
+        ("n_valid", C.c_int64),
+        ("sum_l3", C.c_double),
+        ("min", C.c_double),
+        ("max", C.c_double),
+        ("lower", C.c_double),
+        ("upper", C.c_double),
+        ("median", C.c_double),
+    ]
+
+
+class MomOut(C.Structure):
+    _fields_ = [("n_axes", C.c_int32), ("n_directions", C.c_int32), ("axis", MomAxis * 3), ("mom_median", C.c_double),
+                ("mom_mean", C.c_double)]
+
+
 _lib = None
 
 
@@ -324,6 +371,12 @@ def load():
     L.me_plane_fetch.argtypes = [vp, C.c_int, vp, C.c_int64, C.POINTER(C.c_int64), ip]
     L.me_plane_keep.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.POINTER(OutlierInfo)]
     for f in ("me_segment_planes", "me_plane_fetch", "me_plane_keep"):
+        getattr(L, f).restype = C.c_int
+    L.me_group_order_stats.argtypes = [vp, dp, ip, C.c_int64, C.c_int32, vp]
+    L.me_mom_select_axes.argtypes = [vp, C.c_int32, C.POINTER(MomParams), ip, C.POINTER(MomAxes)]
+    L.me_mom.argtypes = [vp, C.c_int, C.POINTER(MomParams), C.POINTER(MomOut)]
+    L.me_mom_fetch.argtypes = [vp, C.c_int, vp]
+    for f in ("me_group_order_stats", "me_mom_select_axes", "me_mom", "me_mom_fetch"):
         getattr(L, f).restype = C.c_int
     L.me_upload_cloud.argtypes = [vp, C.c_int, dp, C.c_int64, dp, C.c_double]
     L.me_upload_cloud_device.argtypes = [vp, C.c_int, dp, C.c_int64, dp, C.c_double]

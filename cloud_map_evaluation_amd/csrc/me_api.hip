@@ -370,6 +370,25 @@ int me_plane_keep(me_ctx *ctx, int slot, int plane, int invert, uint8_t *keep, m
     return me::plane_keep(ctx, slot, plane, invert, keep, info);
 }
 
+int me_group_order_stats(me_ctx *ctx, const double *values, const int32_t *group, int64_t n, int32_t n_groups, me_group_stats *out) {
+    if (!ctx) return ME_ERR_ARG;
+    return me::group_order_stats(ctx, values, group, n, n_groups, out);
+}
+
+int me_mom_select_axes(const me_plane_record *planes, int32_t n_planes, const me_mom_params *p, int32_t *dir_of_plane, me_mom_axes *axes) {
+    return me::mom_select_axes(planes, n_planes, p, dir_of_plane, axes);
+}
+
+int me_mom(me_ctx *ctx, int slot, const me_mom_params *p, me_mom_out *out) {
+    if (!ctx) return ME_ERR_ARG;
+    return me::mom(ctx, slot, p, out);
+}
+
+int me_mom_fetch(me_ctx *ctx, int slot, int8_t *axis) {
+    if (!ctx) return ME_ERR_ARG;
+    return me::mom_fetch(ctx, slot, axis);
+}
+
 int me_transform_cloud(me_ctx *ctx, int slot, const double *T) {
     if (!ctx) return ME_ERR_ARG;
     return me::cloud_transform(ctx, slot, T);

@@ -240,6 +240,13 @@ struct Cloud {
     DevBuf plane_labels;
     std::vector<me_plane_record> plane_rec;
     bool plane_valid = false;
+    // every me_local_geometry / me_segment_planes that completes on this cloud gets a new serial: a product of both (me_mom.hip) is
+    // current only while both flags are set and both serials are the ones it was made from
+    unsigned long long lg_serial = 0, plane_serial = 0;
+    // axis byte per point (int8[n], cloud order, -1 = not used) of the last me_mom (me_mom.hip); dropped with the labels and the eigenvalues
+    DevBuf mom_axis;
+    bool mom_have = false;
+    unsigned long long mom_lg_serial = 0, mom_plane_serial = 0;
 };
 
 struct TimerRec {
@@ -315,6 +322,7 @@ struct me_ctx {
     long long mme_keep_n = -1;
     me::DevBuf outlier_tmp[2];                   // me_outlier.hip: per-point avg_dist / counts and the fallback list, kept for repeated calls
     me::DevBuf cluster_tmp[5];                   // me_cluster.hip: parent, smallest index per root, the two flag arrays, the border list
+    me::DevBuf mom_tmp[3];                       // me_mom.hip: selection keys, group bytes, the small state block (histograms, ranks, results)
     me::DevBuf plane_tmp[7];                     // me_plane.hip: remaining flags and list, the compacted coordinates, hypotheses, scores, scalars
     me::DevBuf nn1_dbg_buf;                      // octree-walk counters (nodes opened, leaves scanned, points, max per query)
     unsigned long long *nn1_dbg() {
@@ -505,6 +513,11 @@ int segment_planes(me_ctx *ctx, int slot, const me_plane_params *p, me_plane_rec
                    me_plane_info *info);
 int plane_fetch(me_ctx *ctx, int slot, me_plane_record *planes_host, long long capacity, long long *n_planes, int32_t *labels_host);
 int plane_keep(me_ctx *ctx, int slot, int plane, int invert, uint8_t *keep_host, me_outlier_info *info);
+// ---- me_mom.hip ----
+int group_order_stats(me_ctx *ctx, const double *values_host, const int32_t *group_host, long long n, int n_groups, me_group_stats *out);
+int mom_select_axes(const me_plane_record *planes, int n_planes, const me_mom_params *p, int32_t *dir_of_plane, me_mom_axes *axes);
+int mom(me_ctx *ctx, int slot, const me_mom_params *p, me_mom_out *out);
+int mom_fetch(me_ctx *ctx, int slot, int8_t *axis_host);
 // ---- me_cluster.hip ----
 int cluster_dbscan(me_ctx *ctx, int slot, double eps, int min_points, int32_t *labels_host, int32_t *counts_host, me_cluster_info *info);
 int cluster_sizes(me_ctx *ctx, int slot, int64_t *sizes_host, long long capacity, long long *n_clusters);

@@ -194,6 +194,7 @@ int local_geometry(me_ctx *ctx, int slot, double radius, int min_k, me_local_geo
         ME_TRY(mg.sync());
     }
     c.lg_have = true;
+    ++c.lg_serial;
     if (out) {
         out->n = n;
         out->n_valid = h[6].i;

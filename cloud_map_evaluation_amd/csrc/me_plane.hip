@@ -484,6 +484,7 @@ int segment_planes(me_ctx *ctx, int slot, const me_plane_params *p, me_plane_rec
     if (planes_host) std::copy(recs.begin(), recs.end(), planes_host);
     c.plane_rec = recs;
     c.plane_valid = true;
+    ++c.plane_serial;
     if (info) {
         info->n_in = n;
         info->n_planes = (int64_t) recs.size();

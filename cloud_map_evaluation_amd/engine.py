@@ -8,6 +8,7 @@ module is what tests/ and bench.py drive.
 from __future__ import annotations
 
 import ctypes as C
+import math
 from dataclasses import dataclass, field
 from typing import Optional
 
@@ -618,6 +619,90 @@ class Engine:
     def mpv(self, slot: int, radius: float, min_k: int = 5) -> float:
         """Mean plane variance: the mean smallest covariance eigenvalue over the valid points (0.0 without one)."""
         return self.local_geometry(slot, radius, min_k)["mpv"]
+
+    # ---- MOM: plane variance on mutually orthogonal planes, exact medians (me_mom.hip) ----
+    def group_order_stats(self, values, groups, n_groups: int) -> dict:
+        """me_group_order_stats: per group g in [0, n_groups) of the entries with groups[i] == g (-1 = ignored): count, sum, min, max
+        and the two middle elements lower = sorted[(count - 1) // 2], upper = sorted[count // 2], all but the sum exact; median =
+        (lower + upper) / 2.  Returns a dict of arrays of n_groups entries."""
+        values = np.ascontiguousarray(values, dtype=np.float64).reshape(-1)
+        groups = np.ascontiguousarray(groups, dtype=np.int32).reshape(-1)
+        if values.shape != groups.shape:
+            raise ValueError("values and groups differ in length")
+        out = (_lib.GroupStats * max(1, min(int(n_groups), 64)))()
+        self._ck(self._L.me_group_order_stats(self._ctx, _addr(values), _addr(groups), int(values.shape[0]), int(n_groups), C.addressof(out)))
+        res = {f: np.array([getattr(out[g], f) for g in range(int(n_groups))], np.int64 if f == "count" else np.float64)
+               for f, _ in _lib.GroupStats._fields_}
+        res["median"] = (res["lower"] + res["upper"]) / 2
+        return res
+
+    @staticmethod
+    def _mom_params(parallel_deg: float, orthogonal_deg: float, min_axis_points: int) -> _lib.MomParams:
+        # planes within parallel_deg of each other share a direction; directions within orthogonal_deg of a right angle are orthogonal
+        # (math, not numpy: the C library's cos / sin, which the C++ host calls too)
+        return _lib.MomParams(math.cos(float(parallel_deg) * (math.pi / 180.0)), math.sin(float(orthogonal_deg) * (math.pi / 180.0)),
+                              int(min_axis_points))
+
+    @staticmethod
+    def mom_select_axes(planes, parallel_deg: float = 10.0, orthogonal_deg: float = 10.0, min_axis_points: int = 1000, *,
+                        cos_parallel: float | None = None, cos_orthogonal: float | None = None):
+        """me_mom_select_axes (host arithmetic, no device): planes = the dicts of segment_planes (their "plane" and "count").  The
+        thresholds are given in degrees, or directly as the cosines the library takes.  Returns (dir_of_plane [n_planes] int32, axes) —
+        axes = {"n_axes", "n_directions", "axes": [{"direction", "n_planes", "weight", "rep"}, ...]}."""
+        L = _lib.load()
+        prm = Engine._mom_params(parallel_deg, orthogonal_deg, min_axis_points)
+        if cos_parallel is not None:
+            prm.cos_parallel = float(cos_parallel)
+        if cos_orthogonal is not None:
+            prm.cos_orthogonal = float(cos_orthogonal)
+        n = len(planes)
+        recs = (_lib.PlaneRecord * max(1, n))()
+        for r, pl in enumerate(planes[:len(recs)]):
+            recs[r].count = int(pl["count"])
+            for e in range(4):
+                recs[r].plane[e] = float(pl["plane"][e]) if e < len(pl["plane"]) else 0.0
+        dirs = np.full(max(1, n), -1, np.int32)
+        ax = _lib.MomAxes()
+        rc = L.me_mom_select_axes(C.addressof(recs), n, C.byref(prm), _addr(dirs), C.byref(ax))
+        if rc != 0:
+            raise MapEvalError(f"[{rc}] me_mom_select_axes: needs 0 <= cos_orthogonal < cos_parallel <= 1, min_axis_points >= 1 and at most 64 planes")
+        axes = [{"direction": int(a.direction), "n_planes": int(a.n_planes), "weight": int(a.weight), "rep": np.array(list(a.rep))}
+                for a in list(ax.axis)[:ax.n_axes]]
+        return dirs[:n], {"n_axes": int(ax.n_axes), "n_directions": int(ax.n_directions), "axes": axes}
+
+    def _has_result(self, rc: int) -> bool:
+        if rc == _lib.ME_ERR_STATE:
+            return False
+        self._ck(rc)
+        return True
+
+    def mom(self, slot: int, radius: float | None = None, min_k: int = 5, parallel_deg: float = 10.0, orthogonal_deg: float = 10.0,
+            min_axis_points: int = 1000, plane_kwargs: dict | None = None, fetch: bool = False):
+        """me_mom: the mutually orthogonal metric of a resident cloud, from the slot's local_geometry eigenvalues and segment_planes
+        labels.  A stage whose result the slot lacks is run first when its arguments are given (radius and min_k; plane_kwargs = the
+        keyword arguments of segment_planes); a current result is never recomputed.  Returns a dict: n_axes, n_directions, mom_median
+        (the sum of the axis medians), mom_mean, axes = one dict per axis (direction, n_planes, rep, n_points, n_valid, sum_l3, min,
+        max, lower, upper, median); with fetch=True also the axis byte per point ([N] int8 in cloud order, -1 = not used)."""
+        if radius is not None and not self._has_result(self._L.me_local_geometry_fetch(self._ctx, int(slot), 0, 0, 0)):
+            self.local_geometry(slot, radius, min_k)
+        if plane_kwargs is not None:
+            m = C.c_int64(0)
+            if not self._has_result(self._L.me_plane_fetch(self._ctx, int(slot), 0, 0, C.byref(m), 0)):
+                self.segment_planes(slot, **plane_kwargs)
+        prm = self._mom_params(parallel_deg, orthogonal_deg, min_axis_points)
+        o = _lib.MomOut()
+        self._ck(self._L.me_mom(self._ctx, int(slot), C.byref(prm), C.byref(o)))
+        axes = []
+        for a in list(o.axis)[:o.n_axes]:
+            d = {f: getattr(a, f) for f, _ in a._fields_ if f != "rep"}
+            d["rep"] = np.array(list(a.rep))
+            axes.append(d)
+        res = {"n_axes": int(o.n_axes), "n_directions": int(o.n_directions), "mom_median": o.mom_median, "mom_mean": o.mom_mean, "axes": axes}
+        if not fetch:
+            return res
+        axis = np.empty(self.size(slot), np.int8)
+        self._ck(self._L.me_mom_fetch(self._ctx, int(slot), _addr(axis)))
+        return res, axis
 
     # ---- voxels ----
     def voxel_build(self, slot: int, voxel_size: float) -> int:

@@ -268,6 +268,29 @@ Param loadParametersFromYAML(const std::string &yaml_file_path) {
         if (param.plane_min_inliers < 3) throw std::runtime_error("plane_min_inliers: must be >= 3");
         if (param.segment_planes && param.num_gpus > 1) throw std::runtime_error("segment_planes: single GPU only (num_gpus must be 1)");
     }
+    // MOM (no reference counterpart): its two inputs take the mpv_* and plane_* keys, checked here when their own stages are off
+    if (config.has("evaluate_mom")) param.evaluate_mom = config.as_bool("evaluate_mom");
+    if (config.has("mom_parallel_deg")) param.mom_parallel_deg = config.as_double("mom_parallel_deg");
+    if (config.has("mom_orthogonal_deg")) param.mom_orthogonal_deg = config.as_double("mom_orthogonal_deg");
+    if (config.has("mom_min_axis_points")) param.mom_min_axis_points = (int64_t) config.as_double("mom_min_axis_points");
+    param.evaluate_gt_mom = config.has("evaluate_gt_mom") ? config.as_bool("evaluate_gt_mom") : param.evaluate_gt_mme_;
+    if (param.evaluate_mom) {
+        if (!(param.mom_parallel_deg >= 0) || !(param.mom_parallel_deg < 90)) throw std::runtime_error("mom_parallel_deg: must lie in [0, 90)");
+        if (!(param.mom_orthogonal_deg >= 0) || !(param.mom_orthogonal_deg < 90))
+            throw std::runtime_error("mom_orthogonal_deg: must lie in [0, 90)");
+        if (!(param.mom_parallel_deg + param.mom_orthogonal_deg < 90))
+            throw std::runtime_error("mom_parallel_deg + mom_orthogonal_deg: must be < 90 (a direction cannot be parallel and orthogonal to another)");
+        if (param.mom_min_axis_points < 1) throw std::runtime_error("mom_min_axis_points: must be >= 1");
+        if (!(param.mpv_radius > 0) || !std::isfinite(param.mpv_radius)) throw std::runtime_error("mpv_radius: must be > 0");
+        if (param.mpv_min_points < 2) throw std::runtime_error("mpv_min_points: must be >= 2 (the covariance divides by k - 1)");
+        if (!(param.plane_distance_threshold > 0) || !std::isfinite(param.plane_distance_threshold))
+            throw std::runtime_error("plane_distance_threshold: must be > 0");
+        if (param.plane_num_iterations < 1 || param.plane_num_iterations > (1 << 24))
+            throw std::runtime_error("plane_num_iterations: must lie in 1..2^24");
+        if (param.plane_max_planes < 1 || param.plane_max_planes > 64) throw std::runtime_error("plane_max_planes: must lie in 1..64");
+        if (param.plane_min_inliers < 3) throw std::runtime_error("plane_min_inliers: must be >= 3");
+        if (param.num_gpus > 1) throw std::runtime_error("evaluate_mom: single GPU only (num_gpus must be 1)");
+    }
     return param;
 }
 
@@ -312,7 +335,9 @@ std::string paramToJson(const Param &p) {
       << ", \"segment_planes\": " << b(p.segment_planes) << ", \"plane_distance_threshold\": " << p.plane_distance_threshold
       << ", \"plane_num_iterations\": " << p.plane_num_iterations << ", \"plane_max_planes\": " << p.plane_max_planes
       << ", \"plane_min_inliers\": " << p.plane_min_inliers << ", \"plane_seed\": " << p.plane_seed << ", \"plane_refit\": " << b(p.plane_refit)
-      << ", \"segment_gt_planes\": " << b(p.segment_gt_planes) << "}";
+      << ", \"segment_gt_planes\": " << b(p.segment_gt_planes) << ", \"evaluate_mom\": " << b(p.evaluate_mom)
+      << ", \"mom_parallel_deg\": " << p.mom_parallel_deg << ", \"mom_orthogonal_deg\": " << p.mom_orthogonal_deg
+      << ", \"mom_min_axis_points\": " << p.mom_min_axis_points << ", \"evaluate_gt_mom\": " << b(p.evaluate_gt_mom) << "}";
     return o.str();
 }
 
@@ -394,7 +419,9 @@ int MapEval::process() {
     if (mpv && comm_) return fail("evaluate_mpv: single GPU only (num_gpus must be 1)");
     const bool planes = param_.segment_planes;  // (likewise)
     if (planes && comm_) return fail("segment_planes: single GPU only (num_gpus must be 1)");
-    if (one_call && !noised && !filter && !mpv && !planes && !(param_.downsample_size > 0)) {
+    const bool mom = param_.evaluate_mom;  // (likewise)
+    if (mom && comm_) return fail("evaluate_mom: single GPU only (num_gpus must be 1)");
+    if (one_call && !noised && !filter && !mpv && !planes && !mom && !(param_.downsample_size > 0)) {
         file_result << std::fixed << std::setprecision(15) << "Estimated-Ground Truth point count: " << map_3d_->size() << " / "
                     << gt_3d_->size() << std::endl;
         if (param_.enable_debug)
@@ -439,6 +466,7 @@ int MapEval::process() {
                   << " points (Ground Truth)." << std::endl;
     if (mpv && computeMPV() != 0) return -1;  // (the clouds as loaded, where computeMME runs: before the transform)
     if (planes && segmentPlanes() != 0) return -1;  // (likewise)
+    if (mom && computeMOM() != 0) return -1;  // (likewise; after its two inputs)
     if (comm_) return processDist(tic_toc.toc());  // num_gpus > 1 (map_eval_dist.cpp)
     if (one_call) {  // (the down-sampled or perturbed clouds are resident)
         const int rc = processOneCall(false, tic_toc.toc());
@@ -464,6 +492,7 @@ int MapEval::process() {
     }
     if (mpv && param_.save_immediate_result_) saveMpvResults();
     if (planes && param_.save_immediate_result_) savePlaneResults();
+    if (mom && param_.save_immediate_result_) saveMomResults();
 
     if (param_.evaluate_using_initial_) {
         if (param_.enable_debug) std::cout << "INFO: Using initial matrix without registration." << std::endl;
@@ -824,6 +853,7 @@ int MapEval::processOneCall(bool from_host, double t_loaded) {
     }
     if (param_.evaluate_mpv && param_.save_immediate_result_) saveMpvResults();
     if (param_.segment_planes && param_.save_immediate_result_) savePlaneResults();
+    if (param_.evaluate_mom && param_.save_immediate_result_) saveMomResults();
     t2 = t1 + so.stage_ms[0] + so.stage_ms[4] + so.stage_ms[5];
     // ---- calculateMetricsWithInitialMatrix's members (:1204-1260) ----
     if (param_.enable_debug) std::cout << "INFO: Using initial matrix without registration." << std::endl;
@@ -1219,6 +1249,66 @@ void MapEval::savePlaneResults() {
             std::fprintf(f, "%s %zu %lld %lld %.17g %.17g %.17g %.17g %.17g %.17g %.17g %d\n", s == ME_SLOT_EST ? "est" : "gt", i,
                          (long long) r.count, (long long) r.h, r.plane[0], r.plane[1], r.plane[2], r.plane[3], r.rms, r.mean_abs, r.max_abs,
                          (int) r.refit_degenerate);
+        }
+    }
+    if (std::fclose(f) != 0) fail("writing " + path + " failed");
+}
+
+me_mom_params MapEval::momParams() const {
+    me_mom_params mp{};
+    mp.cos_parallel = std::cos(param_.mom_parallel_deg * (M_PI / 180.0));
+    mp.cos_orthogonal = std::sin(param_.mom_orthogonal_deg * (M_PI / 180.0));  // cos(90 - deg)
+    mp.min_axis_points = param_.mom_min_axis_points;
+    return mp;
+}
+
+// me_mom per cloud; an input whose own stage (evaluate_mpv / segment_planes) did not run on that cloud is computed here, with the same
+// keys, and leaves no line or file of its own
+int MapEval::computeMOM() {
+    const me_mom_params mp = momParams();
+    for (int s : {ME_SLOT_EST, ME_SLOT_GT}) {
+        if (s == ME_SLOT_GT && !param_.evaluate_gt_mom) break;
+        const bool have_lg = param_.evaluate_mpv && (s == ME_SLOT_EST || param_.evaluate_gt_mpv);
+        const bool have_planes = param_.segment_planes && (s == ME_SLOT_EST || param_.segment_gt_planes);
+        if (!have_lg && me_local_geometry(ctx_, s, param_.mpv_radius, param_.mpv_min_points, nullptr) != ME_OK)
+            return fail(std::string("evaluate_mom: ") + me_last_error(ctx_));
+        if (!have_planes) {
+            const me_plane_params pp = planeParams(param_.plane_max_planes);
+            if (me_segment_planes(ctx_, s, &pp, nullptr, nullptr, nullptr, nullptr) != ME_OK)
+                return fail(std::string("evaluate_mom: ") + me_last_error(ctx_));
+        }
+        if (me_mom(ctx_, s, &mp, &mom_out[s]) != ME_OK) return fail(std::string("evaluate_mom: ") + me_last_error(ctx_));
+    }
+    if (param_.evaluate_gt_mom) std::cout << "MOM EST-GT: " << mom_out[ME_SLOT_EST].mom_median << " " << mom_out[ME_SLOT_GT].mom_median << std::endl;
+    else std::cout << "MOM EST: " << mom_out[ME_SLOT_EST].mom_median << std::endl;
+    return 0;
+}
+
+void MapEval::saveMomResults() {
+    const bool gt = param_.evaluate_gt_mom;
+    // the sum of the axis medians per cloud, then the number of axes it was taken over
+    file_result << std::fixed << std::setprecision(5) << "MOM est-gt: " << mom_out[ME_SLOT_EST].mom_median;
+    if (gt) file_result << " " << mom_out[ME_SLOT_GT].mom_median;
+    file_result << " n_axes " << mom_out[ME_SLOT_EST].n_axes;
+    if (gt) file_result << " " << mom_out[ME_SLOT_GT].n_axes;
+    file_result << std::endl;
+    // mom.txt: the parameters ("name value"), then per cloud one row per axis:
+    // cloud axis direction n_planes n_points n_valid rep_x rep_y rep_z sum_l3 min max lower upper median
+    const std::string path = results_subfolder + "mom.txt";
+    FILE *f = std::fopen(path.c_str(), "w");
+    if (!f) {
+        fail("cannot write " + path);
+        return;
+    }
+    std::fprintf(f, "parallel_deg %.17g\northogonal_deg %.17g\nmin_axis_points %lld\nradius %.17g\nmin_points %d\n", param_.mom_parallel_deg,
+                 param_.mom_orthogonal_deg, (long long) param_.mom_min_axis_points, param_.mpv_radius, param_.mpv_min_points);
+    for (int s : {ME_SLOT_EST, ME_SLOT_GT}) {
+        if (s == ME_SLOT_GT && !gt) break;
+        for (int k = 0; k < mom_out[s].n_axes; ++k) {
+            const me_mom_axis &a = mom_out[s].axis[k];
+            std::fprintf(f, "%s %d %d %d %lld %lld %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g\n", s == ME_SLOT_EST ? "est" : "gt", k,
+                         (int) a.direction, (int) a.n_planes, (long long) a.n_points, (long long) a.n_valid, a.rep[0], a.rep[1], a.rep[2], a.sum_l3,
+                         a.min, a.max, a.lower, a.upper, a.median);
         }
     }
     if (std::fclose(f) != 0) fail("writing " + path + " failed");

@@ -107,6 +107,14 @@ struct Param {
     uint64_t plane_seed = 0;                 // `plane_seed:` Philox seed
     bool plane_refit = true;                 // `plane_refit:` least-squares plane of the inliers
     bool segment_gt_planes = false;          // `segment_gt_planes:` also on the ground truth (default: evaluate_gt_mme)
+    // MOM, the plane variance on mutually orthogonal planes (optional keys; no reference counterpart): me_mom on the clouds as loaded,
+    // from me_local_geometry (the mpv_* keys) and me_segment_planes (the plane_* keys), which it runs itself when their own keys are
+    // off; a `MOM est-gt:` line after the `Planes` line, and mom.txt
+    bool evaluate_mom = false;               // `evaluate_mom:`
+    double mom_parallel_deg = 10.0;          // `mom_parallel_deg:` planes within this angle share a direction
+    double mom_orthogonal_deg = 10.0;        // `mom_orthogonal_deg:` directions within this angle of a right angle are orthogonal
+    int64_t mom_min_axis_points = 1000;      // `mom_min_axis_points:` labelled points a direction needs, >= 1
+    bool evaluate_gt_mom = false;            // `evaluate_gt_mom:` also on the ground truth (default: evaluate_gt_mme)
     int dist_rank = 0;              // (set by the launcher, not a YAML key)
     void printParam() const;
 };
@@ -145,6 +153,9 @@ public:
     me_plane_params planeParams(int max_planes) const;      // the plane_* keys as me_segment_planes' parameters
     int segmentPlanes();                                    // segment_planes: me_segment_planes on both clouds (no reference counterpart)
     void savePlaneResults();                                // its result line and plane_segmentation.txt
+    me_mom_params momParams() const;                        // the mom_* keys (degrees) as me_mom's cosines
+    int computeMOM();                                       // evaluate_mom: me_mom on both clouds (no reference counterpart)
+    void saveMomResults();                                  // its result line and mom.txt
     int globalRegistration(double T_c[16]);                 // global_registration.txt (global_registration; no reference counterpart)                                   // noise_sweep.txt (noise_sweep; no reference counterpart)
 
     // multi-GPU (map_eval_dist.cpp): the communicator of this rank; forced = take the distributed path with one rank too
@@ -162,6 +173,7 @@ public:
     double vmd = 0.0, full_chamfer_dist = 0.0, scs_overall = 0.0;
     double mme_est = 0.0, mme_gt = 0.0, max_abs_entropy = 0.0, min_abs_entropy = 0.0;
     std::vector<me_plane_record> plane_rec[2];  // segment_planes: [ME_SLOT_EST], [ME_SLOT_GT] (the latter with segment_gt_planes)
+    me_mom_out mom_out[2] = {};  // evaluate_mom: [ME_SLOT_EST], [ME_SLOT_GT] (the latter with evaluate_gt_mom)
     me_local_geom_out mpv_out[2] = {};  // evaluate_mpv: [ME_SLOT_EST], [ME_SLOT_GT] (the latter with evaluate_gt_mpv)
     std::vector<double> est_entropies, gt_entropies;
     std::vector<uint8_t> valid_entropy_points, gt_valid_entropy_points;

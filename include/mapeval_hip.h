@@ -512,6 +512,83 @@ int me_segment_planes(me_ctx *ctx, int slot, const me_plane_params *p, me_plane_
 int me_plane_fetch(me_ctx *ctx, int slot, me_plane_record *planes, int64_t capacity, int64_t *n_planes, int32_t *labels);
 int me_plane_keep(me_ctx *ctx, int slot, int plane, int invert, uint8_t *keep, me_outlier_info *info);
 
+/* ---- MOM: plane variance on mutually orthogonal planes, aggregated by exact medians ---------------------------------------------- */
+/* (DESIGN.md section 4.12).  The mutually orthogonal metric of Kornilova and Ferrer 2021: the smallest covariance eigenvalue l3 of
+ * me_local_geometry, taken only on the points of planes (me_segment_planes) whose directions are mutually orthogonal, and aggregated
+ * per axis by the median.  Three pieces: a grouped exact order statistic on the device, the choice of the axes on the host, and the
+ * metric on a resident cloud.
+ *
+ * me_group_order_stats (1 <= n_groups <= 64 and n >= 0, else ME_ERR_ARG; host pointers, values / group of n entries).  group[i] in
+ * [-1, n_groups), -1 = the entry is ignored; values finite and >= 0 (-0.0 counts as +0.0).  Anything else is ME_ERR_ARG, detected on
+ * the device and reported after the call (`out` is then unspecified).  The selection key of an entry is the bit pattern of v + 0.0
+ * read as an unsigned 64-bit integer: on non-negative doubles its order is the numeric order.  Per group g, over its entries:
+ *   count           their number
+ *   sum             per-block partials (tiles of 2048 entries; inside a tile a fixed tree) combined in block order, 256 chunks, then one
+ *                   block: no floating-point atomics, bit-identical from run to run
+ *   min, max        the smallest and the largest entry
+ *   lower, upper    sorted[(count - 1) / 2] and sorted[count / 2]: the two middle elements (the same one for an odd count)
+ * count, min, max, lower and upper are EXACT — elements of the input, found by a radix select over the keys (eight passes of eight
+ * bits, integer histograms: independent of any order).  The median is (lower + upper) / 2, formed by the caller in exactly this
+ * form.  A group without an entry has every field 0.  Device timer "group_select".
+ *
+ * me_mom_select_axes: pure host arithmetic, no context (like me_nn_finalize).  0 <= cos_orthogonal < cos_parallel <= 1,
+ * min_axis_points >= 1, 0 <= n_planes <= 64, planes / p / axes non-NULL (planes and dir_of_plane may be NULL when n_planes = 0), else
+ * ME_ERR_ARG.  With dot(u, v) = (u0 v0 + u1 v1) + u2 v2 (fp64, no contraction), n_r = planes[r].plane[0..2], c_r = planes[r].count:
+ *   1. Directions.  r ascending: plane r joins the SMALLEST existing direction g with |dot(n_r, rep_g)| >= cos_parallel, rep_g = the
+ *      normal of the plane that founded g; otherwise it founds a new direction.  dir_of_plane[r] = g; W_g = the sum of its c_r.
+ *   2. A direction is eligible iff W_g >= min_axis_points.
+ *   3. g and h are orthogonal iff |dot(rep_g, rep_h)| <= cos_orthogonal.  Both thresholds are inclusive.
+ *   4. The largest s in {3, 2, 1} with an eligible, pairwise orthogonal s-subset; among those subsets the largest min W, then the
+ *      largest sum W, then the lexicographically smallest ascending tuple.  n_axes = s (0 without an eligible direction); the axes in
+ *      ascending g, each with its direction, the number of its planes, W and rep.  Unused axis entries are zero.
+ * The thresholds are cosines, so that no trigonometry has to agree between languages.
+ *
+ * me_mom (parameters as above, else ME_ERR_ARG; single GPU only: slab or shard mode is ME_ERR_ARG).  ME_ERR_STATE unless the slot
+ * holds both a current me_local_geometry result and current me_segment_planes labels; the two stages may run in either order
+ * (me_segment_planes builds no index, me_local_geometry discards only what depends on the sorted order).  The axes are chosen from
+ * the slot's plane records as me_mom_select_axes does.  Point i is USED by axis a iff its label is >= 0, the direction of its plane
+ * is axis a, and its local-geometry validity byte is set; it then contributes its l3 to the group a of me_group_order_stats.  Per
+ * axis: direction, n_planes, rep, n_points = W (the labelled points of the direction), n_valid = the used points, sum_l3, min, max,
+ * lower, upper and median = (lower + upper) / 2 of their l3.  mom_median = the sum of the medians in axis order (map_metrics'
+ * definition), mom_mean = the sum of sum_l3 / n_valid; an axis without a used point contributes 0 to both and says so by
+ * n_valid = 0.  n_axes = 0 is a result (ME_OK, both metrics 0), not an error.  Device timers "mom" and "group_select".
+ *
+ * me_mom_fetch: axis[N] in cloud order, the axis that used the point, -1 = not used.  ME_ERR_STATE without a current me_mom result:
+ * it is dropped with the labels and with the eigenvalues (a changed cloud, a later me_segment_planes or me_local_geometry). */
+typedef struct me_group_stats {
+    int64_t count;
+    double sum, min, max, lower, upper;
+} me_group_stats;
+typedef struct me_mom_params {
+    double cos_parallel;     /* planes whose normals have |dot| >= this share a direction */
+    double cos_orthogonal;   /* directions whose representatives have |dot| <= this are orthogonal */
+    int64_t min_axis_points; /* labelled points a direction needs to be eligible */
+} me_mom_params;
+typedef struct me_mom_axis_choice {
+    int32_t direction, n_planes;
+    int64_t weight; /* W */
+    double rep[3];
+} me_mom_axis_choice;
+typedef struct me_mom_axes {
+    int32_t n_axes, n_directions;
+    me_mom_axis_choice axis[3];
+} me_mom_axes;
+typedef struct me_mom_axis {
+    int32_t direction, n_planes;
+    double rep[3];
+    int64_t n_points, n_valid;
+    double sum_l3, min, max, lower, upper, median;
+} me_mom_axis;
+typedef struct me_mom_out {
+    int32_t n_axes, n_directions;
+    me_mom_axis axis[3];
+    double mom_median, mom_mean;
+} me_mom_out;
+int me_group_order_stats(me_ctx *ctx, const double *values, const int32_t *group, int64_t n, int32_t n_groups, me_group_stats *out);
+int me_mom_select_axes(const me_plane_record *planes, int32_t n_planes, const me_mom_params *p, int32_t *dir_of_plane, me_mom_axes *axes);
+int me_mom(me_ctx *ctx, int slot, const me_mom_params *p, me_mom_out *out);
+int me_mom_fetch(me_ctx *ctx, int slot, int8_t *axis);
+
 int64_t me_cloud_size(me_ctx *ctx, int slot);
 /* transformed points back to the host (N x 3), original order — what map_3d_->points_ holds after :1206 */
 int me_download_cloud(me_ctx *ctx, int slot, double *xyz_host);
@@ -719,7 +796,7 @@ int me_run_suite_from(me_ctx *ctx, const double *est, int64_t n_est, const doubl
 
 /* ---- instrumentation (bench.py roofline leg) ------------------------------------------------------------- */
 /* Average device time (ms, HIP events on the context's stream) and launch count of a named kernel family since
- * the last me_timers_reset: "nn_grid", "nn1", "mme", "sort", "morton", "gather", "cells" (the cell tables), "octree", "nn_stats", "voxel", "voxel_metrics", "w2", "scs", "slab_filter", "halo_pack", "perturb", "fpfh", "fpfh_match", "ransac", "ransac_validate", "plane", "plane_score".  Enabled by me_timers_enable(1).
+ * the last me_timers_reset: "nn_grid", "nn1", "mme", "sort", "morton", "gather", "cells" (the cell tables), "octree", "nn_stats", "voxel", "voxel_metrics", "w2", "scs", "slab_filter", "halo_pack", "perturb", "fpfh", "fpfh_match", "ransac", "ransac_validate", "plane", "plane_score", "mom", "group_select".  Enabled by me_timers_enable(1).
  * Counters (total_ms = 0, value in *launches): "mme_pairs" (accepted (query, neighbour) pairs of the MME launches: the useful work of
  * the VALU-bound kernel, bench.py's roofline.valu), "mme_refined" (queries whose thin neighbourhood — smallest covariance eigenvalue below ~1.8e-6 cell^2 — the MME pass
  * recomputed two-pass about the query itself; counted whether or not timers are on), "nn_queries" / "nn_fallback_queries" (1-NN queries, and those that needed the
