@@ -37,6 +37,7 @@ SYMBOLS = [
     "me_local_geometry", "me_local_geometry_fetch",
     "me_segment_planes", "me_plane_fetch", "me_plane_keep",
     "me_group_order_stats", "me_mom_select_axes", "me_mom", "me_mom_fetch",
+    "me_rank_select", "me_sqrt_threshold", "me_nn_error_distribution", "me_fscore_finalize",
     "me_set_normals", "me_get_normals", "me_estimate_normals", "me_gicp_covariances", "me_get_covariances", "me_icp_lsq_sums",
     "me_nn1", "me_icp_p2p_sums", "me_render_distance", "me_render_entropy", "me_nn_stats", "me_nn_partial_sums", "me_nn_sigma_sums", "me_nn_finalize", "me_chamfer",
     "me_mme", "me_voxel_gaussians", "me_voxel_metrics", "me_awd_scs", "me_w2_batch", "me_scs_table", "me_run_suite", "me_run_suite_from", "me_mme_fetch",
@@ -284,6 +285,45 @@ class MomOut(C.Structure):
                 ("mom_mean", C.c_double)]
 
 
+ME_RANK_MAX = 16
+ME_ERRDIST_MAX_THRESHOLDS = 8
+ME_ERRDIST_MAX_BINS = 4096
+
+
+class RankStats(C.Structure):
+    _fields_ = [("count", C.c_int64), ("sum", C.c_double), ("min", C.c_double), ("max", C.c_double), ("value", C.c_double * ME_RANK_MAX)]
+
+
+class ErrDistParams(C.Structure):
+    _fields_ = [
+        ("gate", C.c_double),
+        ("gate_mode", C.c_int32),
+        ("n_quantiles", C.c_int32),
+        ("prob", C.c_double * ME_RANK_MAX),
+        ("n_thresholds", C.c_int32),
+        ("tau", C.c_double * ME_ERRDIST_MAX_THRESHOLDS),
+        ("n_bins", C.c_int32),
+        ("bin_width", C.c_double),
+    ]
+
+
+class ErrDistOut(C.Structure):
+    _fields_ = [
+        ("n_query", C.c_int64),
+        ("n_used", C.c_int64),
+        ("sum_d", C.c_double),
+        ("sum_d2", C.c_double),
+        ("min_d", C.c_double),
+        ("max_d", C.c_double),
+        ("argmax", C.c_int64),
+        ("rank", C.c_int64 * ME_RANK_MAX),
+        ("quantile_d", C.c_double * ME_RANK_MAX),
+        ("quantile_d2", C.c_double * ME_RANK_MAX),
+        ("n_within", C.c_int64 * ME_ERRDIST_MAX_THRESHOLDS),
+        ("n_overflow", C.c_int64),
+    ]
+
+
 _lib = None
 
 
@@ -378,6 +418,14 @@ def load():
     L.me_mom_fetch.argtypes = [vp, C.c_int, vp]
     for f in ("me_group_order_stats", "me_mom_select_axes", "me_mom", "me_mom_fetch"):
         getattr(L, f).restype = C.c_int
+    L.me_rank_select.argtypes = [vp, dp, vp, C.c_int64, vp, C.c_int32, C.POINTER(RankStats)]
+    L.me_rank_select.restype = C.c_int
+    L.me_sqrt_threshold.argtypes = [C.c_double]
+    L.me_sqrt_threshold.restype = C.c_double
+    L.me_nn_error_distribution.argtypes = [vp, C.c_int, C.POINTER(ErrDistParams), C.POINTER(ErrDistOut), vp]
+    L.me_nn_error_distribution.restype = C.c_int
+    L.me_fscore_finalize.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_double * 3)]
+    L.me_fscore_finalize.restype = None
     L.me_upload_cloud.argtypes = [vp, C.c_int, dp, C.c_int64, dp, C.c_double]
     L.me_upload_cloud_device.argtypes = [vp, C.c_int, dp, C.c_int64, dp, C.c_double]
     L.me_cloud_size.restype = C.c_int64

@@ -3,6 +3,7 @@
 #include <cstring>
 
 #include "me_internal.hpp"
+#include "me_stat.hpp"
 
 static std::string g_create_error;
 
@@ -389,6 +390,22 @@ int me_mom_fetch(me_ctx *ctx, int slot, int8_t *axis) {
     return me::mom_fetch(ctx, slot, axis);
 }
 
+int me_rank_select(me_ctx *ctx, const double *values, const uint8_t *use, int64_t n, const int64_t *ranks, int32_t n_ranks, me_rank_stats *out) {
+    if (!ctx) return ME_ERR_ARG;
+    return me::rank_select(ctx, values, use, n, ranks, n_ranks, out);
+}
+
+int me_nn_error_distribution(me_ctx *ctx, int query_slot, const me_errdist_params *p, me_errdist_out *out, int64_t *hist) {
+    if (!ctx) return ME_ERR_ARG;
+    return me::nn_error_distribution(ctx, query_slot, p, out, hist);
+}
+
+void me_fscore_finalize(int64_t n_within_est, int64_t n_est, int64_t n_within_gt, int64_t n_gt, double prf[3]) {
+    me::fscore_finalize(n_within_est, n_est, n_within_gt, n_gt, prf);
+}
+
+double me_sqrt_threshold(double t) { return me::sqrt_threshold(t); }
+
 int me_transform_cloud(me_ctx *ctx, int slot, const double *T) {
     if (!ctx) return ME_ERR_ARG;
     return me::cloud_transform(ctx, slot, T);
@@ -761,6 +778,12 @@ int me_timer_get(me_ctx *ctx, const char *name, double *total_ms, int64_t *launc
     if (std::strcmp(name, "mme_refined") == 0) {  // queries recomputed by k_mme_refine (thin neighbourhoods) since the last reset; counted always
         if (total_ms) *total_ms = 0.0;
         if (launches) *launches = ctx->mme_refined;
+        return ME_OK;
+    }
+    if (std::strcmp(name, "rank_select_compactions") == 0 || std::strcmp(name, "rank_select_list") == 0) {
+        // of the context's last select (me_rank_select, me_nn_error_distribution): compactions done / entries of the list its last pass read
+        if (total_ms) *total_ms = 0.0;
+        if (launches) *launches = ctx->rs_compact[name[12] == 'c' ? 0 : 1];
         return ME_OK;
     }
     if (std::strncmp(name, "nn1_", 4) == 0 && std::strlen(name) > 4) {

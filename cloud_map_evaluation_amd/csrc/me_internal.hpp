@@ -323,6 +323,8 @@ struct me_ctx {
     me::DevBuf outlier_tmp[2];                   // me_outlier.hip: per-point avg_dist / counts and the fallback list, kept for repeated calls
     me::DevBuf cluster_tmp[5];                   // me_cluster.hip: parent, smallest index per root, the two flag arrays, the border list
     me::DevBuf mom_tmp[3];                       // me_mom.hip: selection keys, group bytes, the small state block (histograms, ranks, results)
+    me::DevBuf rs_tmp[4];                        // me_errdist.hip: the select's state block, the two compacted lists, the use bytes
+    long long rs_compact[2] = {0, 0};            // ... of the last select: compactions done, entries of the last list (me_timer_get)
     me::DevBuf plane_tmp[7];                     // me_plane.hip: remaining flags and list, the compacted coordinates, hypotheses, scores, scalars
     me::DevBuf nn1_dbg_buf;                      // octree-walk counters (nodes opened, leaves scanned, points, max per query)
     unsigned long long *nn1_dbg() {
@@ -518,6 +520,11 @@ int group_order_stats(me_ctx *ctx, const double *values_host, const int32_t *gro
 int mom_select_axes(const me_plane_record *planes, int n_planes, const me_mom_params *p, int32_t *dir_of_plane, me_mom_axes *axes);
 int mom(me_ctx *ctx, int slot, const me_mom_params *p, me_mom_out *out);
 int mom_fetch(me_ctx *ctx, int slot, int8_t *axis_host);
+// ---- me_errdist.hip ----
+int rank_select(me_ctx *ctx, const double *values_host, const uint8_t *use_host, long long n, const int64_t *ranks, int n_ranks,
+                me_rank_stats *out);
+int nn_error_distribution(me_ctx *ctx, int qslot, const me_errdist_params *p, me_errdist_out *out, int64_t *hist_host);
+void fscore_finalize(long long n_within_est, long long n_est, long long n_within_gt, long long n_gt, double prf[3]);
 // ---- me_cluster.hip ----
 int cluster_dbscan(me_ctx *ctx, int slot, double eps, int min_points, int32_t *labels_host, int32_t *counts_host, me_cluster_info *info);
 int cluster_sizes(me_ctx *ctx, int slot, int64_t *sizes_host, long long capacity, long long *n_clusters);

@@ -22,6 +22,16 @@ __device__ __forceinline__ bool gate_pass(const StatParams &sp, double d2) {
 }
 #endif
 
+// The largest double x with sqrt_rn(x) <= t (-1 when t is not >= 0): a device compares d2 against it, so that a count of "distance <= t"
+// does not depend on the device's sqrt rounding.  me_sqrt_threshold; the thresholds of make_params and of me_errdist.hip.
+inline double sqrt_threshold(double t) {
+    if (!(t >= 0)) return -1.0;
+    double x = t * t;
+    while (std::sqrt(std::nextafter(x, INFINITY)) <= t) x = std::nextafter(x, INFINITY);
+    while (x > 0 && std::sqrt(x) > t) x = std::nextafter(x, -INFINITY);
+    return x;
+}
+
 inline StatParams make_params(double gate, int gate_mode, const double trunc[5]) {
     StatParams sp;
     if (gate < 0) {
@@ -34,19 +44,7 @@ inline StatParams make_params(double gate, int gate_mode, const double trunc[5])
         sp.gate = gate;
         sp.gate_strict = 0;
     }
-    for (int k = 0; k < 5; ++k) {
-        // largest double x with sqrt_rn(x) <= t, so the device compares d2 against it and the inlier count does
-        // not depend on the device's sqrt rounding
-        const double t = trunc ? trunc[k] : 0.0;
-        if (!(t >= 0)) {
-            sp.t2max[k] = -1.0;
-            continue;
-        }
-        double x = t * t;
-        while (std::sqrt(std::nextafter(x, INFINITY)) <= t) x = std::nextafter(x, INFINITY);
-        while (x > 0 && std::sqrt(x) > t) x = std::nextafter(x, -INFINITY);
-        sp.t2max[k] = x;
-    }
+    for (int k = 0; k < 5; ++k) sp.t2max[k] = sqrt_threshold(trunc ? trunc[k] : 0.0);
     return sp;
 }
 

@@ -704,6 +704,73 @@ class Engine:
         self._ck(self._L.me_mom_fetch(self._ctx, int(slot), _addr(axis)))
         return res, axis
 
+    # ---- error distribution: exact quantiles, Hausdorff distance, F-score, error CDF (me_errdist.hip) ----
+    def rank_select(self, values, ranks, use=None) -> dict:
+        """me_rank_select: of the entries with use[i] != 0 (None: all): count, sum, min, max and value[j] = sorted_used[ranks[j]] (0-based
+        ranks, unsorted and repeated ones allowed, at most 16), all but the sum exact.  Returns a dict; "value" has len(ranks) entries."""
+        values = np.ascontiguousarray(values, dtype=np.float64).reshape(-1)
+        ranks = np.ascontiguousarray(ranks, dtype=np.int64).reshape(-1)
+        if use is not None:
+            use = np.ascontiguousarray(np.asarray(use) != 0, dtype=np.uint8).reshape(-1)
+            if use.shape != values.shape:
+                raise ValueError("values and use differ in length")
+        o = _lib.RankStats()
+        self._ck(self._L.me_rank_select(self._ctx, _addr(values), _addr(use), int(values.shape[0]), _addr(ranks), int(ranks.shape[0]), C.byref(o)))
+        return {"count": int(o.count), "sum": o.sum, "min": o.min, "max": o.max,
+                "value": np.array(list(o.value)[:min(int(ranks.shape[0]), _lib.ME_RANK_MAX)], np.float64)}
+
+    @staticmethod
+    def sqrt_threshold(t: float) -> float:
+        """me_sqrt_threshold: the largest double whose correctly rounded sqrt is <= t (host arithmetic)."""
+        return float(_lib.load().me_sqrt_threshold(float(t)))
+
+    @staticmethod
+    def fscore(n_within_est: int, n_est: int, n_within_gt: int, n_gt: int):
+        """me_fscore_finalize (host arithmetic): (precision, recall, fscore)."""
+        prf = (C.c_double * 3)()
+        _lib.load().me_fscore_finalize(int(n_within_est), int(n_est), int(n_within_gt), int(n_gt), C.byref(prf))
+        return prf[0], prf[1], prf[2]
+
+    def nn_error_distribution(self, query_slot: int, quantiles=(0.5, 0.9, 0.95, 0.99), thresholds=(), bins: int = 0, bin_width: float = 0.0,
+                              gate: float = -1.0, gate_mode: int = ME_GATE_LE_UNSQUARED) -> dict:
+        """me_nn_error_distribution on the current 1-NN result of query_slot: n_query, n_used, sum_d, sum_d2, min_d, max_d (the
+        one-sided Hausdorff distance), argmax (original index of the worst query), per quantile rank / quantile_d / quantile_d2
+        (nearest rank, exact), per threshold n_within, and with bins > 0 hist[bins] (counts between the edges j * bin_width) and
+        n_overflow.  gate < 0: every query."""
+        quantiles = [float(x) for x in quantiles]
+        thresholds = [float(x) for x in thresholds]
+        if len(quantiles) > _lib.ME_RANK_MAX or len(thresholds) > _lib.ME_ERRDIST_MAX_THRESHOLDS:
+            raise MapEvalError("[-1] nn_error_distribution: at most 16 quantiles and 8 thresholds")
+        p = _lib.ErrDistParams()
+        p.gate, p.gate_mode = float(gate), int(gate_mode)
+        p.n_quantiles, p.n_thresholds = len(quantiles), len(thresholds)
+        for j, x in enumerate(quantiles):
+            p.prob[j] = x
+        for k, x in enumerate(thresholds):
+            p.tau[k] = x
+        p.n_bins, p.bin_width = int(bins), float(bin_width)
+        hist = np.zeros(max(0, min(int(bins), _lib.ME_ERRDIST_MAX_BINS)), np.int64)
+        o = _lib.ErrDistOut()
+        self._ck(self._L.me_nn_error_distribution(self._ctx, int(query_slot), C.byref(p), C.byref(o), _addr(hist) if hist.size else 0))
+        nq, nt = len(quantiles), len(thresholds)
+        return {"n_query": int(o.n_query), "n_used": int(o.n_used), "sum_d": o.sum_d, "sum_d2": o.sum_d2, "min_d": o.min_d, "max_d": o.max_d,
+                "argmax": int(o.argmax), "prob": np.array(quantiles, np.float64), "rank": np.array(list(o.rank)[:nq], np.int64),
+                "quantile_d": np.array(list(o.quantile_d)[:nq], np.float64), "quantile_d2": np.array(list(o.quantile_d2)[:nq], np.float64),
+                "tau": np.array(thresholds, np.float64), "n_within": np.array(list(o.n_within)[:nt], np.int64), "hist": hist,
+                "n_overflow": int(o.n_overflow), "bin_width": float(bin_width)}
+
+    def error_report(self, thresholds, quantiles=(0.5, 0.9, 0.95, 0.99), bins: int = 0, bin_width: float = 0.0, gate: float = -1.0,
+                     gate_mode: int = ME_GATE_LE_UNSQUARED) -> dict:
+        """Both directions from the resident 1-NN results of slots 0 and 1: "est" / "gt" = nn_error_distribution of each, hausdorff =
+        max(max_d_est, max_d_gt), and per threshold precision (est points within tau of the ground truth / used est points), recall
+        (the same from the ground truth's side) and fscore through me_fscore_finalize."""
+        est = self.nn_error_distribution(ME_SLOT_EST, quantiles, thresholds, bins, bin_width, gate, gate_mode)
+        gt = self.nn_error_distribution(ME_SLOT_GT, quantiles, thresholds, bins, bin_width, gate, gate_mode)
+        prf = np.array([self.fscore(est["n_within"][k], est["n_used"], gt["n_within"][k], gt["n_used"]) for k in range(len(est["tau"]))],
+                       np.float64).reshape(-1, 3)
+        return {"est": est, "gt": gt, "hausdorff": max(est["max_d"], gt["max_d"]), "tau": est["tau"], "precision": prf[:, 0],
+                "recall": prf[:, 1], "fscore": prf[:, 2]}
+
     # ---- voxels ----
     def voxel_build(self, slot: int, voxel_size: float) -> int:
         """Builds (and caches on the cloud) the voxel-Gaussian table without exporting it; returns the voxel count."""

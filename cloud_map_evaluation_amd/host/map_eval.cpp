@@ -291,6 +291,36 @@ Param loadParametersFromYAML(const std::string &yaml_file_path) {
         if (param.plane_min_inliers < 3) throw std::runtime_error("plane_min_inliers: must be >= 3");
         if (param.num_gpus > 1) throw std::runtime_error("evaluate_mom: single GPU only (num_gpus must be 1)");
     }
+    // the error distribution of both directions (no reference counterpart)
+    if (config.has("evaluate_error_distribution")) param.evaluate_error_distribution = config.as_bool("evaluate_error_distribution");
+    std::string error_not_a_list;  // a list key that holds a scalar or a block sequence: refused below, when the stage is on
+    for (const char *key : {"error_quantiles", "error_thresholds"})
+        if (config.has(key) && (!config.at(key).scalar.empty() || !config.at(key).rows.empty()) && error_not_a_list.empty()) error_not_a_list = key;
+    if (config.has("error_quantiles")) {
+        param.error_quantiles.clear();
+        for (const auto &v : config.at("error_quantiles").seq) param.error_quantiles.push_back(yaml_lite::Document::to_double(v, "error_quantiles"));
+    }
+    if (config.has("error_thresholds")) {
+        for (const auto &v : config.at("error_thresholds").seq) param.error_thresholds.push_back(yaml_lite::Document::to_double(v, "error_thresholds"));
+    } else {
+        param.error_thresholds.assign(param.trunc_dist_.begin(), param.trunc_dist_.end());
+    }
+    if (config.has("error_cdf_bins")) param.error_cdf_bins = config.as_int("error_cdf_bins");
+    param.error_cdf_max = config.has("error_cdf_max") ? config.as_double("error_cdf_max") : param.icp_max_distance_;
+    if (config.has("error_gated")) param.error_gated = config.as_bool("error_gated");
+    if (param.evaluate_error_distribution) {
+        if (!error_not_a_list.empty()) throw std::runtime_error(error_not_a_list + ": must be a list [a, b, ...]");
+        if (param.error_quantiles.size() > ME_RANK_MAX) throw std::runtime_error("error_quantiles: at most 16 values");
+        for (const double q : param.error_quantiles)
+            if (!(q >= 0.0 && q <= 1.0)) throw std::runtime_error("error_quantiles: every value must lie in [0, 1]");
+        if (param.error_thresholds.size() > ME_ERRDIST_MAX_THRESHOLDS) throw std::runtime_error("error_thresholds: at most 8 values");
+        for (const double t : param.error_thresholds)
+            if (!(t >= 0.0) || !std::isfinite(t)) throw std::runtime_error("error_thresholds: every value must be finite and >= 0");
+        if (param.error_cdf_bins < 0 || param.error_cdf_bins > ME_ERRDIST_MAX_BINS) throw std::runtime_error("error_cdf_bins: must lie in 0..4096");
+        if (param.error_cdf_bins > 0 && (!(param.error_cdf_max > 0) || !std::isfinite(param.error_cdf_max)))
+            throw std::runtime_error("error_cdf_max: must be > 0");
+        if (param.num_gpus > 1) throw std::runtime_error("evaluate_error_distribution: single GPU only (num_gpus must be 1)");
+    }
     return param;
 }
 
@@ -337,7 +367,13 @@ std::string paramToJson(const Param &p) {
       << ", \"plane_min_inliers\": " << p.plane_min_inliers << ", \"plane_seed\": " << p.plane_seed << ", \"plane_refit\": " << b(p.plane_refit)
       << ", \"segment_gt_planes\": " << b(p.segment_gt_planes) << ", \"evaluate_mom\": " << b(p.evaluate_mom)
       << ", \"mom_parallel_deg\": " << p.mom_parallel_deg << ", \"mom_orthogonal_deg\": " << p.mom_orthogonal_deg
-      << ", \"mom_min_axis_points\": " << p.mom_min_axis_points << ", \"evaluate_gt_mom\": " << b(p.evaluate_gt_mom) << "}";
+      << ", \"mom_min_axis_points\": " << p.mom_min_axis_points << ", \"evaluate_gt_mom\": " << b(p.evaluate_gt_mom)
+      << ", \"evaluate_error_distribution\": " << b(p.evaluate_error_distribution) << ", \"error_quantiles\": [";
+    for (size_t i = 0; i < p.error_quantiles.size(); ++i) o << (i ? ", " : "") << p.error_quantiles[i];
+    o << "], \"error_thresholds\": [";
+    for (size_t i = 0; i < p.error_thresholds.size(); ++i) o << (i ? ", " : "") << p.error_thresholds[i];
+    o << "], \"error_cdf_bins\": " << p.error_cdf_bins << ", \"error_cdf_max\": " << p.error_cdf_max << ", \"error_gated\": " << b(p.error_gated)
+      << "}";
     return o.str();
 }
 
@@ -421,6 +457,7 @@ int MapEval::process() {
     if (planes && comm_) return fail("segment_planes: single GPU only (num_gpus must be 1)");
     const bool mom = param_.evaluate_mom;  // (likewise)
     if (mom && comm_) return fail("evaluate_mom: single GPU only (num_gpus must be 1)");
+    if (param_.evaluate_error_distribution && comm_) return fail("evaluate_error_distribution: single GPU only (num_gpus must be 1)");
     if (one_call && !noised && !filter && !mpv && !planes && !mom && !(param_.downsample_size > 0)) {
         file_result << std::fixed << std::setprecision(15) << "Estimated-Ground Truth point count: " << map_3d_->size() << " / "
                     << gt_3d_->size() << std::endl;
@@ -735,6 +772,7 @@ void MapEval::finishRegistrationMetrics(const me_nn_stats_out &eg, const me_nn_s
     TicToc t1_;
     full_chamfer_dist = eg.mean_nn_dist + ge.mean_nn_dist;  // computeChamferDistance (:1194, :1429): same two searches
     t_fcd = t1_.toc() / 1000.0;
+    if (param_.evaluate_error_distribution && computeErrorDistribution(ME_GATE_LT_SQUARED) != 0) return;
     if (param_.dist_rank > 0) return;
     std::cout << "INFO: RMSE/AC: " << eigen_row(est_gt_results[1], 6) << std::endl;
     std::cout << "INFO: Fitness/Overlap: " << eigen_row(est_gt_results[2], 6) << std::endl;
@@ -947,6 +985,7 @@ void MapEval::finishInitialMatrixMetrics(const me_nn_stats_out &eg, const me_nn_
     // FULL CD: the reference never computes it on this path (stays 0.0); it is free here (same two searches).
     full_chamfer_dist = param_.strict_reference ? 0.0 : (eg.mean_nn_dist + ge.mean_nn_dist);  // (:1429)
     t_fcd = tt.toc() / 1000.0;
+    if (param_.evaluate_error_distribution && computeErrorDistribution(ME_GATE_LE_UNSQUARED) != 0) return;
     if (param_.dist_rank > 0) return;
     std::cout << "INFO: Chamfer Distance: " << eigen_row(cd_vec, 6) << std::endl;
     std::cout << "INFO: F1 Score: " << eigen_row(f1_vec, 6) << std::endl;
@@ -1314,11 +1353,92 @@ void MapEval::saveMomResults() {
     if (std::fclose(f) != 0) fail("writing " + path + " failed");
 }
 
+// me_nn_error_distribution on the 1-NN results of both directions, which the metric path has just used for its statistics (the gate
+// and gate mode are that path's when error_gated is set, none otherwise)
+int MapEval::computeErrorDistribution(int gate_mode) {
+    me_errdist_params &p = errdist_params;
+    p = me_errdist_params{};
+    p.gate = param_.error_gated ? param_.icp_max_distance_ : -1.0;
+    p.gate_mode = gate_mode;
+    p.n_quantiles = (int32_t) param_.error_quantiles.size();
+    for (int j = 0; j < p.n_quantiles; ++j) p.prob[j] = param_.error_quantiles[(size_t) j];
+    p.n_thresholds = (int32_t) param_.error_thresholds.size();
+    for (int k = 0; k < p.n_thresholds; ++k) p.tau[k] = param_.error_thresholds[(size_t) k];
+    p.n_bins = param_.error_cdf_bins;
+    p.bin_width = p.n_bins > 0 ? param_.error_cdf_max / (double) p.n_bins : 0.0;
+    for (int s = ME_SLOT_EST; s <= ME_SLOT_GT; ++s) {
+        errdist_hist[s].assign((size_t) p.n_bins, 0);
+        if (me_nn_error_distribution(ctx_, s, &p, &errdist_out[s], p.n_bins > 0 ? errdist_hist[s].data() : nullptr) != ME_OK)
+            return fail(std::string("evaluate_error_distribution: ") + me_last_error(ctx_));
+    }
+    if (param_.dist_rank == 0)
+        std::cout << "INFO: Hausdorff est-gt-sym: " << errdist_out[0].max_d << " " << errdist_out[1].max_d << " "
+                  << std::max(errdist_out[0].max_d, errdist_out[1].max_d) << std::endl;
+    return 0;
+}
+
+void MapEval::saveErrorDistribution() {
+    const me_errdist_params &p = errdist_params;
+    const me_errdist_out *o = errdist_out;
+    file_result << std::fixed << std::setprecision(5) << "Hausdorff est-gt-sym: " << o[0].max_d << " " << o[1].max_d << " "
+                << std::max(o[0].max_d, o[1].max_d) << std::endl;
+    file_result << std::fixed << std::setprecision(5) << "Error quantiles est|gt:";
+    for (int j = 0; j < p.n_quantiles; ++j) file_result << " " << p.prob[j];
+    file_result << " |";
+    for (int j = 0; j < p.n_quantiles; ++j) file_result << " " << o[0].quantile_d[j];
+    file_result << " |";
+    for (int j = 0; j < p.n_quantiles; ++j) file_result << " " << o[1].quantile_d[j];
+    file_result << std::endl;
+    file_result << std::fixed << std::setprecision(5) << "Fscore P-R-F @t:";
+    for (int k = 0; k < p.n_thresholds; ++k) {
+        double prf[3];
+        me_fscore_finalize(o[0].n_within[k], o[0].n_used, o[1].n_within[k], o[1].n_used, prf);
+        file_result << " " << p.tau[k] << " " << prf[0] << " " << prf[1] << " " << prf[2];
+    }
+    file_result << std::endl;
+    // error_distribution.txt: the parameters ("name value ..."), then per direction the scalar row
+    //   cloud n_query n_used sum_d sum_d2 min_d max_d argmax x y z
+    // the quantile rows `cloud q prob rank quantile_d quantile_d2`, the threshold rows `cloud t tau n_within`, and the CDF rows
+    // `cloud c edge count cumulative fraction`, closed by `cloud overflow n_overflow` (doubles as %.17g)
+    const std::string path = results_subfolder + "error_distribution.txt";
+    FILE *f = std::fopen(path.c_str(), "w");
+    if (!f) {
+        fail("cannot write " + path);
+        return;
+    }
+    std::fprintf(f, "gate %.17g\ngate_mode %d\nquantiles", p.gate, (int) p.gate_mode);
+    for (int j = 0; j < p.n_quantiles; ++j) std::fprintf(f, " %.17g", p.prob[j]);
+    std::fprintf(f, "\nthresholds");
+    for (int k = 0; k < p.n_thresholds; ++k) std::fprintf(f, " %.17g", p.tau[k]);
+    std::fprintf(f, "\ncdf_bins %d\ncdf_bin_width %.17g\n", (int) p.n_bins, p.bin_width);
+    for (int s = ME_SLOT_EST; s <= ME_SLOT_GT; ++s) {
+        const char *tag = s == ME_SLOT_EST ? "est" : "gt";
+        const std::vector<double> &pts = (s == ME_SLOT_EST ? map_3d_ : gt_3d_)->points_;
+        double xyz[3] = {0, 0, 0};
+        if (o[s].argmax >= 0 && (size_t) o[s].argmax * 3 + 2 < pts.size())
+            for (int d = 0; d < 3; ++d) xyz[d] = pts[(size_t) o[s].argmax * 3 + (size_t) d];
+        std::fprintf(f, "%s %lld %lld %.17g %.17g %.17g %.17g %lld %.17g %.17g %.17g\n", tag, (long long) o[s].n_query, (long long) o[s].n_used,
+                     o[s].sum_d, o[s].sum_d2, o[s].min_d, o[s].max_d, (long long) o[s].argmax, xyz[0], xyz[1], xyz[2]);
+        for (int j = 0; j < p.n_quantiles; ++j)
+            std::fprintf(f, "%s q %.17g %lld %.17g %.17g\n", tag, p.prob[j], (long long) o[s].rank[j], o[s].quantile_d[j], o[s].quantile_d2[j]);
+        for (int k = 0; k < p.n_thresholds; ++k) std::fprintf(f, "%s t %.17g %lld\n", tag, p.tau[k], (long long) o[s].n_within[k]);
+        long long cum = 0;
+        for (int j = 0; j < p.n_bins; ++j) {
+            cum += errdist_hist[s][(size_t) j];
+            std::fprintf(f, "%s c %.17g %lld %lld %.17g\n", tag, (double) (j + 1) * p.bin_width, (long long) errdist_hist[s][(size_t) j], cum,
+                         o[s].n_used > 0 ? (double) cum / (double) o[s].n_used : 0.0);
+        }
+        if (p.n_bins > 0) std::fprintf(f, "%s overflow %lld\n", tag, (long long) o[s].n_overflow);
+    }
+    if (std::fclose(f) != 0) fail("writing " + path + " failed");
+}
+
 void MapEval::saveRegistrationResults() {
     // identical lines and precisions to map_eval.cpp:439-476
     file_result << std::fixed << std::setprecision(15) << "RMSE/AC: " << eigen_row(est_gt_results.at(1), 15) << std::endl;
     file_result << std::fixed << std::setprecision(15) << "Comp: " << eigen_row(est_gt_results.at(2), 15) << std::endl;
     file_result << std::fixed << std::setprecision(5) << "FULL CD: " << full_chamfer_dist << std::endl;
+    if (param_.evaluate_error_distribution) saveErrorDistribution();
     file_result << std::fixed << std::setprecision(5) << "VMD: " << vmd << std::endl;
     file_result << std::fixed << std::setprecision(5) << "SCS: " << scs_overall << std::endl;
     if (param_.evaluate_using_initial_)

@@ -115,6 +115,15 @@ struct Param {
     double mom_orthogonal_deg = 10.0;        // `mom_orthogonal_deg:` directions within this angle of a right angle are orthogonal
     int64_t mom_min_axis_points = 1000;      // `mom_min_axis_points:` labelled points a direction needs, >= 1
     bool evaluate_gt_mom = false;            // `evaluate_gt_mom:` also on the ground truth (default: evaluate_gt_mme)
+    // the error distribution of both directions (optional keys; no reference counterpart): me_nn_error_distribution on the 1-NN results
+    // the metric path leaves resident, after its two me_nn_stats calls (single GPU); three lines after `FULL CD`, and
+    // error_distribution.txt
+    bool evaluate_error_distribution = false;  // `evaluate_error_distribution:`
+    std::vector<double> error_quantiles{0.5, 0.9, 0.95, 0.99};  // `error_quantiles: [..]` at most 16, each in [0, 1]
+    std::vector<double> error_thresholds;      // `error_thresholds: [..]` at most 8, each >= 0 (default: accuracy_level)
+    int error_cdf_bins = 1000;                 // `error_cdf_bins:` 0 .. 4096 (0: no CDF)
+    double error_cdf_max = 0;                  // `error_cdf_max:` the last bin edge (default: icp_max_distance); bin width = max / bins
+    bool error_gated = false;                  // `error_gated:` true = the metric path's own gate and gate mode apply
     int dist_rank = 0;              // (set by the launcher, not a YAML key)
     void printParam() const;
 };
@@ -156,6 +165,8 @@ public:
     me_mom_params momParams() const;                        // the mom_* keys (degrees) as me_mom's cosines
     int computeMOM();                                       // evaluate_mom: me_mom on both clouds (no reference counterpart)
     void saveMomResults();                                  // its result line and mom.txt
+    int computeErrorDistribution(int gate_mode);            // evaluate_error_distribution: both directions (no reference counterpart)
+    void saveErrorDistribution();                           // its three result lines and error_distribution.txt
     int globalRegistration(double T_c[16]);                 // global_registration.txt (global_registration; no reference counterpart)                                   // noise_sweep.txt (noise_sweep; no reference counterpart)
 
     // multi-GPU (map_eval_dist.cpp): the communicator of this rank; forced = take the distributed path with one rank too
@@ -173,6 +184,9 @@ public:
     double vmd = 0.0, full_chamfer_dist = 0.0, scs_overall = 0.0;
     double mme_est = 0.0, mme_gt = 0.0, max_abs_entropy = 0.0, min_abs_entropy = 0.0;
     std::vector<me_plane_record> plane_rec[2];  // segment_planes: [ME_SLOT_EST], [ME_SLOT_GT] (the latter with segment_gt_planes)
+    me_errdist_params errdist_params = {};  // evaluate_error_distribution: what both directions were asked for
+    me_errdist_out errdist_out[2] = {};     // ... [ME_SLOT_EST], [ME_SLOT_GT]
+    std::vector<int64_t> errdist_hist[2];
     me_mom_out mom_out[2] = {};  // evaluate_mom: [ME_SLOT_EST], [ME_SLOT_GT] (the latter with evaluate_gt_mom)
     me_local_geom_out mpv_out[2] = {};  // evaluate_mpv: [ME_SLOT_EST], [ME_SLOT_GT] (the latter with evaluate_gt_mpv)
     std::vector<double> est_entropies, gt_entropies;

@@ -589,6 +589,82 @@ int me_mom_select_axes(const me_plane_record *planes, int32_t n_planes, const me
 int me_mom(me_ctx *ctx, int slot, const me_mom_params *p, me_mom_out *out);
 int me_mom_fetch(me_ctx *ctx, int slot, int8_t *axis);
 
+/* ---- Error distribution: exact quantiles, Hausdorff distance, F-score counts, error histogram --------------------------------------- */
+/* (DESIGN.md section 4.13).  Everything the library reported about a direction's 1-NN distances was a mean: the truncated RMSE of
+ * AC, the mean of CD (computeChamferDistance, map_eval.cpp:1398-1431), one count ratio per threshold; the reference's own attempt at
+ * more, f1_vec (map_eval.cpp:1245-1253), mixes a ratio with metres and is reproduced as it is.  These calls add the shape of the
+ * error.  Every quantity they return except the two sums is an element of the input or an integer count.
+ *
+ * me_rank_select (host pointers; n >= 0, 0 <= n_ranks <= ME_RANK_MAX, else ME_ERR_ARG).  The entries USED are those with use[i] != 0
+ * (use == NULL: all).  Used values are finite and >= 0 (-0.0 counts as +0.0); the selection key is the bit pattern of v + 0.0, as
+ * for me_group_order_stats.  ranks[j] are 0-based, may be unsorted and may repeat, each in [0, count).  A bad value or rank is
+ * ME_ERR_ARG, detected on the device and reported after the call (`out` is then unspecified).
+ *   count           the used entries
+ *   sum             per-block partials (a fixed grid of at most 1024 blocks; a thread adds its entries in order, a block by a fixed
+ *                   tree) combined in block order: no floating-point atomics, bit-identical from run to run
+ *   min, max        the smallest and the largest used entry
+ *   value[j]        sorted_used[ranks[j]]; 0 for j >= n_ranks
+ * count, min, max and value[] are EXACT: a most-significant-digit radix select over the keys, eight passes of eight bits, integer
+ * histograms only, all ranks at once (ranks that share a prefix share a histogram).  After a pass in which at most 1/8 of the
+ * entries read carried a live prefix (and the list had at least 32768 entries), those entries are copied, in order, to a compact list
+ * which the later passes read instead.  count == 0 (then n_ranks must be 0): every field 0.  Device timer "rank_select";
+ * me_timer_get "rank_select_compactions" / "rank_select_list": compactions done by the context's last select / entries its last
+ * pass read.
+ *
+ * me_sqrt_threshold(t): the largest double x whose correctly rounded sqrt is <= t (-1 unless t >= 0).  Host arithmetic.  "d <= t"
+ * is decided everywhere as d2 <= me_sqrt_threshold(t), so that no count depends on how a device rounds sqrt.
+ *
+ * me_nn_error_distribution: the current 1-NN result of query_slot (me_nn1, me_set_nn_result or the suite; ME_ERR_STATE without
+ * one).  Single GPU only (slab or shard mode: ME_ERR_ARG); any parameter out of range is ME_ERR_ARG.  The USED set: every entry with
+ * d2 >= 0 that passes the gate (gate / gate_mode as me_nn_stats; gate < 0: every query, CD's population).
+ *   n_query, n_used   entries with d2 >= 0; the used ones
+ *   sum_d, sum_d2     sums over the used set (sqrt on the device), block-order sums as above
+ *   min_d, max_d      host sqrt of the exact smallest / largest used d2; max_d is the one-sided Hausdorff distance
+ *   argmax            ORIGINAL index of the used query with the largest d2, ties -> smallest index; -1 when n_used == 0
+ *   rank[j]           min(n_used - 1, max(0, (int64) ceil(prob[j] * (double) n_used) - 1)): the nearest-rank definition, one fp64
+ *                     multiplication; quantile_d2[j] = the used d2 of that rank (exact, by the select above on nn_d2 in place),
+ *                     quantile_d[j] = its host sqrt — sqrt is monotone, so it is that order statistic of the distances.
+ *                     n_used == 0: ranks -1, values 0
+ *   n_within[k]       used entries with d2 <= me_sqrt_threshold(tau[k])
+ *   hist[j]           with E_j = me_sqrt_threshold((double) j * bin_width), j = 1 .. n_bins, and E_0 = -inf: the used entries with
+ *                     E_j < d2 <= E_{j+1}, j = 0 .. n_bins - 1; n_overflow those with d2 > E_{n_bins}.  The cumulative sums of hist
+ *                     are the empirical CDF of the distances at the edges j * bin_width under the rule "d <= t"
+ * The call leaves the slot's 1-NN result untouched.  Device timers "errdist" and "rank_select".
+ *
+ * me_fscore_finalize: pure host arithmetic, no context (like me_nn_finalize).  prf = {P, R, F}: P = n_within_est / n_est,
+ * R = n_within_gt / n_gt (a zero denominator gives 0 for that ratio), F = 2 P R / (P + R) when P + R > 0, else 0. */
+#define ME_RANK_MAX 16
+#define ME_ERRDIST_MAX_THRESHOLDS 8
+#define ME_ERRDIST_MAX_BINS 4096
+typedef struct me_rank_stats {
+    int64_t count;
+    double sum, min, max;
+    double value[ME_RANK_MAX];
+} me_rank_stats;
+typedef struct me_errdist_params {
+    double gate;
+    int32_t gate_mode; /* as me_nn_stats; gate < 0: every query */
+    int32_t n_quantiles;
+    double prob[ME_RANK_MAX]; /* each in [0, 1] */
+    int32_t n_thresholds;
+    double tau[ME_ERRDIST_MAX_THRESHOLDS]; /* each >= 0 */
+    int32_t n_bins; /* 0: no histogram */
+    double bin_width; /* > 0 when n_bins > 0 */
+} me_errdist_params;
+typedef struct me_errdist_out {
+    int64_t n_query, n_used;
+    double sum_d, sum_d2, min_d, max_d;
+    int64_t argmax;
+    int64_t rank[ME_RANK_MAX];
+    double quantile_d[ME_RANK_MAX], quantile_d2[ME_RANK_MAX];
+    int64_t n_within[ME_ERRDIST_MAX_THRESHOLDS];
+    int64_t n_overflow;
+} me_errdist_out;
+int me_rank_select(me_ctx *ctx, const double *values, const uint8_t *use, int64_t n, const int64_t *ranks, int32_t n_ranks, me_rank_stats *out);
+double me_sqrt_threshold(double t);
+int me_nn_error_distribution(me_ctx *ctx, int query_slot, const me_errdist_params *p, me_errdist_out *out, int64_t *hist);
+void me_fscore_finalize(int64_t n_within_est, int64_t n_est, int64_t n_within_gt, int64_t n_gt, double prf[3]);
+
 int64_t me_cloud_size(me_ctx *ctx, int slot);
 /* transformed points back to the host (N x 3), original order — what map_3d_->points_ holds after :1206 */
 int me_download_cloud(me_ctx *ctx, int slot, double *xyz_host);
