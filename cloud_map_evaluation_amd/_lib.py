@@ -34,7 +34,7 @@ SYMBOLS = [
     "me_transform_cloud", "me_perturb_cloud", "me_voxel_downsample_into", "me_fpfh", "me_fpfh_match", "me_global_register",
     "me_statistical_outlier", "me_radius_outlier", "me_outlier_select_into",
     "me_cluster_dbscan", "me_cluster_sizes", "me_cluster_keep",
-    "me_local_geometry", "me_local_geometry_fetch",
+    "me_local_geometry", "me_local_geometry_fetch", "me_radius_normals", "me_nn_surface_error", "me_nn_surface_fetch",
     "me_segment_planes", "me_plane_fetch", "me_plane_keep",
     "me_group_order_stats", "me_mom_select_axes", "me_mom", "me_mom_fetch",
     "me_rank_select", "me_sqrt_threshold", "me_nn_error_distribution", "me_fscore_finalize",
@@ -324,6 +324,42 @@ class ErrDistOut(C.Structure):
     ]
 
 
+ME_SURFACE_MAX_ANGLES = 8
+
+
+class RadiusNormalsOut(C.Structure):
+    _fields_ = [("n", C.c_int64), ("n_valid", C.c_int64), ("sum_k", C.c_int64)]
+
+
+class SurfaceParams(C.Structure):
+    _fields_ = [
+        ("gate", C.c_double),
+        ("gate_mode", C.c_int32),
+        ("n_thresholds", C.c_int32),
+        ("tau", C.c_double * ME_ERRDIST_MAX_THRESHOLDS),
+        ("n_angles", C.c_int32),
+        ("reserved", C.c_int32),
+        ("cos_min", C.c_double * ME_SURFACE_MAX_ANGLES),
+    ]
+
+
+class SurfaceOut(C.Structure):
+    _fields_ = [
+        ("n_query", C.c_int64),
+        ("n_used", C.c_int64),
+        ("n_normal_used", C.c_int64),
+        ("sum_e", C.c_double),
+        ("sum_e2", C.c_double),
+        ("sum_t2", C.c_double),
+        ("sum_c", C.c_double),
+        ("max_e", C.c_double),
+        ("argmax", C.c_int64),
+        ("n_within", C.c_int64 * ME_ERRDIST_MAX_THRESHOLDS),
+        ("sum_e2_within", C.c_double * ME_ERRDIST_MAX_THRESHOLDS),
+        ("n_angle", C.c_int64 * ME_SURFACE_MAX_ANGLES),
+    ]
+
+
 _lib = None
 
 
@@ -406,6 +442,11 @@ def load():
     L.me_local_geometry.argtypes = [vp, C.c_int, C.c_double, C.c_int, C.POINTER(LocalGeomOut)]
     L.me_local_geometry_fetch.argtypes = [vp, C.c_int, dp, ip, vp]
     for f in ("me_local_geometry", "me_local_geometry_fetch"):
+        getattr(L, f).restype = C.c_int
+    L.me_radius_normals.argtypes = [vp, C.c_int, C.c_double, C.c_int, dp, C.c_int, C.POINTER(RadiusNormalsOut)]
+    L.me_nn_surface_error.argtypes = [vp, C.c_int, C.POINTER(SurfaceParams), C.POINTER(SurfaceOut)]
+    L.me_nn_surface_fetch.argtypes = [vp, C.c_int, dp, dp]
+    for f in ("me_radius_normals", "me_nn_surface_error", "me_nn_surface_fetch"):
         getattr(L, f).restype = C.c_int
     L.me_segment_planes.argtypes = [vp, C.c_int, C.POINTER(PlaneParams), vp, ip, vp, C.POINTER(PlaneInfo)]
     L.me_plane_fetch.argtypes = [vp, C.c_int, vp, C.c_int64, C.POINTER(C.c_int64), ip]

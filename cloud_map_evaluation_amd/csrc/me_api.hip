@@ -347,6 +347,21 @@ int me_local_geometry(me_ctx *ctx, int slot, double radius, int min_k, me_local_
     return me::local_geometry(ctx, slot, radius, min_k, out);
 }
 
+int me_radius_normals(me_ctx *ctx, int slot, double radius, int min_k, const double *viewpoint, int invalid_z, me_radius_normals_out *out) {
+    if (!ctx) return ME_ERR_ARG;
+    return me::radius_normals(ctx, slot, radius, min_k, viewpoint, invalid_z, out);
+}
+
+int me_nn_surface_error(me_ctx *ctx, int query_slot, const me_surface_params *p, me_surface_out *out) {
+    if (!ctx) return ME_ERR_ARG;
+    return me::nn_surface_error(ctx, query_slot, p, out);
+}
+
+int me_nn_surface_fetch(me_ctx *ctx, int query_slot, double *plane_d, double *cos_n) {
+    if (!ctx) return ME_ERR_ARG;
+    return me::nn_surface_fetch(ctx, query_slot, plane_d, cos_n);
+}
+
 int me_local_geometry_fetch(me_ctx *ctx, int slot, double *eig, int32_t *k, uint8_t *valid) {
     if (!ctx) return ME_ERR_ARG;
     return me::local_geometry_fetch(ctx, slot, eig, k, valid);

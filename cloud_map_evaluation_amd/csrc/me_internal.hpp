@@ -246,6 +246,10 @@ struct Cloud {
     // axis byte per point (int8[n], cloud order, -1 = not used) of the last me_mom (me_mom.hip); dropped with the labels and the eigenvalues
     DevBuf mom_axis;
     bool mom_have = false;
+    // e and c of the last me_nn_surface_error with this cloud as the query, SORTED order, -1 where the pair was not used
+    // (me_surface.hip); current only while the 1-NN result is (nn_ref_slot >= 0): a new one (nn_search, set_nn_result) clears the flag
+    DevBuf surf_e, surf_c;
+    bool surf_have = false;
     unsigned long long mom_lg_serial = 0, mom_plane_serial = 0;
 };
 
@@ -510,6 +514,10 @@ int outlier_select_into(me_ctx *src_ctx, int src_slot, me_ctx *dst_ctx, int dst_
 // ---- me_localgeom.hip ----
 int local_geometry(me_ctx *ctx, int slot, double radius, int min_k, me_local_geom_out *out);
 int local_geometry_fetch(me_ctx *ctx, int slot, double *eig_host, int32_t *k_host, uint8_t *valid_host);
+int radius_normals(me_ctx *ctx, int slot, double radius, int min_k, const double *viewpoint, int invalid_z, me_radius_normals_out *out);
+// ---- me_surface.hip ----
+int nn_surface_error(me_ctx *ctx, int qslot, const me_surface_params *p, me_surface_out *out);
+int nn_surface_fetch(me_ctx *ctx, int qslot, double *plane_d_host, double *cos_n_host);
 // ---- me_plane.hip ----
 int segment_planes(me_ctx *ctx, int slot, const me_plane_params *p, me_plane_record *planes_host, int32_t *labels_host, int64_t *scores_host,
                    me_plane_info *info);

@@ -10,7 +10,10 @@
 //   k_lg_final     the block partials in block order (256 chunks, then one block): a fixed order, bit-identical from run to run, no
 //                  floating-point atomics                                                             (me_local_geometry, "local_geom")
 //   k_lg_unpermute the per-point results, kept in SORTED order on the cloud, back in cloud order           (me_local_geometry_fetch)
-// The file is compiled with -ffp-contract=off: tests/_localgeom_ref.py restates the neighbour test.
+//   k_local_geom_normals  the same pass (one body, a template flag) for me_radius_normals ("radius_normals"): it also keeps the column of Jacobi's V that belongs
+//                  to the smallest eigenvalue, scaled to unit length and optionally turned towards a viewpoint, and stores it in the
+//                  cloud's normals (CLOUD order) — three more stores per point, no second pass over the moments
+// The file is compiled with -ffp-contract=off: tests/_localgeom_ref.py and tests/_surface_ref.py restate the neighbour test.
 #include <algorithm>
 #include <cmath>
 
@@ -30,13 +33,23 @@ union LgWord {
     long long i;
 };
 
+// what k_local_geom_normals needs beyond the eigenvalues (unused by k_local_geom)
+struct LgNormalArgs {
+    double *normals;  // double[n][3], cloud order
+    double vx, vy, vz;
+    int have_view, invalid_z;
+};
+
 // One kernel: the streaming loop alone needs 76 VGPRs (the 9 fp64 sums, the query, d and its products next to the stream's own
 // state), the eigen-solve epilogue brings the kernel to 78 — 6 waves per SIMD either way, no scratch — so a second launch for the
 // epilogue would only add 152 bytes of traffic per point (measured at compile time both ways: DESIGN.md section 4.10).
-__global__ void __launch_bounds__(256)
-k_local_geom(const SPoint *__restrict__ sp, const unsigned long long *__restrict__ codes, long long n, GridView g, double r2, int min_k,
-             double *__restrict__ eig_s, int *__restrict__ k_s, unsigned char *__restrict__ valid_s, LgWord *__restrict__ part,
-             unsigned int nb) {
+// NORMALS: the eigenvector of the smallest eigenvalue goes to na.normals; the eigenvalue path is the same code, and k_local_geom, the
+// <false> instantiation, is the kernel as it was (78 VGPRs, no scratch, 6 waves per SIMD).
+template <bool NORMALS>
+__device__ __forceinline__ void
+local_geom_body(const SPoint *__restrict__ sp, const unsigned long long *__restrict__ codes, long long n, const GridView &g, double r2, int min_k,
+                double *__restrict__ eig_s, int *__restrict__ k_s, unsigned char *__restrict__ valid_s, LgWord *__restrict__ part,
+                unsigned int nb, const LgNormalArgs &na) {
     __shared__ WaveTile s_tile[4];
     __shared__ int2 s_tab[4][kGroupTab + 1];
     __shared__ double smd[4];
@@ -66,6 +79,7 @@ k_local_geom(const SPoint *__restrict__ sp, const unsigned long long *__restrict
     const int k = q.active ? cnt - 1 : 0;
     double l1 = 0, l2 = 0, l3 = 0;
     bool ok = false;
+    double nx = 0, ny = 0, nz = 0;
     if (q.active && k >= min_k) {
         const double kd = (double) k, km = (double) (k - 1);
         double a[9], d[3], V[9];
@@ -83,6 +97,28 @@ k_local_geom(const SPoint *__restrict__ sp, const unsigned long long *__restrict
         if (e0 < e1) t = e0, e0 = e1, e1 = t;
         ok = e0 > 0.0;
         if (ok) l1 = e0, l2 = e1, l3 = e2;
+        if (NORMALS && ok) {
+            // the column of the smallest eigenvalue before the clamp, the lowest index among equal ones (selects, not a
+            // dynamic index: V stays in registers)
+            const bool b1 = d[1] < d[0];
+            const double dm = b1 ? d[1] : d[0];
+            const bool b2 = d[2] < dm;
+            nx = b2 ? V[2] : (b1 ? V[1] : V[0]);
+            ny = b2 ? V[5] : (b1 ? V[4] : V[3]);
+            nz = b2 ? V[8] : (b1 ? V[7] : V[6]);
+            const double len = sqrt((nx * nx + ny * ny) + nz * nz);
+            nx /= len;
+            ny /= len;
+            nz /= len;
+            if (na.have_view) {
+                // the query is read AGAIN here and below (volatile: the compiler may not keep the first copy), so that neither its
+                // coordinates nor its index stay in registers across the eigen-solve: that is what keeps this kernel within 80 VGPRs
+                // without scratch
+                const volatile double *qv = &sp[i].x;
+                const double vx = na.vx - qv[0], vy = na.vy - qv[1], vz = na.vz - qv[2];
+                if ((nx * vx + ny * vy) + nz * vz < 0.0) nx = -nx, ny = -ny, nz = -nz;
+            }
+        }
     }
     if (q.active) {
         eig_s[3 * i] = l1;
@@ -90,6 +126,12 @@ k_local_geom(const SPoint *__restrict__ sp, const unsigned long long *__restrict
         eig_s[3 * i + 2] = l3;
         k_s[i] = k;
         valid_s[i] = ok ? 1 : 0;
+        if (NORMALS) {  // the point's place in the cloud: a permutation of [0, n)
+            const long long o = *(const volatile long long *) &sp[i].idx;
+            na.normals[3 * o] = nx;
+            na.normals[3 * o + 1] = ny;
+            na.normals[3 * o + 2] = (!ok && na.invalid_z) ? 1.0 : nz;
+        }
     }
     // (the denominators are > 0 on a valid point; every other lane adds zeros)
     const double lin = ok ? (l1 - l2) / l1 : 0.0, pla = ok ? (l2 - l3) / l1 : 0.0, sph = ok ? l3 / l1 : 0.0;
@@ -110,6 +152,22 @@ k_local_geom(const SPoint *__restrict__ sp, const unsigned long long *__restrict
         part[5 * (size_t) nb + blockIdx.x].i = b5;
         part[6 * (size_t) nb + blockIdx.x].i = b6;
     }
+}
+
+__global__ void __launch_bounds__(256)
+k_local_geom(const SPoint *__restrict__ sp, const unsigned long long *__restrict__ codes, long long n, GridView g, double r2, int min_k,
+             double *__restrict__ eig_s, int *__restrict__ k_s, unsigned char *__restrict__ valid_s, LgWord *__restrict__ part,
+             unsigned int nb) {
+    local_geom_body<false>(sp, codes, n, g, r2, min_k, eig_s, k_s, valid_s, part, nb, LgNormalArgs{});
+}
+
+// the sibling of me_radius_normals: keeping V through the eigen-solve costs registers the eigenvalue kernel does not pay, so this one
+// alone is held to six waves per SIMD (80 VGPRs) by the attribute — the resource lines of both are in DESIGN.md section 4.14
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 6)))
+k_local_geom_normals(const SPoint *__restrict__ sp, const unsigned long long *__restrict__ codes, long long n, GridView g, double r2, int min_k,
+                     double *__restrict__ eig_s, int *__restrict__ k_s, unsigned char *__restrict__ valid_s, LgWord *__restrict__ part,
+                     unsigned int nb, LgNormalArgs na) {
+    local_geom_body<true>(sp, codes, n, g, r2, min_k, eig_s, k_s, valid_s, part, nb, na);
 }
 
 // row v of `in` ([kLgSums][nb]) -> out[v * gridDim.x + block]: block b sums the chunk [b chunk, (b + 1) chunk) of the row, thread t
@@ -153,10 +211,13 @@ k_lg_unpermute(const SPoint *__restrict__ sp, long long n, const double *__restr
 
 }  // namespace
 
-int local_geometry(me_ctx *ctx, int slot, double radius, int min_k, me_local_geom_out *out) {
-    ME_TRY(need_single_gpu_cloud(ctx, slot, "me_local_geometry"));
-    if (!(radius > 0) || !std::isfinite(radius)) return ctx->fail(ME_ERR_ARG, "me_local_geometry: radius must be finite and > 0");
-    if (min_k < 2) return ctx->fail(ME_ERR_ARG, "me_local_geometry: min_k must be >= 2 (the covariance divides by k - 1)");
+namespace {
+
+// the pass of me_local_geometry (nrm == nullptr) and of me_radius_normals: the per-point results on the slot, the seven totals in h
+int run_local_geom(me_ctx *ctx, int slot, double radius, int min_k, const LgNormalArgs *nrm, const char *who, LgWord h[7]) {
+    ME_TRY(need_single_gpu_cloud(ctx, slot, who));
+    if (!(radius > 0) || !std::isfinite(radius)) return ctx->fail(ME_ERR_ARG, std::string(who) + ": radius must be finite and > 0");
+    if (min_k < 2) return ctx->fail(ME_ERR_ARG, std::string(who) + ": min_k must be >= 2 (the covariance divides by k - 1)");
     Cloud &c = ctx->cloud[slot];
     ME_CHECK(ctx, hipSetDevice(ctx->device));
     // the radius grid, rebuilt as me_mme / me_radius_outlier do: the 27-cell stencil is exact when the cell edge is >= r
@@ -178,23 +239,40 @@ int local_geometry(me_ctx *ctx, int slot, double radius, int min_k, me_local_geo
     LgWord *part2 = part + (size_t) nb * kLgSums;
     LgWord *tot = part2 + (size_t) kLgStage * kLgSums;
     {
-        TimerScope ts(ctx, "local_geom");
-        hipLaunchKernelGGL(k_local_geom, dim3(nb), dim3(256), 0, ctx->stream, c.sp.as<SPoint>(), c.codes.as<unsigned long long>(), n, c.grid,
-                           radius * radius, min_k, c.lg_eig.as<double>(), c.lg_k.as<int>(), c.lg_val.as<unsigned char>(), part, nb);
+        TimerScope ts(ctx, nrm ? "radius_normals" : "local_geom");
+        if (nrm) {
+            c.have_normals = false;  // (the pass overwrites them: whatever was there is gone even if the call fails afterwards)
+            ME_CHECK(ctx, c.normals.ensure((size_t) n * 24));
+            LgNormalArgs na = *nrm;
+            na.normals = c.normals.as<double>();
+            hipLaunchKernelGGL(k_local_geom_normals, dim3(nb), dim3(256), 0, ctx->stream, c.sp.as<SPoint>(), c.codes.as<unsigned long long>(), n,
+                               c.grid, radius * radius, min_k, c.lg_eig.as<double>(), c.lg_k.as<int>(), c.lg_val.as<unsigned char>(), part, nb, na);
+        } else {
+            hipLaunchKernelGGL(k_local_geom, dim3(nb), dim3(256), 0, ctx->stream, c.sp.as<SPoint>(), c.codes.as<unsigned long long>(), n,
+                               c.grid, radius * radius, min_k, c.lg_eig.as<double>(), c.lg_k.as<int>(), c.lg_val.as<unsigned char>(), part, nb);
+        }
         const long long chunk = ((long long) nb + kLgStage - 1) / kLgStage;
         hipLaunchKernelGGL(k_lg_final, dim3(kLgStage), dim3(256), 0, ctx->stream, (const LgWord *) part, (long long) nb, chunk, part2);
         hipLaunchKernelGGL(k_lg_final, dim3(1), dim3(256), 0, ctx->stream, (const LgWord *) part2, (long long) kLgStage, (long long) kLgStage,
                            tot);
     }
     ME_CHECK(ctx, hipGetLastError());
-    LgWord h[7];
     {
         MailGuard mg(ctx);
-        ME_TRY(mail_post(ctx, h, tot, sizeof(h)));
+        ME_TRY(mail_post(ctx, h, tot, 7 * sizeof(LgWord)));
         ME_TRY(mg.sync());
     }
     c.lg_have = true;
     ++c.lg_serial;
+    return ME_OK;
+}
+
+}  // namespace
+
+int local_geometry(me_ctx *ctx, int slot, double radius, int min_k, me_local_geom_out *out) {
+    LgWord h[7];
+    ME_TRY(run_local_geom(ctx, slot, radius, min_k, nullptr, "me_local_geometry", h));
+    const long long n = ctx->cloud[slot].n;
     if (out) {
         out->n = n;
         out->n_valid = h[6].i;
@@ -205,6 +283,28 @@ int local_geometry(me_ctx *ctx, int slot, double radius, int min_k, me_local_geo
         out->sum_surface_variation = h[4].d;
         out->sum_k = h[5].i;
     }
+    return ME_OK;
+}
+
+int radius_normals(me_ctx *ctx, int slot, double radius, int min_k, const double *viewpoint, int invalid_z, me_radius_normals_out *out) {
+    if (!out) return ctx->fail(ME_ERR_ARG, "me_radius_normals: out is NULL");
+    LgNormalArgs na{};
+    if (viewpoint) {
+        if (!std::isfinite(viewpoint[0]) || !std::isfinite(viewpoint[1]) || !std::isfinite(viewpoint[2]))
+            return ctx->fail(ME_ERR_ARG, "me_radius_normals: the viewpoint must be finite");
+        na.vx = viewpoint[0], na.vy = viewpoint[1], na.vz = viewpoint[2];
+        na.have_view = 1;
+    }
+    na.invalid_z = invalid_z != 0;
+    LgWord h[7];
+    ME_TRY(run_local_geom(ctx, slot, radius, min_k, &na, "me_radius_normals", h));
+    Cloud &c = ctx->cloud[slot];
+    c.have_normals = true;
+    c.have_cov = false;
+    c.fpfh_valid = false;
+    out->n = c.n;
+    out->n_valid = h[6].i;
+    out->sum_k = h[5].i;
     return ME_OK;
 }
 

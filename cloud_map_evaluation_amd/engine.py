@@ -771,6 +771,83 @@ class Engine:
         return {"est": est, "gt": gt, "hausdorff": max(est["max_d"], gt["max_d"]), "tau": est["tau"], "precision": prf[:, 0],
                 "recall": prf[:, 1], "fscore": prf[:, 2]}
 
+    # ---- radius-search normals and the normal-aware map error (me_localgeom.hip, me_surface.hip) ----
+    def radius_normals(self, slot: int, radius: float, min_k: int = 5, viewpoint=None, invalid_z: bool = False, fetch: bool = False):
+        """me_radius_normals: the unit eigenvector of the smallest eigenvalue of every point's radius-neighbourhood covariance (the
+        neighbourhood and arithmetic of local_geometry, whose per-point result the call stores too) as the slot's normals; turned
+        towards `viewpoint` (3 values) when given; (0, 0, 0), or (0, 0, 1) with invalid_z, where the point is invalid.  Returns the
+        info dict (n, n_valid, sum_k, mean_k), and with fetch=True also the normals (N,3) in cloud order.  The call may rebuild the
+        slot's index and so discard the 1-NN results: normals first, then nn1."""
+        vp = None if viewpoint is None else np.ascontiguousarray(viewpoint, dtype=np.float64).reshape(-1)
+        if vp is not None and vp.shape != (3,):
+            raise ValueError("viewpoint must hold 3 values")
+        o = _lib.RadiusNormalsOut()
+        self._ck(self._L.me_radius_normals(self._ctx, int(slot), float(radius), int(min_k), _addr(vp), 1 if invalid_z else 0, C.byref(o)))
+        info = {"n": int(o.n), "n_valid": int(o.n_valid), "sum_k": int(o.sum_k), "mean_k": o.sum_k / o.n_valid if o.n_valid > 0 else 0.0}
+        return (info, self.get_normals(slot)) if fetch else info
+
+    def nn_surface_error(self, query_slot: int, plane_thresholds=(), angle_thresholds_deg=(), gate: float = -1.0,
+                         gate_mode: int = ME_GATE_LE_UNSQUARED, fetch: bool = False):
+        """me_nn_surface_error on the current 1-NN result of query_slot, with the reference slot's normals (and the query's, when it
+        has them): n_query, n_used, n_normal_used, sum_e, sum_e2, sum_t2, sum_c, max_e, argmax, per plane threshold n_within /
+        sum_e2_within (e <= tau), per angle threshold n_angle (c >= cos_min; the cosine of the angle is taken here with math.cos).
+        With fetch=True also (plane_d[N], cos_n[N]) in cloud order, -1 where the pair was not used."""
+        taus = [float(x) for x in plane_thresholds]
+        angs = [float(x) for x in angle_thresholds_deg]
+        if len(taus) > _lib.ME_ERRDIST_MAX_THRESHOLDS or len(angs) > _lib.ME_SURFACE_MAX_ANGLES:
+            raise MapEvalError("[-1] nn_surface_error: at most 8 plane thresholds and 8 angle thresholds")
+        p = _lib.SurfaceParams()
+        p.gate, p.gate_mode = float(gate), int(gate_mode)
+        p.n_thresholds, p.n_angles = len(taus), len(angs)
+        cos_min = [math.cos(a * (math.pi / 180.0)) for a in angs]
+        for k, x in enumerate(taus):
+            p.tau[k] = x
+        for k, x in enumerate(cos_min):
+            p.cos_min[k] = x
+        o = _lib.SurfaceOut()
+        self._ck(self._L.me_nn_surface_error(self._ctx, int(query_slot), C.byref(p), C.byref(o)))
+        nt, na = len(taus), len(angs)
+        res = {"n_query": int(o.n_query), "n_used": int(o.n_used), "n_normal_used": int(o.n_normal_used), "sum_e": o.sum_e,
+               "sum_e2": o.sum_e2, "sum_t2": o.sum_t2, "sum_c": o.sum_c, "max_e": o.max_e, "argmax": int(o.argmax),
+               "tau": np.array(taus, np.float64), "n_within": np.array(list(o.n_within)[:nt], np.int64),
+               "sum_e2_within": np.array(list(o.sum_e2_within)[:nt], np.float64), "angle_deg": np.array(angs, np.float64),
+               "cos_min": np.array(cos_min, np.float64), "n_angle": np.array(list(o.n_angle)[:na], np.int64)}
+        return (res, *self.nn_surface_fetch(query_slot)) if fetch else res
+
+    def nn_surface_fetch(self, query_slot: int):
+        """me_nn_surface_fetch -> (plane_d[N], cos_n[N]) of the slot's last nn_surface_error, cloud order, -1 = pair not used."""
+        n = self.size(query_slot)
+        e = np.empty(n, np.float64)
+        c = np.empty(n, np.float64)
+        self._ck(self._L.me_nn_surface_fetch(self._ctx, int(query_slot), _addr(e), _addr(c)))
+        return e, c
+
+    def surface_report(self, plane_thresholds=(), angle_thresholds_deg=(5.0, 10.0, 20.0), quantiles=(), gate: float = -1.0,
+                       gate_mode: int = ME_GATE_LE_UNSQUARED) -> dict:
+        """Both directions from the resident 1-NN results of slots 0 and 1 (each slot needs the other's normals): "est" / "gt" =
+        nn_surface_error of each plus mean_e, rms_e, mean_c, plane_rmse per threshold (sqrt(sum_e2_within / n_within), 0 without an
+        inlier) and, for the quantiles given, rank / quantile_e (nearest rank, exact: rank_select on the fetched e with use = e >= 0);
+        plane_chamfer = mean_e(est) + mean_e(gt)."""
+        probs = [float(x) for x in quantiles]
+        rep = {}
+        for name, slot in (("est", ME_SLOT_EST), ("gt", ME_SLOT_GT)):
+            d, e, _ = self.nn_surface_error(slot, plane_thresholds, angle_thresholds_deg, gate, gate_mode, fetch=True)
+            nu, nn = d["n_used"], d["n_normal_used"]
+            d["mean_e"] = d["sum_e"] / nu if nu > 0 else 0.0
+            d["rms_e"] = math.sqrt(d["sum_e2"] / nu) if nu > 0 else 0.0
+            d["mean_c"] = d["sum_c"] / nn if nn > 0 else 0.0
+            d["plane_rmse"] = np.array([math.sqrt(s / m) if m > 0 else 0.0 for s, m in zip(d["sum_e2_within"], d["n_within"])], np.float64)
+            d["prob"] = np.array(probs, np.float64)
+            ranks = [min(nu - 1, max(0, int(math.ceil(pr * float(nu))) - 1)) if nu > 0 else -1 for pr in probs]
+            d["rank"] = np.array(ranks, np.int64)
+            if probs and nu > 0:
+                d["quantile_e"] = self.rank_select(e, ranks, use=e >= 0)["value"]
+            else:
+                d["quantile_e"] = np.zeros(len(probs), np.float64)
+            rep[name] = d
+        rep["plane_chamfer"] = rep["est"]["mean_e"] + rep["gt"]["mean_e"]
+        return rep
+
     # ---- voxels ----
     def voxel_build(self, slot: int, voxel_size: float) -> int:
         """Builds (and caches on the cloud) the voxel-Gaussian table without exporting it; returns the voxel count."""

@@ -321,6 +321,38 @@ Param loadParametersFromYAML(const std::string &yaml_file_path) {
             throw std::runtime_error("error_cdf_max: must be > 0");
         if (param.num_gpus > 1) throw std::runtime_error("evaluate_error_distribution: single GPU only (num_gpus must be 1)");
     }
+    // the normal-aware map error (no reference counterpart)
+    if (config.has("evaluate_surface_error")) param.evaluate_surface_error = config.as_bool("evaluate_surface_error");
+    param.normal_radius = config.has("normal_radius") ? config.as_double("normal_radius") : param.nn_radius_;
+    if (config.has("normal_min_points")) param.normal_min_points = config.as_int("normal_min_points");
+    std::string surface_not_a_list;
+    for (const char *key : {"surface_thresholds", "surface_angles_deg"})
+        if (config.has(key) && (!config.at(key).scalar.empty() || !config.at(key).rows.empty()) && surface_not_a_list.empty()) surface_not_a_list = key;
+    if (config.has("surface_thresholds")) {
+        for (const auto &v : config.at("surface_thresholds").seq) param.surface_thresholds.push_back(yaml_lite::Document::to_double(v, "surface_thresholds"));
+    } else {
+        param.surface_thresholds.assign(param.trunc_dist_.begin(), param.trunc_dist_.end());
+    }
+    if (config.has("surface_angles_deg")) {
+        param.surface_angles_deg.clear();
+        for (const auto &v : config.at("surface_angles_deg").seq) param.surface_angles_deg.push_back(yaml_lite::Document::to_double(v, "surface_angles_deg"));
+    }
+    if (config.has("surface_gated")) param.surface_gated = config.as_bool("surface_gated");
+    if (param.evaluate_surface_error) {
+        if (!surface_not_a_list.empty()) throw std::runtime_error(surface_not_a_list + ": must be a list [a, b, ...]");
+        if (!(param.normal_radius > 0) || !std::isfinite(param.normal_radius)) throw std::runtime_error("normal_radius: must be > 0");
+        if (param.normal_min_points < 2) throw std::runtime_error("normal_min_points: must be >= 2 (the covariance divides by k - 1)");
+        if (param.surface_thresholds.size() > ME_ERRDIST_MAX_THRESHOLDS) throw std::runtime_error("surface_thresholds: at most 8 values");
+        for (const double t : param.surface_thresholds)
+            if (!(t >= 0.0) || !std::isfinite(t)) throw std::runtime_error("surface_thresholds: every value must be finite and >= 0");
+        if (param.surface_angles_deg.size() > ME_SURFACE_MAX_ANGLES) throw std::runtime_error("surface_angles_deg: at most 8 values");
+        for (const double a : param.surface_angles_deg)
+            if (!(a >= 0.0 && a <= 90.0)) throw std::runtime_error("surface_angles_deg: every value must lie in [0, 90]");
+        if (!param.evaluate_using_initial_)
+            throw std::runtime_error("evaluate_surface_error: needs evaluate_using_initial (the registration path estimates and uses normals of its own)");
+        if (param.evaluate_noised_gt_) throw std::runtime_error("evaluate_surface_error: not with evaluate_noised_gt");
+        if (param.num_gpus > 1) throw std::runtime_error("evaluate_surface_error: single GPU only (num_gpus must be 1)");
+    }
     return param;
 }
 
@@ -373,7 +405,12 @@ std::string paramToJson(const Param &p) {
     o << "], \"error_thresholds\": [";
     for (size_t i = 0; i < p.error_thresholds.size(); ++i) o << (i ? ", " : "") << p.error_thresholds[i];
     o << "], \"error_cdf_bins\": " << p.error_cdf_bins << ", \"error_cdf_max\": " << p.error_cdf_max << ", \"error_gated\": " << b(p.error_gated)
-      << "}";
+      << ", \"evaluate_surface_error\": " << b(p.evaluate_surface_error) << ", \"normal_radius\": " << p.normal_radius
+      << ", \"normal_min_points\": " << p.normal_min_points << ", \"surface_thresholds\": [";
+    for (size_t i = 0; i < p.surface_thresholds.size(); ++i) o << (i ? ", " : "") << p.surface_thresholds[i];
+    o << "], \"surface_angles_deg\": [";
+    for (size_t i = 0; i < p.surface_angles_deg.size(); ++i) o << (i ? ", " : "") << p.surface_angles_deg[i];
+    o << "], \"surface_gated\": " << b(p.surface_gated) << "}";
     return o.str();
 }
 
@@ -458,7 +495,9 @@ int MapEval::process() {
     const bool mom = param_.evaluate_mom;  // (likewise)
     if (mom && comm_) return fail("evaluate_mom: single GPU only (num_gpus must be 1)");
     if (param_.evaluate_error_distribution && comm_) return fail("evaluate_error_distribution: single GPU only (num_gpus must be 1)");
-    if (one_call && !noised && !filter && !mpv && !planes && !mom && !(param_.downsample_size > 0)) {
+    const bool surf = param_.evaluate_surface_error;  // (its normals are estimated on resident clouds, before the one call transforms the map)
+    if (surf && comm_) return fail("evaluate_surface_error: single GPU only (num_gpus must be 1)");
+    if (one_call && !noised && !filter && !mpv && !planes && !mom && !surf && !(param_.downsample_size > 0)) {
         file_result << std::fixed << std::setprecision(15) << "Estimated-Ground Truth point count: " << map_3d_->size() << " / "
                     << gt_3d_->size() << std::endl;
         if (param_.enable_debug)
@@ -504,6 +543,9 @@ int MapEval::process() {
     if (mpv && computeMPV() != 0) return -1;  // (the clouds as loaded, where computeMME runs: before the transform)
     if (planes && segmentPlanes() != 0) return -1;  // (likewise)
     if (mom && computeMOM() != 0) return -1;  // (likewise; after its two inputs)
+    // (last of the stages on the clouds as loaded: it may rebuild the indices at its own radius, and its normals then ride
+    // me_transform_cloud and the one call — me_run_suite_from uploads nothing on this resident path, so it keeps them)
+    if (surf && computeSurfaceNormals() != 0) return -1;
     if (comm_) return processDist(tic_toc.toc());  // num_gpus > 1 (map_eval_dist.cpp)
     if (one_call) {  // (the down-sampled or perturbed clouds are resident)
         const int rc = processOneCall(false, tic_toc.toc());
@@ -986,6 +1028,7 @@ void MapEval::finishInitialMatrixMetrics(const me_nn_stats_out &eg, const me_nn_
     full_chamfer_dist = param_.strict_reference ? 0.0 : (eg.mean_nn_dist + ge.mean_nn_dist);  // (:1429)
     t_fcd = tt.toc() / 1000.0;
     if (param_.evaluate_error_distribution && computeErrorDistribution(ME_GATE_LE_UNSQUARED) != 0) return;
+    if (param_.evaluate_surface_error && computeSurfaceError(ME_GATE_LE_UNSQUARED) != 0) return;
     if (param_.dist_rank > 0) return;
     std::cout << "INFO: Chamfer Distance: " << eigen_row(cd_vec, 6) << std::endl;
     std::cout << "INFO: F1 Score: " << eigen_row(f1_vec, 6) << std::endl;
@@ -1433,12 +1476,79 @@ void MapEval::saveErrorDistribution() {
     if (std::fclose(f) != 0) fail("writing " + path + " failed");
 }
 
+// me_radius_normals on both clouds as loaded (the ground truth's file normals, if any, are replaced: this path's metrics use none)
+int MapEval::computeSurfaceNormals() {
+    for (int s = ME_SLOT_EST; s <= ME_SLOT_GT; ++s)
+        if (me_radius_normals(ctx_, s, param_.normal_radius, param_.normal_min_points, nullptr, 0, &surface_normals[s]) != ME_OK)
+            return fail(std::string("evaluate_surface_error: ") + me_last_error(ctx_));
+    return 0;
+}
+
+// me_nn_surface_error on the 1-NN results of both directions, after the metric path's statistics (the gate is that path's when
+// surface_gated is set, none otherwise); the cosines of the angle thresholds are taken here, with the C library's cos
+int MapEval::computeSurfaceError(int gate_mode) {
+    me_surface_params &p = surface_params;
+    p = me_surface_params{};
+    p.gate = param_.surface_gated ? param_.icp_max_distance_ : -1.0;
+    p.gate_mode = gate_mode;
+    p.n_thresholds = (int32_t) param_.surface_thresholds.size();
+    for (int k = 0; k < p.n_thresholds; ++k) p.tau[k] = param_.surface_thresholds[(size_t) k];
+    p.n_angles = (int32_t) param_.surface_angles_deg.size();
+    for (int k = 0; k < p.n_angles; ++k) p.cos_min[k] = std::cos(param_.surface_angles_deg[(size_t) k] * (M_PI / 180.0));
+    for (int s = ME_SLOT_EST; s <= ME_SLOT_GT; ++s)
+        if (me_nn_surface_error(ctx_, s, &p, &surface_out[s]) != ME_OK) return fail(std::string("evaluate_surface_error: ") + me_last_error(ctx_));
+    return 0;
+}
+
+void MapEval::saveSurfaceError() {
+    const me_surface_params &p = surface_params;
+    const me_surface_out *o = surface_out;
+    auto mean = [](double s, int64_t n) { return n > 0 ? s / (double) n : 0.0; };
+    const double me[2] = {mean(o[0].sum_e, o[0].n_used), mean(o[1].sum_e, o[1].n_used)};
+    file_result << std::fixed << std::setprecision(5) << "PlaneError est-gt-chamfer: " << me[0] << " " << me[1] << " " << me[0] + me[1] << std::endl;
+    file_result << std::fixed << std::setprecision(5) << "PlaneAC @t:";
+    for (int k = 0; k < p.n_thresholds; ++k)
+        file_result << " " << p.tau[k] << " " << (o[0].n_within[k] > 0 ? std::sqrt(o[0].sum_e2_within[k] / (double) o[0].n_within[k]) : 0.0);
+    file_result << std::endl;
+    file_result << std::fixed << std::setprecision(5) << "NormalConsistency est-gt: " << mean(o[0].sum_c, o[0].n_normal_used) << " "
+                << mean(o[1].sum_c, o[1].n_normal_used) << std::endl;
+    // surface_error.txt: the parameters ("name value ..."), then per direction the normals row `cloud normals n n_valid sum_k` (of
+    // that cloud's own me_radius_normals), the scalar row
+    //   cloud n_query n_used n_normal_used sum_e sum_e2 sum_t2 sum_c max_e argmax
+    // the rows `cloud t tau n_within sum_e2_within` and `cloud a angle_deg cos_min n_angle` (doubles as %.17g)
+    const std::string path = results_subfolder + "surface_error.txt";
+    FILE *f = std::fopen(path.c_str(), "w");
+    if (!f) {
+        fail("cannot write " + path);
+        return;
+    }
+    std::fprintf(f, "normal_radius %.17g\nnormal_min_points %d\ngate %.17g\ngate_mode %d\nthresholds", param_.normal_radius,
+                 param_.normal_min_points, p.gate, (int) p.gate_mode);
+    for (int k = 0; k < p.n_thresholds; ++k) std::fprintf(f, " %.17g", p.tau[k]);
+    std::fprintf(f, "\nangles_deg");
+    for (int k = 0; k < p.n_angles; ++k) std::fprintf(f, " %.17g", param_.surface_angles_deg[(size_t) k]);
+    std::fprintf(f, "\n");
+    for (int s = ME_SLOT_EST; s <= ME_SLOT_GT; ++s) {
+        const char *tag = s == ME_SLOT_EST ? "est" : "gt";
+        const me_radius_normals_out &rn = surface_normals[s];
+        std::fprintf(f, "%s normals %lld %lld %lld\n", tag, (long long) rn.n, (long long) rn.n_valid, (long long) rn.sum_k);
+        std::fprintf(f, "%s %lld %lld %lld %.17g %.17g %.17g %.17g %.17g %lld\n", tag, (long long) o[s].n_query, (long long) o[s].n_used,
+                     (long long) o[s].n_normal_used, o[s].sum_e, o[s].sum_e2, o[s].sum_t2, o[s].sum_c, o[s].max_e, (long long) o[s].argmax);
+        for (int k = 0; k < p.n_thresholds; ++k)
+            std::fprintf(f, "%s t %.17g %lld %.17g\n", tag, p.tau[k], (long long) o[s].n_within[k], o[s].sum_e2_within[k]);
+        for (int k = 0; k < p.n_angles; ++k)
+            std::fprintf(f, "%s a %.17g %.17g %lld\n", tag, param_.surface_angles_deg[(size_t) k], p.cos_min[k], (long long) o[s].n_angle[k]);
+    }
+    if (std::fclose(f) != 0) fail("writing " + path + " failed");
+}
+
 void MapEval::saveRegistrationResults() {
     // identical lines and precisions to map_eval.cpp:439-476
     file_result << std::fixed << std::setprecision(15) << "RMSE/AC: " << eigen_row(est_gt_results.at(1), 15) << std::endl;
     file_result << std::fixed << std::setprecision(15) << "Comp: " << eigen_row(est_gt_results.at(2), 15) << std::endl;
     file_result << std::fixed << std::setprecision(5) << "FULL CD: " << full_chamfer_dist << std::endl;
     if (param_.evaluate_error_distribution) saveErrorDistribution();
+    if (param_.evaluate_surface_error) saveSurfaceError();
     file_result << std::fixed << std::setprecision(5) << "VMD: " << vmd << std::endl;
     file_result << std::fixed << std::setprecision(5) << "SCS: " << scs_overall << std::endl;
     if (param_.evaluate_using_initial_)

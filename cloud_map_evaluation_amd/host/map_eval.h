@@ -121,6 +121,15 @@ struct Param {
     bool evaluate_error_distribution = false;  // `evaluate_error_distribution:`
     std::vector<double> error_quantiles{0.5, 0.9, 0.95, 0.99};  // `error_quantiles: [..]` at most 16, each in [0, 1]
     std::vector<double> error_thresholds;      // `error_thresholds: [..]` at most 8, each >= 0 (default: accuracy_level)
+    // the normal-aware map error (optional keys; no reference counterpart): me_radius_normals on both clouds as loaded, where the MPV
+    // stage runs, then me_nn_surface_error on the 1-NN results the initial-matrix metric path leaves resident (single GPU, with
+    // evaluate_using_initial); three lines after the error-distribution lines, and surface_error.txt
+    bool evaluate_surface_error = false;       // `evaluate_surface_error:`
+    double normal_radius = 0.0;                // `normal_radius:` > 0 (default: nn_radius)
+    int normal_min_points = 5;                 // `normal_min_points:` neighbours a point needs for a normal, >= 2
+    std::vector<double> surface_thresholds;    // `surface_thresholds: [..]` at most 8, each >= 0 (default: accuracy_level)
+    std::vector<double> surface_angles_deg{5.0, 10.0, 20.0};  // `surface_angles_deg: [..]` at most 8, each in [0, 90]
+    bool surface_gated = false;                // `surface_gated:` the metric path's correspondence gate (default: every pair)
     int error_cdf_bins = 1000;                 // `error_cdf_bins:` 0 .. 4096 (0: no CDF)
     double error_cdf_max = 0;                  // `error_cdf_max:` the last bin edge (default: icp_max_distance); bin width = max / bins
     bool error_gated = false;                  // `error_gated:` true = the metric path's own gate and gate mode apply
@@ -166,6 +175,9 @@ public:
     int computeMOM();                                       // evaluate_mom: me_mom on both clouds (no reference counterpart)
     void saveMomResults();                                  // its result line and mom.txt
     int computeErrorDistribution(int gate_mode);            // evaluate_error_distribution: both directions (no reference counterpart)
+    int computeSurfaceNormals();                            // evaluate_surface_error: me_radius_normals on both clouds as loaded
+    int computeSurfaceError(int gate_mode);                 // ... me_nn_surface_error on both directions (no reference counterpart)
+    void saveSurfaceError();                                // its three result lines and surface_error.txt
     void saveErrorDistribution();                           // its three result lines and error_distribution.txt
     int globalRegistration(double T_c[16]);                 // global_registration.txt (global_registration; no reference counterpart)                                   // noise_sweep.txt (noise_sweep; no reference counterpart)
 
@@ -187,6 +199,9 @@ public:
     me_errdist_params errdist_params = {};  // evaluate_error_distribution: what both directions were asked for
     me_errdist_out errdist_out[2] = {};     // ... [ME_SLOT_EST], [ME_SLOT_GT]
     std::vector<int64_t> errdist_hist[2];
+    me_surface_params surface_params = {};      // evaluate_surface_error: what both directions were asked for
+    me_surface_out surface_out[2] = {};         // ... [ME_SLOT_EST], [ME_SLOT_GT]
+    me_radius_normals_out surface_normals[2] = {};
     me_mom_out mom_out[2] = {};  // evaluate_mom: [ME_SLOT_EST], [ME_SLOT_GT] (the latter with evaluate_gt_mom)
     me_local_geom_out mpv_out[2] = {};  // evaluate_mpv: [ME_SLOT_EST], [ME_SLOT_GT] (the latter with evaluate_gt_mpv)
     std::vector<double> est_entropies, gt_entropies;

@@ -448,6 +448,33 @@ typedef struct me_local_geom_out {
 int me_local_geometry(me_ctx *ctx, int slot, double radius, int min_k, me_local_geom_out *out);
 int me_local_geometry_fetch(me_ctx *ctx, int slot, double *eig, int32_t *k, uint8_t *valid);
 
+/* ---- radius-search normals: the eigenVECTOR of the same covariance ------------------------------------------------------------- */
+/* (DESIGN.md section 4.14).  me_estimate_normals is k-NN (Open3D's default): its neighbourhood in metres changes with the density,
+ * which is wrong for a metric.  me_radius_normals takes the neighbourhood of me_local_geometry — a fixed radius — in the same
+ * kernel pass.  Single GPU only: slab or shard mode is ME_ERR_ARG.  Device timer "radius_normals".
+ *
+ * me_radius_normals (radius finite and > 0, min_k >= 2, out non-NULL, else ME_ERR_ARG; viewpoint = 3 finite doubles or NULL).
+ *   1. Neighbour set, moments about the query, covariance, cyclic Jacobi, clamp and ordering: steps 1 - 3 of me_local_geometry,
+ *      the same arithmetic.  The call ALSO stores the slot's local-geometry result (eigenvalues, k, validity; a new serial),
+ *      bit-identical to what me_local_geometry(slot, radius, min_k) stores: me_local_geometry_fetch and me_mom work after either.
+ *   2. The normal of a valid point: the column of Jacobi's V that belongs to the smallest eigenvalue BEFORE the clamp; among equal
+ *      eigenvalues the column with the LOWEST index (d[0], d[1], d[2] in Jacobi's own order: b = 0; d[1] < d[b] -> 1; d[2] < d[b]
+ *      -> 2).  The column is scaled once to unit length, n / sqrt((nx*nx + ny*ny) + nz*nz): the accumulated rotations leave it
+ *      within some 1e-15 of unit length, the scaling within 3 ulp.
+ *   3. Sign.  viewpoint == NULL: as Jacobi yields it — a pure function of the cloud, identical from run to run and from a fresh
+ *      context.  Otherwise, with v = viewpoint - p_i component by component, n is negated iff ((nx*vx + ny*vy) + nz*vz) < 0.
+ *   4. An invalid point (k_i < min_k, or l1 == 0) gets (0, 0, 0); with invalid_z != 0 it gets (0, 0, 1), what me_estimate_normals
+ *      writes where a normal is undefined and what the ICP / GICP consumers expect.
+ * The normals go into the slot's normals (cloud order), as me_set_normals / me_estimate_normals put theirs: they follow
+ * me_transform_cloud (n <- R n), me_get_normals, me_icp_lsq_sums and me_gicp_covariances; covariances on the slot are dropped, as
+ * me_set_normals drops them.  out: n, n_valid, sum_k (over the valid points).
+ * ORDER OF USE: like me_local_geometry the call may rebuild the slot's index at the radius level, which discards the 1-NN result
+ * of the slot and of its twin, the other slot (it searched in this one) — estimate the normals first, then call me_nn1. */
+typedef struct me_radius_normals_out {
+    int64_t n, n_valid, sum_k;
+} me_radius_normals_out;
+int me_radius_normals(me_ctx *ctx, int slot, double radius, int min_k, const double *viewpoint, int invalid_z, me_radius_normals_out *out);
+
 /* ---- plane segmentation: RANSAC plane fit and multi-plane extraction on a resident cloud ---------------------------------------- */
 /* (DESIGN.md section 4.11).  The model is Open3D's PointCloud::SegmentPlane(distance_threshold, 3, num_iterations), applied
  * repeatedly to what is left; the deviations are listed in DESIGN.md section 5.  Single GPU only: slab or shard mode is ME_ERR_ARG.
@@ -664,6 +691,57 @@ int me_rank_select(me_ctx *ctx, const double *values, const uint8_t *use, int64_
 double me_sqrt_threshold(double t);
 int me_nn_error_distribution(me_ctx *ctx, int query_slot, const me_errdist_params *p, me_errdist_out *out, int64_t *hist);
 void me_fscore_finalize(int64_t n_within_est, int64_t n_est, int64_t n_within_gt, int64_t n_gt, double prf[3]);
+
+/* ---- Normal-aware map error over the resident 1-NN pairs: point-to-plane distance and normal consistency ------------------------- */
+/* (DESIGN.md section 4.14).  The distances of getDiffRegResultWithCorrespondence (map_eval.cpp:1069-1145) and of
+ * computeChamferDistance (map_eval.cpp:1398-1431) are nearest-POINT distances: on a surface sampled at spacing s a map point lying
+ * on the surface still sits about s / 3 from its nearest sample.  These calls refine that quantity with the reference cloud's
+ * normals (me_set_normals, me_estimate_normals or me_radius_normals): the distance to the neighbour's local plane, the tangential
+ * remainder, and the agreement of the two normals.  Single GPU only (slab or shard mode: ME_ERR_ARG).
+ *
+ * me_nn_surface_error: the current 1-NN result of query_slot (ME_ERR_STATE without one); the reference slot must have normals
+ * (ME_ERR_STATE), the query's are optional.  gate / gate_mode as me_nn_stats (gate < 0: every query); 0 <= n_thresholds <=
+ * ME_ERRDIST_MAX_THRESHOLDS, every tau finite and >= 0; 0 <= n_angles <= ME_SURFACE_MAX_ANGLES, every cos_min in [0, 1]; else
+ * ME_ERR_ARG.  Normals are used AS STORED, not re-normalised, and must be finite.
+ *   The pair (i, j = nn_idx[i]) is USED iff d2_i >= 0, it passes the gate, j names a reference point (a result placed by
+ *   me_set_nn_result has no neighbour indices: none of its pairs is used) and the reference normal n = normals_ref[j] is not the
+ *   zero vector.  It is NORMAL-USED iff moreover the query has normals and m = normals_query[i] is not the zero vector.
+ *   Per used pair, with d = p_i - g_j component by component (fp64, no FMA):
+ *     e  = fabs((nx*dx + ny*dy) + nz*dz)          the point-to-plane distance
+ *     t2 = fmax(d2 - e*e, 0)                      the squared tangential remainder
+ *     c  = fabs((mx*nx + my*ny) + mz*nz)          (normal-used pairs) the normal consistency
+ *   n_query           entries with d2 >= 0;  n_used, n_normal_used: the used / normal-used pairs
+ *   sum_e, sum_e2, sum_t2   over the used pairs;  sum_c over the normal-used ones.  Per-block partials (a fixed grid of at most 1024
+ *                     blocks; a thread adds its entries in order, a block by a fixed tree) combined in block order: no floating-point
+ *                     atomics, bit-identical from run to run
+ *   max_e, argmax     the largest e and the ORIGINAL index of its query, ties -> smallest index; 0 and -1 when n_used == 0
+ *   n_within[k], sum_e2_within[k]   the used pairs with e <= tau[k] and the sum of their e*e
+ *   n_angle[k]        the normal-used pairs with c >= cos_min[k].  The caller passes the COSINE: no count depends on a device cos
+ * n_used == 0: every sum and count but n_query is 0.  The call leaves the 1-NN result untouched.  Device timer "surface".
+ *
+ * me_nn_surface_fetch: e (plane_d) and c (cos_n) of the slot's last me_nn_surface_error in cloud order (N entries each, nullable),
+ * -1.0 where the pair was not used (cos_n: not normal-used).  ME_ERR_STATE without a current result: it is discarded with the 1-NN
+ * result.  Exact quantiles of e: me_rank_select on plane_d with use = (plane_d >= 0). */
+#define ME_SURFACE_MAX_ANGLES 8
+typedef struct me_surface_params {
+    double gate;
+    int32_t gate_mode; /* as me_nn_stats; gate < 0: every query */
+    int32_t n_thresholds;
+    double tau[ME_ERRDIST_MAX_THRESHOLDS]; /* each finite and >= 0 */
+    int32_t n_angles;
+    int32_t reserved;
+    double cos_min[ME_SURFACE_MAX_ANGLES]; /* each in [0, 1] */
+} me_surface_params;
+typedef struct me_surface_out {
+    int64_t n_query, n_used, n_normal_used;
+    double sum_e, sum_e2, sum_t2, sum_c, max_e;
+    int64_t argmax;
+    int64_t n_within[ME_ERRDIST_MAX_THRESHOLDS];
+    double sum_e2_within[ME_ERRDIST_MAX_THRESHOLDS];
+    int64_t n_angle[ME_SURFACE_MAX_ANGLES];
+} me_surface_out;
+int me_nn_surface_error(me_ctx *ctx, int query_slot, const me_surface_params *p, me_surface_out *out);
+int me_nn_surface_fetch(me_ctx *ctx, int query_slot, double *plane_d, double *cos_n);
 
 int64_t me_cloud_size(me_ctx *ctx, int slot);
 /* transformed points back to the host (N x 3), original order — what map_3d_->points_ holds after :1206 */
