@@ -109,6 +109,17 @@ void mail_drop(me_ctx *ctx) {
     ctx->mail_used = 0;
 }
 
+int tail_stream_ensure(me_ctx *ctx) {
+    if (ctx->tail_stream) return ME_OK;
+    ME_CHECK(ctx, hipSetDevice(ctx->device));
+    for (void *&ev : ctx->tail_event)
+        if (!ev) ME_CHECK(ctx, hipEventCreateWithFlags(reinterpret_cast<hipEvent_t *>(&ev), hipEventDisableTiming));
+    int least = 0, greatest = 0;
+    (void) hipDeviceGetStreamPriorityRange(&least, &greatest);
+    ME_CHECK(ctx, hipStreamCreateWithPriority(&ctx->tail_stream, hipStreamNonBlocking, greatest));  // (the primary stream's priority)
+    return ME_OK;
+}
+
 int need_single_gpu_cloud(me_ctx *ctx, int slot, const char *who) {
     if (slot < 0 || slot > 1) return ctx->fail(ME_ERR_ARG, std::string(who) + ": bad slot");
     Cloud &c = ctx->cloud[slot];
@@ -212,6 +223,12 @@ void me_destroy(me_ctx *ctx) {
     for (auto e : ctx->event_pool) (void) hipEventDestroy(e);
     if (ctx->suite_event) (void) hipEventDestroy(static_cast<hipEvent_t>(ctx->suite_event));
     if (ctx->stream) (void) hipStreamDestroy(ctx->stream);
+    if (ctx->tail_stream) {
+        (void) hipStreamSynchronize(ctx->tail_stream);
+        (void) hipStreamDestroy(ctx->tail_stream);
+    }
+    for (void *ev : ctx->tail_event)
+        if (ev) (void) hipEventDestroy(static_cast<hipEvent_t>(ev));
     if (ctx->mail_h) (void) hipHostFree(ctx->mail_h);
     delete ctx;
 }

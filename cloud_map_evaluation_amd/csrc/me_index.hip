@@ -915,6 +915,43 @@ static int build_octree(me_ctx *ctx, Cloud &c, int nn_shift, bool small_top) {
     return ME_OK;
 }
 
+// The part of cloud_build_index after the radix sort on the context's priority stream (me_ctx::index_tail: me_run_suite_from's second
+// lane).  The lane's own stream has the lowest priority: its gather (vector-heavy, it also emits the voxel records) took 14 ms instead of
+// 1.8 under the main lane's k_mme3 and the cell tables were complete only when that kernel had drained — the main lane's second k_mme3
+// waited 1.5 ms for them (profiles/r06_timeline.txt).  The sort stays where it is (onesweep must not share the chip with the MME at
+// all: ME_TUNE_SUITE_SORT_FIRST).  Between begin() and end() ctx->stream IS the priority stream, so that every helper on the way (scans,
+// mailbox reads, timers) follows; every kernel there is a grid of 256-thread blocks or one block of <= 256 threads.
+struct IndexTail {
+    me_ctx *c;
+    hipStream_t home = nullptr;
+    bool on = false;
+    explicit IndexTail(me_ctx *ctx) : c(ctx) {}
+    int begin() {  // the tail starts when the sort (everything queued on the lane's stream so far) is complete
+        if (!c->index_tail || !c->tail_stream) return ME_OK;
+        ME_CHECK(c, hipEventRecord(static_cast<hipEvent_t>(c->tail_event[0]), c->stream));
+        ME_CHECK(c, hipStreamWaitEvent(c->tail_stream, static_cast<hipEvent_t>(c->tail_event[0]), 0));
+        home = c->stream;
+        c->stream = c->tail_stream;
+        on = true;
+        return ME_OK;
+    }
+    int end() {  // back on the lane's stream, which is ordered behind everything the tail has queued
+        if (!on) return ME_OK;
+        on = false;
+        hipStream_t tail = c->stream;
+        c->stream = home;
+        ME_CHECK(c, hipEventRecord(static_cast<hipEvent_t>(c->tail_event[1]), tail));
+        ME_CHECK(c, hipStreamWaitEvent(home, static_cast<hipEvent_t>(c->tail_event[1]), 0));
+        return ME_OK;
+    }
+    ~IndexTail() {  // (an early return: nothing of the tail may still be in flight when the caller reuses the buffers)
+        if (on) {
+            (void) hipStreamSynchronize(c->stream);
+            (void) end();
+        }
+    }
+};
+
 int cloud_build_index(me_ctx *ctx, int slot, double cell_size) {
     Cloud &c = ctx->cloud[slot];
     ME_TRACE_POINT(ctx, slot == 0 ? "cloud_build_index(est): enter" : "cloud_build_index(gt): enter");
@@ -1009,6 +1046,8 @@ int cloud_build_index(me_ctx *ctx, int slot, double cell_size) {
         ME_TRY(sort_pairs_u64_u32(ctx, codes_in.as<unsigned long long>(), c.codes.as<unsigned long long>(),
                                   iota.as<unsigned int>(), perm.as<unsigned int>(), n, 3 * sort_min_level, 63));
     if (ctx->sort_hook) ctx->sort_hook(ctx->sort_hook_arg, ctx->stream);  // (me_run_suite_from: see SuiteLane::sort_queued)
+    IndexTail tail(ctx);
+    ME_TRY(tail.begin());
     // voxel run records on the side, when the context carries a voxel size for them (me_run_suite_from) and their sort key fits
     VoxPack vp{};
     c.vox_rec_valid = false;
@@ -1082,6 +1121,7 @@ int cloud_build_index(me_ctx *ctx, int slot, double cell_size) {
             c.hint_shift = c.shift;
             c.hint_cell_h = cell_h;
             ts.end();
+            ME_TRY(tail.end());  // (the rebuild's k_morton, on the lane's stream, overwrites what the gather is reading)
             return cloud_build_index(ctx, slot, c.cell_size_req);
         }
         ME_TRY(build_grid_table_counted(ctx, c, c.shift, c.grid_tab, c.grid, nblk, d_bhist, d_boff, true));
@@ -1121,7 +1161,9 @@ int cloud_build_index(me_ctx *ctx, int slot, double cell_size) {
     // k_cell_fill (then k_hash_insert) was still filling the table they probe.  Python's hand-over latency hid it; the C++ lanes of me_run_suite_from
     // (microseconds) did not: the second evaluation of a process (fresh buffers holding stale bytes instead of the previous,
     // identical table) spun in hash_lookup for minutes at 50 M points (profiles/EXPERIMENTS.md "Round 5").
+    // (With the tail on the priority stream that is the stream synchronised here; the lane's own stream is then ordered behind it.)
     ME_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    ME_TRY(tail.end());
     c.index_valid = true;
     ME_TRACE_POINT(ctx, "cloud_build_index: done (host side)");
     return ME_OK;

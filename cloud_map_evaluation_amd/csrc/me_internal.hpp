@@ -280,6 +280,13 @@ struct me_ctx {
     void *suite_event = nullptr;  // hipEvent_t of me_run_suite_from's "sort queued" hand-over, created on first use
     void *suite_worker = nullptr;
     void (*suite_worker_free)(void *) = nullptr;
+    // me_run_suite_from's second lane (a twin, whose own stream has the lowest priority): while `index_tail` is set, cloud_build_index
+    // queues everything AFTER its radix sort — gather, level histogram, block counts, scans, cell tables — on `tail_stream`, which has
+    // the main lane's priority, ordered by tail_event[0] (sort done -> tail) and tail_event[1] (tail done -> `stream`).  Created by
+    // me::tail_stream_ensure, destroyed with the context.
+    hipStream_t tail_stream = nullptr;
+    void *tail_event[2] = {nullptr, nullptr};  // hipEvent_t
+    bool index_tail = false;
     // Small device -> host results (sums, counts, the level histogram) go through a pinned, device-mapped MAILBOX written by a
     // one-wavefront kernel (me::mail_post / me::mail_sync, me_api.hip; round 4).  hipMemcpyAsync to pageable host memory is a blit
     // kernel of ONE 1024-thread workgroup: it needs 16 free wave slots on one CU at once, and while the other lane's k_nn_grid /
@@ -445,6 +452,13 @@ struct TimerScope {  // (scopes do not nest: a scope that calls into another tim
 #ifndef ME_TUNE_SUITE_NN_FIRST
 #define ME_TUNE_SUITE_NN_FIRST 1  // me_run_suite_from, second lane: the reverse 1-NN search before the voxel tables (0: round 5's order)
 #endif
+#ifndef ME_TUNE_SUITE_GT_TAIL_PRIO
+// me_run_suite_from, device input with MME: the ground truth's index AFTER its sort on a priority stream of the second lane, and the map's
+// octree built by the second lane instead of between the two MMEs (0: round 6's schedule; 2: the second lane's reverse search starts
+// as soon as the lane gets there, under the map's MME; 1: it is held until the map's MME has ended, where it started in round 6.
+// Bench step 44.07 / 43.98 / 43.76 / 43.18 ms for the parent / 0 / 1 / 2: profiles/EXPERIMENTS.md "Round 7")
+#define ME_TUNE_SUITE_GT_TAIL_PRIO 2
+#endif
 inline unsigned int xcd_chunk_setting() { return (unsigned int) ME_TUNE_XCD_CHUNK; }
 // blocks of `block` threads for n items, at least one: a kernel launched for n == 0 bounds-checks its index, a zero-sized grid is a launch error
 inline unsigned int blocks_of(long long n, int block = 256) { return (unsigned int) std::max<long long>(1, (n + block - 1) / block); }
@@ -457,6 +471,8 @@ constexpr size_t kMailBytes = 128 * 1024;
 int mail_post(me_ctx *ctx, void *host_dst, const void *dev_src, size_t bytes);  // asynchronous on ctx->stream
 int mail_sync(me_ctx *ctx);                                                     // hipStreamSynchronize + delivery of what was posted
 void mail_drop(me_ctx *ctx);                                                    // forget what was posted (nothing is delivered)
+// ---- me_api.hip: the context's priority stream for the tail of an index build (me_ctx::tail_stream) and its two events, on first use ----
+int tail_stream_ensure(me_ctx *ctx);
 // ---- me_api.hip: the check of the single-GPU features: slot in range, no slab or shard mode, uploaded ----
 int need_single_gpu_cloud(me_ctx *ctx, int slot, const char *who);
 // The host destinations of mail_post are usually LOCALS of the posting function: if it returns before its mail_sync (a failed

@@ -13,15 +13,16 @@
 //   upload + index the map, WITHOUT its octree          [host input: wait until the map has crossed the link]
 //   (the gathers also emit the voxel run records        upload + index the ground truth, without its octree (its radix sort
 //    for vmd_voxel_size: me_vox_rows.hpp)                BEFORE the map's MME starts: onesweep crawls beside a full chip; the
-//   wait: ground truth's sort queued (event)             rest under that MME)
-//   MME of the map            (VALU-bound)              -> "ground truth indexed"; its octree (cloud_finish_octree)
-//   [T: transform + re-index the map, :1206]            voxel Gaussians of the ground truth, then of the map, from the gathers'
-//   the map's octree (cloud_finish_octree)               records (~40 launch-sized kernels each: they hide under the MMEs)
-//   [host input: voxel Gaussians of the map]            wait: map's octree
-//   wait: ground truth indexed                          1-NN ground truth -> map + partial sums + ITS sigma pass
-//   MME of the ground truth                             [no records (three-pass build): the voxel tables here, after the search;
-//   wait: ground truth's octree                          the map's by whichever lane gets to it first]
-//   1-NN map -> ground truth + partial sums + ITS sigma pass
+//   wait: ground truth's sort queued (event)             rest under that MME — device input: on the lane's PRIORITY stream, so
+//   MME of the map            (VALU-bound)               that the cell tables exist long before that MME ends, round 7)
+//   [T: transform + re-index the map, :1206]            -> "ground truth indexed"; its octree (cloud_finish_octree)
+//   [host input: the map's octree, then its             voxel Gaussians of the ground truth, then of the map, from the gathers'
+//    voxel Gaussians]                                    records (~40 launch-sized kernels each: they hide under the MMEs)
+//   wait: ground truth indexed                          device input: the map's octree (round 6 built it on the main lane between
+//   MME of the ground truth                              the two MMEs: nothing launch-sized stands there any more); else wait for it
+//   wait: both octrees                                  1-NN ground truth -> map + partial sums + ITS sigma pass
+//   1-NN map -> ground truth + partial sums + ITS       [no records (three-pass build): the voxel tables here, after the search;
+//   sigma pass                                           the map's by whichever lane gets to it first]
 //   AWD / CDF / SCS if both tables are ready (beside the second lane's tail); join; [AWD / CDF / SCS otherwise]
 //
 // Measured on the 50 M + 50 M bench pair (profiles/EXPERIMENTS.md "Round 6"): the step is the SUM of its kernels' work on the vector
@@ -81,6 +82,12 @@ struct SuiteLane {
     // event before the map's MME: ~0.3 ms later for the MME, ~12 ms earlier for everything on this lane.
     hipEvent_t sort_event = nullptr;
     bool sort_queued = false;    // lane -> main: sort_event has been recorded (or there is no sort to wait for)
+    // ME_TUNE_SUITE_GT_TAIL_PRIO: the ground truth's index after its sort runs on the twin's priority stream (me_index.hip: IndexTail) and
+    // is complete a few milliseconds into the map's MME instead of at its end, so that the two k_mme3 launches follow each other on the
+    // main stream.  Nothing launch-sized may then stand between them: THIS lane builds the map's octree (and sets est_tree), after the
+    // ground truth's, under the map's MME.
+    bool tail_prio = false;
+    bool est_mme_done = false;   // main -> lane: the map's MME has ended (where the reverse search started in round 6)
     static void sort_hook(void *self, hipStream_t stream) {
         SuiteLane *l = static_cast<SuiteLane *>(self);
         if (l->sort_event && !l->sort_queued) {
@@ -120,6 +127,7 @@ struct SuiteLane {
             std::lock_guard<std::mutex> g(m);
             gt_ready = true;
             gt_tree = true;
+            if (tail_prio) est_tree = true;
             sort_queued = true;
             finished = true;
         }
@@ -139,8 +147,10 @@ struct SuiteLane {
             if (wait_for_link && !wait(&SuiteLane::est_on_device)) return ME_OK;
             t->sort_hook = sort_event ? &SuiteLane::sort_hook : nullptr;
             t->sort_hook_arg = this;
+            t->index_tail = tail_prio;
             const int urc = me::cloud_upload(t, ME_SLOT_GT, gt, gt_on_device, n_gt, nullptr, p->nn_radius);
             t->sort_hook = nullptr;
+            t->index_tail = false;
             if (urc != ME_OK) return urc;
         }
         set(&SuiteLane::sort_queued);  // (nothing to wait for any more, whatever happened above)
@@ -166,6 +176,11 @@ struct SuiteLane {
         }
 #endif
         if (!wait(&SuiteLane::est_final)) return ME_OK;
+        if (tail_prio) {
+            // (the twin and the primary context share the Cloud objects; the main lane is in its MME kernels, which read the cell tables only)
+            ME_TRY(me::cloud_finish_octree(t, ME_SLOT_EST));
+            set(&SuiteLane::est_tree);
+        }
 #if ME_TUNE_SUITE_VOX_EARLY
         if (gt_table && !est_voxel_on_main && t->cloud[ME_SLOT_EST].vox_rec_valid && !est_voxel_taken.exchange(1)) {
             ME_TRY(me::voxel_build(t, ME_SLOT_EST, p->vmd_voxel_size, false));
@@ -173,6 +188,12 @@ struct SuiteLane {
         }
 #endif
         if (!wait(&SuiteLane::est_tree)) return ME_OK;
+#if ME_TUNE_SUITE_GT_TAIL_PRIO == 1
+        // (measurement variant: the search held where it started in round 6, when the map's MME has ended.  The lane gets here ~10 ms
+        // earlier now; its k_nn_grid is vector-bound like the k_mme3 beside it and stretches that kernel by what it takes — the sum is
+        // conserved — but held back the lane idles under the map's MME, and the step is 0.6 ms longer: profiles/EXPERIMENTS.md "Round 7")
+        if (tail_prio && !wait(&SuiteLane::est_mme_done)) return ME_OK;
+#endif
         ME_TRY(me::nn_search(t, ME_SLOT_GT, ME_SLOT_EST));
         ME_TRY(me::nn_partial(t, ME_SLOT_GT, p->icp_max_distance, p->gate_mode, p->trunc, &back));
         ME_TRY(back_sigma());
@@ -184,6 +205,10 @@ struct SuiteLane {
         ME_TRY(me::voxel_build(t, ME_SLOT_GT, p->vmd_voxel_size, false));
         if (!wait(&SuiteLane::est_final)) return ME_OK;
         if (!est_voxel_on_main) ME_TRY(me::voxel_build(t, ME_SLOT_EST, p->vmd_voxel_size, false));  // (never both lanes: same buffers)
+        if (tail_prio) {
+            ME_TRY(me::cloud_finish_octree(t, ME_SLOT_EST));
+            set(&SuiteLane::est_tree);
+        }
         if (!wait(&SuiteLane::est_tree)) return ME_OK;
         ME_TRY(me::nn_search(t, ME_SLOT_GT, ME_SLOT_EST));
         ME_TRY(me::nn_partial(t, ME_SLOT_GT, p->icp_max_distance, p->gate_mode, p->trunc, &back));
@@ -431,6 +456,15 @@ int me_run_suite_from(me_ctx *ctx, const double *est, int64_t n_est, const doubl
             lane.sort_event = static_cast<hipEvent_t>(ctx->suite_event);
         }
 #endif
+#if ME_TUNE_SUITE_GT_TAIL_PRIO
+        if (upload && on_device && p->evaluate_mme) {  // (host input: the ground truth's index follows a 20 ms copy — nothing waits for it)
+            if (me::tail_stream_ensure(lane.t) != ME_OK) {
+                ctx->err = lane.t->err;
+                return ME_ERR_HIP;
+            }
+            lane.tail_prio = true;
+        }
+#endif
         worker->post(&lane);
     }
     bool est_pinned = false, gt_pinned_here = false;
@@ -466,6 +500,7 @@ int me_run_suite_from(me_ctx *ctx, const double *est, int64_t n_est, const doubl
             out->mme_est = nv > 0 ? s / (double) nv : 0.0;
             out->mme_est_valid = nv;
         }
+        if (overlap) lane.set(&SuiteLane::est_mme_done);
         if (moved) {  // *map_3d_ = map_3d_->Transform(initial_matrix) (:1206), after the MME of the map as loaded (:56)
             t0 = Clock::now();
             if (p->evaluate_mme) ME_TRY(me::mme_carry_out(ctx, ME_SLOT_EST));
@@ -476,8 +511,12 @@ int me_run_suite_from(me_ctx *ctx, const double *est, int64_t n_est, const doubl
         }
         // the map's octree, left out of its index build: the MME above started that much earlier, and this lane would now wait for the
         // ground truth's cell tables anyway
-        ME_TRY(me::cloud_finish_octree(ctx, ME_SLOT_EST));
-        if (overlap) lane.set(&SuiteLane::est_tree);
+        // (ME_TUNE_SUITE_GT_TAIL_PRIO: the ground truth is indexed by now and its MME follows the map's at once — the second lane builds
+        // this octree, and the search below waits for it)
+        if (!(overlap && lane.tail_prio)) {
+            ME_TRY(me::cloud_finish_octree(ctx, ME_SLOT_EST));
+            if (overlap) lane.set(&SuiteLane::est_tree);
+        }
         if (overlap && upload && !on_device) {
             // host input: the ground truth is still crossing PCIe (the map's index + MME are shorter than its copy) and this lane would
             // idle until it is indexed — the map's voxel table is built here instead of on the second lane after the ground truth's
@@ -505,6 +544,10 @@ int me_run_suite_from(me_ctx *ctx, const double *est, int64_t n_est, const doubl
         if (overlap) {
             lane.wait(&SuiteLane::gt_tree);
             if (lane.rc.load() != ME_OK) return lane.rc.load();
+            if (lane.tail_prio) {  // (set ~30 ms ago on the bench pair; a map much smaller than the ground truth truly waits here)
+                lane.wait(&SuiteLane::est_tree);
+                if (lane.rc.load() != ME_OK) return lane.rc.load();
+            }
         } else {
             ME_TRY(me::cloud_finish_octree(ctx, ME_SLOT_GT));
         }
