@@ -35,6 +35,7 @@ SYMBOLS = [
     "me_statistical_outlier", "me_radius_outlier", "me_outlier_select_into",
     "me_cluster_dbscan", "me_cluster_sizes", "me_cluster_keep",
     "me_local_geometry", "me_local_geometry_fetch", "me_radius_normals", "me_nn_surface_error", "me_nn_surface_fetch",
+    "me_m3c2", "me_m3c2_fetch",
     "me_segment_planes", "me_plane_fetch", "me_plane_keep",
     "me_group_order_stats", "me_mom_select_axes", "me_mom", "me_mom_fetch",
     "me_rank_select", "me_sqrt_threshold", "me_nn_error_distribution", "me_fscore_finalize",
@@ -331,6 +332,33 @@ class RadiusNormalsOut(C.Structure):
     _fields_ = [("n", C.c_int64), ("n_valid", C.c_int64), ("sum_k", C.c_int64)]
 
 
+class M3c2Params(C.Structure):
+    _fields_ = [
+        ("projection_radius", C.c_double),
+        ("max_depth", C.c_double),
+        ("reg_error", C.c_double),
+        ("min_points", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+
+class M3c2Out(C.Structure):
+    _fields_ = [
+        ("n_core", C.c_int64),
+        ("n_no_normal", C.c_int64),
+        ("n_valid", C.c_int64),
+        ("n_significant", C.c_int64),
+        ("sum_dist", C.c_double),
+        ("sum_abs_dist", C.c_double),
+        ("sum_dist2", C.c_double),
+        ("sum_lod", C.c_double),
+        ("sum_n_own", C.c_int64),
+        ("sum_n_other", C.c_int64),
+        ("max_abs_dist", C.c_double),
+        ("argmax", C.c_int64),
+    ]
+
+
 class SurfaceParams(C.Structure):
     _fields_ = [
         ("gate", C.c_double),
@@ -447,6 +475,10 @@ def load():
     L.me_nn_surface_error.argtypes = [vp, C.c_int, C.POINTER(SurfaceParams), C.POINTER(SurfaceOut)]
     L.me_nn_surface_fetch.argtypes = [vp, C.c_int, dp, dp]
     for f in ("me_radius_normals", "me_nn_surface_error", "me_nn_surface_fetch"):
+        getattr(L, f).restype = C.c_int
+    L.me_m3c2.argtypes = [vp, C.c_int, C.POINTER(M3c2Params), vp, C.POINTER(M3c2Out)]
+    L.me_m3c2_fetch.argtypes = [vp, C.c_int, dp, dp, dp, dp, ip, ip, vp]
+    for f in ("me_m3c2", "me_m3c2_fetch"):
         getattr(L, f).restype = C.c_int
     L.me_segment_planes.argtypes = [vp, C.c_int, C.POINTER(PlaneParams), vp, ip, vp, C.POINTER(PlaneInfo)]
     L.me_plane_fetch.argtypes = [vp, C.c_int, vp, C.c_int64, C.POINTER(C.c_int64), ip]

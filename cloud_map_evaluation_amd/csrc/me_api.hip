@@ -379,6 +379,17 @@ int me_nn_surface_fetch(me_ctx *ctx, int query_slot, double *plane_d, double *co
     return me::nn_surface_fetch(ctx, query_slot, plane_d, cos_n);
 }
 
+int me_m3c2(me_ctx *ctx, int query_slot, const me_m3c2_params *p, const uint8_t *core_mask, me_m3c2_out *out) {
+    if (!ctx) return ME_ERR_ARG;
+    return me::m3c2(ctx, query_slot, p, core_mask, out);
+}
+
+int me_m3c2_fetch(me_ctx *ctx, int query_slot, double *dist, double *lod, double *var_own, double *var_other, int32_t *n_own, int32_t *n_other,
+                  uint8_t *flags) {
+    if (!ctx) return ME_ERR_ARG;
+    return me::m3c2_fetch(ctx, query_slot, dist, lod, var_own, var_other, n_own, n_other, flags);
+}
+
 int me_local_geometry_fetch(me_ctx *ctx, int slot, double *eig, int32_t *k, uint8_t *valid) {
     if (!ctx) return ME_ERR_ARG;
     return me::local_geometry_fetch(ctx, slot, eig, k, valid);

@@ -652,7 +652,9 @@ int cloud_upload(me_ctx *ctx, int slot, const double *src, bool src_on_device, l
         e.cluster_valid = false;
         e.plane_valid = false;
         e.lg_have = false;
+        e.m3c2_have = false;
         ctx->cloud[1 - slot].nn_ref_slot = -1;
+        ctx->cloud[1 - slot].m3c2_have = false;
         return ME_OK;
     }
     if (!src) return ctx->fail(ME_ERR_ARG, "xyz is NULL");
@@ -760,6 +762,7 @@ int cloud_finish(me_ctx *ctx, int slot, bool bbox_ready) {
     c.cluster_valid = false;
     c.plane_valid = false;
     ctx->cloud[1 - slot].nn_ref_slot = -1;
+    ctx->cloud[1 - slot].m3c2_have = false;  // (an M3C2 result compared the other slot's points with these; this slot's own goes with its index)
     // bbox
     const unsigned int nb = (unsigned int) std::min<long long>(1024, (n + 255) / 256);
     ME_CHECK(ctx, ctx->red.ensure((size_t) nb * 6 * sizeof(double)));
@@ -811,6 +814,8 @@ void cloud_reset_replaced(me_ctx *ctx, int slot, long long n, double cell_size_r
     D.cluster_valid = false;
     D.plane_valid = false;
     D.lg_have = false;
+    D.m3c2_have = false;
+    ctx->cloud[1 - slot].m3c2_have = false;
     D.slab = ctx->slab;
     D.n_unres = 0;
     D.slab_identity = true;
@@ -981,6 +986,7 @@ int cloud_build_index(me_ctx *ctx, int slot, double cell_size) {
     c.index_valid = false;
     c.mme_have = false;  // (the sorted order changes)
     c.lg_have = false;
+    c.m3c2_have = false;
 #ifdef ME_AB
     c.mme_feat_valid = false;
 #endif

@@ -250,6 +250,11 @@ struct Cloud {
     // (me_surface.hip); current only while the 1-NN result is (nn_ref_slot >= 0): a new one (nn_search, set_nn_result) clears the flag
     DevBuf surf_e, surf_c;
     bool surf_have = false;
+    // last me_m3c2 with this cloud as the query, SORTED order (me_m3c2.hip): the counts int32[2][n] (own, other), the moments
+    // double[4][n] (S_own, Q_own, S_other, Q_other; scratch of the call), the results double[4][n] (dist, lod, var_own, var_other) and
+    // the flag byte (bit 0 valid, bit 1 significant); dropped with the sorted order (cloud_build_index) and with the points of EITHER slot
+    DevBuf m3_cnt, m3_mom, m3_res, m3_flags;
+    bool m3c2_have = false;
     unsigned long long mom_lg_serial = 0, mom_plane_serial = 0;
 };
 
@@ -534,6 +539,10 @@ int radius_normals(me_ctx *ctx, int slot, double radius, int min_k, const double
 // ---- me_surface.hip ----
 int nn_surface_error(me_ctx *ctx, int qslot, const me_surface_params *p, me_surface_out *out);
 int nn_surface_fetch(me_ctx *ctx, int qslot, double *plane_d_host, double *cos_n_host);
+// ---- me_m3c2.hip ----
+int m3c2(me_ctx *ctx, int qslot, const me_m3c2_params *p, const uint8_t *core_mask_host, me_m3c2_out *out);
+int m3c2_fetch(me_ctx *ctx, int qslot, double *dist_host, double *lod_host, double *var_own_host, double *var_other_host, int32_t *n_own_host,
+               int32_t *n_other_host, uint8_t *flags_host);
 // ---- me_plane.hip ----
 int segment_planes(me_ctx *ctx, int slot, const me_plane_params *p, me_plane_record *planes_host, int32_t *labels_host, int64_t *scores_host,
                    me_plane_info *info);

@@ -207,7 +207,9 @@ int perturb_cloud(me_ctx *ctx, int dst_slot, int src_slot, const me_perturb_para
     D.vox_rec_valid = false;
     D.mme_have = false;
     D.lg_have = false;
+    D.m3c2_have = false;
     ctx->cloud[1 - dst_slot].nn_ref_slot = -1;
+    ctx->cloud[1 - dst_slot].m3c2_have = false;
     D.n = total;
     D.n_total = total;
     D.have_normals = D.have_cov = false;

@@ -848,6 +848,92 @@ class Engine:
         rep["plane_chamfer"] = rep["est"]["mean_e"] + rep["gt"]["mean_e"]
         return rep
 
+    # ---- M3C2: the signed distance between the two clouds along the query's normals (me_m3c2.hip) ----
+    def m3c2(self, query_slot: int, projection_radius: float, max_depth: float, min_points: int = 5, reg_error: float = 0.0,
+             core_mask=None, fetch: bool = False):
+        """me_m3c2 with the points of query_slot (thinned by core_mask, (N,) of zero / non-zero, cloud order) as the core points, the
+        slot's resident normals and the other slot as the compared cloud: per core point both clouds are averaged inside the cylinder
+        of radius projection_radius and half-length max_depth along the normal; dist = mean_other - mean_own, lod = 1.96 *
+        (sqrt(var_own / n_own + var_other / n_other) + reg_error).  Returns the totals (n_core, n_no_normal, n_valid, n_significant,
+        sum_dist, sum_abs_dist, sum_dist2, sum_lod, sum_n_own, sum_n_other, max_abs_dist, argmax) with mean_dist, mean_abs_dist,
+        rms_dist, mean_lod, mean_n_own, mean_n_other and significant_share over the valid points (0 without one); with fetch=True
+        also the per-point dict of m3c2_fetch.  The call may re-index both slots and so discard the 1-NN and local-geometry results:
+        normals first, then m3c2, then nn1."""
+        n = self.size(query_slot)
+        mask = None
+        if core_mask is not None:
+            mask = np.ascontiguousarray(np.asarray(core_mask) != 0, dtype=np.uint8).reshape(-1)
+            if mask.shape != (n,):
+                raise ValueError("core_mask must hold one entry per point of the query slot")
+        p = _lib.M3c2Params()
+        p.projection_radius, p.max_depth, p.reg_error, p.min_points = float(projection_radius), float(max_depth), float(reg_error), int(min_points)
+        o = _lib.M3c2Out()
+        self._ck(self._L.me_m3c2(self._ctx, int(query_slot), C.byref(p), _addr(mask), C.byref(o)))
+        nv = int(o.n_valid)
+        res = {"n_core": int(o.n_core), "n_no_normal": int(o.n_no_normal), "n_valid": nv, "n_significant": int(o.n_significant),
+               "sum_dist": o.sum_dist, "sum_abs_dist": o.sum_abs_dist, "sum_dist2": o.sum_dist2, "sum_lod": o.sum_lod,
+               "sum_n_own": int(o.sum_n_own), "sum_n_other": int(o.sum_n_other), "max_abs_dist": o.max_abs_dist, "argmax": int(o.argmax)}
+        mean = (lambda v: v / nv) if nv > 0 else (lambda v: 0.0)
+        res.update(mean_dist=mean(o.sum_dist), mean_abs_dist=mean(o.sum_abs_dist), rms_dist=math.sqrt(mean(o.sum_dist2)),
+                   mean_lod=mean(o.sum_lod), mean_n_own=mean(o.sum_n_own), mean_n_other=mean(o.sum_n_other),
+                   significant_share=mean(o.n_significant))
+        return (res, self.m3c2_fetch(query_slot)) if fetch else res
+
+    def m3c2_fetch(self, query_slot: int) -> dict:
+        """me_m3c2_fetch -> dict of the slot's last m3c2 in cloud order: dist, lod, var_own, var_other (float64), n_own, n_other
+        (int32), valid, significant (bool)."""
+        n = self.size(query_slot)
+        d = {k: np.empty(n, np.float64) for k in ("dist", "lod", "var_own", "var_other")}
+        d["n_own"] = np.empty(n, np.int32)
+        d["n_other"] = np.empty(n, np.int32)
+        fl = np.empty(n, np.uint8)
+        self._ck(self._L.me_m3c2_fetch(self._ctx, int(query_slot), _addr(d["dist"]), _addr(d["lod"]), _addr(d["var_own"]),
+                                       _addr(d["var_other"]), _addr(d["n_own"]), _addr(d["n_other"]), _addr(fl)))
+        d["valid"] = (fl & 1) != 0
+        d["significant"] = (fl & 2) != 0
+        return d
+
+    def m3c2_report(self, normal_radius: float, projection_radius: float, max_depth: float, min_points: int = 5, reg_error: float = 0.0,
+                    normal_min_points: int = 5, quantiles=(0.05, 0.5, 0.95), core_every: int = 1) -> dict:
+        """radius_normals(normal_radius) on each slot in turn (the normals as Jacobi yields them: no viewpoint), then m3c2 in both
+        directions: "est" / "gt" = the totals of m3c2 with that slot as the query, plus "normals" (the info of its radius_normals)
+        and, for the quantiles given, rank / quantile_dist (nearest rank, exact: rank_select with use = valid, on the magnitudes of the
+        negative distances and of the others in turn, since it orders non-negative keys).
+        core_every = k > 1 keeps every k-th point of each cloud as a core point."""
+        probs = [float(x) for x in quantiles]
+        rep = {}
+        infos = {slot: self.radius_normals(slot, normal_radius, normal_min_points) for slot in (ME_SLOT_EST, ME_SLOT_GT)}
+        for name, slot in (("est", ME_SLOT_EST), ("gt", ME_SLOT_GT)):
+            mask = None
+            if int(core_every) > 1:
+                mask = np.zeros(self.size(slot), np.uint8)
+                mask[::int(core_every)] = 1
+            d, pp = self.m3c2(slot, projection_radius, max_depth, min_points, reg_error, mask, fetch=True)
+            nv = d["n_valid"]
+            d["normals"] = infos[slot]
+            d["prob"] = np.array(probs, np.float64)
+            ranks = [min(nv - 1, max(0, int(math.ceil(pr * float(nv))) - 1)) if nv > 0 else -1 for pr in probs]
+            d["rank"] = np.array(ranks, np.int64)
+            if probs and nv > 0:
+                # rank_select orders non-negative keys: the negative distances are selected by magnitude from their far end (the
+                # k-th smallest of m negatives is minus the (m - 1 - k)-th smallest magnitude), the others directly
+                dist, valid = pp["dist"], pp["valid"]
+                neg = valid & (dist < 0)
+                m = int(neg.sum())
+                mag = np.abs(dist) + 0.0
+                q = np.zeros(len(ranks), np.float64)
+                lo = [j for j, r in enumerate(ranks) if r < m]
+                hi = [j for j, r in enumerate(ranks) if r >= m]
+                if lo:
+                    q[lo] = -self.rank_select(mag, [m - 1 - ranks[j] for j in lo], use=neg)["value"]
+                if hi:
+                    q[hi] = self.rank_select(mag, [ranks[j] - m for j in hi], use=valid & ~neg)["value"]
+                d["quantile_dist"] = q
+            else:
+                d["quantile_dist"] = np.zeros(len(probs), np.float64)
+            rep[name] = d
+        return rep
+
     # ---- voxels ----
     def voxel_build(self, slot: int, voxel_size: float) -> int:
         """Builds (and caches on the cloud) the voxel-Gaussian table without exporting it; returns the voxel count."""

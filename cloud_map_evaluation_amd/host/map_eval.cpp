@@ -353,6 +353,27 @@ Param loadParametersFromYAML(const std::string &yaml_file_path) {
         if (param.evaluate_noised_gt_) throw std::runtime_error("evaluate_surface_error: not with evaluate_noised_gt");
         if (param.num_gpus > 1) throw std::runtime_error("evaluate_surface_error: single GPU only (num_gpus must be 1)");
     }
+    // M3C2 (no reference counterpart)
+    if (config.has("evaluate_m3c2")) param.evaluate_m3c2 = config.as_bool("evaluate_m3c2");
+    param.m3c2_normal_radius = config.has("m3c2_normal_radius") ? config.as_double("m3c2_normal_radius") : param.nn_radius_;
+    param.m3c2_projection_radius = config.has("m3c2_projection_radius") ? config.as_double("m3c2_projection_radius") : param.nn_radius_;
+    param.m3c2_max_depth = config.has("m3c2_max_depth") ? config.as_double("m3c2_max_depth") : 4.0 * param.nn_radius_;
+    if (config.has("m3c2_min_points")) param.m3c2_min_points = config.as_int("m3c2_min_points");
+    if (config.has("m3c2_reg_error")) param.m3c2_reg_error = config.as_double("m3c2_reg_error");
+    if (config.has("m3c2_core_every")) param.m3c2_core_every = config.as_int("m3c2_core_every");
+    if (param.evaluate_m3c2) {
+        if (!(param.m3c2_normal_radius > 0) || !std::isfinite(param.m3c2_normal_radius)) throw std::runtime_error("m3c2_normal_radius: must be > 0");
+        if (!(param.m3c2_projection_radius > 0) || !std::isfinite(param.m3c2_projection_radius))
+            throw std::runtime_error("m3c2_projection_radius: must be > 0");
+        if (!(param.m3c2_max_depth > 0) || !std::isfinite(param.m3c2_max_depth)) throw std::runtime_error("m3c2_max_depth: must be > 0");
+        if (param.m3c2_min_points < 2) throw std::runtime_error("m3c2_min_points: must be >= 2 (the variance divides by n - 1)");
+        if (!(param.m3c2_reg_error >= 0) || !std::isfinite(param.m3c2_reg_error)) throw std::runtime_error("m3c2_reg_error: must be >= 0");
+        if (param.m3c2_core_every < 1) throw std::runtime_error("m3c2_core_every: must be >= 1");
+        if (!param.evaluate_using_initial_)
+            throw std::runtime_error("evaluate_m3c2: needs evaluate_using_initial (the clouds are compared where initial_matrix puts them)");
+        if (param.evaluate_noised_gt_) throw std::runtime_error("evaluate_m3c2: not with evaluate_noised_gt");
+        if (param.num_gpus > 1) throw std::runtime_error("evaluate_m3c2: single GPU only (num_gpus must be 1)");
+    }
     return param;
 }
 
@@ -410,7 +431,10 @@ std::string paramToJson(const Param &p) {
     for (size_t i = 0; i < p.surface_thresholds.size(); ++i) o << (i ? ", " : "") << p.surface_thresholds[i];
     o << "], \"surface_angles_deg\": [";
     for (size_t i = 0; i < p.surface_angles_deg.size(); ++i) o << (i ? ", " : "") << p.surface_angles_deg[i];
-    o << "], \"surface_gated\": " << b(p.surface_gated) << "}";
+    o << "], \"surface_gated\": " << b(p.surface_gated) << ", \"evaluate_m3c2\": " << b(p.evaluate_m3c2)
+      << ", \"m3c2_normal_radius\": " << p.m3c2_normal_radius << ", \"m3c2_projection_radius\": " << p.m3c2_projection_radius
+      << ", \"m3c2_max_depth\": " << p.m3c2_max_depth << ", \"m3c2_min_points\": " << p.m3c2_min_points
+      << ", \"m3c2_reg_error\": " << p.m3c2_reg_error << ", \"m3c2_core_every\": " << p.m3c2_core_every << "}";
     return o.str();
 }
 
@@ -497,7 +521,10 @@ int MapEval::process() {
     if (param_.evaluate_error_distribution && comm_) return fail("evaluate_error_distribution: single GPU only (num_gpus must be 1)");
     const bool surf = param_.evaluate_surface_error;  // (its normals are estimated on resident clouds, before the one call transforms the map)
     if (surf && comm_) return fail("evaluate_surface_error: single GPU only (num_gpus must be 1)");
-    if (one_call && !noised && !filter && !mpv && !planes && !mom && !surf && !(param_.downsample_size > 0)) {
+    const bool m3c2 = param_.evaluate_m3c2;  // (on resident clouds, the map moved by initial_matrix for it alone)
+    if (m3c2 && (comm_ || noised || !param_.evaluate_using_initial_))
+        return fail("evaluate_m3c2: single GPU only, with evaluate_using_initial and not with evaluate_noised_gt");
+    if (one_call && !noised && !filter && !mpv && !planes && !mom && !surf && !m3c2 && !(param_.downsample_size > 0)) {
         file_result << std::fixed << std::setprecision(15) << "Estimated-Ground Truth point count: " << map_3d_->size() << " / "
                     << gt_3d_->size() << std::endl;
         if (param_.enable_debug)
@@ -540,6 +567,24 @@ int MapEval::process() {
     if (param_.enable_debug)
         std::cout << "INFO: Loaded point clouds: " << map_3d_->size() << " points (Map), " << gt_3d_->size()
                   << " points (Ground Truth)." << std::endl;
+    if (m3c2) {
+        // FIRST of the stages on the resident clouds: it moves the map, replaces both clouds' normals and re-indexes both at the
+        // cylinder's bounding radius.  Both clouds are then uploaded again from the host's copies (the clouds as loaded: the map's is
+        // still untransformed) with the normals their files brought, so that every later stage — the surface-error normals, the
+        // one call's MME, transform and searches — starts from exactly the state it finds without this key.
+        if (computeM3C2() != 0) return -1;
+        if (me_upload_cloud(ctx_, ME_SLOT_GT, gt_3d_->points_.data(), (int64_t) gt_3d_->size(), nullptr, param_.nn_radius_) != ME_OK ||
+            me_upload_cloud(ctx_, ME_SLOT_EST, map_3d_->points_.data(), (int64_t) map_3d_->size(), nullptr, param_.nn_radius_) != ME_OK)
+            return fail(me_last_error(ctx_));
+        if (!(param_.downsample_size > 0) && !filter) {  // (a down-sampled or filtered cloud carried its normals on the device only: none of
+            // the initial-matrix stages reads them)
+            if (gt_normals.size() == gt_3d_->points_.size() && !gt_normals.empty() && me_set_normals(ctx_, ME_SLOT_GT, gt_normals.data()) != ME_OK)
+                return fail(me_last_error(ctx_));
+            if (map_normals.size() == map_3d_->points_.size() && !map_normals.empty() &&
+                me_set_normals(ctx_, ME_SLOT_EST, map_normals.data()) != ME_OK)
+                return fail(me_last_error(ctx_));
+        }
+    }
     if (mpv && computeMPV() != 0) return -1;  // (the clouds as loaded, where computeMME runs: before the transform)
     if (planes && segmentPlanes() != 0) return -1;  // (likewise)
     if (mom && computeMOM() != 0) return -1;  // (likewise; after its two inputs)
@@ -1484,6 +1529,65 @@ int MapEval::computeSurfaceNormals() {
     return 0;
 }
 
+// evaluate_m3c2: the map where initial_matrix puts it (me_transform_cloud; the host's copy stays as loaded), me_radius_normals on both
+// clouds at m3c2_normal_radius (normal_min_points neighbours; the sign as Jacobi yields it), then me_m3c2 with each cloud as the query.
+// Every m3c2_core_every-th point of a cloud, in the order of its slot, is a core point.
+int MapEval::computeM3C2() {
+    const double *T = param_.initial_matrix_.data();
+    bool identity = true;
+    for (int i = 0; i < 16; ++i) identity = identity && (T[i] == ((i % 5 == 0) ? 1.0 : 0.0));
+    if (!identity && me_transform_cloud(ctx_, ME_SLOT_EST, T) != ME_OK) return fail(std::string("evaluate_m3c2: ") + me_last_error(ctx_));
+    for (int s = ME_SLOT_EST; s <= ME_SLOT_GT; ++s)
+        if (me_radius_normals(ctx_, s, param_.m3c2_normal_radius, param_.normal_min_points, nullptr, 0, &m3c2_normals[s]) != ME_OK)
+            return fail(std::string("evaluate_m3c2: ") + me_last_error(ctx_));
+    me_m3c2_params p{};
+    p.projection_radius = param_.m3c2_projection_radius;
+    p.max_depth = param_.m3c2_max_depth;
+    p.reg_error = param_.m3c2_reg_error;
+    p.min_points = param_.m3c2_min_points;
+    for (int s = ME_SLOT_EST; s <= ME_SLOT_GT; ++s) {
+        std::vector<uint8_t> mask;
+        if (param_.m3c2_core_every > 1) {
+            mask.assign((size_t) me_cloud_size(ctx_, s), 0);
+            for (size_t i = 0; i < mask.size(); i += (size_t) param_.m3c2_core_every) mask[i] = 1;
+        }
+        if (me_m3c2(ctx_, s, &p, mask.empty() ? nullptr : mask.data(), &m3c2_out[s]) != ME_OK)
+            return fail(std::string("evaluate_m3c2: ") + me_last_error(ctx_));
+    }
+    return 0;
+}
+
+void MapEval::saveM3C2() {
+    const me_m3c2_out *o = m3c2_out;
+    auto mean = [](double s, int64_t n) { return n > 0 ? s / (double) n : 0.0; };
+    file_result << std::fixed << std::setprecision(5) << "M3C2 est-gt: " << mean(o[0].sum_dist, o[0].n_valid) << " "
+                << mean(o[0].sum_abs_dist, o[0].n_valid) << " " << std::sqrt(mean(o[0].sum_dist2, o[0].n_valid)) << " "
+                << mean((double) o[0].n_significant, o[0].n_valid) << std::endl;
+    // m3c2.txt: the parameters ("name value"), then per direction (the query cloud's tag) the normals row `cloud normals n n_valid sum_k`,
+    // the totals row
+    //   cloud n_core n_no_normal n_valid n_significant sum_dist sum_abs_dist sum_dist2 sum_lod sum_n_own sum_n_other
+    // and the worst point `cloud worst max_abs_dist argmax` (doubles as %.17g)
+    const std::string path = results_subfolder + "m3c2.txt";
+    FILE *f = std::fopen(path.c_str(), "w");
+    if (!f) {
+        fail("cannot write " + path);
+        return;
+    }
+    std::fprintf(f, "normal_radius %.17g\nnormal_min_points %d\nprojection_radius %.17g\nmax_depth %.17g\nmin_points %d\nreg_error %.17g\ncore_every %d\n",
+                 param_.m3c2_normal_radius, param_.normal_min_points, param_.m3c2_projection_radius, param_.m3c2_max_depth, param_.m3c2_min_points,
+                 param_.m3c2_reg_error, param_.m3c2_core_every);
+    for (int s = ME_SLOT_EST; s <= ME_SLOT_GT; ++s) {
+        const char *tag = s == ME_SLOT_EST ? "est" : "gt";
+        const me_radius_normals_out &rn = m3c2_normals[s];
+        std::fprintf(f, "%s normals %lld %lld %lld\n", tag, (long long) rn.n, (long long) rn.n_valid, (long long) rn.sum_k);
+        std::fprintf(f, "%s %lld %lld %lld %lld %.17g %.17g %.17g %.17g %lld %lld\n", tag, (long long) o[s].n_core, (long long) o[s].n_no_normal,
+                     (long long) o[s].n_valid, (long long) o[s].n_significant, o[s].sum_dist, o[s].sum_abs_dist, o[s].sum_dist2, o[s].sum_lod,
+                     (long long) o[s].sum_n_own, (long long) o[s].sum_n_other);
+        std::fprintf(f, "%s worst %.17g %lld\n", tag, o[s].max_abs_dist, (long long) o[s].argmax);
+    }
+    if (std::fclose(f) != 0) fail("writing " + path + " failed");
+}
+
 // me_nn_surface_error on the 1-NN results of both directions, after the metric path's statistics (the gate is that path's when
 // surface_gated is set, none otherwise); the cosines of the angle thresholds are taken here, with the C library's cos
 int MapEval::computeSurfaceError(int gate_mode) {
@@ -1549,6 +1653,7 @@ void MapEval::saveRegistrationResults() {
     file_result << std::fixed << std::setprecision(5) << "FULL CD: " << full_chamfer_dist << std::endl;
     if (param_.evaluate_error_distribution) saveErrorDistribution();
     if (param_.evaluate_surface_error) saveSurfaceError();
+    if (param_.evaluate_m3c2) saveM3C2();
     file_result << std::fixed << std::setprecision(5) << "VMD: " << vmd << std::endl;
     file_result << std::fixed << std::setprecision(5) << "SCS: " << scs_overall << std::endl;
     if (param_.evaluate_using_initial_)

@@ -133,6 +133,16 @@ struct Param {
     int error_cdf_bins = 1000;                 // `error_cdf_bins:` 0 .. 4096 (0: no CDF)
     double error_cdf_max = 0;                  // `error_cdf_max:` the last bin edge (default: icp_max_distance); bin width = max / bins
     bool error_gated = false;                  // `error_gated:` true = the metric path's own gate and gate mode apply
+    // M3C2, the signed cloud-to-cloud distance (optional keys; no reference counterpart): on the resident clouds with the map moved by
+    // initial_matrix, before every other stage — me_radius_normals on both clouds, me_m3c2 in both directions — after which both clouds
+    // are uploaded again as loaded (single GPU, with evaluate_using_initial); one line before `VMD`, and m3c2.txt
+    bool evaluate_m3c2 = false;                // `evaluate_m3c2:`
+    double m3c2_normal_radius = 0.0;           // `m3c2_normal_radius:` > 0 (default: nn_radius)
+    double m3c2_projection_radius = 0.0;       // `m3c2_projection_radius:` the cylinder's radius, > 0 (default: nn_radius)
+    double m3c2_max_depth = 0.0;               // `m3c2_max_depth:` the cylinder's half-length, > 0 (default: 4 nn_radius)
+    int m3c2_min_points = 5;                   // `m3c2_min_points:` points either cloud needs inside the cylinder, >= 2
+    double m3c2_reg_error = 0.0;               // `m3c2_reg_error:` the registration error added to the level of detection, >= 0
+    int m3c2_core_every = 1;                   // `m3c2_core_every:` every k-th point of a cloud, in file order, is a core point, >= 1
     int dist_rank = 0;              // (set by the launcher, not a YAML key)
     void printParam() const;
 };
@@ -178,6 +188,8 @@ public:
     int computeSurfaceNormals();                            // evaluate_surface_error: me_radius_normals on both clouds as loaded
     int computeSurfaceError(int gate_mode);                 // ... me_nn_surface_error on both directions (no reference counterpart)
     void saveSurfaceError();                                // its three result lines and surface_error.txt
+    int computeM3C2();                                      // evaluate_m3c2: normals and me_m3c2 on both clouds, the map moved (no reference counterpart)
+    void saveM3C2();                                        // its result line and m3c2.txt
     void saveErrorDistribution();                           // its three result lines and error_distribution.txt
     int globalRegistration(double T_c[16]);                 // global_registration.txt (global_registration; no reference counterpart)                                   // noise_sweep.txt (noise_sweep; no reference counterpart)
 
@@ -202,6 +214,8 @@ public:
     me_surface_params surface_params = {};      // evaluate_surface_error: what both directions were asked for
     me_surface_out surface_out[2] = {};         // ... [ME_SLOT_EST], [ME_SLOT_GT]
     me_radius_normals_out surface_normals[2] = {};
+    me_m3c2_out m3c2_out[2] = {};               // evaluate_m3c2: [ME_SLOT_EST], [ME_SLOT_GT] as the query
+    me_radius_normals_out m3c2_normals[2] = {};
     me_mom_out mom_out[2] = {};  // evaluate_mom: [ME_SLOT_EST], [ME_SLOT_GT] (the latter with evaluate_gt_mom)
     me_local_geom_out mpv_out[2] = {};  // evaluate_mpv: [ME_SLOT_EST], [ME_SLOT_GT] (the latter with evaluate_gt_mpv)
     std::vector<double> est_entropies, gt_entropies;

@@ -743,6 +743,69 @@ typedef struct me_surface_out {
 int me_nn_surface_error(me_ctx *ctx, int query_slot, const me_surface_params *p, me_surface_out *out);
 int me_nn_surface_fetch(me_ctx *ctx, int query_slot, double *plane_d, double *cos_n);
 
+/* ---- M3C2: the signed cloud-to-cloud distance along the query cloud's normals, with a level of detection -------------------------- */
+/* (Lague, Brodu, Leroux 2013).  Every 1-NN figure compares one point with one sample and has no sign.  M3C2
+ * averages BOTH clouds inside a cylinder around each core point's normal and reports the signed offset of the two averages and
+ * whether it can be told from roughness and density.  Single GPU only (slab or shard mode: ME_ERR_ARG).  Device timer "m3c2".
+ *
+ * me_m3c2.  The core points are the points of query_slot ("own" cloud), thinned by core_mask (host, uint8[N], cloud order, != 0 =
+ * core point; NULL = every point); the other slot is the compared cloud ("other").  The query slot's resident normals are used AS
+ * STORED (me_set_normals, me_estimate_normals or me_radius_normals; not re-normalised; must be finite).  Parameters:
+ * projection_radius rp (half of M3C2's d) and max_depth L (the cylinder's half-length) finite and > 0, min_points >= 2, reg_error
+ * finite and >= 0, p and out non-NULL, else ME_ERR_ARG.  ME_ERR_STATE: either slot holds no cloud, or the query slot has no normals.
+ *   Membership.  For the core point q with stored normal N = (nx, ny, nz) and a candidate p of either cloud (fp64, no FMA):
+ *       dx = px-qx, dy = py-qy, dz = pz-qz
+ *       d2 = (dx*dx + dy*dy) + dz*dz
+ *       t  = (nx*dx + ny*dy) + nz*dz
+ *       inside  <=>  fabs(t) < L  &&  d2 - t*t < rp*rp
+ *     Both tests are strict (the library's radius convention).  The core point counts in its own cloud's cylinder (t = 0, as in
+ *     M3C2); coincident duplicates count as often as they occur.  A zero normal gives t = 0 for every candidate: the counts are those
+ *     of the ball of radius rp, and the point is invalid.
+ *   Per cloud c in {own, other}: n_c = the points inside; S_c = sum t, Q_c = sum t*t, added per core point in the order the
+ *     candidates are streamed — moments about the core point, so that no term exceeds L^2 —; mean_c = S_c / n_c,
+ *     var_c = max((Q_c - S_c*S_c/n_c) / (n_c - 1), 0).
+ *   A core point is VALID iff its normal is not the zero vector, n_own >= min_points and n_other >= min_points.  On a valid one
+ *       dist        = mean_other - mean_own        (positive: the other cloud lies further along +N)
+ *       lod         = 1.96 * (sqrt(var_own/n_own + var_other/n_other) + reg_error)
+ *       significant = fabs(dist) > lod
+ *     Error bounds against exactly summed moments of the same t: |dist| within (n_own + n_other) 2^-53 L, each var_c within
+ *     (3 n_c + 10) 2^-53 L^2 (<= 8 n_c 2^-53 L^2).
+ *   An invalid core point stores dist = lod = var_own = var_other = 0 and flags 0 but KEEPS its two counts (they say why it is
+ *   invalid); a masked-out point stores zeros throughout and enters no total.
+ *   out: n_core (the core points), n_no_normal (core points with a zero normal), n_valid, n_significant; over the VALID points
+ *     sum_dist, sum_abs_dist, sum_dist2, sum_lod, sum_n_own, sum_n_other, and max_abs_dist with argmax = the ORIGINAL index of its
+ *     core point, ties -> smallest index (0 and -1 when n_valid == 0).  Per-block partials (a fixed grid of at most 1024 blocks; a
+ *     thread adds its entries in order, a block by a fixed tree) combined in block order: no floating-point atomics, bit-identical
+ *     from run to run on the same index.
+ * INDEX AND ORDER OF USE.  Both slots need an index whose cell edge is >= R = sqrt(L*L + rp*rp), the radius of the cylinder's
+ * bounding ball; a slot whose cell is smaller than R or larger than 1.5 R is re-indexed at R (me_local_geometry's rule; the cell size
+ * asked for at the upload is remembered).  That DISCARDS the resident 1-NN results of both slots (me_nn1 and everything read from
+ * it, me_nn_surface_error's result included) and the re-indexed slot's local-geometry result (me_local_geometry_fetch, me_mom).
+ * Normals are kept in cloud order and survive.  So: normals first, then me_m3c2, then me_nn1 and what depends on it.
+ * COST.  The search visits the ball of radius R, not the cylinder: the work per core point grows like (R / spacing)^2.  Thin the core
+ * points with core_mask when L is long or the clouds are dense.
+ *
+ * me_m3c2_fetch: the per-point arrays of the slot's last me_m3c2 in cloud order (N entries each, all nullable); flags bit 0 = valid,
+ * bit 1 = significant.  ME_ERR_STATE without a current result: it is discarded when either slot's points change (upload,
+ * down-sample, transform, perturbation, selection) or the query slot is re-indexed. */
+typedef struct me_m3c2_params {
+    double projection_radius; /* rp, finite and > 0 */
+    double max_depth;         /* L, finite and > 0 */
+    double reg_error;         /* finite and >= 0 */
+    int32_t min_points;       /* >= 2 */
+    int32_t reserved;
+} me_m3c2_params;
+typedef struct me_m3c2_out {
+    int64_t n_core, n_no_normal, n_valid, n_significant;
+    double sum_dist, sum_abs_dist, sum_dist2, sum_lod;
+    int64_t sum_n_own, sum_n_other;
+    double max_abs_dist;
+    int64_t argmax;
+} me_m3c2_out;
+int me_m3c2(me_ctx *ctx, int query_slot, const me_m3c2_params *p, const uint8_t *core_mask, me_m3c2_out *out);
+int me_m3c2_fetch(me_ctx *ctx, int query_slot, double *dist, double *lod, double *var_own, double *var_other, int32_t *n_own,
+                  int32_t *n_other, uint8_t *flags);
+
 int64_t me_cloud_size(me_ctx *ctx, int slot);
 /* transformed points back to the host (N x 3), original order — what map_3d_->points_ holds after :1206 */
 int me_download_cloud(me_ctx *ctx, int slot, double *xyz_host);
