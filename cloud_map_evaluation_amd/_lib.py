@@ -36,6 +36,7 @@ SYMBOLS = [
     "me_cluster_dbscan", "me_cluster_sizes", "me_cluster_keep",
     "me_local_geometry", "me_local_geometry_fetch", "me_radius_normals", "me_nn_surface_error", "me_nn_surface_fetch",
     "me_m3c2", "me_m3c2_fetch",
+    "me_knn_search", "me_hybrid_search", "me_radius_search", "me_search_sort_tile",
     "me_segment_planes", "me_plane_fetch", "me_plane_keep",
     "me_group_order_stats", "me_mom_select_axes", "me_mom", "me_mom_fetch",
     "me_rank_select", "me_sqrt_threshold", "me_nn_error_distribution", "me_fscore_finalize",
@@ -479,6 +480,12 @@ def load():
     L.me_m3c2.argtypes = [vp, C.c_int, C.POINTER(M3c2Params), vp, C.POINTER(M3c2Out)]
     L.me_m3c2_fetch.argtypes = [vp, C.c_int, dp, dp, dp, dp, ip, ip, vp]
     for f in ("me_m3c2", "me_m3c2_fetch"):
+        getattr(L, f).restype = C.c_int
+    L.me_knn_search.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, ip, dp]
+    L.me_hybrid_search.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_int, vp, ip, ip, dp]
+    L.me_radius_search.argtypes = [vp, C.c_int, C.c_int, C.c_double, vp, vp, ip, dp, C.c_int64, C.POINTER(C.c_int64)]
+    L.me_search_sort_tile.argtypes = []
+    for f in ("me_knn_search", "me_hybrid_search", "me_radius_search", "me_search_sort_tile"):
         getattr(L, f).restype = C.c_int
     L.me_segment_planes.argtypes = [vp, C.c_int, C.POINTER(PlaneParams), vp, ip, vp, C.POINTER(PlaneInfo)]
     L.me_plane_fetch.argtypes = [vp, C.c_int, vp, C.c_int64, C.POINTER(C.c_int64), ip]

@@ -390,6 +390,25 @@ int me_m3c2_fetch(me_ctx *ctx, int query_slot, double *dist, double *lod, double
     return me::m3c2_fetch(ctx, query_slot, dist, lod, var_own, var_other, n_own, n_other, flags);
 }
 
+int me_knn_search(me_ctx *ctx, int query_slot, int ref_slot, int k, const uint8_t *query_mask, int32_t *idx, double *d2) {
+    if (!ctx) return ME_ERR_ARG;
+    return me::knn_search(ctx, query_slot, ref_slot, k, query_mask, idx, d2);
+}
+
+int me_hybrid_search(me_ctx *ctx, int query_slot, int ref_slot, double radius, int max_nn, const uint8_t *query_mask, int32_t *counts,
+                     int32_t *idx, double *d2) {
+    if (!ctx) return ME_ERR_ARG;
+    return me::hybrid_search(ctx, query_slot, ref_slot, radius, max_nn, query_mask, counts, idx, d2);
+}
+
+int me_radius_search(me_ctx *ctx, int query_slot, int ref_slot, double radius, const uint8_t *query_mask, int64_t *offsets, int32_t *idx,
+                     double *d2, int64_t capacity, int64_t *total) {
+    if (!ctx) return ME_ERR_ARG;
+    return me::radius_search(ctx, query_slot, ref_slot, radius, query_mask, offsets, idx, d2, capacity, total);
+}
+
+int me_search_sort_tile(void) { return me::kSearchSortTile; }
+
 int me_local_geometry_fetch(me_ctx *ctx, int slot, double *eig, int32_t *k, uint8_t *valid) {
     if (!ctx) return ME_ERR_ARG;
     return me::local_geometry_fetch(ctx, slot, eig, k, valid);

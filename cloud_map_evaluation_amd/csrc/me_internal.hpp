@@ -507,6 +507,7 @@ int cell_start_ranks(me_ctx *ctx, const unsigned long long *codes, long long n, 
 int sort_keys_f64(me_ctx *ctx, const double *in, double *out, long long n);
 int sort_keys_u64(me_ctx *ctx, const unsigned long long *in, unsigned long long *out, long long n, int begin_bit, int end_bit);
 int select_flagged_u32(me_ctx *ctx, const unsigned char *flags, long long n, unsigned int *out, unsigned int *count_device);
+int exclusive_scan_i32_i64(me_ctx *ctx, const int *in, long long *out, long long n);  // 64-bit prefix sums of 32-bit counts
 
 // ---- me_index.hip ----
 int cloud_upload(me_ctx *ctx, int slot, const double *src, bool src_on_device, long long n, const double *T,
@@ -543,6 +544,13 @@ int nn_surface_fetch(me_ctx *ctx, int qslot, double *plane_d_host, double *cos_n
 int m3c2(me_ctx *ctx, int qslot, const me_m3c2_params *p, const uint8_t *core_mask_host, me_m3c2_out *out);
 int m3c2_fetch(me_ctx *ctx, int qslot, double *dist_host, double *lod_host, double *var_own_host, double *var_other_host, int32_t *n_own_host,
                int32_t *n_other_host, uint8_t *flags_host);
+// ---- me_search.hip ----
+constexpr int kSearchSortTile = 512;  // entries of a radius row that one wave sorts in LDS; longer rows are sorted in global memory
+int knn_search(me_ctx *ctx, int qslot, int rslot, int k, const uint8_t *mask_host, int32_t *idx_host, double *d2_host);
+int hybrid_search(me_ctx *ctx, int qslot, int rslot, double radius, int max_nn, const uint8_t *mask_host, int32_t *counts_host, int32_t *idx_host,
+                  double *d2_host);
+int radius_search(me_ctx *ctx, int qslot, int rslot, double radius, const uint8_t *mask_host, int64_t *offsets_host, int32_t *idx_host,
+                  double *d2_host, long long capacity, int64_t *total_host);
 // ---- me_plane.hip ----
 int segment_planes(me_ctx *ctx, int slot, const me_plane_params *p, me_plane_record *planes_host, int32_t *labels_host, int64_t *scores_host,
                    me_plane_info *info);

@@ -147,6 +147,21 @@ int cell_start_ranks(me_ctx *ctx, const unsigned long long *codes, long long n, 
     return ME_OK;
 }
 
+// out[i] = in[0] + ... + in[i - 1] in 64 bits (row offsets from per-row counts: me_search.hip)
+struct WidenI32 {
+    __device__ long long operator()(int v) const { return (long long) v; }
+};
+
+int exclusive_scan_i32_i64(me_ctx *ctx, const int *in, long long *out, long long n) {
+    if (n <= 0) return ME_OK;
+    auto wide = rocprim::make_transform_iterator(in, WidenI32{});
+    size_t bytes = 0;
+    ME_CHECK(ctx, rocprim::exclusive_scan(nullptr, bytes, wide, out, 0LL, (size_t) n, rocprim::plus<long long>(), ctx->stream));
+    ME_CHECK(ctx, ctx->tmp[5].ensure(bytes));
+    ME_CHECK(ctx, rocprim::exclusive_scan(ctx->tmp[5].p, bytes, wide, out, 0LL, (size_t) n, rocprim::plus<long long>(), ctx->stream));
+    return ME_OK;
+}
+
 // out[0 .. *count) = the indices i < n with flags[i] != 0, ascending (a stream compaction; the count stays on the device)
 int select_flagged_u32(me_ctx *ctx, const unsigned char *flags, long long n, unsigned int *out, unsigned int *count_device) {
     if (n <= 0) return ME_OK;

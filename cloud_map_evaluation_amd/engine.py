@@ -893,6 +893,57 @@ class Engine:
         d["significant"] = (fl & 2) != 0
         return d
 
+    # ---- neighbour lists between the resident clouds (me_search.hip) ----
+    def _query_mask(self, query_slot: int, mask):
+        if mask is None:
+            return None
+        m = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8).reshape(-1)
+        if m.shape != (self.size(query_slot),):
+            raise ValueError("mask must hold one entry per point of the query slot")
+        return m
+
+    def knn_search(self, query_slot: int, ref_slot: int, k: int, mask=None):
+        """me_knn_search: the k nearest points of ref_slot for every point of query_slot (the slots may be equal) -> (idx[N, k] int32,
+        d2[N, k] float64), rows ascending by (d2, index), -1 / inf where the reference cloud has fewer than k points or the query is
+        masked out (mask: (N,) of zero / non-zero, cloud order).  Leaves everything resident on both slots as it is."""
+        n = self.size(query_slot)
+        m = self._query_mask(query_slot, mask)
+        idx = np.empty((n, max(int(k), 0)), np.int32)
+        d2 = np.empty((n, max(int(k), 0)), np.float64)
+        self._ck(self._L.me_knn_search(self._ctx, int(query_slot), int(ref_slot), int(k), _addr(m), _addr(idx), _addr(d2)))
+        return idx, d2
+
+    def hybrid_search(self, query_slot: int, ref_slot: int, radius: float, max_nn: int, mask=None):
+        """me_hybrid_search: the max_nn nearest among the points of ref_slot with d2 < radius^2 -> (counts[N] int32, idx[N, max_nn],
+        d2[N, max_nn]), padded with -1 / inf past counts[i]."""
+        n = self.size(query_slot)
+        m = self._query_mask(query_slot, mask)
+        cnt = np.empty(n, np.int32)
+        idx = np.empty((n, max(int(max_nn), 0)), np.int32)
+        d2 = np.empty((n, max(int(max_nn), 0)), np.float64)
+        self._ck(self._L.me_hybrid_search(self._ctx, int(query_slot), int(ref_slot), float(radius), int(max_nn), _addr(m), _addr(cnt),
+                                          _addr(idx), _addr(d2)))
+        return cnt, idx, d2
+
+    def radius_search(self, query_slot: int, ref_slot: int, radius: float, counts_only: bool = False, mask=None):
+        """me_radius_search: every point of ref_slot with d2 < radius^2 (strict) per point of query_slot, as CSR -> (offsets int64[N + 1],
+        idx int32[total], d2 float64[total]); row i is idx[offsets[i]:offsets[i + 1]], ascending by (d2, index).  The sizing call,
+        the allocation and the filling call; counts_only=True returns the offsets alone."""
+        n = self.size(query_slot)
+        m = self._query_mask(query_slot, mask)
+        off = np.empty(n + 1, np.int64)
+        total = C.c_int64(0)
+        self._ck(self._L.me_radius_search(self._ctx, int(query_slot), int(ref_slot), float(radius), _addr(m), _addr(off), 0, 0, 0,
+                                          C.byref(total)))
+        if counts_only:
+            return off
+        idx = np.empty(total.value, np.int32)
+        d2 = np.empty(total.value, np.float64)
+        if total.value > 0:
+            self._ck(self._L.me_radius_search(self._ctx, int(query_slot), int(ref_slot), float(radius), _addr(m), _addr(off), _addr(idx),
+                                              _addr(d2), total.value, C.byref(total)))
+        return off, idx, d2
+
     def m3c2_report(self, normal_radius: float, projection_radius: float, max_depth: float, min_points: int = 5, reg_error: float = 0.0,
                     normal_min_points: int = 5, quantiles=(0.05, 0.5, 0.95), core_every: int = 1) -> dict:
         """radius_normals(normal_radius) on each slot in turn (the normals as Jacobi yields them: no viewpoint), then m3c2 in both

@@ -806,6 +806,45 @@ int me_m3c2(me_ctx *ctx, int query_slot, const me_m3c2_params *p, const uint8_t 
 int me_m3c2_fetch(me_ctx *ctx, int query_slot, double *dist, double *lod, double *var_own, double *var_other, int32_t *n_own,
                   int32_t *n_other, uint8_t *flags);
 
+/* ---- neighbour lists between the resident clouds: KDTreeFlann::SearchKNN / SearchHybrid / SearchRadius for every point of a
+ * cloud (the reference's loops over them: map_eval.cpp:1213-1218, 1448-1454, 1670) ---- */
+/* The three searches below hand the neighbours themselves to the caller, for every point of query_slot among the points of
+ * ref_slot.  Common to all three:
+ *   SLOTS.  query_slot and ref_slot are each 0 or 1 and may be equal: a search of a cloud in itself, in which a query point is its
+ *     own first neighbour with d2 = 0 (as in Open3D).  Single-GPU plain clouds only (no slab, no shard); both slots uploaded.
+ *   DISTANCE.  d2 = (dx*dx + dy*dy) + dz*dz in fp64 without contraction: the expression of me_nn1 and of the CPU path, bit-identical.
+ *   ORDER.  Every list is ascending by (d2, index of the reference point): equal distances resolve to the smaller index, between
+ *     coincident and between equidistant points alike.  Results are identical from run to run.
+ *   RADIUS.  Membership is strict, d2 < radius * radius, the product formed once on the host in fp64 (me_mme's convention).
+ *   INDICES are original (upload-order) indices of the reference cloud, int32; row offsets and totals are int64.
+ *   query_mask (nullable): uint8[N_query] in cloud order, non-zero = search this point.  A masked-out query gets an empty row
+ *     (radius) or a row of padding and a count of 0 (k-NN, hybrid) and costs no search work.
+ *   STATE.  The searches walk the reference cloud's octree, which every index carries at any cell size: no slot is re-indexed for k
+ *     or for a radius, and everything resident on both slots (1-NN results, normals, covariances, MME, local geometry, M3C2, voxel
+ *     tables, labels) stays as it is and stays fetchable.  The one exception is a slot whose points were replaced on the device and
+ *     that has no index at the time of the call: it is indexed at the cell size asked for at its upload, exactly as the next
+ *     me_nn1 would, with what that rebuild discards (the 1-NN results of both slots, that slot's MME, local-geometry and M3C2 results).
+ *   ERRORS.  ME_ERR_ARG: bad slot, k / max_nn outside [1, 40], radius not finite or not > 0, idx without d2 or the reverse, slab or
+ *     shard mode; ME_ERR_STATE: a slot that holds no cloud — never uploaded, or offered an empty cloud, which me_upload_cloud itself
+ *     rejects with ME_ERR_ARG, so that no slot can hold zero points (the searches check the count all the same); ME_ERR_HIP: a
+ *     device allocation failed (the lists take 12 bytes per entry on the device for the time of the call and are released on return).
+ *
+ * me_knn_search — SearchKNN(q, k): idx / d2 are N_query x k (host), padded with -1 / +inf where the reference cloud has fewer than
+ *   k points.  1 <= k <= 40.
+ * me_hybrid_search — SearchHybrid(q, radius, max_nn): the max_nn nearest among those with d2 < radius^2.  idx / d2 are N_query x
+ *   max_nn, padded as above; counts[N_query] = entries used per row (nullable).  1 <= max_nn <= 40.
+ * me_radius_search — SearchRadius(q, radius) as CSR: offsets[N_query + 1] (host, nullable), *total = offsets[N_query] (nullable).
+ *   With idx == d2 == NULL only the counts are computed (the sizing call).  Otherwise capacity >= total is required — ME_ERR_ARG
+ *   whose message names the needed total if not, and then NOTHING is written, *total and offsets included — and idx / d2 [total]
+ *   receive the rows.  Rows of up to me_search_sort_tile() entries are sorted by one wavefront in LDS, longer ones by one workgroup
+ *   in global memory: same order, more time per entry.  Memory: 12 bytes per entry plus 12 per query on the device. */
+int me_knn_search(me_ctx *ctx, int query_slot, int ref_slot, int k, const uint8_t *query_mask, int32_t *idx, double *d2);
+int me_hybrid_search(me_ctx *ctx, int query_slot, int ref_slot, double radius, int max_nn, const uint8_t *query_mask, int32_t *counts,
+                     int32_t *idx, double *d2);
+int me_radius_search(me_ctx *ctx, int query_slot, int ref_slot, double radius, const uint8_t *query_mask, int64_t *offsets, int32_t *idx,
+                     double *d2, int64_t capacity, int64_t *total);
+int me_search_sort_tile(void);
+
 int64_t me_cloud_size(me_ctx *ctx, int slot);
 /* transformed points back to the host (N x 3), original order — what map_3d_->points_ holds after :1206 */
 int me_download_cloud(me_ctx *ctx, int slot, double *xyz_host);
