@@ -41,6 +41,7 @@ SYMBOLS = [
     "me_group_order_stats", "me_mom_select_axes", "me_mom", "me_mom_fetch",
     "me_rank_select", "me_sqrt_threshold", "me_nn_error_distribution", "me_fscore_finalize",
     "me_set_normals", "me_get_normals", "me_estimate_normals", "me_gicp_covariances", "me_get_covariances", "me_icp_lsq_sums",
+    "me_icp_lsq_sums_robust", "me_icp_information",
     "me_nn1", "me_icp_p2p_sums", "me_render_distance", "me_render_entropy", "me_nn_stats", "me_nn_partial_sums", "me_nn_sigma_sums", "me_nn_finalize", "me_chamfer",
     "me_mme", "me_voxel_gaussians", "me_voxel_metrics", "me_awd_scs", "me_w2_batch", "me_scs_table", "me_run_suite", "me_run_suite_from", "me_mme_fetch",
     "me_set_voxel_hint", "me_timers_enable", "me_timers_reset", "me_timer_get",
@@ -84,6 +85,27 @@ class IcpLsq(C.Structure):
         ("JTr", C.c_double * 6),
         ("r2", C.c_double),
         ("sum_d2", C.c_double),
+    ]
+
+
+# me_icp_lsq_sums_robust: the loss kernels of Open3D's RobustKernel.cpp [upstream]
+ME_ROBUST_L2, ME_ROBUST_L1, ME_ROBUST_HUBER, ME_ROBUST_CAUCHY, ME_ROBUST_GM, ME_ROBUST_TUKEY = range(6)
+ROBUST_KERNELS = {"l2": ME_ROBUST_L2, "l1": ME_ROBUST_L1, "huber": ME_ROBUST_HUBER, "cauchy": ME_ROBUST_CAUCHY, "gm": ME_ROBUST_GM,
+                  "tukey": ME_ROBUST_TUKEY}
+
+
+class IcpRobust(C.Structure):
+    _fields_ = [
+        ("n_corr", C.c_int64),
+        ("n_source", C.c_int64),
+        ("n_zero_weight", C.c_int64),
+        ("n_degenerate", C.c_int64),
+        ("JTJ", C.c_double * 36),
+        ("JTr", C.c_double * 6),
+        ("r2", C.c_double),
+        ("sum_d2", C.c_double),
+        ("sum_w", C.c_double),
+        ("sum_wr2", C.c_double),
     ]
 
 
@@ -521,7 +543,10 @@ def load():
     L.me_get_covariances.argtypes = [vp, C.c_int, dp]
     L.me_get_covariances.restype = C.c_int
     L.me_icp_lsq_sums.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.POINTER(IcpLsq)]
-    for f in ("me_set_normals", "me_get_normals", "me_estimate_normals", "me_gicp_covariances", "me_icp_lsq_sums"):
+    L.me_icp_lsq_sums_robust.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, C.POINTER(IcpRobust)]
+    L.me_icp_information.argtypes = [vp, C.c_int, C.c_double, dp, C.POINTER(C.c_int64)]
+    for f in ("me_set_normals", "me_get_normals", "me_estimate_normals", "me_gicp_covariances", "me_icp_lsq_sums", "me_icp_lsq_sums_robust",
+              "me_icp_information"):
         getattr(L, f).restype = C.c_int
     L.me_render_distance.argtypes = [vp, C.c_int, C.c_double, C.c_double, C.c_int, vp, vp]
     L.me_render_distance.restype = C.c_int

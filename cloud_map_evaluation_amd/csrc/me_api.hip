@@ -516,6 +516,20 @@ int me_icp_lsq_sums(me_ctx *ctx, int query_slot, int mode, double max_distance, 
     return me::icp_lsq_sums(ctx, query_slot, mode, max_distance, out);
 }
 
+int me_icp_lsq_sums_robust(me_ctx *ctx, int query_slot, int mode, double max_distance, int kernel, double k, me_icp_robust *out) {
+    if (!ctx) return ME_ERR_ARG;
+    return me::icp_lsq_sums_robust(ctx, query_slot, mode, max_distance, kernel, k, out);
+}
+
+int me_icp_information(me_ctx *ctx, int query_slot, double max_distance, double info[36], int64_t *n_corr) {
+    if (!ctx) return ME_ERR_ARG;
+    if (!n_corr) return ctx->fail(ME_ERR_ARG, "me_icp_information: n_corr is NULL");
+    long long n = 0;
+    const int rc = me::icp_information(ctx, query_slot, max_distance, info, &n);
+    if (rc == ME_OK) *n_corr = n;
+    return rc;
+}
+
 int me_render_distance(me_ctx *ctx, int query_slot, double dis, double gate, int gate_mode, double *rgb, uint8_t *inlier) {
     if (!ctx) return ME_ERR_ARG;
     return me::render_distance(ctx, query_slot, dis, gate, gate_mode, rgb, inlier);

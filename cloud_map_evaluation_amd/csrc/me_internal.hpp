@@ -594,6 +594,8 @@ int gicp_covariances(me_ctx *ctx, int slot, double epsilon, double *cov_host);
 int get_covariances(me_ctx *ctx, int slot, double *cov_host);
 int rotate_attributes(me_ctx *ctx, int slot, const double *T);
 int icp_lsq_sums(me_ctx *ctx, int qslot, int mode, double max_distance, me_icp_lsq *out);
+int icp_lsq_sums_robust(me_ctx *ctx, int qslot, int mode, double max_distance, int kernel, double k, me_icp_robust *out);
+int icp_information(me_ctx *ctx, int qslot, double max_distance, double *info, long long *n_corr);
 // the k nearest neighbours of every point of a slot in that slot (the walk of me_estimate_normals; normals untouched): idx / d2 [n][k],
 // original order, ascending by (d2, index), -1 / inf past the end.  Device buffers; queued on ctx->stream.
 constexpr int kKnnMax = 40;

@@ -15,6 +15,7 @@
 #include <cmath>
 #include <cstring>
 
+#include "me_horn.hpp"
 #include "me_internal.hpp"
 #include "me_oct_walk.hpp"
 
@@ -449,23 +450,187 @@ k_lsq_sums(const SPoint *__restrict__ qsp, const double *__restrict__ d2s, const
     if (threadIdx.x == 0) pc[blockIdx.x] = rc;
 }
 
+// D double columns and NC counters per block -> their totals (block k < D: column k; block D + c: counter c)
+template <int D, int NC>
 __global__ void __launch_bounds__(256)
 k_lsq_final(const double *__restrict__ pd, const long long *__restrict__ pc, int nblocks, double *__restrict__ out_d,
             long long *__restrict__ out_c) {
-    const int k = blockIdx.x;  // 0..kLsqD-1: a double component; kLsqD: the count
+    const int k = blockIdx.x;
     __shared__ double smd[4];
     __shared__ long long smi[4];
-    if (k < kLsqD) {
+    if (k < D) {
         double s = 0;
-        for (int b = threadIdx.x; b < nblocks; b += 256) s += pd[(long long) b * kLsqD + k];
+        for (int b = threadIdx.x; b < nblocks; b += 256) s += pd[(long long) b * D + k];
         const double r = block_sum_256(s, smd);
         if (threadIdx.x == 0) out_d[k] = r;
     } else {
+        const int c = k - D;
         long long s = 0;
-        for (int b = threadIdx.x; b < nblocks; b += 256) s += pc[b];
+        for (int b = threadIdx.x; b < nblocks; b += 256) s += pc[(long long) b * NC + c];
         const long long r = block_sum_256_ll(s, smi);
-        if (threadIdx.x == 0) *out_c = r;
+        if (threadIdx.x == 0) out_c[c] = r;
     }
+}
+
+// ---- the same step under a robust loss (Open3D RobustKernel.cpp [upstream]); DESIGN.md section 4.17 ----
+constexpr int kRobD = 31;  // the 29 of k_lsq_sums, then sum w and sum w r^2
+constexpr int kRobC = 3;   // n_corr, n_zero_weight, n_degenerate
+
+// w(r): + - * / fabs fmin fmax only, so that a numpy model restates every weight bit for bit
+template <int KERNEL>
+__device__ __forceinline__ double robust_weight(double r, double k) {
+    const double a = fabs(r);
+    if (KERNEL == ME_ROBUST_L1) return a == 0.0 ? 0.0 : 1.0 / a;  // (upstream divides by zero at r == 0)
+    if (KERNEL == ME_ROBUST_HUBER) return k / fmax(a, k);
+    if (KERNEL == ME_ROBUST_CAUCHY) {
+        const double q = r / k;
+        return 1.0 / (1.0 + q * q);
+    }
+    if (KERNEL == ME_ROBUST_GM) {
+        const double t = k + r * r;
+        return k / (t * t);
+    }
+    const double q = fmin(1.0, a / k);  // Tukey
+    const double u = 1.0 - q * q;
+    return u * u;
+}
+
+template <int MODE, int KERNEL>
+__global__ void __launch_bounds__(256)
+k_lsq_sums_robust(const SPoint *__restrict__ qsp, const double *__restrict__ d2s, const int *__restrict__ idxs,
+                  const double *__restrict__ ref_xyz, const double *__restrict__ src_attr, const double *__restrict__ ref_attr,
+                  long long n, double gate2, double kk, double *__restrict__ pd, long long *__restrict__ pc) {
+    double s[kRobD];
+#pragma unroll
+    for (int k = 0; k < kRobD; ++k) s[k] = 0;
+    long long cnt = 0, nzero = 0, ndeg = 0;
+    for (long long i = (long long) blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long) gridDim.x * blockDim.x) {
+        const double d2 = d2s[i];
+        if (!(d2 >= 0.0 && d2 < gate2)) continue;
+        const long long j = idxs[i];
+        const SPoint sq = qsp[i];
+        const double vs[3] = {sq.x, sq.y, sq.z};
+        const double d[3] = {vs[0] - ref_xyz[3 * j], vs[1] - ref_xyz[3 * j + 1], vs[2] - ref_xyz[3 * j + 2]};
+        s[28] += d2;
+        ++cnt;
+        if (MODE == 1) {
+            const double nt[3] = {ref_attr[3 * j], ref_attr[3 * j + 1], ref_attr[3 * j + 2]};
+            double J[6];
+            cross3(vs, nt, J);
+            J[3] = nt[0];
+            J[4] = nt[1];
+            J[5] = nt[2];
+            const double r = dot3(d, nt);
+            const double w = robust_weight<KERNEL>(r, kk);
+            if (w == 0.0) ++nzero;
+            int t = 0;
+#pragma unroll
+            for (int a = 0; a < 6; ++a) {
+                const double Jw = J[a] * w;
+#pragma unroll
+                for (int b = a; b < 6; ++b) s[t++] += Jw * J[b];
+                s[21 + a] += Jw * r;
+            }
+            s[27] += r * r;
+            s[29] += w;
+            s[30] += w * (r * r);
+        } else {
+            double M[9], lam[3], V[9];
+            const long long si = sq.idx;
+#pragma unroll
+            for (int e = 0; e < 9; ++e) M[e] = ref_attr[9 * j + e] + src_attr[9 * si + e];
+            jacobi_sym(3, M, lam, V);  // eigenvectors in the columns of V
+            // (x - x == 0.0) is false for inf and NaN
+            if (!(lam[0] > 0.0 && lam[1] > 0.0 && lam[2] > 0.0 && lam[0] - lam[0] == 0.0 && lam[1] - lam[1] == 0.0 &&
+                  lam[2] - lam[2] == 0.0)) {
+                ++ndeg;
+                continue;
+            }
+            const double is[3] = {1.0 / sqrt(lam[0]), 1.0 / sqrt(lam[1]), 1.0 / sqrt(lam[2])};
+            // W = V diag(1 / sqrt(lam)) V^T: the upper triangle as ((V_i0 s0) V_j0 + (V_i1 s1) V_j1) + (V_i2 s2) V_j2, mirrored
+            double W[9];
+#pragma unroll
+            for (int a = 0; a < 3; ++a)
+#pragma unroll
+                for (int b = a; b < 3; ++b) {
+                    const double v =
+                        ((V[3 * a] * is[0]) * V[3 * b] + (V[3 * a + 1] * is[1]) * V[3 * b + 1]) + (V[3 * a + 2] * is[2]) * V[3 * b + 2];
+                    W[3 * a + b] = v;
+                    W[3 * b + a] = v;
+                }
+            const double x = vs[0], y = vs[1], z = vs[2];
+            const double Jm[18] = {0, z, -y, 1, 0, 0, -z, 0, x, 0, 1, 0, y, -x, 0, 0, 0, 1};  // [-skew(vs) | I]
+            double WJ[18], r[3], w[3];
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+#pragma unroll
+                for (int c = 0; c < 6; ++c) WJ[6 * a + c] = (W[3 * a] * Jm[c] + W[3 * a + 1] * Jm[6 + c]) + W[3 * a + 2] * Jm[12 + c];
+                r[a] = (W[3 * a] * d[0] + W[3 * a + 1] * d[1]) + W[3 * a + 2] * d[2];
+                w[a] = robust_weight<KERNEL>(r[a], kk);
+                if (w[a] == 0.0) ++nzero;
+            }
+            int t = 0;
+#pragma unroll
+            for (int a = 0; a < 6; ++a) {
+                const double J0 = WJ[a] * w[0], J1 = WJ[6 + a] * w[1], J2 = WJ[12 + a] * w[2];
+#pragma unroll
+                for (int b = a; b < 6; ++b) s[t++] += (J0 * WJ[b] + J1 * WJ[6 + b]) + J2 * WJ[12 + b];
+                s[21 + a] += (J0 * r[0] + J1 * r[1]) + J2 * r[2];
+            }
+            s[27] += (r[0] * r[0] + r[1] * r[1]) + r[2] * r[2];
+            s[29] += (w[0] + w[1]) + w[2];
+            s[30] += (w[0] * (r[0] * r[0]) + w[1] * (r[1] * r[1])) + w[2] * (r[2] * r[2]);
+        }
+    }
+    __shared__ double smd[4];
+    __shared__ long long smi[4];
+#pragma unroll
+    for (int k = 0; k < kRobD; ++k) {
+        const double r = block_sum_256(s[k], smd);
+        if (threadIdx.x == 0) pd[(long long) blockIdx.x * kRobD + k] = r;
+    }
+    const long long rc = block_sum_256_ll(cnt, smi);
+    const long long rz = block_sum_256_ll(nzero, smi);
+    const long long rg = block_sum_256_ll(ndeg, smi);
+    if (threadIdx.x == 0) {
+        pc[(long long) blockIdx.x * kRobC] = rc;
+        pc[(long long) blockIdx.x * kRobC + 1] = rz;
+        pc[(long long) blockIdx.x * kRobC + 2] = rg;
+    }
+}
+
+// ---- GetInformationMatrixFromPointClouds [upstream]: sum G^T G, G = [-skew(t) | I], t the target point ----
+constexpr int kInfoD = 21;
+
+__global__ void __launch_bounds__(256)
+k_info_sums(const double *__restrict__ d2s, const int *__restrict__ idxs, const double *__restrict__ ref_xyz, long long n,
+            double gate2, double *__restrict__ pd, long long *__restrict__ pc) {
+    double s[kInfoD];
+#pragma unroll
+    for (int k = 0; k < kInfoD; ++k) s[k] = 0;
+    long long cnt = 0;
+    for (long long i = (long long) blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long) gridDim.x * blockDim.x) {
+        const double d2 = d2s[i];
+        if (!(d2 >= 0.0 && d2 < gate2)) continue;
+        const long long j = idxs[i];
+        const double x = ref_xyz[3 * j], y = ref_xyz[3 * j + 1], z = ref_xyz[3 * j + 2];
+        const double G[18] = {0, z, -y, 1, 0, 0, -z, 0, x, 0, 1, 0, y, -x, 0, 0, 0, 1};
+        int t = 0;
+#pragma unroll
+        for (int a = 0; a < 6; ++a)
+#pragma unroll
+            for (int b = a; b < 6; ++b) s[t++] += (G[a] * G[b] + G[6 + a] * G[6 + b]) + G[12 + a] * G[12 + b];
+        ++cnt;
+    }
+    __shared__ double smd[4];
+    __shared__ long long smi[4];
+#pragma unroll
+    for (int k = 0; k < kInfoD; ++k) {
+        const double r = block_sum_256(s[k], smd);
+        if (threadIdx.x == 0) pd[(long long) blockIdx.x * kInfoD + k] = r;
+    }
+    const long long rc = block_sum_256_ll(cnt, smi);
+    if (threadIdx.x == 0) pc[blockIdx.x] = rc;
 }
 
 int need_plain_cloud(me_ctx *ctx, int slot, const char *who, bool need_index) {
@@ -631,7 +796,7 @@ int icp_lsq_sums(me_ctx *ctx, int qslot, int mode, double max_distance, me_icp_l
             hipLaunchKernelGGL(k_lsq_sums<2>, dim3(nb), dim3(256), 0, ctx->stream, q.sp.as<SPoint>() + sb, q.nn_d2.as<double>() + sb,
                                q.nn_idx.as<int>() + sb, r.xyz.as<double>(), q.cov.as<double>(), r.cov.as<double>(), n,
                                max_distance * max_distance, pd, pc);
-        hipLaunchKernelGGL(k_lsq_final, dim3(kLsqD + 1), dim3(256), 0, ctx->stream, pd, pc, nb, pd + (size_t) nb * kLsqD, pc + nb);
+        hipLaunchKernelGGL((k_lsq_final<kLsqD, 1>), dim3(kLsqD + 1), dim3(256), 0, ctx->stream, pd, pc, nb, pd + (size_t) nb * kLsqD, pc + nb);
     }
     double hd[kLsqD];
     long long hc = 0;
@@ -651,6 +816,139 @@ int icp_lsq_sums(me_ctx *ctx, int qslot, int mode, double max_distance, me_icp_l
     for (int a = 0; a < 6; ++a) out->JTr[a] = hd[21 + a];
     out->r2 = hd[27];
     out->sum_d2 = hd[28];
+    return ME_OK;
+}
+
+namespace {
+
+template <int MODE, int KERNEL>
+void launch_robust(me_ctx *ctx, Cloud &q, Cloud &r, long long n, int nb, double gate2, double k, double *pd, long long *pc) {
+    hipLaunchKernelGGL((k_lsq_sums_robust<MODE, KERNEL>), dim3(nb), dim3(256), 0, ctx->stream, q.sp.as<SPoint>(), q.nn_d2.as<double>(),
+                       q.nn_idx.as<int>(), r.xyz.as<double>(), MODE == 2 ? q.cov.as<double>() : (const double *) nullptr,
+                       MODE == 2 ? r.cov.as<double>() : r.normals.as<double>(), n, gate2, k, pd, pc);
+}
+
+template <int MODE>
+void launch_robust_kernel(me_ctx *ctx, int kernel, Cloud &q, Cloud &r, long long n, int nb, double gate2, double k, double *pd,
+                          long long *pc) {
+    switch (kernel) {
+    case ME_ROBUST_L1: launch_robust<MODE, ME_ROBUST_L1>(ctx, q, r, n, nb, gate2, k, pd, pc); break;
+    case ME_ROBUST_HUBER: launch_robust<MODE, ME_ROBUST_HUBER>(ctx, q, r, n, nb, gate2, k, pd, pc); break;
+    case ME_ROBUST_CAUCHY: launch_robust<MODE, ME_ROBUST_CAUCHY>(ctx, q, r, n, nb, gate2, k, pd, pc); break;
+    case ME_ROBUST_GM: launch_robust<MODE, ME_ROBUST_GM>(ctx, q, r, n, nb, gate2, k, pd, pc); break;
+    default: launch_robust<MODE, ME_ROBUST_TUKEY>(ctx, q, r, n, nb, gate2, k, pd, pc); break;
+    }
+}
+
+// the checks shared by the two single-GPU entry points below: ARG first, then STATE, as me_icp_lsq_sums orders them
+int need_nn_pair(me_ctx *ctx, int qslot, const char *who) {
+    if (ctx->shard_world != 1 || ctx->slab.axis >= 0 || ctx->cloud[qslot].slab.axis >= 0)
+        return ctx->fail(ME_ERR_ARG, std::string(who) + ": single GPU only (no slab or shard mode)");
+    if (ctx->cloud[qslot].nn_ref_slot < 0) return ctx->fail(ME_ERR_STATE, std::string(who) + ": call me_nn1(query_slot, ref_slot) first");
+    return ME_OK;
+}
+
+}  // namespace
+
+int icp_lsq_sums_robust(me_ctx *ctx, int qslot, int mode, double max_distance, int kernel, double k, me_icp_robust *out) {
+    if (qslot < 0 || qslot > 1 || !out || !(max_distance > 0) || (mode != ME_ICP_POINT_TO_PLANE && mode != ME_ICP_GENERALIZED))
+        return ctx->fail(ME_ERR_ARG, "me_icp_lsq_sums_robust: bad argument");
+    if (kernel < ME_ROBUST_L2 || kernel > ME_ROBUST_TUKEY) return ctx->fail(ME_ERR_ARG, "me_icp_lsq_sums_robust: unknown kernel");
+    if (kernel >= ME_ROBUST_HUBER && !(k > 0 && k - k == 0.0))
+        return ctx->fail(ME_ERR_ARG, "me_icp_lsq_sums_robust: the kernel's scale k must be finite and > 0");
+    ME_TRY(need_nn_pair(ctx, qslot, "me_icp_lsq_sums_robust"));
+    Cloud &q = ctx->cloud[qslot];
+    Cloud &r = ctx->cloud[q.nn_ref_slot];
+    if (mode == ME_ICP_POINT_TO_PLANE && !r.have_normals)
+        return ctx->fail(ME_ERR_STATE, "me_icp_lsq_sums_robust: point-to-plane needs normals on the target cloud "
+                                       "(me_set_normals / me_estimate_normals)");
+    if (mode == ME_ICP_GENERALIZED && (!r.have_cov || !q.have_cov))
+        return ctx->fail(ME_ERR_STATE, "me_icp_lsq_sums_robust: generalized ICP needs me_gicp_covariances on both clouds");
+    std::memset(out, 0, sizeof(*out));
+    if (kernel == ME_ROBUST_L2) {  // the plain step itself: k_lsq_sums, every weight 1
+        me_icp_lsq l;
+        ME_TRY(icp_lsq_sums(ctx, qslot, mode, max_distance, &l));
+        out->n_corr = l.n_corr;
+        out->n_source = l.n_source;
+        std::memcpy(out->JTJ, l.JTJ, sizeof(l.JTJ));
+        std::memcpy(out->JTr, l.JTr, sizeof(l.JTr));
+        out->r2 = l.r2;
+        out->sum_d2 = l.sum_d2;
+        out->sum_w = (double) (mode == ME_ICP_GENERALIZED ? 3 * l.n_corr : l.n_corr);
+        out->sum_wr2 = l.r2;
+        return ME_OK;
+    }
+    ME_CHECK(ctx, hipSetDevice(ctx->device));
+    const long long n = q.n;
+    const int nb = (int) std::max<long long>(1, std::min<long long>(1024, (n + 255) / 256));
+    const size_t bytes_d = (size_t) (nb + 1) * kRobD * 8;
+    ME_CHECK(ctx, ctx->red.ensure(bytes_d + (size_t) (nb + 1) * kRobC * 8));
+    double *pd = ctx->red.as<double>();
+    long long *pc = reinterpret_cast<long long *>(ctx->red.as<char>() + bytes_d);
+    {
+        TimerScope ts(ctx, "icp");
+        if (mode == ME_ICP_POINT_TO_PLANE) launch_robust_kernel<1>(ctx, kernel, q, r, n, nb, max_distance * max_distance, k, pd, pc);
+        else launch_robust_kernel<2>(ctx, kernel, q, r, n, nb, max_distance * max_distance, k, pd, pc);
+        hipLaunchKernelGGL((k_lsq_final<kRobD, kRobC>), dim3(kRobD + kRobC), dim3(256), 0, ctx->stream, pd, pc, nb, pd + (size_t) nb * kRobD,
+                           pc + (size_t) nb * kRobC);
+    }
+    double hd[kRobD];
+    long long hc[kRobC] = {0, 0, 0};
+    ME_TRY(copy_d2h(ctx, hd, pd + (size_t) nb * kRobD, sizeof(hd)));
+    ME_TRY(copy_d2h(ctx, hc, pc + (size_t) nb * kRobC, sizeof(hc)));
+    ME_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    ME_CHECK(ctx, hipGetLastError());
+    out->n_corr = hc[0];
+    out->n_source = q.n;
+    out->n_zero_weight = hc[1];
+    out->n_degenerate = hc[2];
+    int t = 0;
+    for (int a = 0; a < 6; ++a)
+        for (int b = a; b < 6; ++b) {
+            out->JTJ[6 * a + b] = hd[t];
+            out->JTJ[6 * b + a] = hd[t];
+            ++t;
+        }
+    for (int a = 0; a < 6; ++a) out->JTr[a] = hd[21 + a];
+    out->r2 = hd[27];
+    out->sum_d2 = hd[28];
+    out->sum_w = hd[29];
+    out->sum_wr2 = hd[30];
+    return ME_OK;
+}
+
+int icp_information(me_ctx *ctx, int qslot, double max_distance, double *info, long long *n_corr) {
+    if (qslot < 0 || qslot > 1 || !info || !n_corr || !(max_distance > 0)) return ctx->fail(ME_ERR_ARG, "me_icp_information: bad argument");
+    ME_TRY(need_nn_pair(ctx, qslot, "me_icp_information"));
+    Cloud &q = ctx->cloud[qslot];
+    Cloud &r = ctx->cloud[q.nn_ref_slot];
+    ME_CHECK(ctx, hipSetDevice(ctx->device));
+    const long long n = q.n;
+    const int nb = (int) std::max<long long>(1, std::min<long long>(1024, (n + 255) / 256));
+    const size_t bytes_d = (size_t) (nb + 1) * kInfoD * 8;
+    ME_CHECK(ctx, ctx->red.ensure(bytes_d + (size_t) (nb + 1) * 8));
+    double *pd = ctx->red.as<double>();
+    long long *pc = reinterpret_cast<long long *>(ctx->red.as<char>() + bytes_d);
+    {
+        TimerScope ts(ctx, "icp");
+        hipLaunchKernelGGL(k_info_sums, dim3(nb), dim3(256), 0, ctx->stream, q.nn_d2.as<double>(), q.nn_idx.as<int>(), r.xyz.as<double>(), n,
+                           max_distance * max_distance, pd, pc);
+        hipLaunchKernelGGL((k_lsq_final<kInfoD, 1>), dim3(kInfoD + 1), dim3(256), 0, ctx->stream, pd, pc, nb, pd + (size_t) nb * kInfoD, pc + nb);
+    }
+    double hd[kInfoD];
+    long long hc = 0;
+    ME_TRY(copy_d2h(ctx, hd, pd + (size_t) nb * kInfoD, sizeof(hd)));
+    ME_TRY(copy_d2h(ctx, &hc, pc + nb, 8));
+    ME_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    ME_CHECK(ctx, hipGetLastError());
+    int t = 0;
+    for (int a = 0; a < 6; ++a)
+        for (int b = a; b < 6; ++b) {
+            info[6 * a + b] = hd[t];
+            info[6 * b + a] = hd[t];
+            ++t;
+        }
+    *n_corr = hc;
     return ME_OK;
 }
 

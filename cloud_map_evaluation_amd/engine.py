@@ -549,11 +549,34 @@ class Engine:
         self._ck(self._L.me_icp_lsq_sums(self._ctx, query_slot, int(mode), float(max_distance), C.byref(out)))
         return out
 
-    def performICPRegistration(self, max_distance: float, method: int = 0, **criteria):
-        """map_eval.cpp:1366-1394: registration_methods 0 point-to-point, 1 point-to-plane, 2 generalized ICP (see icp.py)."""
+    def icp_lsq_sums_robust(self, query_slot: int, mode: int, max_distance: float, kernel, k: float = 1.0) -> _lib.IcpRobust:
+        """me_icp_lsq_sums_robust: the step of icp_lsq_sums under a robust loss (Open3D RobustKernel [upstream]).  kernel: an ME_ROBUST_*
+        id or one of "l2", "l1", "huber", "cauchy", "gm", "tukey"; k: the scale of Huber, Cauchy, GM and Tukey."""
+        if isinstance(kernel, str):
+            if kernel.lower() not in _lib.ROBUST_KERNELS:
+                raise ValueError(f"unknown robust kernel {kernel!r}")
+            kernel = _lib.ROBUST_KERNELS[kernel.lower()]
+        out = _lib.IcpRobust()
+        self._ck(self._L.me_icp_lsq_sums_robust(self._ctx, query_slot, int(mode), float(max_distance), int(kernel), float(k), C.byref(out)))
+        return out
+
+    def icp_information(self, query_slot: int, max_distance: float):
+        """me_icp_information: Open3D GetInformationMatrixFromPointClouds over the last nn1(query_slot, ...) -> ((6,6), n_corr)."""
+        info = np.zeros(36, np.float64)
+        n = C.c_int64(0)
+        self._ck(self._L.me_icp_information(self._ctx, query_slot, float(max_distance), _addr(info), C.byref(n)))
+        return info.reshape(6, 6), n.value
+
+    def performICPRegistration(self, max_distance: float, method: int = 0, kernel=None, kernel_scale=None, **criteria):
+        """map_eval.cpp:1366-1394: registration_methods 0 point-to-point, 1 point-to-plane, 2 generalized ICP (see icp.py).
+        kernel / kernel_scale: a robust loss for methods 1 and 2 (icp_lsq_sums_robust); point-to-point takes none, as upstream."""
         from . import icp
         if method == 0:
+            if kernel is not None:
+                raise ValueError("point-to-point ICP takes no robust kernel")
             return icp.icp_point_to_point(self, max_distance, **criteria)
+        if kernel is not None:
+            criteria = dict(criteria, kernel=kernel, kernel_scale=kernel_scale)
         if method == 1:
             return icp.icp_point_to_plane(self, max_distance, **criteria)
         if method == 2:

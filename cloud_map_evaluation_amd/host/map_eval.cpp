@@ -200,6 +200,47 @@ Param loadParametersFromYAML(const std::string &yaml_file_path) {
     if (!(param.global_edge_ratio > 0 && param.global_edge_ratio <= 1)) throw std::runtime_error("global_edge_ratio: must lie in (0, 1]");
     if (param.global_max_nn < 1 || param.global_max_nn > 40) throw std::runtime_error("global_max_nn: must lie in 1..40");
     if (param.global_normal_knn < 1 || param.global_normal_knn > 40) throw std::runtime_error("global_normal_knn: must lie in 1..40");
+    if (config.has("icp_robust_kernel")) {
+        const std::string k = config.as_string("icp_robust_kernel");
+        const char *names[6] = {"none", "l1", "huber", "cauchy", "gm", "tukey"};  // (ME_ROBUST_L2 .. ME_ROBUST_TUKEY)
+        int id = -1;
+        for (int i = 0; i < 6; ++i)
+            if (k == names[i]) id = i;
+        if (id < 0) throw std::runtime_error("icp_robust_kernel: expected none, l1, huber, cauchy, gm or tukey, got '" + k + "'");
+        param.icp_robust_kernel = id;
+    }
+    if (config.has("icp_robust_scale")) {
+        param.icp_robust_scale = config.as_double("icp_robust_scale");
+        if (!(param.icp_robust_scale > 0) || !std::isfinite(param.icp_robust_scale))
+            throw std::runtime_error("icp_robust_scale: must be finite and > 0");
+    } else if (param.icp_robust_kernel >= ME_ROBUST_HUBER) {
+        throw std::runtime_error("icp_robust_kernel: " + config.as_string("icp_robust_kernel") + " needs icp_robust_scale (no default is invented)");
+    }
+    {
+        const char *keys[3] = {"icp_multi_scale_voxels", "icp_multi_scale_distances", "icp_multi_scale_iterations"};
+        const int given = (int) config.has(keys[0]) + (int) config.has(keys[1]) + (int) config.has(keys[2]);
+        if (given != 0 && given != 3)
+            throw std::runtime_error("icp_multi_scale_voxels, icp_multi_scale_distances and icp_multi_scale_iterations: give all three or none");
+        if (given == 3) {
+            for (const auto &v : config.at(keys[0]).seq) param.icp_multi_scale_voxels.push_back(yaml_lite::Document::to_double(v, keys[0]));
+            for (const auto &v : config.at(keys[1]).seq) param.icp_multi_scale_distances.push_back(yaml_lite::Document::to_double(v, keys[1]));
+            for (const auto &v : config.at(keys[2]).seq) param.icp_multi_scale_iterations.push_back((int) yaml_lite::Document::to_double(v, keys[2]));
+            const size_t n = param.icp_multi_scale_voxels.size();
+            if (n == 0 || param.icp_multi_scale_distances.size() != n || param.icp_multi_scale_iterations.size() != n)
+                throw std::runtime_error("icp_multi_scale_*: three flow lists of the same, non-zero length are expected");
+            for (size_t l = 0; l < n; ++l)
+                if (!(param.icp_multi_scale_distances[l] > 0) || param.icp_multi_scale_iterations[l] < 0)
+                    throw std::runtime_error("icp_multi_scale_*: distances must be > 0 and iterations >= 0");
+        }
+    }
+    if (config.has("icp_information_matrix")) param.icp_information_matrix = config.as_bool("icp_information_matrix");
+    if (param.icp_robust_kernel != 0 || !param.icp_multi_scale_voxels.empty() || param.icp_information_matrix) {
+        const char *who = param.icp_robust_kernel != 0 ? "icp_robust_kernel" : !param.icp_multi_scale_voxels.empty() ? "icp_multi_scale_voxels"
+                                                                                                                      : "icp_information_matrix";
+        if (param.evaluate_using_initial_)
+            throw std::runtime_error(std::string(who) + ": needs the registration path (evaluate_using_initial: false): there is no ICP to run");
+        if (param.num_gpus > 1) throw std::runtime_error(std::string(who) + ": single GPU only (num_gpus must be 1)");
+    }
     if (config.has("global_outlier_nb_neighbors")) param.global_outlier_nb_neighbors = config.as_int("global_outlier_nb_neighbors");
     if (config.has("global_outlier_std_ratio")) param.global_outlier_std_ratio = config.as_double("global_outlier_std_ratio");
     if (param.global_outlier_nb_neighbors < 0 || param.global_outlier_nb_neighbors > 40)
@@ -775,13 +816,26 @@ int MapEval::performRegistration(bool metrics) {
     if (!identity && me_transform_cloud(ctx_, ME_SLOT_EST, trans.data()) != ME_OK) return fail(me_last_error(ctx_));
     me_icp_sums s;
     me_icp_lsq q;
-    auto evaluate = [&](double &fit, double &rmse) -> bool {
-        if (me_nn1(ctx_, ME_SLOT_EST, ME_SLOT_GT, nullptr, nullptr) != ME_OK) return false;
+    const int robust = method == 0 ? ME_ROBUST_L2 : param_.icp_robust_kernel;  // point-to-point takes no kernel (as upstream)
+    auto evaluate = [&](me_ctx *c, double max_d, double &fit, double &rmse) -> bool {
+        if (me_nn1(c, ME_SLOT_EST, ME_SLOT_GT, nullptr, nullptr) != ME_OK) return false;
         if (method == 0) {
-            if (me_icp_p2p_sums(ctx_, ME_SLOT_EST, param_.icp_max_distance_, &s) != ME_OK) return false;
+            if (me_icp_p2p_sums(c, ME_SLOT_EST, max_d, &s) != ME_OK) return false;
+        } else if (robust != ME_ROBUST_L2) {
+            // TransformationEstimationPointToPlane(kernel) / ForGeneralizedICP(epsilon, kernel) [Open3D, upstream]
+            me_icp_robust rq;
+            if (me_icp_lsq_sums_robust(c, ME_SLOT_EST, method == 1 ? ME_ICP_POINT_TO_PLANE : ME_ICP_GENERALIZED, max_d, robust,
+                                       param_.icp_robust_scale > 0 ? param_.icp_robust_scale : 1.0, &rq) != ME_OK)
+                return false;
+            for (int i = 0; i < 36; ++i) q.JTJ[i] = rq.JTJ[i];
+            for (int i = 0; i < 6; ++i) q.JTr[i] = rq.JTr[i];
+            q.n_corr = s.n_corr = rq.n_corr;
+            q.n_source = s.n_source = rq.n_source;
+            q.r2 = rq.r2;
+            q.sum_d2 = s.sum_d2 = rq.sum_d2;
         } else {
             // TransformationEstimationPointToPlane (:1373-1377) needs normals on the target, as in Open3D
-            if (me_icp_lsq_sums(ctx_, ME_SLOT_EST, method == 1 ? ME_ICP_POINT_TO_PLANE : ME_ICP_GENERALIZED, param_.icp_max_distance_, &q) != ME_OK)
+            if (me_icp_lsq_sums(c, ME_SLOT_EST, method == 1 ? ME_ICP_POINT_TO_PLANE : ME_ICP_GENERALIZED, max_d, &q) != ME_OK)
                 return false;
             s.n_corr = q.n_corr;
             s.n_source = q.n_source;
@@ -793,18 +847,56 @@ int MapEval::performRegistration(bool metrics) {
         return true;
     };
     double fit = 0, rmse = 0;
-    if (!evaluate(fit, rmse)) return fail(me_last_error(ctx_));
-    int it = 0;
-    for (it = 1; it <= 30; ++it) {
-        if (method == 0 ? s.n_corr < 3 : s.n_corr == 0) break;
-        double upd[16];
-        if (method == 0) kabsch_from_sums(s, upd);
-        else lsq_update(q, upd);
-        matmul4(upd, trans.data(), trans.data());
-        if (me_transform_cloud(ctx_, ME_SLOT_EST, upd) != ME_OK) return fail(me_last_error(ctx_));
-        const double pf = fit, pr = rmse;
-        if (!evaluate(fit, rmse)) return fail(me_last_error(ctx_));
-        if (std::fabs(pf - fit) < 1e-6 && std::fabs(pr - rmse) < 1e-6) break;
+    // the loop of RegistrationICP on context c; `total` is multiplied by every update
+    auto run_loop = [&](me_ctx *c, double max_d, int max_iteration, double *total) -> bool {
+        if (!evaluate(c, max_d, fit, rmse)) return fail(me_last_error(c)), false;
+        for (int it = 1; it <= max_iteration; ++it) {
+            if (method == 0 ? s.n_corr < 3 : s.n_corr == 0) break;
+            double upd[16];
+            if (method == 0) kabsch_from_sums(s, upd);
+            else lsq_update(q, upd);
+            matmul4(upd, total, total);
+            if (me_transform_cloud(c, ME_SLOT_EST, upd) != ME_OK) return fail(me_last_error(c)), false;
+            const double pf = fit, pr = rmse;
+            if (!evaluate(c, max_d, fit, rmse)) return fail(me_last_error(c)), false;
+            if (std::fabs(pf - fit) < 1e-6 && std::fabs(pr - rmse) < 1e-6) break;
+        }
+        return true;
+    };
+    if (param_.icp_multi_scale_voxels.empty()) {
+        if (!run_loop(ctx_, param_.icp_max_distance_, 30, trans.data())) return -1;
+    } else {
+        // icp_multi_scale_*: coarse to fine.  A level with a voxel > 0 runs on voxel down-samples of both resident clouds, as posed, in
+        // a private context (the copies carry no attributes: method 1 estimates the target copy's normals from 20 neighbours, method 2
+        // the covariances of both copies); its update then moves the resident map.  A level <= 0 runs on the resident clouds.
+        for (size_t l = 0; l < param_.icp_multi_scale_voxels.size(); ++l) {
+            const double v = param_.icp_multi_scale_voxels[l], max_d = param_.icp_multi_scale_distances[l];
+            const int iters = param_.icp_multi_scale_iterations[l];
+            if (!(v > 0)) {
+                if (!run_loop(ctx_, max_d, iters, trans.data())) return -1;
+                continue;
+            }
+            me_ctx *co = me_create(param_.gpu_device, 0);
+            if (!co) return fail(std::string("icp_multi_scale_voxels: ") + me_last_error(nullptr));
+            struct Destroy {
+                me_ctx *c;
+                ~Destroy() { me_destroy(c); }
+            } d{co};
+            int64_t n = 0;
+            if (me_voxel_downsample_into(ctx_, ME_SLOT_EST, co, ME_SLOT_EST, v, &n) != ME_OK ||
+                me_voxel_downsample_into(ctx_, ME_SLOT_GT, co, ME_SLOT_GT, v, &n) != ME_OK)
+                return fail(std::string("icp_multi_scale_voxels: ") + me_last_error(co));
+            if (method == 1 && me_estimate_normals(co, ME_SLOT_GT, 20, nullptr, nullptr, nullptr) != ME_OK)
+                return fail(std::string("icp_multi_scale_voxels: ") + me_last_error(co));
+            if (method == 2 && (me_gicp_covariances(co, ME_SLOT_EST, 1e-3, nullptr) != ME_OK ||
+                                me_gicp_covariances(co, ME_SLOT_GT, 1e-3, nullptr) != ME_OK))
+                return fail(std::string("icp_multi_scale_voxels: ") + me_last_error(co));
+            double level[16];
+            for (int i = 0; i < 16; ++i) level[i] = (i % 5 == 0) ? 1.0 : 0.0;
+            if (!run_loop(co, max_d, iters, level)) return -1;
+            matmul4(level, trans.data(), trans.data());
+            if (me_transform_cloud(ctx_, ME_SLOT_EST, level) != ME_OK) return fail(me_last_error(ctx_));
+        }
     }
     t3 = 0;  // no mesh stage
     t4 = tic_toc.toc();
@@ -825,9 +917,40 @@ int MapEval::performRegistration(bool metrics) {
     //  matrix, one space between columns, one row per line)
     file_result << std::fixed << std::setprecision(5) << "Aligned cloud: " << eigen_matrix4(trans.data(), 5) << std::endl;
     file_result << std::fixed << std::setprecision(5) << "Aligned results: " << fit << " " << s.n_corr << std::endl;
+    if (param_.icp_information_matrix && writeRegistrationInformation() != 0) return -1;
     if (metrics) calculateMetrics();
     t5 = tic_toc.toc();
     return last_error.empty() ? 0 : -1;
+}
+
+// registration_information.txt (icp_information_matrix: true; no reference counterpart): Open3D's GetInformationMatrixFromPointClouds
+// [upstream] of the final alignment over the pairs inside icp_max_distance (me_icp_information).  Six rows of the matrix (%.17g), then
+// "n_corr N", "eigenvalues e0 .. e5" ascending (the Jacobi decomposition of csrc/me_horn.hpp) and "ratio smallest/largest": a ratio
+// near zero names a direction of the pose that the pair does not constrain (a corridor, a single plane).
+int MapEval::writeRegistrationInformation() {
+    double info[36], a[36], ev[6], V[36];
+    int64_t n = 0;
+    if (me_nn1(ctx_, ME_SLOT_EST, ME_SLOT_GT, nullptr, nullptr) != ME_OK ||
+        me_icp_information(ctx_, ME_SLOT_EST, param_.icp_max_distance_, info, &n) != ME_OK)
+        return fail(std::string("icp_information_matrix: ") + me_last_error(ctx_));
+    for (int i = 0; i < 36; ++i) a[i] = info[i];
+    me::jacobi_sym(6, a, ev, V);
+    std::sort(ev, ev + 6);
+    const double ratio = ev[5] != 0.0 ? ev[0] / ev[5] : 0.0;
+    std::filesystem::create_directories(results_subfolder);
+    const std::string path = results_subfolder + "registration_information.txt";
+    FILE *f = std::fopen(path.c_str(), "w");
+    if (!f) return fail("cannot write " + path);
+    for (int r = 0; r < 6; ++r)
+        std::fprintf(f, "%.17g %.17g %.17g %.17g %.17g %.17g\n", info[6 * r], info[6 * r + 1], info[6 * r + 2], info[6 * r + 3],
+                     info[6 * r + 4], info[6 * r + 5]);
+    std::fprintf(f, "n_corr %lld\neigenvalues %.17g %.17g %.17g %.17g %.17g %.17g\nratio %.17g\n", (long long) n, ev[0], ev[1], ev[2], ev[3],
+                 ev[4], ev[5], ratio);
+    if (std::fclose(f) != 0) return fail("writing " + path + " failed");
+    if (param_.dist_rank == 0)
+        std::cout << "INFO: Information matrix eigenvalue ratio (smallest / largest): " << ratio << " over " << n << " correspondences"
+                  << std::endl;
+    return 0;
 }
 
 void MapEval::calculateMetrics() {

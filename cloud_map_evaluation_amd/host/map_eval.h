@@ -79,6 +79,14 @@ struct Param {
     int global_outlier_nb_neighbors = 0;   // `global_outlier_nb_neighbors:` > 0: statistical outlier removal (this k) on full-resolution
                                            // copies of both clouds before global_voxel_size (me_statistical_outlier)
     double global_outlier_std_ratio = 2.0; // `global_outlier_std_ratio:`
+    // robust / multi-scale ICP and the information matrix (no reference counterpart; registration path, single GPU; DESIGN.md section
+    // 4.17): Open3D's robust loss on the point-to-plane / generalized step, a coarse-to-fine schedule, GetInformationMatrixFromPointClouds
+    int icp_robust_kernel = 0;             // `icp_robust_kernel:` none | l1 | huber | cauchy | gm | tukey (an ME_ROBUST_* id; 0 = none)
+    double icp_robust_scale = 0.0;         // `icp_robust_scale:` k of huber / cauchy / gm / tukey (required for them: no default)
+    std::vector<double> icp_multi_scale_voxels;     // `icp_multi_scale_voxels: [v0, v1, ..]` (<= 0: the resident clouds themselves)
+    std::vector<double> icp_multi_scale_distances;  // `icp_multi_scale_distances: [..]` the level's correspondence distance
+    std::vector<int> icp_multi_scale_iterations;    // `icp_multi_scale_iterations: [..]` the level's iteration cap
+    bool icp_information_matrix = false;   // `icp_information_matrix:` -> map_results/registration_information.txt
     // outlier removal in front of the evaluation (remove_outliers: statistical | radius; no reference counterpart): the map, and with
     // outlier_filter_gt the ground truth, filtered in place on the device after downsample_size -> map_results/outlier_removal.txt
     std::string remove_outliers = "none";  // `remove_outliers:` none | statistical | radius | cluster | plane (the largest plane: plane_* keys)
@@ -191,6 +199,7 @@ public:
     int computeM3C2();                                      // evaluate_m3c2: normals and me_m3c2 on both clouds, the map moved (no reference counterpart)
     void saveM3C2();                                        // its result line and m3c2.txt
     void saveErrorDistribution();                           // its three result lines and error_distribution.txt
+    int writeRegistrationInformation();                     // registration_information.txt (icp_information_matrix; no reference counterpart)
     int globalRegistration(double T_c[16]);                 // global_registration.txt (global_registration; no reference counterpart)                                   // noise_sweep.txt (noise_sweep; no reference counterpart)
 
     // multi-GPU (map_eval_dist.cpp): the communicator of this rank; forced = take the distributed path with one rank too

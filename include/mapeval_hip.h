@@ -920,6 +920,39 @@ int me_gicp_covariances(me_ctx *ctx, int slot, double epsilon, double *cov);
 int me_get_covariances(me_ctx *ctx, int slot, double *cov); /* the current N x 9 covariances (after any transform) */
 int me_icp_lsq_sums(me_ctx *ctx, int query_slot, int mode, double max_distance, me_icp_lsq *out);
 
+/* The same step under a robust loss: Open3D's TransformationEstimationPointToPlane(kernel) and
+ * TransformationEstimationForGeneralizedICP(epsilon, kernel) [upstream], the refinement that performICPRegistration
+ * (map_eval.cpp:1366-1394) asks for when the map carries ghost points.  The weights restate RobustKernel.cpp [upstream]:
+ *   L1 1 / |r|      Huber k / max(|r|, k)      Cauchy 1 / (1 + (r / k)^2)      GM k / (k + r^2)^2
+ *   Tukey (1 - min(1, |r| / k)^2)^2
+ * Each row contributes (J[a] w) J[b] and (J[a] w) r, as utility::ComputeJTJandJTr weights them; r2 stays the unweighted
+ * sum r^2.  Point-to-plane has one row per correspondence (J, r of me_icp_lsq_sums).  Generalized ICP has three, the
+ * rows of W [-skew(vs) | I] and of W d with W = (Ct + Cs)^(-1/2) from a Jacobi decomposition,
+ * each with its own weight.  sum_w and sum_wr2 are the sums of w and of w r^2 over the rows; n_zero_weight counts the
+ * rows with w == 0 (L1 at r == 0 is one: 0 here where upstream divides by zero); n_degenerate counts the generalized
+ * correspondences whose Ct + Cs has an eigenvalue <= 0 or not finite: they stay in n_corr and sum_d2 only.
+ * ME_ROBUST_L2 runs me_icp_lsq_sums itself (sum_w = rows, sum_wr2 = r2).  k is read by Huber, Cauchy, GM and Tukey and
+ * must be finite and > 0 for them.  Point-to-point takes no kernel (as upstream).  Single GPU: slab or shard mode is ME_ERR_ARG for
+ * every kernel id, ME_ROBUST_L2 included, although me_icp_lsq_sums itself serves a shard. */
+#define ME_ROBUST_L2 0
+#define ME_ROBUST_L1 1
+#define ME_ROBUST_HUBER 2
+#define ME_ROBUST_CAUCHY 3
+#define ME_ROBUST_GM 4
+#define ME_ROBUST_TUKEY 5
+typedef struct me_icp_robust {
+    int64_t n_corr, n_source, n_zero_weight, n_degenerate;
+    double JTJ[36], JTr[6], r2, sum_d2, sum_w, sum_wr2;
+} me_icp_robust;
+int me_icp_lsq_sums_robust(me_ctx *ctx, int query_slot, int mode, double max_distance, int kernel, double k,
+                           me_icp_robust *out);
+
+/* Open3D GetInformationMatrixFromPointClouds(source, target, max_distance, T) [upstream] for the alignment that
+ * performICPRegistration (map_eval.cpp:1366-1394) ends with: info = sum G^T G over the correspondences of the last
+ * me_nn1(query_slot, ref) with d2 < max_distance^2, G = [-skew(t) | I] with t the TARGET point (6x6 row-major, rotation
+ * first).  An eigenvalue near zero is a direction of the pose that the pair does not constrain.  Single GPU. */
+int me_icp_information(me_ctx *ctx, int query_slot, double max_distance, double info[36], int64_t *n_corr);
+
 /* renderDistanceOnPointCloud (map_eval.cpp:586-607; raw_rendered_dis_map.pcd / inlier_rendered_dis_map.pcd, :485-495) for
  * the queries of the last me_nn1(query_slot, ...): rgb[N][3] in the caller's cloud order = ColorMapJet(min(d2, dis) / dis)
  * (the SQUARED distance against the unsquared `dis`, as the reference does; it repeats a serial KD-tree pass for it,
