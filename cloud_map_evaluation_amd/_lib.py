@@ -36,6 +36,7 @@ SYMBOLS = [
     "me_cluster_dbscan", "me_cluster_sizes", "me_cluster_keep",
     "me_local_geometry", "me_local_geometry_fetch", "me_radius_normals", "me_nn_surface_error", "me_nn_surface_fetch",
     "me_m3c2", "me_m3c2_fetch",
+    "me_mesh_upload", "me_mesh_clear", "me_mesh_info", "me_mesh_distance", "me_mesh_distance_fetch", "me_mesh_sample",
     "me_knn_search", "me_hybrid_search", "me_radius_search", "me_search_sort_tile",
     "me_segment_planes", "me_plane_fetch", "me_plane_keep",
     "me_group_order_stats", "me_mom_select_axes", "me_mom", "me_mom_fetch",
@@ -382,6 +383,42 @@ class M3c2Out(C.Structure):
     ]
 
 
+ME_MESH_MAX_THRESHOLDS = 8
+# region codes of me_mesh_distance_fetch
+MESH_FACE, MESH_EDGE_AB, MESH_EDGE_BC, MESH_EDGE_CA, MESH_VERTEX_A, MESH_VERTEX_B, MESH_VERTEX_C = range(7)
+
+
+class MeshParams(C.Structure):
+    _fields_ = [("max_distance", C.c_double), ("n_thresholds", C.c_int64), ("thresholds", C.c_double * ME_MESH_MAX_THRESHOLDS)]
+
+
+class MeshOut(C.Structure):
+    _fields_ = [
+        ("n_query", C.c_int64),
+        ("n_matched", C.c_int64),
+        ("n_face", C.c_int64),
+        ("sum_d", C.c_double),
+        ("sum_d2", C.c_double),
+        ("max_d", C.c_double),
+        ("argmax", C.c_int64),
+        ("n_within", C.c_int64 * ME_MESH_MAX_THRESHOLDS),
+        ("sum_signed", C.c_double),
+        ("sum_abs_signed", C.c_double),
+    ]
+
+
+class MeshInfoOut(C.Structure):
+    _fields_ = [
+        ("n_vertices", C.c_int64),
+        ("n_triangles", C.c_int64),
+        ("n_degenerate", C.c_int64),
+        ("depth", C.c_int64),
+        ("bbox_lo", C.c_double * 3),
+        ("bbox_hi", C.c_double * 3),
+        ("area", C.c_double),
+    ]
+
+
 class SurfaceParams(C.Structure):
     _fields_ = [
         ("gate", C.c_double),
@@ -502,6 +539,14 @@ def load():
     L.me_m3c2.argtypes = [vp, C.c_int, C.POINTER(M3c2Params), vp, C.POINTER(M3c2Out)]
     L.me_m3c2_fetch.argtypes = [vp, C.c_int, dp, dp, dp, dp, ip, ip, vp]
     for f in ("me_m3c2", "me_m3c2_fetch"):
+        getattr(L, f).restype = C.c_int
+    L.me_mesh_upload.argtypes = [vp, dp, C.c_int64, ip, C.c_int64, dp]
+    L.me_mesh_clear.argtypes = [vp]
+    L.me_mesh_info.argtypes = [vp, C.POINTER(MeshInfoOut)]
+    L.me_mesh_distance.argtypes = [vp, C.c_int, C.POINTER(MeshParams), C.POINTER(MeshOut)]
+    L.me_mesh_distance_fetch.argtypes = [vp, C.c_int, dp, ip, vp, dp, dp]
+    L.me_mesh_sample.argtypes = [vp, C.c_int, C.c_int64, C.c_uint64]
+    for f in ("me_mesh_upload", "me_mesh_clear", "me_mesh_info", "me_mesh_distance", "me_mesh_distance_fetch", "me_mesh_sample"):
         getattr(L, f).restype = C.c_int
     L.me_knn_search.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, ip, dp]
     L.me_hybrid_search.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_int, vp, ip, ip, dp]

@@ -186,6 +186,7 @@ me_ctx *me_twin(me_ctx *ctx) {
     t->is_twin = true;
     t->cloud.p[0] = ctx->cloud.p[0];
     t->cloud.p[1] = ctx->cloud.p[1];
+    t->mesh = ctx->mesh;
     t->shard_rank = ctx->shard_rank;
     t->shard_world = ctx->shard_world;
     t->borrow_device_input = ctx->borrow_device_input;
@@ -388,6 +389,36 @@ int me_m3c2_fetch(me_ctx *ctx, int query_slot, double *dist, double *lod, double
                   uint8_t *flags) {
     if (!ctx) return ME_ERR_ARG;
     return me::m3c2_fetch(ctx, query_slot, dist, lod, var_own, var_other, n_own, n_other, flags);
+}
+
+int me_mesh_upload(me_ctx *ctx, const double *vertices, int64_t n_vertices, const int32_t *triangles, int64_t n_triangles, const double *T) {
+    if (!ctx) return ME_ERR_ARG;
+    return me::mesh_upload(ctx, vertices, n_vertices, triangles, n_triangles, T);
+}
+
+int me_mesh_clear(me_ctx *ctx) {
+    if (!ctx) return ME_ERR_ARG;
+    return me::mesh_clear(ctx);
+}
+
+int me_mesh_info(me_ctx *ctx, me_mesh_info_out *out) {
+    if (!ctx) return ME_ERR_ARG;
+    return me::mesh_info(ctx, out);
+}
+
+int me_mesh_distance(me_ctx *ctx, int query_slot, const me_mesh_params *p, me_mesh_out *out) {
+    if (!ctx) return ME_ERR_ARG;
+    return me::mesh_distance(ctx, query_slot, p, out);
+}
+
+int me_mesh_distance_fetch(me_ctx *ctx, int query_slot, double *d2, int32_t *tri, uint8_t *region, double *closest, double *signed_d) {
+    if (!ctx) return ME_ERR_ARG;
+    return me::mesh_distance_fetch(ctx, query_slot, d2, tri, region, closest, signed_d);
+}
+
+int me_mesh_sample(me_ctx *ctx, int dst_slot, int64_t n_points, uint64_t seed) {
+    if (!ctx) return ME_ERR_ARG;
+    return me::mesh_sample(ctx, dst_slot, n_points, seed);
 }
 
 int me_knn_search(me_ctx *ctx, int query_slot, int ref_slot, int k, const uint8_t *query_mask, int32_t *idx, double *d2) {

@@ -653,6 +653,7 @@ int cloud_upload(me_ctx *ctx, int slot, const double *src, bool src_on_device, l
         e.plane_valid = false;
         e.lg_have = false;
         e.m3c2_have = false;
+        e.mesh_have = false;
         ctx->cloud[1 - slot].nn_ref_slot = -1;
         ctx->cloud[1 - slot].m3c2_have = false;
         return ME_OK;
@@ -815,6 +816,7 @@ void cloud_reset_replaced(me_ctx *ctx, int slot, long long n, double cell_size_r
     D.plane_valid = false;
     D.lg_have = false;
     D.m3c2_have = false;
+    D.mesh_have = false;
     ctx->cloud[1 - slot].m3c2_have = false;
     D.slab = ctx->slab;
     D.n_unres = 0;
@@ -987,6 +989,7 @@ int cloud_build_index(me_ctx *ctx, int slot, double cell_size) {
     c.mme_have = false;  // (the sorted order changes)
     c.lg_have = false;
     c.m3c2_have = false;
+    c.mesh_have = false;
 #ifdef ME_AB
     c.mme_feat_valid = false;
 #endif

@@ -256,6 +256,29 @@ struct Cloud {
     DevBuf m3_cnt, m3_mom, m3_res, m3_flags;
     bool m3c2_have = false;
     unsigned long long mom_lg_serial = 0, mom_plane_serial = 0;
+    // last me_mesh_distance with this cloud as the query, SORTED order (me_mesh.hip): d2 double[n], caller's triangle index int32[n],
+    // region byte, closest point double[3][n], signed distance double[n] (NaN off the face region); dropped with the sorted order
+    // (cloud_build_index), with the points, and with the mesh (me_mesh_upload, me_mesh_clear)
+    DevBuf mesh_d2, mesh_tri, mesh_reg, mesh_cp, mesh_sd;
+    bool mesh_have = false;
+};
+
+// The resident triangle mesh (me_mesh.hip): one per primary context, beside the two clouds and untouched by what happens to them.
+constexpr int kMeshMaxLevels = 12;        // 8^11 leaves of 8 triangles: more than the 2^31 triangles an upload accepts
+constexpr double kMeshDeltaUlps = 32.0;   // the closest point of a triangle is evaluated to within this many 2^-53 |coordinate|max
+struct Mesh {
+    bool have = false;
+    long long nv = 0, nt = 0, n_deg = 0;
+    double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};  // bounding box of the referenced vertices
+    double area = 0, max_abs = 0;                 // total area (= cum[nt - 1]); largest |coordinate| of a referenced vertex
+    int n_levels = 0;                             // level 0 = leaves (8 consecutive sorted triangles) ... n_levels - 1 = the root
+    int lv_off[kMeshMaxLevels] = {0}, lv_cnt[kMeshMaxLevels] = {0};
+    DevBuf tri_in;  // double[nt][9] corner coordinates, the CALLER's triangle order (the sampler's)
+    DevBuf tri_s;   // the same sorted by the Morton code of the centroid
+    DevBuf orig;    // uint32[nt] caller index of every sorted triangle, bit 31 = degenerate
+    DevBuf cum;     // double[nt] cumulative area, caller's order
+    DevBuf boxes;   // double[nodes][6] of all levels
+    DevBuf lv;      // int2[kMeshMaxLevels] (offset, count) per level
 };
 
 struct TimerRec {
@@ -277,6 +300,8 @@ struct me_ctx {
         me::Cloud &operator[](int i) const { return *p[i]; }
     } cloud;
     me_ctx *twin = nullptr;  // owned by the primary context
+    me::Mesh own_mesh;       // the resident mesh lives in the primary context; a twin's `mesh` points at it
+    me::Mesh *mesh = &own_mesh;
     // called by cloud_build_index right after its radix sort has been QUEUED on the context's stream (me_run_suite_from's second lane
     // uses it to let the main lane order its MME behind the sort: me_suite.hip)
     void (*sort_hook)(void *arg, hipStream_t stream) = nullptr;
@@ -544,6 +569,14 @@ int nn_surface_fetch(me_ctx *ctx, int qslot, double *plane_d_host, double *cos_n
 int m3c2(me_ctx *ctx, int qslot, const me_m3c2_params *p, const uint8_t *core_mask_host, me_m3c2_out *out);
 int m3c2_fetch(me_ctx *ctx, int qslot, double *dist_host, double *lod_host, double *var_own_host, double *var_other_host, int32_t *n_own_host,
                int32_t *n_other_host, uint8_t *flags_host);
+// ---- me_mesh.hip ----
+int mesh_upload(me_ctx *ctx, const double *vertices_host, long long n_vertices, const int32_t *triangles_host, long long n_triangles, const double *T);
+int mesh_clear(me_ctx *ctx);
+int mesh_info(me_ctx *ctx, me_mesh_info_out *out);
+int mesh_distance(me_ctx *ctx, int qslot, const me_mesh_params *p, me_mesh_out *out);
+int mesh_distance_fetch(me_ctx *ctx, int qslot, double *d2_host, int32_t *tri_host, uint8_t *region_host, double *closest_host,
+                        double *signed_host);
+int mesh_sample(me_ctx *ctx, int dst_slot, long long n_points, unsigned long long seed);
 // ---- me_search.hip ----
 constexpr int kSearchSortTile = 512;  // entries of a radius row that one wave sorts in LDS; longer rows are sorted in global memory
 int knn_search(me_ctx *ctx, int qslot, int rslot, int k, const uint8_t *mask_host, int32_t *idx_host, double *d2_host);

@@ -916,6 +916,89 @@ class Engine:
         d["significant"] = (fl & 2) != 0
         return d
 
+    # ---- cloud-to-mesh distance against a resident triangle mesh, and its area-uniform sample (me_mesh.hip) ----
+    def mesh_upload(self, vertices, triangles, T=None):
+        """me_mesh_upload: vertices (V,3) float64, triangles (F,3) int32 indices into them, T an optional 4x4 applied as upload() applies
+        it.  The mesh stays resident beside the two clouds until the next mesh_upload or mesh_clear."""
+        v = np.ascontiguousarray(vertices, dtype=np.float64)
+        t = np.ascontiguousarray(triangles, dtype=np.int32)
+        if v.ndim != 2 or v.shape[1] != 3 or t.ndim != 2 or t.shape[1] != 3:
+            raise ValueError("expected (V,3) vertices and (F,3) triangles")
+        Tm = None if T is None else np.ascontiguousarray(T, dtype=np.float64).reshape(16)
+        self._ck(self._L.me_mesh_upload(self._ctx, _addr(v), int(v.shape[0]), _addr(t), int(t.shape[0]), _addr(Tm)))
+
+    def mesh_clear(self):
+        self._ck(self._L.me_mesh_clear(self._ctx))
+
+    def mesh_info(self) -> dict:
+        """me_mesh_info: vertices, triangles, degenerate, depth (tree levels), bbox_lo / bbox_hi of the referenced vertices, area."""
+        o = _lib.MeshInfoOut()
+        self._ck(self._L.me_mesh_info(self._ctx, C.byref(o)))
+        return {"vertices": int(o.n_vertices), "triangles": int(o.n_triangles), "degenerate": int(o.n_degenerate), "depth": int(o.depth),
+                "bbox_lo": np.array(list(o.bbox_lo), np.float64), "bbox_hi": np.array(list(o.bbox_hi), np.float64), "area": o.area}
+
+    def mesh_distance(self, query_slot: int, max_distance: float = math.inf, thresholds=(), fetch: bool = False):
+        """me_mesh_distance: the exact distance from every point of query_slot to the resident mesh.  A point is matched iff
+        d2 <= max_distance^2 (inf: every point).  Returns the totals (n_query, n_matched, n_face, sum_d, sum_d2, sum_signed,
+        sum_abs_signed) with mean, rmse, max, worst_index, n_within per threshold, face_share and, over the matched points whose closest
+        point lies inside a face, signed_mean and signed_mean_abs (the sign is not defined at edges and vertices); zeros without a
+        matched point.  With fetch=True also the per-point dict of mesh_distance_fetch."""
+        ths = [float(x) for x in thresholds]
+        if len(ths) > _lib.ME_MESH_MAX_THRESHOLDS:
+            raise MapEvalError("[-1] mesh_distance: at most 8 thresholds")
+        p = _lib.MeshParams()
+        p.max_distance, p.n_thresholds = float(max_distance), len(ths)
+        for k, x in enumerate(ths):
+            p.thresholds[k] = x
+        o = _lib.MeshOut()
+        self._ck(self._L.me_mesh_distance(self._ctx, int(query_slot), C.byref(p), C.byref(o)))
+        nm, nf = int(o.n_matched), int(o.n_face)
+        res = {"n_query": int(o.n_query), "n_matched": nm, "n_face": nf, "sum_d": o.sum_d, "sum_d2": o.sum_d2, "sum_signed": o.sum_signed,
+               "sum_abs_signed": o.sum_abs_signed, "mean": o.sum_d / nm if nm > 0 else 0.0, "rmse": math.sqrt(o.sum_d2 / nm) if nm > 0 else 0.0,
+               "max": o.max_d, "worst_index": int(o.argmax), "thresholds": np.array(ths, np.float64),
+               "n_within": np.array(list(o.n_within)[:len(ths)], np.int64), "face_share": nf / nm if nm > 0 else 0.0,
+               "signed_mean": o.sum_signed / nf if nf > 0 else 0.0, "signed_mean_abs": o.sum_abs_signed / nf if nf > 0 else 0.0}
+        return (res, self.mesh_distance_fetch(query_slot)) if fetch else res
+
+    def mesh_distance_fetch(self, query_slot: int) -> dict:
+        """me_mesh_distance_fetch -> dict of the slot's last mesh_distance in cloud order: d2 (float64), tri (int32, the caller's triangle
+        index), region (uint8: 0 face, 1-3 edges AB BC CA, 4-6 vertices A B C), closest (N,3), signed_d (NaN outside the face region)."""
+        n = self.size(query_slot)
+        d = {"d2": np.empty(n, np.float64), "tri": np.empty(n, np.int32), "region": np.empty(n, np.uint8),
+             "closest": np.empty((n, 3), np.float64), "signed_d": np.empty(n, np.float64)}
+        self._ck(self._L.me_mesh_distance_fetch(self._ctx, int(query_slot), _addr(d["d2"]), _addr(d["tri"]), _addr(d["region"]),
+                                                _addr(d["closest"]), _addr(d["signed_d"])))
+        return d
+
+    def mesh_sample(self, dst_slot: int, n_points: int, seed: int = 0) -> int:
+        """me_mesh_sample: n_points area-uniform, seeded samples of the resident mesh become the cloud of dst_slot."""
+        self._ck(self._L.me_mesh_sample(self._ctx, int(dst_slot), int(n_points), int(seed) & ((1 << 64) - 1)))
+        self._held.pop(dst_slot, None)
+        return self.size(dst_slot)
+
+    def mesh_report(self, thresholds, quantiles=(0.5, 0.9, 0.95, 0.99), sample_points: int = 0, seed: int = 0,
+                    max_distance: float = math.inf) -> dict:
+        """The cloud-to-mesh figures of slot 0 (mesh_distance) plus prob / rank / quantile_d: exact nearest-rank quantiles of d over the
+        matched points (rank_select on the fetched values).  With sample_points > 0 the mesh is then sampled into slot 1, nn1 runs both
+        ways and "sampled" holds error_report(thresholds, quantiles): completeness (recall) and F-score per threshold."""
+        rep, pts = self.mesh_distance(ME_SLOT_EST, max_distance, thresholds, fetch=True)
+        d = np.sqrt(pts["d2"])
+        nm = rep["n_matched"]
+        probs = [float(x) for x in quantiles]
+        ranks = [min(nm - 1, max(0, int(math.ceil(pr * float(nm))) - 1)) if nm > 0 else -1 for pr in probs]
+        rep["prob"] = np.array(probs, np.float64)
+        rep["rank"] = np.array(ranks, np.int64)
+        if probs and nm > 0:
+            rep["quantile_d"] = self.rank_select(d, ranks, use=pts["d2"] <= float(max_distance) * float(max_distance))["value"]
+        else:
+            rep["quantile_d"] = np.zeros(len(probs), np.float64)
+        if sample_points > 0:
+            self.mesh_sample(ME_SLOT_GT, sample_points, seed)
+            self.nn1(ME_SLOT_EST, ME_SLOT_GT, fetch=False)
+            self.nn1(ME_SLOT_GT, ME_SLOT_EST, fetch=False)
+            rep["sampled"] = self.error_report(thresholds, quantiles)
+        return rep
+
     # ---- neighbour lists between the resident clouds (me_search.hip) ----
     def _query_mask(self, query_slot: int, mask):
         if mask is None:

@@ -15,6 +15,8 @@
 #include <sstream>
 
 #include "../csrc/me_horn.hpp"
+#include <cerrno>
+
 #include "pcd_io.hpp"
 #include "yaml_lite.hpp"
 
@@ -415,6 +417,42 @@ Param loadParametersFromYAML(const std::string &yaml_file_path) {
         if (param.evaluate_noised_gt_) throw std::runtime_error("evaluate_m3c2: not with evaluate_noised_gt");
         if (param.num_gpus > 1) throw std::runtime_error("evaluate_m3c2: single GPU only (num_gpus must be 1)");
     }
+    // cloud-to-mesh distance (the role of the reference's mesh branch, with a supplied mesh)
+    if (config.has("evaluate_mesh_distance")) param.evaluate_mesh_distance = config.as_bool("evaluate_mesh_distance");
+    if (config.has("gt_mesh_path")) param.gt_mesh_path = config.as_string("gt_mesh_path");
+    const bool mesh_not_a_list = config.has("mesh_thresholds") && (!config.at("mesh_thresholds").scalar.empty() || !config.at("mesh_thresholds").rows.empty());
+    if (config.has("mesh_thresholds")) {
+        for (const auto &v : config.at("mesh_thresholds").seq) param.mesh_thresholds.push_back(yaml_lite::Document::to_double(v, "mesh_thresholds"));
+    } else {
+        param.mesh_thresholds.assign(param.trunc_dist_.begin(), param.trunc_dist_.end());
+    }
+    if (config.has("mesh_max_distance")) param.mesh_max_distance = config.as_double("mesh_max_distance");
+    if (!(param.mesh_max_distance > 0)) param.mesh_max_distance = INFINITY;
+    // whole non-negative numbers, read as integers (a seed uses all 64 bits; as_double would round it above 2^53)
+    auto as_u64 = [&](const char *key, uint64_t &out) {
+        const std::string v = config.as_string(key);
+        char *end = nullptr;
+        errno = 0;
+        const unsigned long long x = std::strtoull(v.c_str(), &end, 10);
+        if (v.empty() || v.find_first_not_of("0123456789") != std::string::npos || end != v.c_str() + v.size() || errno == ERANGE)
+            throw std::runtime_error(std::string(key) + ": must be a whole number >= 0 (got '" + v + "')");
+        out = (uint64_t) x;
+    };
+    if (config.has("mesh_sample_points")) {
+        uint64_t n = 0;
+        as_u64("mesh_sample_points", n);
+        if (n >= (1ull << 31)) throw std::runtime_error("mesh_sample_points: must lie in 0 .. 2^31 - 1");
+        param.mesh_sample_points = (int64_t) n;
+    }
+    if (config.has("mesh_seed")) as_u64("mesh_seed", param.mesh_seed);
+    if (param.evaluate_mesh_distance) {
+        if (mesh_not_a_list) throw std::runtime_error("mesh_thresholds: must be a list [a, b, ...]");
+        if (param.gt_mesh_path.empty()) throw std::runtime_error("gt_mesh_path: required with evaluate_mesh_distance");
+        if (param.mesh_thresholds.size() > ME_MESH_MAX_THRESHOLDS) throw std::runtime_error("mesh_thresholds: at most 8 values");
+        for (const double t : param.mesh_thresholds)
+            if (!(t >= 0.0) || !std::isfinite(t)) throw std::runtime_error("mesh_thresholds: every value must be finite and >= 0");
+        if (param.num_gpus > 1) throw std::runtime_error("evaluate_mesh_distance: single GPU only (num_gpus must be 1)");
+    }
     return param;
 }
 
@@ -475,7 +513,19 @@ std::string paramToJson(const Param &p) {
     o << "], \"surface_gated\": " << b(p.surface_gated) << ", \"evaluate_m3c2\": " << b(p.evaluate_m3c2)
       << ", \"m3c2_normal_radius\": " << p.m3c2_normal_radius << ", \"m3c2_projection_radius\": " << p.m3c2_projection_radius
       << ", \"m3c2_max_depth\": " << p.m3c2_max_depth << ", \"m3c2_min_points\": " << p.m3c2_min_points
-      << ", \"m3c2_reg_error\": " << p.m3c2_reg_error << ", \"m3c2_core_every\": " << p.m3c2_core_every << "}";
+      << ", \"m3c2_reg_error\": " << p.m3c2_reg_error << ", \"m3c2_core_every\": " << p.m3c2_core_every
+      << ", \"evaluate_mesh_distance\": " << b(p.evaluate_mesh_distance) << ", \"gt_mesh_path\": \"";
+    for (const char c : p.gt_mesh_path) {  // (a path may hold a quote or a backslash)
+        if (c == '"' || c == '\\') o << '\\' << c;
+        else if ((unsigned char) c < 0x20) o << "\\u00" << "0123456789abcdef"[(c >> 4) & 15] << "0123456789abcdef"[c & 15];
+        else o << c;
+    }
+    o << "\", \"mesh_thresholds\": [";
+    for (size_t i = 0; i < p.mesh_thresholds.size(); ++i) o << (i ? ", " : "") << p.mesh_thresholds[i];
+    o << "], \"mesh_max_distance\": ";
+    if (std::isinf(p.mesh_max_distance)) o << "Infinity";  // (what Python's json reads as inf)
+    else o << p.mesh_max_distance;
+    o << ", \"mesh_sample_points\": " << p.mesh_sample_points << ", \"mesh_seed\": " << p.mesh_seed << "}";
     return o.str();
 }
 
@@ -565,7 +615,9 @@ int MapEval::process() {
     const bool m3c2 = param_.evaluate_m3c2;  // (on resident clouds, the map moved by initial_matrix for it alone)
     if (m3c2 && (comm_ || noised || !param_.evaluate_using_initial_))
         return fail("evaluate_m3c2: single GPU only, with evaluate_using_initial and not with evaluate_noised_gt");
-    if (one_call && !noised && !filter && !mpv && !planes && !mom && !surf && !m3c2 && !(param_.downsample_size > 0)) {
+    const bool mesh = param_.evaluate_mesh_distance;  // (on resident clouds, the map moved by initial_matrix for it alone)
+    if (mesh && comm_) return fail("evaluate_mesh_distance: single GPU only (num_gpus must be 1)");
+    if (one_call && !noised && !filter && !mpv && !planes && !mom && !surf && !m3c2 && !mesh && !(param_.downsample_size > 0)) {
         file_result << std::fixed << std::setprecision(15) << "Estimated-Ground Truth point count: " << map_3d_->size() << " / "
                     << gt_3d_->size() << std::endl;
         if (param_.enable_debug)
@@ -608,12 +660,17 @@ int MapEval::process() {
     if (param_.enable_debug)
         std::cout << "INFO: Loaded point clouds: " << map_3d_->size() << " points (Map), " << gt_3d_->size()
                   << " points (Ground Truth)." << std::endl;
-    if (m3c2) {
+    if (m3c2 || mesh) {
+        // (the mesh stage, like M3C2, moves the map and may replace the ground-truth slot by the mesh's sample: same restoration)
         // FIRST of the stages on the resident clouds: it moves the map, replaces both clouds' normals and re-indexes both at the
         // cylinder's bounding radius.  Both clouds are then uploaded again from the host's copies (the clouds as loaded: the map's is
         // still untransformed) with the normals their files brought, so that every later stage — the surface-error normals, the
         // one call's MME, transform and searches — starts from exactly the state it finds without this key.
-        if (computeM3C2() != 0) return -1;
+        if (m3c2 && computeM3C2() != 0) return -1;
+        if (m3c2 && mesh &&  // (M3C2 has moved the map already: the mesh stage starts from the map as loaded)
+            me_upload_cloud(ctx_, ME_SLOT_EST, map_3d_->points_.data(), (int64_t) map_3d_->size(), nullptr, param_.nn_radius_) != ME_OK)
+            return fail(me_last_error(ctx_));
+        if (mesh && computeMeshDistance() != 0) return -1;
         if (me_upload_cloud(ctx_, ME_SLOT_GT, gt_3d_->points_.data(), (int64_t) gt_3d_->size(), nullptr, param_.nn_radius_) != ME_OK ||
             me_upload_cloud(ctx_, ME_SLOT_EST, map_3d_->points_.data(), (int64_t) map_3d_->size(), nullptr, param_.nn_radius_) != ME_OK)
             return fail(me_last_error(ctx_));
@@ -1711,6 +1768,105 @@ void MapEval::saveM3C2() {
     if (std::fclose(f) != 0) fail("writing " + path + " failed");
 }
 
+// evaluate_mesh_distance: the mesh of gt_mesh_path as it is in the file (like the ground-truth cloud it is not moved), the map where
+// initial_matrix puts it (me_transform_cloud; the host's copy stays as loaded), me_mesh_distance with the map as the query, the exact
+// nearest-rank quantiles of d over the matched points (error_quantiles; me_rank_select on the fetched values) and, with
+// mesh_sample_points > 0, the mesh sampled into the ground-truth slot, me_nn1 both ways and their error distributions at the thresholds.
+int MapEval::computeMeshDistance() {
+    auto bad = [&](const std::string &m) { return fail("evaluate_mesh_distance: " + m); };
+    std::vector<double> vx;
+    std::vector<int32_t> tri;
+    std::string err;
+    if (!pcio::read_ply_mesh(param_.gt_mesh_path, vx, tri, &err)) return bad(err);
+    if (me_mesh_upload(ctx_, vx.data(), (int64_t) (vx.size() / 3), tri.data(), (int64_t) (tri.size() / 3), nullptr) != ME_OK ||
+        me_mesh_info(ctx_, &mesh_info) != ME_OK)
+        return bad(me_last_error(ctx_));
+    const double *T = param_.initial_matrix_.data();
+    bool identity = true;
+    for (int i = 0; i < 16; ++i) identity = identity && (T[i] == ((i % 5 == 0) ? 1.0 : 0.0));
+    if (!identity && me_transform_cloud(ctx_, ME_SLOT_EST, T) != ME_OK) return bad(me_last_error(ctx_));
+    me_mesh_params p{};
+    p.max_distance = param_.mesh_max_distance;
+    p.n_thresholds = (int64_t) param_.mesh_thresholds.size();
+    for (size_t k = 0; k < param_.mesh_thresholds.size(); ++k) p.thresholds[k] = param_.mesh_thresholds[k];
+    if (me_mesh_distance(ctx_, ME_SLOT_EST, &p, &mesh_out) != ME_OK) return bad(me_last_error(ctx_));
+    const size_t n = (size_t) mesh_out.n_query, nq = std::min<size_t>(param_.error_quantiles.size(), ME_RANK_MAX);
+    mesh_rank.assign(nq, -1);
+    mesh_quantile.assign(nq, 0.0);
+    if (nq > 0 && mesh_out.n_matched > 0) {
+        std::vector<double> d(n);
+        std::vector<uint8_t> use(n);
+        if (me_mesh_distance_fetch(ctx_, ME_SLOT_EST, d.data(), nullptr, nullptr, nullptr, nullptr) != ME_OK) return bad(me_last_error(ctx_));
+        const double max2 = p.max_distance * p.max_distance;
+        for (size_t i = 0; i < n; ++i) use[i] = d[i] <= max2, d[i] = std::sqrt(d[i]);
+        const int64_t nm = mesh_out.n_matched;
+        for (size_t j = 0; j < nq; ++j)  // nearest rank: ceil(q n) - 1, clamped
+            mesh_rank[j] = std::min<int64_t>(nm - 1, std::max<int64_t>(0, (int64_t) std::ceil(param_.error_quantiles[j] * (double) nm) - 1));
+        me_rank_stats rs{};
+        if (me_rank_select(ctx_, d.data(), use.data(), (int64_t) n, mesh_rank.data(), (int32_t) nq, &rs) != ME_OK) return bad(me_last_error(ctx_));
+        for (size_t j = 0; j < nq; ++j) mesh_quantile[j] = rs.value[j];
+    }
+    if (param_.mesh_sample_points > 0) {
+        if (me_mesh_sample(ctx_, ME_SLOT_GT, param_.mesh_sample_points, param_.mesh_seed) != ME_OK ||
+            me_nn1(ctx_, ME_SLOT_EST, ME_SLOT_GT, nullptr, nullptr) != ME_OK || me_nn1(ctx_, ME_SLOT_GT, ME_SLOT_EST, nullptr, nullptr) != ME_OK)
+            return bad(me_last_error(ctx_));
+        me_errdist_params ep{};
+        ep.gate = -1.0;
+        ep.n_thresholds = (int32_t) param_.mesh_thresholds.size();
+        for (int k = 0; k < ep.n_thresholds; ++k) ep.tau[k] = param_.mesh_thresholds[(size_t) k];
+        for (int s = ME_SLOT_EST; s <= ME_SLOT_GT; ++s)
+            if (me_nn_error_distribution(ctx_, s, &ep, &mesh_sampled[s], nullptr) != ME_OK) return bad(me_last_error(ctx_));
+        for (int k = 0; k < ep.n_thresholds; ++k)
+            me_fscore_finalize(mesh_sampled[0].n_within[k], mesh_sampled[0].n_used, mesh_sampled[1].n_within[k], mesh_sampled[1].n_used, mesh_prf[k]);
+    }
+    if (me_mesh_clear(ctx_) != ME_OK) return bad(me_last_error(ctx_));
+    return 0;
+}
+
+void MapEval::saveMeshDistance() {
+    const me_mesh_out &o = mesh_out;
+    const double nm = (double) o.n_matched;
+    file_result << std::fixed << std::setprecision(5) << "MeshError mean-rmse-max: " << (o.n_matched > 0 ? o.sum_d / nm : 0.0) << " "
+                << (o.n_matched > 0 ? std::sqrt(o.sum_d2 / nm) : 0.0) << " " << o.max_d << std::endl;
+    file_result << std::fixed << std::setprecision(5) << "MeshAC @t:";  // per threshold: the share of the matched points within it
+    for (size_t k = 0; k < param_.mesh_thresholds.size(); ++k)
+        file_result << " " << param_.mesh_thresholds[k] << " " << (o.n_matched > 0 ? (double) o.n_within[k] / nm : 0.0);
+    file_result << std::endl;
+    // mesh_distance.txt: the info block ("name value ..."), the parameters, the totals row
+    //   totals n_query n_matched n_face sum_d sum_d2 max_d argmax
+    // the signed bias over the face region `signed sum_signed sum_abs_signed mean mean_abs`, the rows `t threshold n_within`,
+    // `q prob rank d`, and with mesh_sample_points the rows `sampled <est|gt> n_query n_used sum_d sum_d2 max_d` and
+    // `f threshold precision recall fscore` (doubles as %.17g)
+    const std::string path = results_subfolder + "mesh_distance.txt";
+    FILE *f = std::fopen(path.c_str(), "w");
+    if (!f) {
+        fail("cannot write " + path);
+        return;
+    }
+    const me_mesh_info_out &mi = mesh_info;
+    std::fprintf(f, "vertices %lld\ntriangles %lld\ndegenerate %lld\ndepth %lld\narea %.17g\nbbox %.17g %.17g %.17g %.17g %.17g %.17g\n",
+                 (long long) mi.n_vertices, (long long) mi.n_triangles, (long long) mi.n_degenerate, (long long) mi.depth, mi.area, mi.bbox_lo[0],
+                 mi.bbox_lo[1], mi.bbox_lo[2], mi.bbox_hi[0], mi.bbox_hi[1], mi.bbox_hi[2]);
+    std::fprintf(f, "max_distance %.17g\nsample_points %lld\nseed %llu\n", param_.mesh_max_distance, (long long) param_.mesh_sample_points,
+                 (unsigned long long) param_.mesh_seed);
+    std::fprintf(f, "totals %lld %lld %lld %.17g %.17g %.17g %lld\n", (long long) o.n_query, (long long) o.n_matched, (long long) o.n_face, o.sum_d,
+                 o.sum_d2, o.max_d, (long long) o.argmax);
+    std::fprintf(f, "signed %.17g %.17g %.17g %.17g\n", o.sum_signed, o.sum_abs_signed, o.n_face > 0 ? o.sum_signed / (double) o.n_face : 0.0,
+                 o.n_face > 0 ? o.sum_abs_signed / (double) o.n_face : 0.0);
+    for (size_t k = 0; k < param_.mesh_thresholds.size(); ++k)
+        std::fprintf(f, "t %.17g %lld\n", param_.mesh_thresholds[k], (long long) o.n_within[k]);
+    for (size_t j = 0; j < mesh_rank.size(); ++j)
+        std::fprintf(f, "q %.17g %lld %.17g\n", param_.error_quantiles[j], (long long) mesh_rank[j], mesh_quantile[j]);
+    if (param_.mesh_sample_points > 0) {
+        for (int s = ME_SLOT_EST; s <= ME_SLOT_GT; ++s)
+            std::fprintf(f, "sampled %s %lld %lld %.17g %.17g %.17g\n", s == ME_SLOT_EST ? "est" : "gt", (long long) mesh_sampled[s].n_query,
+                         (long long) mesh_sampled[s].n_used, mesh_sampled[s].sum_d, mesh_sampled[s].sum_d2, mesh_sampled[s].max_d);
+        for (size_t k = 0; k < param_.mesh_thresholds.size(); ++k)
+            std::fprintf(f, "f %.17g %.17g %.17g %.17g\n", param_.mesh_thresholds[k], mesh_prf[k][0], mesh_prf[k][1], mesh_prf[k][2]);
+    }
+    if (std::fclose(f) != 0) fail("writing " + path + " failed");
+}
+
 // me_nn_surface_error on the 1-NN results of both directions, after the metric path's statistics (the gate is that path's when
 // surface_gated is set, none otherwise); the cosines of the angle thresholds are taken here, with the C library's cos
 int MapEval::computeSurfaceError(int gate_mode) {
@@ -1777,6 +1933,7 @@ void MapEval::saveRegistrationResults() {
     if (param_.evaluate_error_distribution) saveErrorDistribution();
     if (param_.evaluate_surface_error) saveSurfaceError();
     if (param_.evaluate_m3c2) saveM3C2();
+    if (param_.evaluate_mesh_distance) saveMeshDistance();
     file_result << std::fixed << std::setprecision(5) << "VMD: " << vmd << std::endl;
     file_result << std::fixed << std::setprecision(5) << "SCS: " << scs_overall << std::endl;
     if (param_.evaluate_using_initial_)

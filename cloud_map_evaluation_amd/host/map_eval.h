@@ -3,6 +3,7 @@
 // TBB / yaml-cpp: clouds are std::vector<double> (AoS xyz, the same memory layout as open3d PointCloud::points_).
 #pragma once
 
+#include <cmath>
 #include <array>
 #include <fstream>
 #include <memory>
@@ -151,12 +152,22 @@ struct Param {
     int m3c2_min_points = 5;                   // `m3c2_min_points:` points either cloud needs inside the cylinder, >= 2
     double m3c2_reg_error = 0.0;               // `m3c2_reg_error:` the registration error added to the level of detection, >= 0
     int m3c2_core_every = 1;                   // `m3c2_core_every:` every k-th point of a cloud, in file order, is a core point, >= 1
+    // cloud-to-mesh distance against a ground-truth triangle mesh (optional keys; the role of the reference's mesh branch with a mesh
+    // the user supplies): the map moved by initial_matrix against the mesh of `gt_mesh_path` as it is in the file (like the ground-truth
+    // cloud, the mesh is not moved), on the resident clouds before every other stage, after which both clouds are uploaded again as
+    // loaded (single GPU); two lines before `VMD`, and mesh_distance.txt
+    bool evaluate_mesh_distance = false;       // `evaluate_mesh_distance:`
+    std::string gt_mesh_path;                  // `gt_mesh_path:` a PLY with a face element (required with evaluate_mesh_distance)
+    std::vector<double> mesh_thresholds;       // `mesh_thresholds: [..]` at most 8, each >= 0 (default: accuracy_level)
+    double mesh_max_distance = INFINITY;       // `mesh_max_distance:` matched iff d <= this; <= 0 or absent: every point
+    int64_t mesh_sample_points = 0;            // `mesh_sample_points:` > 0: also the mesh sampled into the ground-truth slot, 1-NN both ways
+    uint64_t mesh_seed = 0;                    // `mesh_seed:` the sampler's seed
     int dist_rank = 0;              // (set by the launcher, not a YAML key)
     void printParam() const;
 };
 
 Param loadParametersFromYAML(const std::string &yaml_file_path);  // map_eval_main.cpp:120-208
-std::string paramToJson(const Param &p);                          // for tests (--parse-config)
+std::string paramToJson(const Param &p);                          // for tests (--parse-config); an infinite value prints as Infinity
 
 class MapEval {
 public:
@@ -198,6 +209,8 @@ public:
     void saveSurfaceError();                                // its three result lines and surface_error.txt
     int computeM3C2();                                      // evaluate_m3c2: normals and me_m3c2 on both clouds, the map moved (no reference counterpart)
     void saveM3C2();                                        // its result line and m3c2.txt
+    int computeMeshDistance();                              // evaluate_mesh_distance: me_mesh_distance of the moved map (no reference counterpart)
+    void saveMeshDistance();                                // its two result lines and mesh_distance.txt
     void saveErrorDistribution();                           // its three result lines and error_distribution.txt
     int writeRegistrationInformation();                     // registration_information.txt (icp_information_matrix; no reference counterpart)
     int globalRegistration(double T_c[16]);                 // global_registration.txt (global_registration; no reference counterpart)                                   // noise_sweep.txt (noise_sweep; no reference counterpart)
@@ -225,6 +238,12 @@ public:
     me_radius_normals_out surface_normals[2] = {};
     me_m3c2_out m3c2_out[2] = {};               // evaluate_m3c2: [ME_SLOT_EST], [ME_SLOT_GT] as the query
     me_radius_normals_out m3c2_normals[2] = {};
+    me_mesh_info_out mesh_info = {};            // evaluate_mesh_distance: the mesh, the totals, the quantiles of d, the sampled block
+    me_mesh_out mesh_out = {};
+    std::vector<int64_t> mesh_rank;
+    std::vector<double> mesh_quantile;
+    me_errdist_out mesh_sampled[2] = {};        // ... with mesh_sample_points: 1-NN error of the map in the sample and the reverse
+    double mesh_prf[ME_MESH_MAX_THRESHOLDS][3] = {};
     me_mom_out mom_out[2] = {};  // evaluate_mom: [ME_SLOT_EST], [ME_SLOT_GT] (the latter with evaluate_gt_mom)
     me_local_geom_out mpv_out[2] = {};  // evaluate_mpv: [ME_SLOT_EST], [ME_SLOT_GT] (the latter with evaluate_gt_mpv)
     std::vector<double> est_entropies, gt_entropies;

@@ -1,8 +1,10 @@
 // map_eval_main.cpp — entry point mirroring map_eval/src/map_eval_main.cpp:211-244: reads ../config/config.yaml by default
 // (the reference hard-codes that path and has the argv override commented out; here argv[1] works), prints the banner
 // essentials, runs MapEval::process().  Extra modes used by the tests (no GPU needed):
-//   map_eval --parse-config <yaml>   print the parsed Param as JSON
+//   map_eval --parse-config <yaml>   print the parsed Param as JSON (an infinite mesh_max_distance as the token Infinity, which
+//                                    Python's json reads; strict JSON has no infinity)
 //   map_eval --cloud-info <pcd|ply>  print point count and coordinate sums after NaN/inf removal
+//   map_eval --mesh-info <ply>       print the mesh's counts, area and bounding box from the reader alone
 //
 // Multi-GPU (`num_gpus: N` in the YAML; not a reference key): the process forks N - 1 children BEFORE anything touches HIP;
 // rank r drives device gpu_device + r (one process per GPU), the ranks meet in an RCCL communicator whose ncclUniqueId rank 0
@@ -15,6 +17,7 @@
 #include <sys/prctl.h>
 #include <unistd.h>
 
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <filesystem>
@@ -78,6 +81,33 @@ int main(int argc, char **argv) {
         std::cout << std::setprecision(17) << "{\"points\": " << xyz.size() / 3 << ", \"sum\": [" << s[0] << ", " << s[1] << ", " << s[2]
                   << "], \"normals\": " << nrm.size() / 3 << ", \"normal_sum\": [" << sn[0] << ", " << sn[1] << ", " << sn[2] << "]}"
                   << std::endl;
+        return EXIT_SUCCESS;
+    }
+    if (argc > 2 && std::string(argv[1]) == "--mesh-info") {
+        std::vector<double> xyz;
+        std::vector<int32_t> tri;
+        std::string err;
+        if (!pcio::read_ply_mesh(argv[2], xyz, tri, &err)) {
+            std::cerr << "ERROR: " << err << std::endl;
+            return EXIT_FAILURE;
+        }
+        // area and the degenerate test as me_mesh_upload forms them; the box over the referenced vertices
+        double area = 0.0, lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+        size_t n_deg = 0;
+        for (size_t t = 0; t < tri.size() / 3; ++t) {
+            const double *a = &xyz[3 * (size_t) tri[3 * t]], *b = &xyz[3 * (size_t) tri[3 * t + 1]], *c = &xyz[3 * (size_t) tri[3 * t + 2]];
+            const double ab[3] = {b[0] - a[0], b[1] - a[1], b[2] - a[2]}, ac[3] = {c[0] - a[0], c[1] - a[1], c[2] - a[2]};
+            const double nx = ab[1] * ac[2] - ab[2] * ac[1], ny = ab[2] * ac[0] - ab[0] * ac[2], nz = ab[0] * ac[1] - ab[1] * ac[0];
+            n_deg += nx == 0.0 && ny == 0.0 && nz == 0.0;
+            area += 0.5 * std::sqrt((nx * nx + ny * ny) + nz * nz);
+            for (const double *p : {a, b, c})
+                for (int d = 0; d < 3; ++d) lo[d] = std::fmin(lo[d], p[d]), hi[d] = std::fmax(hi[d], p[d]);
+        }
+        if (tri.empty())
+            for (int d = 0; d < 3; ++d) lo[d] = hi[d] = 0.0;
+        std::cout << std::setprecision(17) << "{\"vertices\": " << xyz.size() / 3 << ", \"triangles\": " << tri.size() / 3
+                  << ", \"degenerate\": " << n_deg << ", \"area\": " << area << ", \"bbox\": [" << lo[0] << ", " << lo[1] << ", " << lo[2]
+                  << ", " << hi[0] << ", " << hi[1] << ", " << hi[2] << "]}" << std::endl;
         return EXIT_SUCCESS;
     }
     if (argc > 1) config_file = argv[1];

@@ -7,6 +7,7 @@
 #include <cstdint>
 #include <cstring>
 #include <fstream>
+#include <iterator>
 #include <sstream>
 #include <stdexcept>
 #include <string>
@@ -296,6 +297,150 @@ inline bool read_ply(const std::string &path, std::vector<double> &xyz, std::str
     } else {
         return fail("unsupported PLY format '" + format + "'");
     }
+    return true;
+}
+
+// A triangle mesh from a PLY file (ascii or binary_little_endian): EVERY vertex in file order (nothing is stripped: the faces index
+// them) and the `face` element's `vertex_indices` / `vertex_index` list, any integer count and index types; polygons with more than
+// three corners are fan-triangulated (0, k, k + 1).  Other face properties and other elements are read past.  Fails on a truncated
+// file, a list count below 3 and an index outside [0, n_vertices).
+inline bool read_ply_mesh(const std::string &path, std::vector<double> &xyz, std::vector<int32_t> &tri, std::string *err = nullptr) {
+    auto fail = [&](const std::string &m) {
+        if (err) *err = m;
+        return false;
+    };
+    std::ifstream f(path, std::ios::binary);
+    if (!f.is_open()) return fail("cannot open " + path);
+    std::string line, format;
+    std::getline(f, line);
+    if (line.substr(0, 3) != "ply") return fail("not a PLY file: " + path);
+    struct Prop { std::string name, type, count_type; bool list = false; };
+    struct Element { std::string name; size_t count = 0; std::vector<Prop> props; };
+    std::vector<Element> elements;
+    bool ended = false;
+    while (std::getline(f, line)) {
+        if (!line.empty() && line.back() == '\r') line.pop_back();
+        std::stringstream ss(line);
+        std::string key;
+        ss >> key;
+        if (key == "format") ss >> format;
+        else if (key == "element") {
+            Element e;
+            if (!(ss >> e.name >> e.count)) return fail("PLY: bad element line: " + line);
+            elements.push_back(e);
+        } else if (key == "property") {
+            if (elements.empty()) return fail("PLY: property before any element");
+            Prop p;
+            ss >> p.type;
+            if (p.type == "list") {
+                p.list = true;
+                ss >> p.count_type >> p.type;
+                if (ply_type_size(p.count_type) < 0 || p.count_type[0] == 'f' || p.count_type[0] == 'd')
+                    return fail("PLY: list count type must be an integer type, got '" + p.count_type + "'");
+            }
+            ss >> p.name;
+            if (ply_type_size(p.type) < 0) return fail("PLY: unknown property type " + p.type);
+            elements.back().props.push_back(p);
+        } else if (key == "end_header") {
+            ended = true;
+            break;
+        }
+    }
+    if (!ended) return fail("truncated PLY header: " + path);
+    const bool ascii = format == "ascii";
+    if (!ascii && format != "binary_little_endian") return fail("unsupported PLY format '" + format + "'");
+    std::vector<unsigned char> buf;  // binary: the whole body
+    size_t pos = 0;
+    if (!ascii) buf.assign(std::istreambuf_iterator<char>(f), std::istreambuf_iterator<char>());
+    bool short_read = false;
+    std::string bad_token;  // ascii: a token that is not a number
+    // the next scalar of the body as a double (every PLY integer type is exact in one)
+    auto next = [&](const std::string &type) -> double {
+        if (ascii) {
+            std::string tok;
+            if (!(f >> tok)) {
+                short_read = true;
+                return 0.0;
+            }
+            char *end = nullptr;
+            const double v = std::strtod(tok.c_str(), &end);
+            if (end != tok.c_str() + tok.size()) {
+                bad_token = tok;
+                return 0.0;
+            }
+            return v;
+        }
+        const size_t sz = (size_t) ply_type_size(type);
+        if (buf.size() - pos < sz) {
+            short_read = true;
+            pos = buf.size();
+            return 0.0;
+        }
+        const char kind = (type[0] == 'f' || type[0] == 'd') ? 'F' : ((type[0] == 'u') ? 'U' : 'I');
+        const double v = read_scalar(buf.data() + pos, kind, (int) sz);
+        pos += sz;
+        return v;
+    };
+    xyz.clear();
+    tri.clear();
+    size_t n_vertex = 0;
+    bool have_vertex = false, have_face = false;
+    std::vector<double> corners;
+    for (const Element &e : elements) {
+        const bool is_vertex = e.name == "vertex", is_face = e.name == "face";
+        int ix = -1, iy = -1, iz = -1, il = -1;
+        for (size_t i = 0; i < e.props.size(); ++i) {
+            const Prop &p = e.props[i];
+            if (is_vertex && p.list) return fail("list property in vertex element not supported");
+            if (is_vertex && p.name == "x") ix = (int) i;
+            if (is_vertex && p.name == "y") iy = (int) i;
+            if (is_vertex && p.name == "z") iz = (int) i;
+            if (is_face && p.list && (p.name == "vertex_indices" || p.name == "vertex_index")) il = (int) i;
+        }
+        if (is_vertex) {
+            if (ix < 0 || iy < 0 || iz < 0) return fail("PLY has no x/y/z vertex properties");
+            have_vertex = true;
+            n_vertex = e.count;
+        }
+        if (is_face) {
+            if (il < 0) return fail("PLY: the face element has no vertex_indices / vertex_index list");
+            have_face = true;
+        }
+        for (size_t r = 0; r < e.count; ++r) {
+            double v[3] = {0, 0, 0};
+            for (size_t i = 0; i < e.props.size(); ++i) {
+                const Prop &p = e.props[i];
+                if (!p.list) {
+                    const double x = next(p.type);
+                    if ((int) i == ix) v[0] = x;
+                    if ((int) i == iy) v[1] = x;
+                    if ((int) i == iz) v[2] = x;
+                } else {
+                    const double cnt = next(p.count_type);
+                    if (short_read) break;
+                    if (!(cnt >= 0) || cnt > 1e9) return fail("PLY: bad list count in element " + e.name);
+                    if ((int) i == il && cnt < 3) return fail("PLY: a face with fewer than 3 corners (list count " + std::to_string((long long) cnt) + ")");
+                    corners.clear();
+                    for (long long k = 0; k < (long long) cnt && !short_read; ++k) corners.push_back(next(p.type));
+                    if ((int) i == il && !short_read)
+                        for (size_t k = 1; k + 1 < corners.size(); ++k)
+                            for (const double c : {corners[0], corners[k], corners[k + 1]}) {
+                                if (!(c >= 0) || c > 2147483647.0 || c != std::floor(c)) return fail("PLY: a face index is not a vertex index");
+                                tri.push_back((int32_t) c);
+                            }
+                }
+                if (short_read) break;
+            }
+            if (short_read) return fail("truncated PLY: " + path + " ends inside element " + e.name);
+            if (!bad_token.empty()) return fail("PLY: '" + bad_token + "' in element " + e.name + " is not a number");
+            if (is_vertex) xyz.insert(xyz.end(), v, v + 3);
+        }
+    }
+    if (!have_vertex) return fail("PLY has no vertex element");
+    if (!have_face) return fail("PLY has no face element");
+    for (const int32_t i : tri)
+        if ((size_t) i >= n_vertex)
+            return fail("PLY: face index " + std::to_string(i) + " is outside [0, " + std::to_string(n_vertex) + ")");
     return true;
 }
 

@@ -249,3 +249,28 @@ def tunnel_pair(n: int, density: float = 2500.0, seed: int = 300, device="cpu", 
     if est.shape[0] < n:
         raise ValueError("oversampling factor too small for the requested point count")
     return est[:n].contiguous(), gt
+
+
+def heightfield_mesh(nx: int, ny: int, step: float, amplitude: float, seed: int = 0):
+    """A smooth bumpy surface z(x, y) over the nx x ny lattice of spacing `step` as a triangle mesh: (vertices (nx*ny, 3) float64,
+    triangles (2 (nx-1) (ny-1), 3) int32), every cell split along the same diagonal, normals towards +z.  z is a sum of four sines
+    whose phases and directions come from `seed`; |z| <= amplitude."""
+    import numpy as np
+
+    if nx < 2 or ny < 2:
+        raise ValueError("heightfield_mesh needs nx >= 2 and ny >= 2")
+    rng = np.random.default_rng(seed)
+    ix, iy = np.meshgrid(np.arange(nx, dtype=np.float64), np.arange(ny, dtype=np.float64), indexing="ij")
+    x, y = ix * step, iy * step
+    z = np.zeros_like(x)
+    for _ in range(4):
+        ang, ph = rng.uniform(0.0, 2.0 * np.pi, 2)
+        wl = rng.uniform(6.0, 14.0) * step
+        z += np.sin((2.0 * np.pi / wl) * (np.cos(ang) * x + np.sin(ang) * y) + ph)
+    z *= amplitude / 4.0
+    vertices = np.stack([x, y, z], axis=-1).reshape(-1, 3)
+    i, j = np.meshgrid(np.arange(nx - 1), np.arange(ny - 1), indexing="ij")
+    v00 = (i * ny + j).reshape(-1)
+    v10, v01, v11 = v00 + ny, v00 + 1, v00 + ny + 1
+    triangles = np.stack([np.stack([v00, v10, v11], -1), np.stack([v00, v11, v01], -1)], 1).reshape(-1, 3).astype(np.int32)
+    return np.ascontiguousarray(vertices), np.ascontiguousarray(triangles)

@@ -806,6 +806,84 @@ int me_m3c2(me_ctx *ctx, int query_slot, const me_m3c2_params *p, const uint8_t 
 int me_m3c2_fetch(me_ctx *ctx, int query_slot, double *dist, double *lod, double *var_own, double *var_other, int32_t *n_own,
                   int32_t *n_other, uint8_t *flags);
 
+/* ---- cloud-to-mesh distance against a ground-truth triangle mesh, and an area-uniform sample of that mesh ---------------------------- */
+/*   Stands in for the reference's mesh branch (map_eval.cpp:194-205, 509-523, renderDistanceOnMesh 738-775),
+ * which measures against a Poisson mesh of the ground truth, and plays the role of computePointCloudDistance (map_eval.cpp:568-584)
+ * with an exact point-to-triangle distance against a mesh the CALLER supplies (CloudCompare's cloud-to-mesh distance); me_mesh_sample
+ * is Open3D's TriangleMesh::SamplePointsUniformly with a stated generator.  Single GPU only (slab or shard mode: ME_ERR_ARG).
+ *
+ * me_mesh_upload: vertices = host fp64 xyz [n_vertices][3], triangles = host int32 [n_triangles][3], T = nullable row-major 4x4 applied
+ *   as me_upload_cloud applies it.  The mesh lives in the primary context beside the two clouds (a twin sees it), survives cloud uploads
+ *   and re-indexing; a second upload replaces it, me_mesh_clear drops it; both discard the mesh-distance results of both slots.
+ *   ME_ERR_ARG: n_triangles < 1, an index outside [0, n_vertices), a non-finite coordinate of a REFERENCED vertex (unreferenced
+ *   vertices are ignored).  A triangle is DEGENERATE iff n = (B - A) x (C - A), each component u1*v2 - u2*v1 in fp64 without
+ *   contraction, is exactly the zero vector; it is kept and searched as its three segments; its area is 0.
+ *   area(t) = 0.5 * sqrt((nx*nx + ny*ny) + nz*nz); the cumulative table is the sequential fp64 sum in the caller's order, formed on the
+ *   host (numpy.cumsum reproduces it bit for bit).  Index: an implicit 8-ary tree of axis-aligned fp64 boxes over the triangles sorted
+ *   by the Morton code of their centroid (leaves = 8 consecutive triangles); device timer "mesh_index" covers the build's own kernels,
+ *   the radix sort between them reports under the library's "sort" timer as in every index build (scopes do not nest).
+ * me_mesh_info: counts, bounding box of the referenced vertices, total area, tree depth (levels, leaves included).  ME_ERR_STATE: no mesh.
+ *
+ * me_mesh_distance: for every point p of query_slot the closest point c of the mesh.  Per triangle ONE fixed sequence of fp64
+ *   operations (no FMA), dot(u, v) = (u0*v0 + u1*v1) + u2*v2, clamp01(x) = fmin(fmax(x, 0), 1) (a NaN quotient gives 0):
+ *       ab = B-A  ac = C-A   d1 = dot(ab, p-A) d2 = dot(ac, p-A)   d3 = dot(ab, p-B) d4 = dot(ac, p-B)   d5 = dot(ab, p-C) d6 = dot(ac, p-C)
+ *       d1 <= 0 && d2 <= 0                               -> vertex A (region 4)
+ *       d3 >= 0 && d4 <= d3                              -> vertex B (5)
+ *       d1*d4 - d3*d2 <= 0 && d1 >= 0 && d3 <= 0         -> edge AB (1)   c = A + clamp01(d1 / (d1 - d3)) * ab
+ *       d6 >= 0 && d5 <= d6                              -> vertex C (6)
+ *       d5*d2 - d1*d6 <= 0 && d2 >= 0 && d6 <= 0         -> edge CA (3)   c = A + clamp01(d2 / (d2 - d6)) * ac
+ *       d3*d6 - d5*d4 <= 0 && d4-d3 >= 0 && d5-d6 >= 0   -> edge BC (2)   c = B + clamp01((d4-d3) / ((d4-d3) + (d5-d6))) * (C-B)
+ *       else                                             -> face (0)      va = d3*d6 - d5*d4, vb = d5*d2 - d1*d6, vc = d1*d4 - d3*d2,
+ *                                                           den = (va + vb) + vc, s = clamp01(vb / den), t = fmin(fmax(vc / den, 0), 1 - s),
+ *                                                           c = (A + s*ab) + t*ac
+ *   the first line that holds decides; d2(p, t) = ((dx*dx + dy*dy) + dz*dz) with d = p - c.  A degenerate triangle: the segments AB, BC,
+ *   CA in this order, a later one only when strictly nearer; per segment P0 P1: e = P1-P0, l = dot(e, e), t = dot(e, p-P0); t <= 0 -> P0
+ *   (its vertex code), t >= l -> P1, else c = P0 + (t / l) * e (the edge's code).
+ *   Per query: the minimal d2; the triangle = the smallest caller index among the bitwise-minimal d2; that triangle's region and c.
+ *   The search is unbounded and exact in this arithmetic (the tree only prunes what cannot win or tie).  Device timer "mesh_dist".
+ *   SIGN.  Only in the face region: s = dot(p - c, n) / sqrt(dot(n, n)), n = (B-A) x (C-A) by the triangle's winding.  At an edge or a
+ *   vertex a single face normal can name the wrong side of a non-convex mesh; angle-weighted pseudo-normals are not built: signed_d is
+ *   NaN there and such points enter neither sum_signed nor sum_abs_signed.
+ *   GATE.  A point is MATCHED iff d2 <= max_distance * max_distance (+inf: every point); only matched points enter the totals.
+ *   n_within[k] counts the matched points with d2 <= thresholds[k] * thresholds[k].  max_d = the largest matched d = sqrt(d2), argmax its
+ *   cloud-order index (ties -> the smaller index; -1 without a matched point).  n_face, sum_signed, sum_abs_signed over the matched points
+ *   whose region is the face.  Sums: per-block partials by a fixed tree, combined in block order; identical from run to run.
+ *   ME_ERR_STATE: no mesh, or no cloud in the slot.  ME_ERR_ARG: bad slot, max_distance negative or NaN, a negative or non-finite
+ *   threshold, n_thresholds outside [0, 8], slab or shard mode.
+ * me_mesh_distance_fetch: the per-point arrays in cloud order, every pointer nullable: d2[N], tri[N] (caller's triangle index),
+ *   region[N], closest[N][3], signed_d[N] (NaN outside the face region).  ME_ERR_STATE without a current result: it is discarded when the
+ *   slot's points change or the slot is re-indexed, and by me_mesh_upload / me_mesh_clear.  It survives me_nn1 and me_mme.
+ *
+ * me_mesh_sample: n_points area-uniform samples of the mesh become the cloud of dst_slot, as an upload would leave it (the cell size
+ *   of the other slot's upload, so that the two grids align).  Sample i: (w0, w1, w2, w3) = Philox4x64-10(counter (i, 0, 0, 0), key
+ *   (seed, 0)); u01(w) = (w >> 11) * 2^-53; u = u01(w0) * total_area; the triangle is the first index whose cumulative area exceeds u
+ *   (a zero-area triangle is never chosen); r1 = sqrt(u01(w1)), r2 = u01(w2); wa = 1 - r1, wb = r1 * (1 - r2), wc = r1 * r2;
+ *   point = (wa*A + wb*B) + wc*C per coordinate.  ME_ERR_ARG: n_points < 1, a total area that is not positive and finite. */
+#define ME_MESH_MAX_THRESHOLDS 8
+typedef struct me_mesh_params {
+    double max_distance; /* >= 0, +inf allowed */
+    int64_t n_thresholds;
+    double thresholds[ME_MESH_MAX_THRESHOLDS];
+} me_mesh_params;
+typedef struct me_mesh_out {
+    int64_t n_query, n_matched, n_face;
+    double sum_d, sum_d2, max_d;
+    int64_t argmax;
+    int64_t n_within[ME_MESH_MAX_THRESHOLDS];
+    double sum_signed, sum_abs_signed;
+} me_mesh_out;
+typedef struct me_mesh_info_out {
+    int64_t n_vertices, n_triangles, n_degenerate, depth;
+    double bbox_lo[3], bbox_hi[3];
+    double area;
+} me_mesh_info_out;
+int me_mesh_upload(me_ctx *ctx, const double *vertices, int64_t n_vertices, const int32_t *triangles, int64_t n_triangles, const double *T);
+int me_mesh_clear(me_ctx *ctx);
+int me_mesh_info(me_ctx *ctx, me_mesh_info_out *out);
+int me_mesh_distance(me_ctx *ctx, int query_slot, const me_mesh_params *p, me_mesh_out *out);
+int me_mesh_distance_fetch(me_ctx *ctx, int query_slot, double *d2, int32_t *tri, uint8_t *region, double *closest, double *signed_d);
+int me_mesh_sample(me_ctx *ctx, int dst_slot, int64_t n_points, uint64_t seed);
+
 /* ---- neighbour lists between the resident clouds: KDTreeFlann::SearchKNN / SearchHybrid / SearchRadius for every point of a
  * cloud (the reference's loops over them: map_eval.cpp:1213-1218, 1448-1454, 1670) ---- */
 /* The three searches below hand the neighbours themselves to the caller, for every point of query_slot among the points of
