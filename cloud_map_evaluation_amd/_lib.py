@@ -37,6 +37,7 @@ SYMBOLS = [
     "me_local_geometry", "me_local_geometry_fetch", "me_radius_normals", "me_nn_surface_error", "me_nn_surface_fetch",
     "me_m3c2", "me_m3c2_fetch",
     "me_mesh_upload", "me_mesh_clear", "me_mesh_info", "me_mesh_distance", "me_mesh_distance_fetch", "me_mesh_sample",
+    "me_reconstruct", "me_isosurface", "me_reconstruct_fetch", "me_reconstruct_nodes_fetch", "me_reconstruct_install",
     "me_knn_search", "me_hybrid_search", "me_radius_search", "me_search_sort_tile",
     "me_segment_planes", "me_plane_fetch", "me_plane_keep",
     "me_group_order_stats", "me_mom_select_axes", "me_mom", "me_mom_fetch",
@@ -419,6 +420,15 @@ class MeshInfoOut(C.Structure):
     ]
 
 
+class ReconParams(C.Structure):
+    _fields_ = [("voxel", C.c_double), ("radius", C.c_double), ("min_k", C.c_int32), ("band", C.c_int32)]
+
+
+class ReconOut(C.Structure):
+    _fields_ = [(k, C.c_int64) for k in ("n_occupied_cells", "n_active_cells", "n_nodes", "n_valid_nodes", "n_cells_extracted", "n_vertices",
+                                         "n_triangles", "n_degenerate", "sum_k")]
+
+
 class SurfaceParams(C.Structure):
     _fields_ = [
         ("gate", C.c_double),
@@ -547,6 +557,13 @@ def load():
     L.me_mesh_distance_fetch.argtypes = [vp, C.c_int, dp, ip, vp, dp, dp]
     L.me_mesh_sample.argtypes = [vp, C.c_int, C.c_int64, C.c_uint64]
     for f in ("me_mesh_upload", "me_mesh_clear", "me_mesh_info", "me_mesh_distance", "me_mesh_distance_fetch", "me_mesh_sample"):
+        getattr(L, f).restype = C.c_int
+    L.me_reconstruct.argtypes = [vp, C.c_int, C.POINTER(ReconParams), C.POINTER(ReconOut)]
+    L.me_isosurface.argtypes = [vp, ip, dp, vp, C.c_int64, C.c_double, C.POINTER(ReconOut)]
+    L.me_reconstruct_fetch.argtypes = [vp, dp, ip, ip]
+    L.me_reconstruct_nodes_fetch.argtypes = [vp, ip, dp, ip, vp]
+    L.me_reconstruct_install.argtypes = [vp]
+    for f in ("me_reconstruct", "me_isosurface", "me_reconstruct_fetch", "me_reconstruct_nodes_fetch", "me_reconstruct_install"):
         getattr(L, f).restype = C.c_int
     L.me_knn_search.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, ip, dp]
     L.me_hybrid_search.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_int, vp, ip, ip, dp]

@@ -187,6 +187,7 @@ me_ctx *me_twin(me_ctx *ctx) {
     t->cloud.p[0] = ctx->cloud.p[0];
     t->cloud.p[1] = ctx->cloud.p[1];
     t->mesh = ctx->mesh;
+    t->recon = ctx->recon;
     t->shard_rank = ctx->shard_rank;
     t->shard_world = ctx->shard_world;
     t->borrow_device_input = ctx->borrow_device_input;
@@ -419,6 +420,31 @@ int me_mesh_distance_fetch(me_ctx *ctx, int query_slot, double *d2, int32_t *tri
 int me_mesh_sample(me_ctx *ctx, int dst_slot, int64_t n_points, uint64_t seed) {
     if (!ctx) return ME_ERR_ARG;
     return me::mesh_sample(ctx, dst_slot, n_points, seed);
+}
+
+int me_reconstruct(me_ctx *ctx, int slot, const me_recon_params *p, me_recon_out *out) {
+    if (!ctx) return ME_ERR_ARG;
+    return me::reconstruct(ctx, slot, p, out);
+}
+
+int me_isosurface(me_ctx *ctx, const int32_t *node_ijk, const double *f, const uint8_t *valid, int64_t n_nodes, double voxel, me_recon_out *out) {
+    if (!ctx) return ME_ERR_ARG;
+    return me::isosurface(ctx, node_ijk, f, valid, n_nodes, voxel, out);
+}
+
+int me_reconstruct_fetch(me_ctx *ctx, double *vertices, int32_t *vertex_edge, int32_t *triangles) {
+    if (!ctx) return ME_ERR_ARG;
+    return me::reconstruct_fetch(ctx, vertices, vertex_edge, triangles);
+}
+
+int me_reconstruct_nodes_fetch(me_ctx *ctx, int32_t *node_ijk, double *f, int32_t *k, uint8_t *valid) {
+    if (!ctx) return ME_ERR_ARG;
+    return me::reconstruct_nodes_fetch(ctx, node_ijk, f, k, valid);
+}
+
+int me_reconstruct_install(me_ctx *ctx) {
+    if (!ctx) return ME_ERR_ARG;
+    return me::reconstruct_install(ctx);
 }
 
 int me_knn_search(me_ctx *ctx, int query_slot, int ref_slot, int k, const uint8_t *query_mask, int32_t *idx, double *d2) {

@@ -281,6 +281,19 @@ struct Mesh {
     DevBuf lv;      // int2[kMeshMaxLevels] (offset, count) per level
 };
 
+// The last reconstruction (me_recon.hip): one per primary context, like the mesh; held until the next me_reconstruct / me_isosurface
+// or me_mesh_clear.  The node arrays are in the Morton order of the lattice frame (origin `base`, 21 bits per axis).
+struct Recon {
+    bool have = false, have_nodes = false;  // have_nodes: the node field is me_reconstruct's (me_isosurface keeps none)
+    long long n_nodes = 0, nv = 0, nt = 0;
+    long long base[3] = {0, 0, 0};
+    double voxel = 0;
+    DevBuf verts, vedge, tris;                          // double[nv][3], int32[nv][4], int32[nt][3]
+    DevBuf node_key, node_f, node_k, node_valid, cell_ok;  // uint64[n], double[n], int32[n], uint8[n], uint8[n] (corner 0 of an active cell)
+    DevBuf counters;                                    // the integer totals of a call
+    DevBuf s[11];                                       // scratch of the lattice build and of the extraction
+};
+
 struct TimerRec {
     double total_ms = 0;
     long long launches = 0;
@@ -302,6 +315,8 @@ struct me_ctx {
     me_ctx *twin = nullptr;  // owned by the primary context
     me::Mesh own_mesh;       // the resident mesh lives in the primary context; a twin's `mesh` points at it
     me::Mesh *mesh = &own_mesh;
+    me::Recon own_recon;     // the last reconstruction, likewise
+    me::Recon *recon = &own_recon;
     // called by cloud_build_index right after its radix sort has been QUEUED on the context's stream (me_run_suite_from's second lane
     // uses it to let the main lane order its MME behind the sort: me_suite.hip)
     void (*sort_hook)(void *arg, hipStream_t stream) = nullptr;
@@ -577,6 +592,14 @@ int mesh_distance(me_ctx *ctx, int qslot, const me_mesh_params *p, me_mesh_out *
 int mesh_distance_fetch(me_ctx *ctx, int qslot, double *d2_host, int32_t *tri_host, uint8_t *region_host, double *closest_host,
                         double *signed_host);
 int mesh_sample(me_ctx *ctx, int dst_slot, long long n_points, unsigned long long seed);
+// ---- me_recon.hip ----
+int reconstruct(me_ctx *ctx, int slot, const me_recon_params *p, me_recon_out *out);
+int isosurface(me_ctx *ctx, const int32_t *node_ijk_host, const double *f_host, const uint8_t *valid_host, long long n_nodes, double voxel,
+               me_recon_out *out);
+int reconstruct_fetch(me_ctx *ctx, double *vertices_host, int32_t *vertex_edge_host, int32_t *triangles_host);
+int reconstruct_nodes_fetch(me_ctx *ctx, int32_t *node_ijk_host, double *f_host, int32_t *k_host, uint8_t *valid_host);
+int reconstruct_install(me_ctx *ctx);
+void reconstruct_drop(me_ctx *ctx);
 // ---- me_search.hip ----
 constexpr int kSearchSortTile = 512;  // entries of a radius row that one wave sorts in LDS; longer rows are sorted in global memory
 int knn_search(me_ctx *ctx, int qslot, int rslot, int k, const uint8_t *mask_host, int32_t *idx_host, double *d2_host);

@@ -545,6 +545,7 @@ int mesh_clear(me_ctx *ctx) {
     m.have = false;
     mesh_drop_results(ctx);
     m.tri_in.release(), m.tri_s.release(), m.orig.release(), m.cum.release(), m.boxes.release(), m.lv.release();
+    reconstruct_drop(ctx);  // (the last reconstruction goes with the mesh it may have become: me_recon.hip)
     return ME_OK;
 }
 

@@ -916,6 +916,67 @@ class Engine:
         d["significant"] = (fl & 2) != 0
         return d
 
+    # ---- surface reconstruction: IMLS field on a sparse voxel lattice + marching tetrahedra (me_recon.hip) ----
+    @staticmethod
+    def _recon_counts(o) -> dict:
+        return {k: int(getattr(o, k)) for k, _ in _lib.ReconOut._fields_}
+
+    def _recon_fetch(self, counts: dict) -> dict:
+        nv, nt = counts["n_vertices"], counts["n_triangles"]
+        d = {"vertices": np.empty((nv, 3), np.float64), "vertex_edge": np.empty((nv, 4), np.int32), "triangles": np.empty((nt, 3), np.int32)}
+        self._ck(self._L.me_reconstruct_fetch(self._ctx, _addr(d["vertices"]), _addr(d["vertex_edge"]), _addr(d["triangles"])))
+        return d
+
+    def reconstruct(self, slot: int, voxel: float, radius=None, min_k: int = 8, band: int = 1, fetch: bool = True, install: bool = False):
+        """me_reconstruct: the IMLS signed-distance field of the slot's points and resident normals (outward; orienting them is the
+        caller's job) on the nodes of the voxel lattice within `band` cells of the points, radius defaulting to 3 * voxel, and its
+        zero set by marching tetrahedra.  Returns the counts (n_occupied_cells, n_active_cells, n_nodes, n_valid_nodes,
+        n_cells_extracted, n_vertices, n_triangles, n_degenerate, sum_k) and, with fetch=True, vertices (V,3), vertex_edge (V,4) =
+        (i, j, k, dir) and triangles (T,3) in the same dict; install=True makes the result the resident mesh (mesh_distance).  The call
+        may re-index the slot and so discard the 1-NN, local-geometry, M3C2 and mesh-distance results: normals first, then
+        reconstruct, then nn1."""
+        p = _lib.ReconParams()
+        p.voxel, p.radius = float(voxel), float(3.0 * voxel if radius is None else radius)
+        p.min_k, p.band = int(min_k), int(band)
+        o = _lib.ReconOut()
+        self._ck(self._L.me_reconstruct(self._ctx, int(slot), C.byref(p), C.byref(o)))
+        res = self._recon_counts(o)
+        self._recon_n_nodes = res["n_nodes"]
+        if fetch:
+            res.update(self._recon_fetch(res))
+        if install:
+            self.reconstruct_install()
+        return res
+
+    def reconstruct_nodes(self) -> dict:
+        """me_reconstruct_nodes_fetch: node_ijk (n,3) int32 in the Morton order of the lattice frame, f, k (int32), valid (bool) of the
+        last reconstruct."""
+        self._ck(self._L.me_reconstruct_nodes_fetch(self._ctx, None, None, None, None))  # (raises without a node field)
+        n = int(self._recon_n_nodes)
+        d = {"node_ijk": np.empty((n, 3), np.int32), "f": np.empty(n, np.float64), "k": np.empty(n, np.int32)}
+        v = np.empty(n, np.uint8)
+        self._ck(self._L.me_reconstruct_nodes_fetch(self._ctx, _addr(d["node_ijk"]), _addr(d["f"]), _addr(d["k"]), _addr(v)))
+        d["valid"] = v != 0
+        return d
+
+    def isosurface(self, node_ijk, f, valid, voxel: float) -> dict:
+        """me_isosurface: marching tetrahedra of a sparse lattice field the caller supplies: node_ijk (n,3) int32, f (n,), valid (n,)
+        of zero / non-zero; a cell is extracted iff all 8 corners are present and valid.  Returns the counts and the three arrays."""
+        ijk = np.ascontiguousarray(node_ijk, dtype=np.int32).reshape(-1, 3)
+        fv = np.ascontiguousarray(f, dtype=np.float64).reshape(-1)
+        ok = np.ascontiguousarray(np.asarray(valid) != 0, dtype=np.uint8).reshape(-1)
+        if fv.shape[0] != ijk.shape[0] or ok.shape[0] != ijk.shape[0]:
+            raise ValueError("node_ijk, f and valid must have one entry per node")
+        o = _lib.ReconOut()
+        self._ck(self._L.me_isosurface(self._ctx, _addr(ijk), _addr(fv), _addr(ok), int(ijk.shape[0]), float(voxel), C.byref(o)))
+        res = self._recon_counts(o)
+        res.update(self._recon_fetch(res))
+        return res
+
+    def reconstruct_install(self):
+        """me_reconstruct_install: the last reconstruction becomes the resident mesh, as mesh_upload of the fetched arrays would."""
+        self._ck(self._L.me_reconstruct_install(self._ctx))
+
     # ---- cloud-to-mesh distance against a resident triangle mesh, and its area-uniform sample (me_mesh.hip) ----
     def mesh_upload(self, vertices, triangles, T=None):
         """me_mesh_upload: vertices (V,3) float64, triangles (F,3) int32 indices into them, T an optional 4x4 applied as upload() applies

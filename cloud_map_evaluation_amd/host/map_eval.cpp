@@ -447,11 +447,38 @@ Param loadParametersFromYAML(const std::string &yaml_file_path) {
     if (config.has("mesh_seed")) as_u64("mesh_seed", param.mesh_seed);
     if (param.evaluate_mesh_distance) {
         if (mesh_not_a_list) throw std::runtime_error("mesh_thresholds: must be a list [a, b, ...]");
-        if (param.gt_mesh_path.empty()) throw std::runtime_error("gt_mesh_path: required with evaluate_mesh_distance");
+        if (param.gt_mesh_path.empty() && !(config.has("evaluate_mesh") && config.as_bool("evaluate_mesh")))
+            throw std::runtime_error("gt_mesh_path: required with evaluate_mesh_distance");
         if (param.mesh_thresholds.size() > ME_MESH_MAX_THRESHOLDS) throw std::runtime_error("mesh_thresholds: at most 8 values");
         for (const double t : param.mesh_thresholds)
             if (!(t >= 0.0) || !std::isfinite(t)) throw std::runtime_error("mesh_thresholds: every value must be finite and >= 0");
         if (param.num_gpus > 1) throw std::runtime_error("evaluate_mesh_distance: single GPU only (num_gpus must be 1)");
+    }
+    // surface reconstruction (the reference's eva_mesh / createMeshFromPCD)
+    if (config.has("evaluate_mesh")) param.evaluate_mesh = config.as_bool("evaluate_mesh");
+    if (config.has("mesh_voxel_size")) param.mesh_voxel_size = config.as_double("mesh_voxel_size");
+    param.mesh_radius = config.has("mesh_radius") ? config.as_double("mesh_radius") : 3.0 * param.mesh_voxel_size;
+    if (config.has("mesh_min_points")) param.mesh_min_points = config.as_int("mesh_min_points");
+    if (config.has("mesh_band")) param.mesh_band = config.as_int("mesh_band");
+    param.mesh_normal_radius = config.has("mesh_normal_radius") ? config.as_double("mesh_normal_radius") : param.nn_radius_;
+    const bool viewpoint_not_a_list = config.has("mesh_viewpoint") && (!config.at("mesh_viewpoint").scalar.empty() || !config.at("mesh_viewpoint").rows.empty());
+    if (config.has("mesh_viewpoint"))
+        for (const auto &v : config.at("mesh_viewpoint").seq) param.mesh_viewpoint.push_back(yaml_lite::Document::to_double(v, "mesh_viewpoint"));
+    if (param.evaluate_mesh) {
+        if (!config.has("mesh_voxel_size")) throw std::runtime_error("mesh_voxel_size: required with evaluate_mesh");
+        if (!(param.mesh_voxel_size > 0) || !std::isfinite(param.mesh_voxel_size)) throw std::runtime_error("mesh_voxel_size: must be finite and > 0");
+        if (!(param.mesh_radius >= param.mesh_voxel_size) || !std::isfinite(param.mesh_radius))
+            throw std::runtime_error("mesh_radius: must be finite and >= mesh_voxel_size");
+        if (param.mesh_min_points < 1) throw std::runtime_error("mesh_min_points: must be >= 1");
+        if (param.mesh_band < 0 || param.mesh_band > 2) throw std::runtime_error("mesh_band: must be 0, 1 or 2");
+        if (!(param.mesh_normal_radius > 0) || !std::isfinite(param.mesh_normal_radius)) throw std::runtime_error("mesh_normal_radius: must be finite and > 0");
+        if (param.normal_min_points < 2) throw std::runtime_error("normal_min_points: must be >= 2 (the covariance divides by k - 1)");
+        if (viewpoint_not_a_list || (config.has("mesh_viewpoint") && param.mesh_viewpoint.size() != 3))
+            throw std::runtime_error("mesh_viewpoint: must be a list of 3 values [x, y, z]");
+        for (const double v : param.mesh_viewpoint)
+            if (!std::isfinite(v)) throw std::runtime_error("mesh_viewpoint: every value must be finite");
+        if (param.evaluate_noised_gt_) throw std::runtime_error("evaluate_mesh: not with evaluate_noised_gt");
+        if (param.num_gpus > 1) throw std::runtime_error("evaluate_mesh: single GPU only (num_gpus must be 1)");
     }
     return param;
 }
@@ -525,7 +552,13 @@ std::string paramToJson(const Param &p) {
     o << "], \"mesh_max_distance\": ";
     if (std::isinf(p.mesh_max_distance)) o << "Infinity";  // (what Python's json reads as inf)
     else o << p.mesh_max_distance;
-    o << ", \"mesh_sample_points\": " << p.mesh_sample_points << ", \"mesh_seed\": " << p.mesh_seed << "}";
+    o << ", \"mesh_sample_points\": " << p.mesh_sample_points << ", \"mesh_seed\": " << p.mesh_seed;
+    o << ", \"evaluate_mesh\": " << b(p.evaluate_mesh) << ", \"mesh_voxel_size\": " << p.mesh_voxel_size << ", \"mesh_radius\": " << p.mesh_radius
+      << ", \"mesh_min_points\": " << p.mesh_min_points << ", \"mesh_band\": " << p.mesh_band << ", \"mesh_normal_radius\": "
+      << p.mesh_normal_radius << ", \"mesh_viewpoint\": ";
+    if (p.mesh_viewpoint.empty()) o << "null";  // (the centre of each cloud's bounding box)
+    else o << "[" << p.mesh_viewpoint[0] << ", " << p.mesh_viewpoint[1] << ", " << p.mesh_viewpoint[2] << "]";
+    o << "}";
     return o.str();
 }
 
@@ -617,7 +650,9 @@ int MapEval::process() {
         return fail("evaluate_m3c2: single GPU only, with evaluate_using_initial and not with evaluate_noised_gt");
     const bool mesh = param_.evaluate_mesh_distance;  // (on resident clouds, the map moved by initial_matrix for it alone)
     if (mesh && comm_) return fail("evaluate_mesh_distance: single GPU only (num_gpus must be 1)");
-    if (one_call && !noised && !filter && !mpv && !planes && !mom && !surf && !m3c2 && !mesh && !(param_.downsample_size > 0)) {
+    const bool recon = param_.evaluate_mesh;  // (on resident clouds as loaded, first of all)
+    if (recon && (comm_ || noised)) return fail("evaluate_mesh: single GPU only (num_gpus must be 1), and not with evaluate_noised_gt");
+    if (one_call && !noised && !filter && !mpv && !planes && !mom && !surf && !m3c2 && !mesh && !recon && !(param_.downsample_size > 0)) {
         file_result << std::fixed << std::setprecision(15) << "Estimated-Ground Truth point count: " << map_3d_->size() << " / "
                     << gt_3d_->size() << std::endl;
         if (param_.enable_debug)
@@ -660,6 +695,21 @@ int MapEval::process() {
     if (param_.enable_debug)
         std::cout << "INFO: Loaded point clouds: " << map_3d_->size() << " points (Map), " << gt_3d_->size()
                   << " points (Ground Truth)." << std::endl;
+    if (recon) {
+        // before every other stage, on the clouds as loaded: it replaces both clouds' normals and may re-index them at mesh_radius.  Both
+        // clouds are then uploaded again from the host's copies with the normals their files brought (the restoration of the M3C2 block).
+        if (computeReconstruction() != 0) return -1;
+        if (me_upload_cloud(ctx_, ME_SLOT_GT, gt_3d_->points_.data(), (int64_t) gt_3d_->size(), nullptr, param_.nn_radius_) != ME_OK ||
+            me_upload_cloud(ctx_, ME_SLOT_EST, map_3d_->points_.data(), (int64_t) map_3d_->size(), nullptr, param_.nn_radius_) != ME_OK)
+            return fail(me_last_error(ctx_));
+        if (!(param_.downsample_size > 0) && !filter) {
+            if (gt_normals.size() == gt_3d_->points_.size() && !gt_normals.empty() && me_set_normals(ctx_, ME_SLOT_GT, gt_normals.data()) != ME_OK)
+                return fail(me_last_error(ctx_));
+            if (map_normals.size() == map_3d_->points_.size() && !map_normals.empty() &&
+                me_set_normals(ctx_, ME_SLOT_EST, map_normals.data()) != ME_OK)
+                return fail(me_last_error(ctx_));
+        }
+    }
     if (m3c2 || mesh) {
         // (the mesh stage, like M3C2, moves the map and may replace the ground-truth slot by the mesh's sample: same restoration)
         // FIRST of the stages on the resident clouds: it moves the map, replaces both clouds' normals and re-indexes both at the
@@ -1777,7 +1827,13 @@ int MapEval::computeMeshDistance() {
     std::vector<double> vx;
     std::vector<int32_t> tri;
     std::string err;
-    if (!pcio::read_ply_mesh(param_.gt_mesh_path, vx, tri, &err)) return bad(err);
+    if (param_.gt_mesh_path.empty() && param_.evaluate_mesh) {  // the ground truth's own reconstruction (computeReconstruction ran before)
+        vx = recon_vertices[ME_SLOT_GT];
+        tri = recon_triangles[ME_SLOT_GT];
+        if (tri.empty()) return bad("the reconstruction of the ground truth has no triangle (mesh_voxel_size, mesh_min_points)");
+    } else if (!pcio::read_ply_mesh(param_.gt_mesh_path, vx, tri, &err)) {
+        return bad(err);
+    }
     if (me_mesh_upload(ctx_, vx.data(), (int64_t) (vx.size() / 3), tri.data(), (int64_t) (tri.size() / 3), nullptr) != ME_OK ||
         me_mesh_info(ctx_, &mesh_info) != ME_OK)
         return bad(me_last_error(ctx_));
@@ -1821,6 +1877,68 @@ int MapEval::computeMeshDistance() {
     }
     if (me_mesh_clear(ctx_) != ME_OK) return bad(me_last_error(ctx_));
     return 0;
+}
+
+// evaluate_mesh: on each cloud as loaded, me_radius_normals at mesh_normal_radius (normal_min_points neighbours) turned towards
+// mesh_viewpoint, or towards the centre of the cloud's bounding box, then me_reconstruct; the meshes are kept on the host for the writers
+// and for computeMeshDistance.
+int MapEval::computeReconstruction() {
+    auto bad = [&](const std::string &m) { return fail("evaluate_mesh: " + m); };
+    me_recon_params rp{};
+    rp.voxel = param_.mesh_voxel_size;
+    rp.radius = param_.mesh_radius;
+    rp.min_k = (int32_t) param_.mesh_min_points;
+    rp.band = (int32_t) param_.mesh_band;
+    for (int s = ME_SLOT_EST; s <= ME_SLOT_GT; ++s) {
+        const std::vector<double> &pts = s == ME_SLOT_EST ? map_3d_->points_ : gt_3d_->points_;
+        double *vp = recon_viewpoint[s];
+        if (param_.mesh_viewpoint.size() == 3) {
+            for (int d = 0; d < 3; ++d) vp[d] = param_.mesh_viewpoint[(size_t) d];
+        } else {
+            double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+            for (size_t i = 0; i + 2 < pts.size(); i += 3)
+                for (int d = 0; d < 3; ++d) lo[d] = std::fmin(lo[d], pts[i + d]), hi[d] = std::fmax(hi[d], pts[i + d]);
+            for (int d = 0; d < 3; ++d) vp[d] = pts.empty() ? 0.0 : 0.5 * (lo[d] + hi[d]);
+        }
+        if (me_radius_normals(ctx_, s, param_.mesh_normal_radius, param_.normal_min_points, vp, 0, &recon_normals[s]) != ME_OK ||
+            me_reconstruct(ctx_, s, &rp, &recon_out[s]) != ME_OK)
+            return bad(me_last_error(ctx_));
+        recon_vertices[s].assign((size_t) recon_out[s].n_vertices * 3, 0.0);
+        recon_triangles[s].assign((size_t) recon_out[s].n_triangles * 3, 0);
+        if (me_reconstruct_fetch(ctx_, recon_vertices[s].data(), nullptr, recon_triangles[s].data()) != ME_OK) return bad(me_last_error(ctx_));
+    }
+    return 0;
+}
+
+// gt_mesh.ply / est_mesh.ply (the reference's names, map_eval.cpp:509-523) and reconstruction.txt: the parameters ("name value"), then per
+// cloud ("<est|gt> name value ...") the viewpoint, the normals' counts and the counts of me_recon_out.
+void MapEval::saveReconstruction() {
+    std::string err;
+    for (int s = ME_SLOT_EST; s <= ME_SLOT_GT; ++s) {
+        const std::string path = results_subfolder + (s == ME_SLOT_EST ? "est_mesh.ply" : "gt_mesh.ply");
+        if (!pcio::write_ply_mesh(path, recon_vertices[s], recon_triangles[s], &err)) fail("evaluate_mesh: " + err);
+    }
+    const std::string path = results_subfolder + "reconstruction.txt";
+    std::FILE *f = std::fopen(path.c_str(), "w");
+    if (!f) {
+        fail("cannot open " + path);
+        return;
+    }
+    std::fprintf(f, "voxel %.17g\nradius %.17g\nmin_points %d\nband %d\nnormal_radius %.17g\nnormal_min_points %d\n", param_.mesh_voxel_size,
+                 param_.mesh_radius, param_.mesh_min_points, param_.mesh_band, param_.mesh_normal_radius, param_.normal_min_points);
+    for (int s = ME_SLOT_EST; s <= ME_SLOT_GT; ++s) {
+        const char *tag = s == ME_SLOT_EST ? "est" : "gt";
+        const me_recon_out &o = recon_out[s];
+        std::fprintf(f, "%s viewpoint %.17g %.17g %.17g\n", tag, recon_viewpoint[s][0], recon_viewpoint[s][1], recon_viewpoint[s][2]);
+        std::fprintf(f, "%s normals %lld %lld %lld\n", tag, (long long) recon_normals[s].n, (long long) recon_normals[s].n_valid,
+                     (long long) recon_normals[s].sum_k);
+        std::fprintf(f, "%s n_occupied_cells %lld\n%s n_active_cells %lld\n%s n_nodes %lld\n%s n_valid_nodes %lld\n%s n_cells_extracted %lld\n", tag,
+                     (long long) o.n_occupied_cells, tag, (long long) o.n_active_cells, tag, (long long) o.n_nodes, tag, (long long) o.n_valid_nodes,
+                     tag, (long long) o.n_cells_extracted);
+        std::fprintf(f, "%s n_vertices %lld\n%s n_triangles %lld\n%s n_degenerate %lld\n%s sum_k %lld\n", tag, (long long) o.n_vertices, tag,
+                     (long long) o.n_triangles, tag, (long long) o.n_degenerate, tag, (long long) o.sum_k);
+    }
+    if (std::fclose(f) != 0) fail("writing " + path + " failed");
 }
 
 void MapEval::saveMeshDistance() {
@@ -1934,6 +2052,7 @@ void MapEval::saveRegistrationResults() {
     if (param_.evaluate_surface_error) saveSurfaceError();
     if (param_.evaluate_m3c2) saveM3C2();
     if (param_.evaluate_mesh_distance) saveMeshDistance();
+    if (param_.evaluate_mesh) saveReconstruction();
     file_result << std::fixed << std::setprecision(5) << "VMD: " << vmd << std::endl;
     file_result << std::fixed << std::setprecision(5) << "SCS: " << scs_overall << std::endl;
     if (param_.evaluate_using_initial_)

@@ -162,6 +162,17 @@ struct Param {
     double mesh_max_distance = INFINITY;       // `mesh_max_distance:` matched iff d <= this; <= 0 or absent: every point
     int64_t mesh_sample_points = 0;            // `mesh_sample_points:` > 0: also the mesh sampled into the ground-truth slot, 1-NN both ways
     uint64_t mesh_seed = 0;                    // `mesh_seed:` the sampler's seed
+    // surface reconstruction of both clouds (optional keys; the reference's createMeshFromPCD, map_eval.cpp:777-826, with the library's
+    // IMLS field + marching tetrahedra instead of Poisson): radius normals turned towards a viewpoint on each cloud as loaded,
+    // me_reconstruct, gt_mesh.ply / est_mesh.ply (the reference's names) and reconstruction.txt in the results folder (single GPU).
+    // With evaluate_mesh_distance and no gt_mesh_path the map is measured against the reconstructed ground-truth mesh.
+    bool evaluate_mesh = false;                // `evaluate_mesh:` the reference's hard-coded eva_mesh
+    double mesh_voxel_size = 0.0;              // `mesh_voxel_size:` the lattice's voxel (required with evaluate_mesh)
+    double mesh_radius = 0.0;                  // `mesh_radius:` the field's support (default 3 mesh_voxel_size), >= mesh_voxel_size
+    int mesh_min_points = 8;                   // `mesh_min_points:` points a node needs, >= 1
+    int mesh_band = 1;                         // `mesh_band:` cells around the occupied ones, 0 .. 2
+    double mesh_normal_radius = 0.0;           // `mesh_normal_radius:` radius of the normals (default nn_radius)
+    std::vector<double> mesh_viewpoint;        // `mesh_viewpoint: [x, y, z]` the normals point towards it (default: each cloud's bbox centre)
     int dist_rank = 0;              // (set by the launcher, not a YAML key)
     void printParam() const;
 };
@@ -211,6 +222,8 @@ public:
     void saveM3C2();                                        // its result line and m3c2.txt
     int computeMeshDistance();                              // evaluate_mesh_distance: me_mesh_distance of the moved map (no reference counterpart)
     void saveMeshDistance();                                // its two result lines and mesh_distance.txt
+    int computeReconstruction();                            // evaluate_mesh: radius normals + me_reconstruct on both clouds as loaded
+    void saveReconstruction();                              // gt_mesh.ply, est_mesh.ply, reconstruction.txt
     void saveErrorDistribution();                           // its three result lines and error_distribution.txt
     int writeRegistrationInformation();                     // registration_information.txt (icp_information_matrix; no reference counterpart)
     int globalRegistration(double T_c[16]);                 // global_registration.txt (global_registration; no reference counterpart)                                   // noise_sweep.txt (noise_sweep; no reference counterpart)
@@ -244,6 +257,11 @@ public:
     std::vector<double> mesh_quantile;
     me_errdist_out mesh_sampled[2] = {};        // ... with mesh_sample_points: 1-NN error of the map in the sample and the reverse
     double mesh_prf[ME_MESH_MAX_THRESHOLDS][3] = {};
+    me_recon_out recon_out[2] = {};             // evaluate_mesh: per slot the counts, the normals' info, the viewpoint used and the mesh
+    me_radius_normals_out recon_normals[2] = {};
+    double recon_viewpoint[2][3] = {};
+    std::vector<double> recon_vertices[2];
+    std::vector<int32_t> recon_triangles[2];
     me_mom_out mom_out[2] = {};  // evaluate_mom: [ME_SLOT_EST], [ME_SLOT_GT] (the latter with evaluate_gt_mom)
     me_local_geom_out mpv_out[2] = {};  // evaluate_mpv: [ME_SLOT_EST], [ME_SLOT_GT] (the latter with evaluate_gt_mpv)
     std::vector<double> est_entropies, gt_entropies;

@@ -444,6 +444,34 @@ inline bool read_ply_mesh(const std::string &path, std::vector<double> &xyz, std
     return true;
 }
 
+// A triangle mesh as a binary_little_endian PLY: `double` x y z per vertex and a `list uchar int vertex_indices` face element, what
+// read_ply_mesh reads back bit for bit (the reference's gt_mesh.ply / est_mesh.ply, map_eval.cpp:509-523).  A mesh without triangles is
+// written with `element face 0`.
+inline bool write_ply_mesh(const std::string &path, const std::vector<double> &xyz, const std::vector<int32_t> &tri, std::string *err = nullptr) {
+    auto fail = [&](const std::string &m) {
+        if (err) *err = m;
+        return false;
+    };
+    if (xyz.size() % 3 != 0 || tri.size() % 3 != 0) return fail("write_ply_mesh: the arrays must hold whole vertices and triangles");
+    const size_t nv = xyz.size() / 3, nt = tri.size() / 3;
+    for (const int32_t i : tri)
+        if (i < 0 || (size_t) i >= nv) return fail("write_ply_mesh: triangle index " + std::to_string(i) + " is outside [0, " + std::to_string(nv) + ")");
+    std::ofstream f(path, std::ios::binary);
+    if (!f.is_open()) return fail("cannot open " + path + " for writing");
+    f << "ply\nformat binary_little_endian 1.0\nelement vertex " << nv << "\nproperty double x\nproperty double y\nproperty double z\n"
+      << "element face " << nt << "\nproperty list uchar int vertex_indices\nend_header\n";
+    if (nv) f.write(reinterpret_cast<const char *>(xyz.data()), (std::streamsize) (nv * 24));
+    std::vector<unsigned char> rows(nt * 13);
+    for (size_t t = 0; t < nt; ++t) {
+        rows[13 * t] = 3;
+        std::memcpy(&rows[13 * t + 1], &tri[3 * t], 12);
+    }
+    if (nt) f.write(reinterpret_cast<const char *>(rows.data()), (std::streamsize) rows.size());
+    f.flush();
+    if (!f) return fail("write error on " + path);
+    return true;
+}
+
 // binary PCD writer: x y z as float64 (8-byte F fields) and an optional packed-float rgb column
 inline bool write_pcd(const std::string &path, const double *xyz, size_t n, const float *rgb_packed = nullptr) {
     std::ofstream f(path, std::ios::binary);

@@ -884,6 +884,71 @@ int me_mesh_distance(me_ctx *ctx, int query_slot, const me_mesh_params *p, me_me
 int me_mesh_distance_fetch(me_ctx *ctx, int query_slot, double *d2, int32_t *tri, uint8_t *region, double *closest, double *signed_d);
 int me_mesh_sample(me_ctx *ctx, int dst_slot, int64_t n_points, uint64_t seed);
 
+/* ---- surface reconstruction of a resident cloud into a triangle mesh ------------------------------------------------------------------ */
+/*   Stands in for the reference's createMeshFromPCD (map_eval.cpp:777-826, called at :194-205), a Poisson
+ * solve, with a LOCAL, deterministic reconstruction whose every number has a stated definition: an implicit-moving-least-squares
+ * (IMLS) signed-distance field on a sparse voxel lattice, from the points of a slot and their resident normals, and its zero set by
+ * marching tetrahedra.  tests/_recon_ref.py restates everything below.  All arithmetic is fp64 without contraction.  The result is
+ * held on the primary context (a twin sees it), like the resident mesh, until the next call of either producer or until the mesh
+ * clear call.  All five entry points are single GPU only (slab or shard mode: ME_ERR_ARG).
+ * Consistent orientation of the normals is the CALLER's job (a viewpoint for the radius normals, or the set-normals call): normals point
+ * outward.  Propagating an orientation across the cloud, hole filling, smoothing, the reference's density trimming and multi-GPU slabs
+ * are out of scope.
+ *
+ * PARAMETERS.  voxel h > 0, finite; radius R finite, R >= h; min_k >= 1; band in {0, 1, 2}.
+ * LATTICE.  The cell of a point is floor(p / h) per axis (a division, getVoxelIndex's).  Node (i, j, k) sits at x = (double(i)*h,
+ *   double(j)*h, double(k)*h).  OCCUPIED cells: the cells of the slot's points.  ACTIVE cells: the occupied cells and every cell within
+ *   Chebyshev distance `band` of one.  NODES: the distinct corners of the active cells.  The active cells must span at most 2^21 - 1
+ *   cells per axis (the 21-bit Morton frame) and |floor(p / h)| < 2^30, else ME_ERR_ARG.
+ * FIELD at a node.  The slot's points p with d = x - p and d2 = (dx*dx + dy*dy) + dz*dz < R*R (strict; R*R formed once), skipping every
+ *   point whose stored normal n is the zero vector or has a non-finite component (it contributes nothing and is not counted):
+ *       q = 1 - d2 / (R*R)     w = (q*q) * (q*q)     s = (nx*dx + ny*dy) + nz*dz
+ *   k = the count, W = sum w, S = sum w*s.  The node is VALID iff k >= min_k and W > 0, and then f = S / W (f = 0 otherwise).  The order
+ *   of the two sums is the neighbourhood stream's and not part of the definition: with |n| <= 1, f is within (2k + 4) 2^-53 R of the
+ *   exactly rounded sums' quotient; k and validity are exact.  A node is INSIDE iff f < 0 (0 and -0.0 are outside).
+ * EXTRACTION.  A cell is extracted iff it is active and all 8 corners are valid.  It is cut into the 6 Kuhn tetrahedra around the
+ *   diagonal (0,0,0)-(1,1,1): for each permutation (a, b, c) of the axes, in lexicographic order, v0 = corner 0, v1 = v0 + e_a,
+ *   v2 = v1 + e_b, v3 = v2 + e_c (translation invariant; matches across cell faces).  Its edges are the 7 directions out of a node,
+ *   dir 0 .. 6 = 100 010 001 110 101 011 111 (dx dy dz).  A VERTEX exists on the edge from origin node a to b = a + dir iff both ends
+ *   are valid, exactly one is inside and at least one extracted cell contains the edge; per coordinate, from the ORIGIN whichever end
+ *   is inside:   t = clamp01(fa / (fa - fb)) (t < 0 -> 0, t > 1 -> 1)     v = xa + t * (xb - xa)
+ *   Triangles of a tetrahedron, tetrahedron-local corner indices ascending, E(x, y) = the vertex on the edge between corners x and y:
+ *       one inside corner p, others q1 q2 q3:      (E(p,q1), E(p,q2), E(p,q3)); kept iff det[q1-p, q2-p, q3-p] > 0
+ *       three inside, p the outside corner:        the same triangle from p;    kept iff det[q1-p, q2-p, q3-p] < 0
+ *       two inside p q, two outside r s:           the quad E(p,r) E(p,s) E(q,s) E(q,r) as (0,1,2) (0,2,3); kept iff det[r-p, s-p, q-p] > 0
+ *   "not kept" swaps the last two corners of each triangle.  The determinants are of integer lattice vectors, never of positions:
+ *   (B-A) x (C-A) points from inside to outside, the sign convention of the mesh distance (signed_d > 0 outside).  A triangle whose
+ *   corners coincide (t was 0 or 1) is kept; n_degenerate counts the triangles the mesh upload would call degenerate.
+ * OUTPUT.  vertices double[V][3], vertex_edge int32[V][4] = (i, j, k, dir), triangles int32[T][3].  The order is the implementation's
+ *   (vertices ascending by (Morton code of the origin node in the lattice frame, dir), triangles cell by cell in that Morton order,
+ *   tetrahedron by tetrahedron) and a pure function of the input: two calls return identical bytes.  V or T >= 2^31: ME_ERR_ARG.
+ *
+ * me_reconstruct: field and extraction for the cloud of `slot`.  The slot's index is brought to a cell edge >= R by the M3C2 rule
+ *   (kept if R (1 + 2^-20) <= cell <= 1.5 R (1 + 2^-20), else rebuilt at R): a rebuild re-sorts the slot and discards the 1-NN results
+ *   of both slots, the slot's local-geometry, M3C2 and mesh-distance results and the other slot's M3C2 result; points and normals stay.
+ *   ME_ERR_STATE: no cloud, or no normals on the slot.  ME_ERR_ARG: bad parameters.  A cloud that yields no extracted cell is not an
+ *   error: zeros.  Device timers "recon_field" and "recon_extract"; the sorts of the lattice build report under "sort".
+ * me_isosurface: the same extraction stage on a lattice field the caller supplies: node_ijk int32[n_nodes][3], f[n_nodes],
+ *   valid uint8[n_nodes] (host).  A cell is extracted iff all 8 corners are present and valid.  ME_ERR_ARG: a duplicate node, a
+ *   non-finite f on a valid node, nodes spanning more than 2^21 - 1 on an axis.  n_nodes = 0 or 1: an empty result.
+ * me_reconstruct_fetch: the mesh; every pointer nullable.  ME_ERR_STATE without a reconstruction.
+ * me_reconstruct_nodes_fetch: node_ijk int32[n_nodes][3] (Morton order of the lattice frame), f, k int32, valid uint8; every pointer
+ *   nullable.  ME_ERR_STATE without one, and after me_isosurface (which keeps no node field).
+ * me_reconstruct_install: the reconstruction becomes the resident mesh, exactly as me_mesh_upload of the fetched arrays (T = NULL).
+ *   ME_ERR_STATE when there are no triangles. */
+typedef struct me_recon_params {
+    double voxel, radius;
+    int32_t min_k, band;
+} me_recon_params;
+typedef struct me_recon_out {
+    int64_t n_occupied_cells, n_active_cells, n_nodes, n_valid_nodes, n_cells_extracted, n_vertices, n_triangles, n_degenerate, sum_k;
+} me_recon_out;
+int me_reconstruct(me_ctx *ctx, int slot, const me_recon_params *p, me_recon_out *out);
+int me_isosurface(me_ctx *ctx, const int32_t *node_ijk, const double *f, const uint8_t *valid, int64_t n_nodes, double voxel, me_recon_out *out);
+int me_reconstruct_fetch(me_ctx *ctx, double *vertices, int32_t *vertex_edge, int32_t *triangles);
+int me_reconstruct_nodes_fetch(me_ctx *ctx, int32_t *node_ijk, double *f, int32_t *k, uint8_t *valid);
+int me_reconstruct_install(me_ctx *ctx);
+
 /* ---- neighbour lists between the resident clouds: KDTreeFlann::SearchKNN / SearchHybrid / SearchRadius for every point of a
  * cloud (the reference's loops over them: map_eval.cpp:1213-1218, 1448-1454, 1670) ---- */
 /* The three searches below hand the neighbours themselves to the caller, for every point of query_slot among the points of
