@@ -11,7 +11,9 @@
 // (see "voxel statistics straight from the Morton-sorted cloud" below): two-pass mean / M2.  Tables come out in ascending
 // (ix,iy,iz) order; est/gt are joined by binary search, W is one voxel pair per lane, SCS is one wavefront per
 // voxel over the (2r+1)^3 stencil with hash probes.
+#include <array>
 #include <cmath>
+#include <cstring>
 
 #include <utility>
 
@@ -700,6 +702,7 @@ static int scs_device(me_ctx *ctx, const unsigned long long *mkey, const double 
     ME_CHECK(ctx, hipMemsetAsync(hk.p, 0xFF, (size_t) hsize * 8, ctx->stream));
     hipLaunchKernelGGL(k_hash_insert_keys, dim3(blocks_of(M)), dim3(256), 0, ctx->stream, mkey, M, hk.as<unsigned long long>(),
                        hv.as<unsigned int>(), (unsigned int) (hsize - 1));
+    ME_CHECK(ctx, hipGetLastError());  // a refused launch is an error here, not a sum over an unwritten buffer later
     const int side = 2 * scs_radius + 1;
     const size_t lds = (size_t) side * side * side * 8;
     {
@@ -708,8 +711,10 @@ static int scs_device(me_ctx *ctx, const unsigned long long *mkey, const double 
                            hv.as<unsigned int>(), (unsigned int) (hsize - 1), scs_radius, scs_d.as<double>(),
                            has_d.as<unsigned int>());
     }
+    ME_CHECK(ctx, hipGetLastError());  // (the dynamic LDS of the stencil, 8 (2 r + 1)^3 bytes, is the launch most likely to be refused)
     hipLaunchKernelGGL(k_sum_masked, dim3(1), dim3(256), 0, ctx->stream, scs_d.as<double>(), has_d.as<unsigned int>(), M, d_sum,
                        d_count);
+    ME_CHECK(ctx, hipGetLastError());
     ME_CHECK(ctx, hipStreamSynchronize(ctx->stream));  // the local buffers die with this frame
     return ME_OK;
 }
@@ -726,7 +731,8 @@ __global__ void k_pack_keys(const int *__restrict__ k3, long long n, unsigned lo
     const long long i = (long long) blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const int x = k3[3 * i], y = k3[3 * i + 1], z = k3[3 * i + 2];
-    if (abs(x) >= kKeyBias - 16 || abs(y) >= kKeyBias - 16 || abs(z) >= kKeyBias - 16) *err = 1;
+    const int lim = kKeyBias - 16;  // (compared without abs(): abs(INT_MIN) is INT_MIN, which passed as "in range")
+    if (x <= -lim || x >= lim || y <= -lim || y >= lim || z <= -lim || z >= lim) *err = 1;
     out[i] = pack_key(x, y, z);
 }
 
@@ -760,6 +766,16 @@ int scs_table(me_ctx *ctx, const int32_t *keys, const double *w, long long n, in
     if (n == 0) {
         *scs = std::nan("");
         return ME_OK;
+    }
+    // W is a distance: a negative or NaN value is refused (k_scs marks an absent stencil cell with w < 0 in LDS, so a negative W
+    // would enter the mean and not the variance), and so is a key listed twice (the reference's map holds one W per voxel)
+    for (long long i = 0; i < n; ++i)
+        if (!(w[i] >= 0.0)) return ctx->fail(ME_ERR_ARG, "me_scs_table: w must be >= 0 and not NaN");
+    {
+        std::vector<std::array<int32_t, 3>> sk((size_t) n);
+        std::memcpy(sk.data(), keys, (size_t) n * 12);
+        std::sort(sk.begin(), sk.end());
+        if (std::adjacent_find(sk.begin(), sk.end()) != sk.end()) return ctx->fail(ME_ERR_ARG, "me_scs_table: duplicate voxel key");
     }
     ME_CHECK(ctx, hipSetDevice(ctx->device));
     DevBuf k3, kk, ww;

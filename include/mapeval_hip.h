@@ -1162,11 +1162,18 @@ int me_awd_scs(me_ctx *ctx, double voxel_size, int min_pts /*100, :280*/, int sc
 /* Batched VoxelCalculator::computeWassersteinDistanceGaussian(voxel1, voxel2) (voxel_calculator.hpp:69,
  * voxel_calculator.cpp:115-140) on caller-provided Gaussians: mu*[count][3], sigma*[count][9] (row-major, AS STORED
  * in VoxelInfo::sigma), n*[count] -> w[count].  Host pointers.  Lets the reference's own voxel_errors.txt be replayed
- * through the device kernel. */
+ * through the device kernel.  n <= 1: the identity stands in for the matrix, which is not read (:118, :126); otherwise
+ * sigma / (n - 1), its symmetric part, eigenvalues raised to 1e-6.  W = sqrt(max(0, D)) with max(0, NaN) = 0 as std::max(0.0, NaN):
+ * a NaN in mu or in a matrix that is read, or a Cholesky pivot that rounding made negative, gives W = 0, never NaN. */
 int me_w2_batch(me_ctx *ctx, const double *mu1, const double *sigma1, const int32_t *n1, const double *mu2,
                 const double *sigma2, const int32_t *n2, int64_t count, double *w);
 
-/* SCS of a caller-provided sparse W table (map_eval.cpp:347-389): keys[n][3] voxel indices, w[n].  Host pointers. */
+/* SCS of a caller-provided sparse W table (map_eval.cpp:347-389): keys[n][3] voxel indices, w[n].  Host pointers.
+ * scs_radius in [1, 10] (here and in me_awd_scs; the stencil's (2 r + 1)^3 doubles live in LDS, 74,088 bytes at 10; a launch the
+ * device refuses is ME_ERR_HIP, never ME_OK).  n = 0, or no voxel with a neighbour: NaN.  ME_ERR_ARG: a voxel index outside
+ * |index| < 2^20 - 16; a w that is negative or NaN (W is a distance; +0, -0 and large values are values like any other, and a
+ * voxel whose neighbours are all 0 gives 0 / 0 = NaN as the reference does); a key listed twice (the reference's map holds one W per
+ * voxel). */
 int me_scs_table(me_ctx *ctx, const int32_t *keys, const double *w, int64_t n, int scs_radius, double *scs);
 
 /* ---- whole suite in one call (what MapEval::process runs between load and save, map_eval.cpp:52-85) -------- */
