@@ -38,6 +38,7 @@ SYMBOLS = [
     "me_m3c2", "me_m3c2_fetch",
     "me_mesh_upload", "me_mesh_clear", "me_mesh_info", "me_mesh_distance", "me_mesh_distance_fetch", "me_mesh_sample",
     "me_reconstruct", "me_isosurface", "me_reconstruct_fetch", "me_reconstruct_nodes_fetch", "me_reconstruct_install",
+    "me_orient_normals", "me_orient_fetch",
     "me_knn_search", "me_hybrid_search", "me_radius_search", "me_search_sort_tile",
     "me_segment_planes", "me_plane_fetch", "me_plane_keep",
     "me_group_order_stats", "me_mom_select_axes", "me_mom", "me_mom_fetch",
@@ -429,6 +430,15 @@ class ReconOut(C.Structure):
                                          "n_triangles", "n_degenerate", "sum_k")]
 
 
+class OrientParams(C.Structure):
+    _fields_ = [("direction", C.c_double * 3), ("k", C.c_int32), ("inward", C.c_int32)]
+
+
+class OrientOut(C.Structure):
+    _fields_ = [(k, C.c_int64) for k in ("n", "n_valid", "n_components", "largest_component", "n_tree_edges", "n_graph_edges", "n_flipped",
+                                         "n_inconsistent_edges")]
+
+
 class SurfaceParams(C.Structure):
     _fields_ = [
         ("gate", C.c_double),
@@ -564,6 +574,10 @@ def load():
     L.me_reconstruct_nodes_fetch.argtypes = [vp, ip, dp, ip, vp]
     L.me_reconstruct_install.argtypes = [vp]
     for f in ("me_reconstruct", "me_isosurface", "me_reconstruct_fetch", "me_reconstruct_nodes_fetch", "me_reconstruct_install"):
+        getattr(L, f).restype = C.c_int
+    L.me_orient_normals.argtypes = [vp, C.c_int, C.POINTER(OrientParams), C.POINTER(OrientOut)]
+    L.me_orient_fetch.argtypes = [vp, C.c_int, ip, vp]
+    for f in ("me_orient_normals", "me_orient_fetch"):
         getattr(L, f).restype = C.c_int
     L.me_knn_search.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, ip, dp]
     L.me_hybrid_search.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_int, vp, ip, ip, dp]

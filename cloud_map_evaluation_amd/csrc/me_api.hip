@@ -447,6 +447,16 @@ int me_reconstruct_install(me_ctx *ctx) {
     return me::reconstruct_install(ctx);
 }
 
+int me_orient_normals(me_ctx *ctx, int slot, const me_orient_params *p, me_orient_out *out) {
+    if (!ctx) return ME_ERR_ARG;
+    return me::orient_normals(ctx, slot, p, out);
+}
+
+int me_orient_fetch(me_ctx *ctx, int slot, int32_t *component, uint8_t *flipped) {
+    if (!ctx) return ME_ERR_ARG;
+    return me::orient_fetch(ctx, slot, component, flipped);
+}
+
 int me_knn_search(me_ctx *ctx, int query_slot, int ref_slot, int k, const uint8_t *query_mask, int32_t *idx, double *d2) {
     if (!ctx) return ME_ERR_ARG;
     return me::knn_search(ctx, query_slot, ref_slot, k, query_mask, idx, d2);
@@ -911,6 +921,11 @@ int me_timer_get(me_ctx *ctx, const char *name, double *total_ms, int64_t *launc
     if (std::strcmp(name, "mme_refined") == 0) {  // queries recomputed by k_mme_refine (thin neighbourhoods) since the last reset; counted always
         if (total_ms) *total_ms = 0.0;
         if (launches) *launches = ctx->mme_refined;
+        return ME_OK;
+    }
+    if (std::strcmp(name, "orient_rounds") == 0) {  // Boruvka rounds of the context's last me_orient_normals (the last one finds no edge)
+        if (total_ms) *total_ms = 0.0;
+        if (launches) *launches = ctx->orient_rounds;
         return ME_OK;
     }
     if (std::strcmp(name, "rank_select_compactions") == 0 || std::strcmp(name, "rank_select_list") == 0) {

@@ -648,6 +648,7 @@ int cloud_upload(me_ctx *ctx, int slot, const double *src, bool src_on_device, l
         e.nn_ref_slot = -1;
         e.vox_valid = e.vox_merged = false;
         e.have_normals = e.have_cov = false;
+        e.orient_have = false;
         e.outlier_keep_valid = false;
         e.cluster_valid = false;
         e.plane_valid = false;
@@ -759,6 +760,7 @@ int cloud_finish(me_ctx *ctx, int slot, bool bbox_ready) {
     c.vox_merged = false;
     c.n_vox = 0;
     c.fpfh_valid = false;
+    c.orient_have = false;
     c.outlier_keep_valid = false;  // (the mask belongs to the points it was computed on)
     c.cluster_valid = false;
     c.plane_valid = false;

@@ -261,6 +261,10 @@ struct Cloud {
     // (cloud_build_index), with the points, and with the mesh (me_mesh_upload, me_mesh_clear)
     DevBuf mesh_d2, mesh_tri, mesh_reg, mesh_cp, mesh_sd;
     bool mesh_have = false;
+    // component (int32[n]) and flip byte per point of the last me_orient_normals, CLOUD order (me_orient.hip); dropped when the slot's
+    // normals or points are next replaced (cloud_finish, the normal producers, rotate_attributes)
+    DevBuf orient_comp, orient_flip;
+    bool orient_have = false;
 };
 
 // The resident triangle mesh (me_mesh.hip): one per primary context, beside the two clouds and untouched by what happens to them.
@@ -381,6 +385,7 @@ struct me_ctx {
     me::DevBuf mom_tmp[3];                       // me_mom.hip: selection keys, group bytes, the small state block (histograms, ranks, results)
     me::DevBuf rs_tmp[4];                        // me_errdist.hip: the select's state block, the two compacted lists, the use bytes
     long long rs_compact[2] = {0, 0};            // ... of the last select: compactions done, entries of the last list (me_timer_get)
+    long long orient_rounds = 0;                 // me_orient.hip: Boruvka rounds of the last me_orient_normals (me_timer_get "orient_rounds")
     me::DevBuf plane_tmp[7];                     // me_plane.hip: remaining flags and list, the compacted coordinates, hypotheses, scores, scalars
     me::DevBuf nn1_dbg_buf;                      // octree-walk counters (nodes opened, leaves scanned, points, max per query)
     unsigned long long *nn1_dbg() {
@@ -600,6 +605,9 @@ int reconstruct_fetch(me_ctx *ctx, double *vertices_host, int32_t *vertex_edge_h
 int reconstruct_nodes_fetch(me_ctx *ctx, int32_t *node_ijk_host, double *f_host, int32_t *k_host, uint8_t *valid_host);
 int reconstruct_install(me_ctx *ctx);
 void reconstruct_drop(me_ctx *ctx);
+// ---- me_orient.hip ----
+int orient_normals(me_ctx *ctx, int slot, const me_orient_params *p, me_orient_out *out);
+int orient_fetch(me_ctx *ctx, int slot, int32_t *component_host, uint8_t *flipped_host);
 // ---- me_search.hip ----
 constexpr int kSearchSortTile = 512;  // entries of a radius row that one wave sorts in LDS; longer rows are sorted in global memory
 int knn_search(me_ctx *ctx, int qslot, int rslot, int k, const uint8_t *mask_host, int32_t *idx_host, double *d2_host);

@@ -242,6 +242,7 @@ int run_local_geom(me_ctx *ctx, int slot, double radius, int min_k, const LgNorm
         TimerScope ts(ctx, nrm ? "radius_normals" : "local_geom");
         if (nrm) {
             c.have_normals = false;  // (the pass overwrites them: whatever was there is gone even if the call fails afterwards)
+            c.orient_have = false;
             ME_CHECK(ctx, c.normals.ensure((size_t) n * 24));
             LgNormalArgs na = *nrm;
             na.normals = c.normals.as<double>();

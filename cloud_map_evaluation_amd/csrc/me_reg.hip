@@ -656,6 +656,7 @@ int set_normals(me_ctx *ctx, int slot, const double *normals_host) {
     c.have_normals = true;
     c.have_cov = false;
     c.fpfh_valid = false;
+    c.orient_have = false;
     return ME_OK;
 }
 
@@ -705,6 +706,7 @@ int estimate_normals(me_ctx *ctx, int slot, int knn, double *normals_host, int32
     c.have_normals = true;
     c.have_cov = false;
     c.fpfh_valid = false;
+    c.orient_have = false;
     return ME_OK;
 }
 

@@ -916,6 +916,36 @@ class Engine:
         d["significant"] = (fl & 2) != 0
         return d
 
+    # ---- consistent normal orientation: one sign propagated over the k-NN graph (me_orient.hip) ----
+    def orient_normals(self, slot: int, k: int = 12, direction=(0.0, 0.0, 1.0), inward: bool = False, fetch: bool = False) -> dict:
+        """me_orient_normals: the resident normals of the slot made consistent by carrying one sign along the minimum spanning forest
+        of the k-NN graph weighted by 1 - |n_i . n_j| (Hoppe et al. 1992; Open3D's orient_normals_consistent_tangent_plane without its
+        Delaunay edges: every component of the k-NN graph has a root of its own).  Per component the root is the extreme point along
+        `direction` and is turned towards it (inward=True: against it).  The normals are replaced in place (get_normals); returns n,
+        n_valid, n_components, largest_component, n_tree_edges, n_graph_edges, n_flipped, n_inconsistent_edges and, with fetch=True,
+        component (int32[N], -1 for a point whose normal is the zero vector) and flipped (bool[N])."""
+        d = np.asarray(direction, dtype=np.float64).reshape(-1)
+        if d.shape[0] != 3:
+            raise ValueError("direction must have 3 components")
+        p = _lib.OrientParams()
+        p.direction[0], p.direction[1], p.direction[2] = float(d[0]), float(d[1]), float(d[2])
+        p.k, p.inward = int(k), 1 if inward else 0
+        o = _lib.OrientOut()
+        self._ck(self._L.me_orient_normals(self._ctx, int(slot), C.byref(p), C.byref(o)))
+        res = {name: int(getattr(o, name)) for name, _ in _lib.OrientOut._fields_}
+        if fetch:
+            res.update(self.orient_fetch(slot))
+        return res
+
+    def orient_fetch(self, slot: int) -> dict:
+        """me_orient_fetch: component (int32[N]) and flipped (bool[N]) of the slot's last orient_normals, in cloud order."""
+        self._ck(self._L.me_orient_fetch(self._ctx, int(slot), None, None))  # (raises without a current result, before the size is asked)
+        n = self.size(slot)
+        comp = np.empty(n, np.int32)
+        fl = np.empty(n, np.uint8)
+        self._ck(self._L.me_orient_fetch(self._ctx, int(slot), _addr(comp), _addr(fl)))
+        return {"component": comp, "flipped": fl != 0}
+
     # ---- surface reconstruction: IMLS field on a sparse voxel lattice + marching tetrahedra (me_recon.hip) ----
     @staticmethod
     def _recon_counts(o) -> dict:
@@ -927,14 +957,18 @@ class Engine:
         self._ck(self._L.me_reconstruct_fetch(self._ctx, _addr(d["vertices"]), _addr(d["vertex_edge"]), _addr(d["triangles"])))
         return d
 
-    def reconstruct(self, slot: int, voxel: float, radius=None, min_k: int = 8, band: int = 1, fetch: bool = True, install: bool = False):
+    def reconstruct(self, slot: int, voxel: float, radius=None, min_k: int = 8, band: int = 1, fetch: bool = True, install: bool = False,
+                    orient_k=None):
         """me_reconstruct: the IMLS signed-distance field of the slot's points and resident normals (outward; orienting them is the
-        caller's job) on the nodes of the voxel lattice within `band` cells of the points, radius defaulting to 3 * voxel, and its
+        caller's job: a viewpoint for radius_normals on a star-shaped scene, else orient_normals, which orient_k=<k> runs first with
+        its defaults) on the nodes of the voxel lattice within `band` cells of the points, radius defaulting to 3 * voxel, and its
         zero set by marching tetrahedra.  Returns the counts (n_occupied_cells, n_active_cells, n_nodes, n_valid_nodes,
         n_cells_extracted, n_vertices, n_triangles, n_degenerate, sum_k) and, with fetch=True, vertices (V,3), vertex_edge (V,4) =
         (i, j, k, dir) and triangles (T,3) in the same dict; install=True makes the result the resident mesh (mesh_distance).  The call
         may re-index the slot and so discard the 1-NN, local-geometry, M3C2 and mesh-distance results: normals first, then
         reconstruct, then nn1."""
+        if orient_k is not None:
+            self.orient_normals(slot, int(orient_k))
         p = _lib.ReconParams()
         p.voxel, p.radius = float(voxel), float(3.0 * voxel if radius is None else radius)
         p.min_k, p.band = int(min_k), int(band)

@@ -464,7 +464,17 @@ Param loadParametersFromYAML(const std::string &yaml_file_path) {
     const bool viewpoint_not_a_list = config.has("mesh_viewpoint") && (!config.at("mesh_viewpoint").scalar.empty() || !config.at("mesh_viewpoint").rows.empty());
     if (config.has("mesh_viewpoint"))
         for (const auto &v : config.at("mesh_viewpoint").seq) param.mesh_viewpoint.push_back(yaml_lite::Document::to_double(v, "mesh_viewpoint"));
+    if (config.has("mesh_orient")) param.mesh_orient = config.as_string("mesh_orient");
+    const double orient_k = config.has("mesh_orient_k") ? config.as_double("mesh_orient_k") : (double) param.mesh_orient_k;
+    const bool orient_k_ok = orient_k >= 1.0 && orient_k <= 39.0 && orient_k == std::floor(orient_k);
+    if (orient_k_ok) param.mesh_orient_k = (int) orient_k;  // (judged below, with the stage on; the stage off, a bad value leaves the default)
+    if (config.has("mesh_orient_inward")) param.mesh_orient_inward = config.as_bool("mesh_orient_inward");
     if (param.evaluate_mesh) {
+        if (param.mesh_orient != "viewpoint" && param.mesh_orient != "propagate")
+            throw std::runtime_error("mesh_orient: expected viewpoint or propagate, got '" + param.mesh_orient + "'");
+        if (!orient_k_ok) throw std::runtime_error("mesh_orient_k: must be an integer in 1 .. 39");
+        if (param.mesh_orient == "propagate" && config.has("mesh_viewpoint"))
+            throw std::runtime_error("mesh_viewpoint: not with mesh_orient: propagate (the orientation is propagated from a root, no viewpoint is used)");
         if (!config.has("mesh_voxel_size")) throw std::runtime_error("mesh_voxel_size: required with evaluate_mesh");
         if (!(param.mesh_voxel_size > 0) || !std::isfinite(param.mesh_voxel_size)) throw std::runtime_error("mesh_voxel_size: must be finite and > 0");
         if (!(param.mesh_radius >= param.mesh_voxel_size) || !std::isfinite(param.mesh_radius))
@@ -558,6 +568,13 @@ std::string paramToJson(const Param &p) {
       << p.mesh_normal_radius << ", \"mesh_viewpoint\": ";
     if (p.mesh_viewpoint.empty()) o << "null";  // (the centre of each cloud's bounding box)
     else o << "[" << p.mesh_viewpoint[0] << ", " << p.mesh_viewpoint[1] << ", " << p.mesh_viewpoint[2] << "]";
+    o << ", \"mesh_orient\": \"";
+    for (const char c : p.mesh_orient) {  // (judged only with evaluate_mesh: the stage off, any text passes through)
+        if (c == '"' || c == '\\') o << '\\' << c;
+        else if ((unsigned char) c < 0x20) o << ' ';
+        else o << c;
+    }
+    o << "\", \"mesh_orient_k\": " << p.mesh_orient_k << ", \"mesh_orient_inward\": " << b(p.mesh_orient_inward);
     o << "}";
     return o.str();
 }
@@ -1881,7 +1898,8 @@ int MapEval::computeMeshDistance() {
 
 // evaluate_mesh: on each cloud as loaded, me_radius_normals at mesh_normal_radius (normal_min_points neighbours) turned towards
 // mesh_viewpoint, or towards the centre of the cloud's bounding box, then me_reconstruct; the meshes are kept on the host for the writers
-// and for computeMeshDistance.
+// and for computeMeshDistance.  With mesh_orient: propagate the radius normals are left unoriented (no viewpoint) and me_orient_normals
+// (mesh_orient_k neighbours, direction +z, mesh_orient_inward) gives them one sign per component of the k-NN graph before me_reconstruct.
 int MapEval::computeReconstruction() {
     auto bad = [&](const std::string &m) { return fail("evaluate_mesh: " + m); };
     me_recon_params rp{};
@@ -1889,9 +1907,23 @@ int MapEval::computeReconstruction() {
     rp.radius = param_.mesh_radius;
     rp.min_k = (int32_t) param_.mesh_min_points;
     rp.band = (int32_t) param_.mesh_band;
+    const bool propagate = param_.mesh_orient == "propagate";
+    me_orient_params op{};
+    op.direction[2] = 1.0;
+    op.k = (int32_t) param_.mesh_orient_k;
+    op.inward = param_.mesh_orient_inward ? 1 : 0;
     for (int s = ME_SLOT_EST; s <= ME_SLOT_GT; ++s) {
         const std::vector<double> &pts = s == ME_SLOT_EST ? map_3d_->points_ : gt_3d_->points_;
         double *vp = recon_viewpoint[s];
+        if (propagate) {  // unoriented radius normals, one sign carried over the k-NN graph from the top point of every component
+            if (me_radius_normals(ctx_, s, param_.mesh_normal_radius, param_.normal_min_points, nullptr, 0, &recon_normals[s]) != ME_OK ||
+                me_orient_normals(ctx_, s, &op, &recon_orient[s]) != ME_OK || me_reconstruct(ctx_, s, &rp, &recon_out[s]) != ME_OK)
+                return bad(me_last_error(ctx_));
+            recon_vertices[s].assign((size_t) recon_out[s].n_vertices * 3, 0.0);
+            recon_triangles[s].assign((size_t) recon_out[s].n_triangles * 3, 0);
+            if (me_reconstruct_fetch(ctx_, recon_vertices[s].data(), nullptr, recon_triangles[s].data()) != ME_OK) return bad(me_last_error(ctx_));
+            continue;
+        }
         if (param_.mesh_viewpoint.size() == 3) {
             for (int d = 0; d < 3; ++d) vp[d] = param_.mesh_viewpoint[(size_t) d];
         } else {
@@ -1911,7 +1943,8 @@ int MapEval::computeReconstruction() {
 }
 
 // gt_mesh.ply / est_mesh.ply (the reference's names, map_eval.cpp:509-523) and reconstruction.txt: the parameters ("name value"), then per
-// cloud ("<est|gt> name value ...") the viewpoint, the normals' counts and the counts of me_recon_out.
+// cloud ("<est|gt> name value ...") the viewpoint, the normals' counts and the counts of me_recon_out.  With mesh_orient: propagate the
+// parameters gain three "orient..." lines and the viewpoint line of each cloud becomes "Orientation <est|gt>: " + the 8 integers of me_orient_out.
 void MapEval::saveReconstruction() {
     std::string err;
     for (int s = ME_SLOT_EST; s <= ME_SLOT_GT; ++s) {
@@ -1926,10 +1959,17 @@ void MapEval::saveReconstruction() {
     }
     std::fprintf(f, "voxel %.17g\nradius %.17g\nmin_points %d\nband %d\nnormal_radius %.17g\nnormal_min_points %d\n", param_.mesh_voxel_size,
                  param_.mesh_radius, param_.mesh_min_points, param_.mesh_band, param_.mesh_normal_radius, param_.normal_min_points);
+    if (param_.mesh_orient == "propagate") std::fprintf(f, "orient propagate\norient_k %d\norient_inward %d\n", param_.mesh_orient_k, param_.mesh_orient_inward ? 1 : 0);
     for (int s = ME_SLOT_EST; s <= ME_SLOT_GT; ++s) {
         const char *tag = s == ME_SLOT_EST ? "est" : "gt";
         const me_recon_out &o = recon_out[s];
-        std::fprintf(f, "%s viewpoint %.17g %.17g %.17g\n", tag, recon_viewpoint[s][0], recon_viewpoint[s][1], recon_viewpoint[s][2]);
+        if (param_.mesh_orient == "propagate") {  // in place of the viewpoint: the integers of me_orient_out, in the struct's order
+            const me_orient_out &r = recon_orient[s];
+            std::fprintf(f, "Orientation %s: %lld %lld %lld %lld %lld %lld %lld %lld\n", tag, (long long) r.n, (long long) r.n_valid,
+                         (long long) r.n_components, (long long) r.largest_component, (long long) r.n_tree_edges, (long long) r.n_graph_edges,
+                         (long long) r.n_flipped, (long long) r.n_inconsistent_edges);
+        } else
+            std::fprintf(f, "%s viewpoint %.17g %.17g %.17g\n", tag, recon_viewpoint[s][0], recon_viewpoint[s][1], recon_viewpoint[s][2]);
         std::fprintf(f, "%s normals %lld %lld %lld\n", tag, (long long) recon_normals[s].n, (long long) recon_normals[s].n_valid,
                      (long long) recon_normals[s].sum_k);
         std::fprintf(f, "%s n_occupied_cells %lld\n%s n_active_cells %lld\n%s n_nodes %lld\n%s n_valid_nodes %lld\n%s n_cells_extracted %lld\n", tag,

@@ -173,6 +173,9 @@ struct Param {
     int mesh_band = 1;                         // `mesh_band:` cells around the occupied ones, 0 .. 2
     double mesh_normal_radius = 0.0;           // `mesh_normal_radius:` radius of the normals (default nn_radius)
     std::vector<double> mesh_viewpoint;        // `mesh_viewpoint: [x, y, z]` the normals point towards it (default: each cloud's bbox centre)
+    std::string mesh_orient = "viewpoint";     // `mesh_orient: viewpoint | propagate`: propagate = me_orient_normals after unoriented radius normals
+    int mesh_orient_k = 12;                    // `mesh_orient_k`: neighbours of the orientation graph, 1 .. 39
+    bool mesh_orient_inward = false;           // `mesh_orient_inward`: the roots are turned against +z instead of towards it
     int dist_rank = 0;              // (set by the launcher, not a YAML key)
     void printParam() const;
 };
@@ -260,6 +263,7 @@ public:
     me_recon_out recon_out[2] = {};             // evaluate_mesh: per slot the counts, the normals' info, the viewpoint used and the mesh
     me_radius_normals_out recon_normals[2] = {};
     double recon_viewpoint[2][3] = {};
+    me_orient_out recon_orient[2] = {};
     std::vector<double> recon_vertices[2];
     std::vector<int32_t> recon_triangles[2];
     me_mom_out mom_out[2] = {};  // evaluate_mom: [ME_SLOT_EST], [ME_SLOT_GT] (the latter with evaluate_gt_mom)

@@ -891,9 +891,9 @@ int me_mesh_sample(me_ctx *ctx, int dst_slot, int64_t n_points, uint64_t seed);
  * marching tetrahedra.  tests/_recon_ref.py restates everything below.  All arithmetic is fp64 without contraction.  The result is
  * held on the primary context (a twin sees it), like the resident mesh, until the next call of either producer or until the mesh
  * clear call.  All five entry points are single GPU only (slab or shard mode: ME_ERR_ARG).
- * Consistent orientation of the normals is the CALLER's job (a viewpoint for the radius normals, or the set-normals call): normals point
- * outward.  Propagating an orientation across the cloud, hole filling, smoothing, the reference's density trimming and multi-GPU slabs
- * are out of scope.
+ * Consistent orientation of the normals is the CALLER's job: normals point outward.  The tools are a viewpoint for the radius normals
+ * (enough for a star-shaped scene), the set-normals call, and the orientation call of the next section, which propagates one sign
+ * across the k-NN graph of the cloud.  Hole filling, smoothing, the reference's density trimming and multi-GPU slabs are out of scope.
  *
  * PARAMETERS.  voxel h > 0, finite; radius R finite, R >= h; min_k >= 1; band in {0, 1, 2}.
  * LATTICE.  The cell of a point is floor(p / h) per axis (a division, getVoxelIndex's).  Node (i, j, k) sits at x = (double(i)*h,
@@ -948,6 +948,66 @@ int me_isosurface(me_ctx *ctx, const int32_t *node_ijk, const double *f, const u
 int me_reconstruct_fetch(me_ctx *ctx, double *vertices, int32_t *vertex_edge, int32_t *triangles);
 int me_reconstruct_nodes_fetch(me_ctx *ctx, int32_t *node_ijk, double *f, int32_t *k, uint8_t *valid);
 int me_reconstruct_install(me_ctx *ctx);
+
+/* ---- consistent normal orientation: one sign propagated over the k-NN graph of a resident cloud ---------------------------------------- */
+/*   The construction of Hoppe et al. 1992, "Surface reconstruction from unorganized points", which Open3D
+ * exposes as PointCloud::OrientNormalsConsistentTangentPlane(k, lambda, cos_alpha_tol): a minimum spanning tree of a neighbour graph
+ * weighted by 1 - |n_i . n_j|, and the sign carried along the tree from a root.  The reconstruction, the signed mesh distance and M3C2
+ * all consume the sign of the resident normals; a single viewpoint cannot give it on a scene that is not star-shaped.
+ * DEVIATIONS from Open3D.  (a) The graph is the k-NN graph alone: Open3D adds the edges of a Delaunay triangulation / Euclidean minimum
+ *   spanning tree so that its graph is connected.  Here every connected component of the k-NN graph is oriented on its own, from a root of
+ *   its own, and n_components says how many there were.  (b) No lambda (edge penalty along the normal) and no cos_alpha_tol.  (c) Equal
+ *   weights do not exist: the edges are in the strict total order of item 3, so the forest, and with it every output, is unique.
+ *   (d) The root is the extreme point along a caller-given direction and is turned towards (or, inward, against) that direction; Open3D
+ *   takes the point of largest z and turns it towards +z, which direction = (0, 0, 1), inward = 0 reproduces up to ties.
+ * tests/_orient_ref.py restates everything below.  All arithmetic is fp64 without contraction.  N = the slot's points, in cloud order.
+ *
+ * 1. VALID POINTS.  A point is valid iff its resident normal is not (0, 0, 0) (each component compared with 0: -0.0 is 0).  An invalid
+ *    point takes no part: it has no edges, keeps its normal, and gets component = -1, flipped = 0.
+ * 2. GRAPH.  For every valid point i take the (k+1)-list of i in its own cloud, exactly the row of the k-NN search call with
+ *    query_slot = ref_slot = slot and k + 1: ascending by (d2, original index), padded with -1.  The edges of i are the entries j of
+ *    that list with j != i, j >= 0 and j valid.  An invalid neighbour is skipped and NOT replaced by the next nearest; where more than
+ *    k + 1 points coincide, i may be missing from its own list and then has k + 1 edges.  The graph is undirected: the edge {i, j} exists
+ *    if either end lists the other, and counts once in n_graph_edges.
+ * 3. EDGE VALUE AND ORDER.  c_ij = (nx*mx + ny*my) + nz*mz on the normals n of i and m of j as resident; bitwise symmetric.  With
+ *    lo < hi the original indices of its ends, edge a PRECEDES edge b iff |c_a| > |c_b|, or the two are equal and (lo, hi)_a is
+ *    lexicographically smaller.  |c| is compared through its bit pattern as an unsigned integer, which for every non-NaN value is the
+ *    numerical order (a NaN, from a non-finite normal, sorts before every number).  A strict total order.
+ * 4. FOREST.  The minimum spanning forest of the graph under that order (the first edge is the cheapest): unique.
+ *    n_tree_edges = n_valid - n_components.  Components are numbered 0 ... by ascending lowest original index of their members;
+ *    largest_component is the largest member count.
+ * 5. ROOT.  Per component the member that maximises (px*dx + py*dy) + pz*dz, d = direction as given (not normalised; -0.0 and +0.0
+ *    are equal), among equal values the lowest original index.  The root is flipped iff ((nx*dx + ny*dy) + nz*dz < 0) != (inward != 0):
+ *    with inward = 0 a product of exactly 0 (or NaN) leaves the root as it is, with inward set it counts as flipped.
+ * 6. PROPAGATION.  Every other member is flipped iff flip(root) XOR (the number of tree edges with c < 0 on its path from the root is
+ *    odd).  c == 0 (and -0.0) does not flip.  A flipped normal is negated exactly, component by component.  n_flipped counts them.
+ * 7. n_inconsistent_edges = the graph edges, tree or not, with (c_ij < 0) XOR flipped_i XOR flipped_j: the edges that still join
+ *    opposed normals afterwards.  0 on a smooth, well-sampled surface; a positive count says that k was too small for the sampling,
+ *    that two sheets lie closer than the sample spacing, or that the normals are noisy.
+ * STATE.  The normals are replaced in place, in cloud order, as the set-normals call would: covariances and FPFH features on the slot
+ *   are dropped.  Everything else resident on both slots stays and stays fetchable (positions, index, 1-NN results, MME, local
+ *   geometry, M3C2, labels, the resident mesh); the slot is not re-indexed, except in the one case the k-NN search documents below.
+ *   component and flipped stay fetchable until the slot's normals or points are next replaced (an upload, a device-side producer, a
+ *   transform, any of the normal estimators, the set-normals call).  Single GPU only.
+ * ERRORS.  ME_ERR_ARG: bad slot; k outside [1, 39]; a non-finite or all-zero direction; p or out NULL; slab or shard mode.
+ *   ME_ERR_STATE: no cloud on the slot, or no normals on it; the fetch without a current result.  ME_ERR_HIP: an allocation failed.
+ * DETERMINISM.  Integer atomics (max, min, add) only; no result depends on the order in which they arrive: two calls, and two
+ *   contexts, return identical bytes.  A second call on an oriented cloud with the same parameters reports n_flipped = 0.
+ * MEMORY for the time of the call: 20 (k + 1) + 38 bytes per point (lists 4 (k + 1), edges 16 (k + 1)), released on return; 5 bytes per
+ *   point stay for the fetch.  Device timers "orient_normals" (the whole call), "orient_walk" (the lists) and "orient_forest" (the rest);
+ *   the timer-get call under the name "orient_rounds" returns the Boruvka rounds of the last call in *launches.
+ *
+ * me_orient_normals: the above for the cloud of `slot`.
+ * me_orient_fetch: component int32[N], flipped uint8[N] (host, cloud order); either pointer nullable. */
+typedef struct me_orient_params {
+    double direction[3];
+    int32_t k, inward;
+} me_orient_params;
+typedef struct me_orient_out {
+    int64_t n, n_valid, n_components, largest_component, n_tree_edges, n_graph_edges, n_flipped, n_inconsistent_edges;
+} me_orient_out;
+int me_orient_normals(me_ctx *ctx, int slot, const me_orient_params *p, me_orient_out *out);
+int me_orient_fetch(me_ctx *ctx, int slot, int32_t *component, uint8_t *flipped);
 
 /* ---- neighbour lists between the resident clouds: KDTreeFlann::SearchKNN / SearchHybrid / SearchRadius for every point of a
  * cloud (the reference's loops over them: map_eval.cpp:1213-1218, 1448-1454, 1670) ---- */
