@@ -633,6 +633,40 @@ static int build_grid_table_counted(me_ctx *ctx, Cloud &c, int shift, GridTable 
 // ------------------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------------------
+// The two lists every reset site shares (tests/_lifetime.py holds the documents' side of them).
+// drop_sorted_results: what is stored in the slot's SORTED order or reads it, gone with every re-sort of the slot — its MME, local
+// geometry (and me_mom's axis bytes, made from its eigenvalues), M3C2 and mesh-distance results, and the 1-NN results of BOTH slots (the
+// other one's holds positions in this slot's sorted array) with the surface errors read from them.
+void drop_sorted_results(me_ctx *ctx, int slot) {
+    Cloud &c = ctx->cloud[slot], &o = ctx->cloud[1 - slot];
+    c.mme_have = false;
+    c.lg_have = false;
+    c.mom_have = false;
+    c.m3c2_have = false;
+    c.mesh_have = false;
+    c.nn_ref_slot = -1;
+    c.surf_have = false;
+    o.nn_ref_slot = -1;
+    o.surf_have = false;
+}
+// drop_point_results: the slot holds other points — the above, and everything kept in cloud order about the old ones: FPFH features,
+// the keep-mask, cluster and plane labels, the orientation bytes, the voxel table and its run records, and the OTHER slot's M3C2
+// result, which compared its points with these.  Normals and covariances are the caller's business (a transform rotates them).
+void drop_point_results(me_ctx *ctx, int slot) {
+    drop_sorted_results(ctx, slot);
+    Cloud &c = ctx->cloud[slot];
+    c.fpfh_valid = false;
+    c.orient_have = false;
+    c.outlier_keep_valid = false;  // (the mask belongs to the points it was computed on)
+    c.cluster_valid = false;
+    c.plane_valid = false;
+    c.vox_valid = false;
+    c.vox_merged = false;
+    c.vox_rec_valid = false;
+    c.n_vox = 0;
+    ctx->cloud[1 - slot].m3c2_have = false;
+}
+
 int cloud_upload(me_ctx *ctx, int slot, const double *src, bool src_on_device, long long n, const double *T,
                  double cell_size, bool prefiltered) {
     if (slot < 0 || slot > 1) return ctx->fail(ME_ERR_ARG, "slot must be ME_SLOT_EST (0) or ME_SLOT_GT (1)");
@@ -645,18 +679,8 @@ int cloud_upload(me_ctx *ctx, int slot, const double *src, bool src_on_device, l
         e.slab_identity = true;
         e.uploaded = true;
         e.index_valid = false;
-        e.nn_ref_slot = -1;
-        e.vox_valid = e.vox_merged = false;
         e.have_normals = e.have_cov = false;
-        e.orient_have = false;
-        e.outlier_keep_valid = false;
-        e.cluster_valid = false;
-        e.plane_valid = false;
-        e.lg_have = false;
-        e.m3c2_have = false;
-        e.mesh_have = false;
-        ctx->cloud[1 - slot].nn_ref_slot = -1;
-        ctx->cloud[1 - slot].m3c2_have = false;
+        drop_point_results(ctx, slot);
         return ME_OK;
     }
     if (!src) return ctx->fail(ME_ERR_ARG, "xyz is NULL");
@@ -666,13 +690,8 @@ int cloud_upload(me_ctx *ctx, int slot, const double *src, bool src_on_device, l
     Cloud &c = ctx->cloud[slot];
     c.uploaded = false;
     c.index_valid = false;
-    c.nn_ref_slot = -1;
-    c.n_vox = 0;
     c.vox_size = 0;
-    c.vox_valid = false;
-    c.vox_merged = false;
-    // any result that used this cloud as the reference is stale now
-    ctx->cloud[1 - slot].nn_ref_slot = -1;
+    drop_point_results(ctx, slot);  // (any result that used this cloud as the reference is stale as well)
     c.n = n;
     c.n_total = n;
     c.have_normals = c.have_cov = false;
@@ -740,7 +759,7 @@ int cloud_upload(me_ctx *ctx, int slot, const double *src, bool src_on_device, l
         c.n = kept;
         if (kept == 0) {  // this rank's slab (+halo) holds nothing of this cloud: every pass returns empty partials
             c.uploaded = true;
-            c.index_valid = false;
+            c.index_valid = false;  // (the results of the cloud the slot held went at the head of this function)
             ME_CHECK(ctx, hipStreamSynchronize(ctx->stream));
             return ME_OK;
         }
@@ -755,17 +774,7 @@ int cloud_finish(me_ctx *ctx, int slot, bool bbox_ready) {
     const long long n = c.n;
     c.uploaded = false;
     c.index_valid = false;
-    c.nn_ref_slot = -1;
-    c.vox_valid = false;
-    c.vox_merged = false;
-    c.n_vox = 0;
-    c.fpfh_valid = false;
-    c.orient_have = false;
-    c.outlier_keep_valid = false;  // (the mask belongs to the points it was computed on)
-    c.cluster_valid = false;
-    c.plane_valid = false;
-    ctx->cloud[1 - slot].nn_ref_slot = -1;
-    ctx->cloud[1 - slot].m3c2_have = false;  // (an M3C2 result compared the other slot's points with these; this slot's own goes with its index)
+    drop_point_results(ctx, slot);
     // bbox
     const unsigned int nb = (unsigned int) std::min<long long>(1024, (n + 255) / 256);
     ME_CHECK(ctx, ctx->red.ensure((size_t) nb * 6 * sizeof(double)));
@@ -801,25 +810,11 @@ void cloud_reset_replaced(me_ctx *ctx, int slot, long long n, double cell_size_r
     Cloud &D = ctx->cloud[slot];
     D.uploaded = false;
     D.index_valid = false;
-    D.nn_ref_slot = -1;
-    D.n_vox = 0;
     D.vox_size = 0;
-    D.vox_valid = false;
-    D.vox_merged = false;
-    D.vox_rec_valid = false;
-    D.mme_have = false;
-    ctx->cloud[1 - slot].nn_ref_slot = -1;
+    drop_point_results(ctx, slot);
     D.n = n;
     D.n_total = n;
     D.have_normals = D.have_cov = false;
-    D.fpfh_valid = false;
-    D.outlier_keep_valid = false;
-    D.cluster_valid = false;
-    D.plane_valid = false;
-    D.lg_have = false;
-    D.m3c2_have = false;
-    D.mesh_have = false;
-    ctx->cloud[1 - slot].m3c2_have = false;
     D.slab = ctx->slab;
     D.n_unres = 0;
     D.slab_identity = true;
@@ -988,15 +983,10 @@ int cloud_build_index(me_ctx *ctx, int slot, double cell_size) {
     c.cell_h = cell_h;
     c.fine_h = std::ldexp(cell_h, -c.shift);
     c.index_valid = false;
-    c.mme_have = false;  // (the sorted order changes)
-    c.lg_have = false;
-    c.m3c2_have = false;
-    c.mesh_have = false;
+    drop_sorted_results(ctx, slot);  // (the sorted order changes)
 #ifdef ME_AB
     c.mme_feat_valid = false;
 #endif
-    c.nn_ref_slot = -1;
-    ctx->cloud[1 - slot].nn_ref_slot = -1;
 
     // --- Morton codes + sort ---
     DevBuf &codes_in = ctx->tmp[0], &iota = ctx->tmp[1], &perm = ctx->tmp[2];

@@ -560,6 +560,10 @@ int cloud_upload(me_ctx *ctx, int slot, const double *src, bool src_on_device, l
 int cloud_build_index(me_ctx *ctx, int slot, double cell_size);
 int cloud_finish_octree(me_ctx *ctx, int slot);
 int cloud_finish(me_ctx *ctx, int slot, bool bbox_ready = false);
+// the two lists of "this result is current" flags that every reset site clears: what goes with the slot's sorted order (every index
+// rebuild), and what goes with its points (the former included); normals and covariances stay with the caller
+void drop_sorted_results(me_ctx *ctx, int slot);
+void drop_point_results(me_ctx *ctx, int slot);
 // the upload-time reset of a slot whose points a device-side producer has just replaced (n points, no normals), before its cloud_finish
 void cloud_reset_replaced(me_ctx *ctx, int slot, long long n, double cell_size_req);
 int cloud_transform(me_ctx *ctx, int slot, const double *T);

@@ -199,17 +199,8 @@ int perturb_cloud(me_ctx *ctx, int dst_slot, int src_slot, const me_perturb_para
     // the upload-time reset of dst (cloud_upload): index, NN, MME, voxel state and per-point attributes are gone
     D.uploaded = false;
     D.index_valid = false;
-    D.nn_ref_slot = -1;
-    D.n_vox = 0;
     D.vox_size = 0;
-    D.vox_valid = false;
-    D.vox_merged = false;
-    D.vox_rec_valid = false;
-    D.mme_have = false;
-    D.lg_have = false;
-    D.m3c2_have = false;
-    ctx->cloud[1 - dst_slot].nn_ref_slot = -1;
-    ctx->cloud[1 - dst_slot].m3c2_have = false;
+    drop_point_results(ctx, dst_slot);
     D.n = total;
     D.n_total = total;
     D.have_normals = D.have_cov = false;

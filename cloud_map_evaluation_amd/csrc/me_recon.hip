@@ -15,7 +15,8 @@
 //                  test d2 < R*R fails and the point contributes nothing and is not counted — at no cost in the candidate loop.
 //                  The slot's index cell edge must be >= R: me_m3c2's rule (rebuilt at R unless R (1 + 2^-20) <= cell_h <= 1.5 R (1 +
 //                  2^-20)), and a rebuild re-sorts the slot: the 1-NN results of both slots, the slot's local-geometry, M3C2 and
-//                  mesh-distance results and the other slot's M3C2 result are dropped; the points and the normals (cloud order) stay.
+//                  mesh-distance results are dropped (drop_sorted_results); the points, the normals (cloud order) and the other
+//                  slot's M3C2 result stay.
 //   extraction     k_rc_cells: a node finds its 7 neighbours a + dir by binary search in the sorted node keys, decides whether the cell
 //                  it is corner 0 of is extracted, packs the 8 inside bits, marks the crossed ones of the cell's 19 Kuhn edges (plain
 //                  byte stores of 1 into a zeroed array: every writer writes the same value) and counts the cell's triangles;

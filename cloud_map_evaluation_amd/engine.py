@@ -83,6 +83,7 @@ class Engine:
         self._L = _lib.load()
         self._ctx = self._L.me_create(int(device), (1 if borrow_device_input else 0) | (2 if morton_order else 0))
         self._held = {}  # slot -> the array / tensor of its last upload (borrowed device inputs must outlive their use)
+        self._shared = {}  # what the Python side remembers about the CONTEXT's results: one dict for the engine and its twin
         if not self._ctx:
             raise MapEvalError(self._L.me_last_error(None).decode())
         self.device = device
@@ -98,6 +99,7 @@ class Engine:
                 raise MapEvalError(self._L.me_last_error(self._ctx).decode())
             t.device = self.device
             t._held = self._held
+            t._shared = self._shared  # (the reconstruction lives in the primary context: a twin's call changes what both fetch)
             t._owned = False
             t._twin = None
             self._twin = t
@@ -632,12 +634,17 @@ class Engine:
                 "surface_variation": mean(o.sum_surface_variation), "mean_k": mean(o.sum_k)}
         if not fetch:
             return info
+        return (info, *self.local_geometry_fetch(slot))
+
+    def local_geometry_fetch(self, slot: int):
+        """me_local_geometry_fetch -> (eig[N, 3], k[N], valid[N]) of the slot's last local_geometry / radius_normals, cloud order."""
+        self._ck(self._L.me_local_geometry_fetch(self._ctx, int(slot), 0, 0, 0))  # (raises without a current result, before the size is asked)
         n = self.size(slot)
         eig = np.empty((n, 3), np.float64)
         k = np.empty(n, np.int32)
         valid = np.empty(n, np.uint8)
         self._ck(self._L.me_local_geometry_fetch(self._ctx, int(slot), _addr(eig), _addr(k), _addr(valid)))
-        return info, eig, k, valid
+        return eig, k, valid
 
     def mpv(self, slot: int, radius: float, min_k: int = 5) -> float:
         """Mean plane variance: the mean smallest covariance eigenvalue over the valid points (0.0 without one)."""
@@ -721,11 +728,14 @@ class Engine:
             d["rep"] = np.array(list(a.rep))
             axes.append(d)
         res = {"n_axes": int(o.n_axes), "n_directions": int(o.n_directions), "mom_median": o.mom_median, "mom_mean": o.mom_mean, "axes": axes}
-        if not fetch:
-            return res
+        return (res, self.mom_fetch(slot)) if fetch else res
+
+    def mom_fetch(self, slot: int) -> np.ndarray:
+        """me_mom_fetch -> the axis byte per point ([N] int8, cloud order, -1 = not used) of the slot's last mom."""
+        self._ck(self._L.me_mom_fetch(self._ctx, int(slot), 0))  # (raises without a current result, before the size is asked)
         axis = np.empty(self.size(slot), np.int8)
         self._ck(self._L.me_mom_fetch(self._ctx, int(slot), _addr(axis)))
-        return res, axis
+        return axis
 
     # ---- error distribution: exact quantiles, Hausdorff distance, F-score, error CDF (me_errdist.hip) ----
     def rank_select(self, values, ranks, use=None) -> dict:
@@ -975,7 +985,7 @@ class Engine:
         o = _lib.ReconOut()
         self._ck(self._L.me_reconstruct(self._ctx, int(slot), C.byref(p), C.byref(o)))
         res = self._recon_counts(o)
-        self._recon_n_nodes = res["n_nodes"]
+        self._shared["recon_n_nodes"] = res["n_nodes"]
         if fetch:
             res.update(self._recon_fetch(res))
         if install:
@@ -986,7 +996,7 @@ class Engine:
         """me_reconstruct_nodes_fetch: node_ijk (n,3) int32 in the Morton order of the lattice frame, f, k (int32), valid (bool) of the
         last reconstruct."""
         self._ck(self._L.me_reconstruct_nodes_fetch(self._ctx, None, None, None, None))  # (raises without a node field)
-        n = int(self._recon_n_nodes)
+        n = int(self._shared["recon_n_nodes"])  # (of the context's last reconstruct, whichever lane ran it)
         d = {"node_ijk": np.empty((n, 3), np.int32), "f": np.empty(n, np.float64), "k": np.empty(n, np.int32)}
         v = np.empty(n, np.uint8)
         self._ck(self._L.me_reconstruct_nodes_fetch(self._ctx, _addr(d["node_ijk"]), _addr(d["f"]), _addr(d["k"]), _addr(v)))

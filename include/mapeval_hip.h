@@ -925,7 +925,8 @@ int me_mesh_sample(me_ctx *ctx, int dst_slot, int64_t n_points, uint64_t seed);
  *
  * me_reconstruct: field and extraction for the cloud of `slot`.  The slot's index is brought to a cell edge >= R by the M3C2 rule
  *   (kept if R (1 + 2^-20) <= cell <= 1.5 R (1 + 2^-20), else rebuilt at R): a rebuild re-sorts the slot and discards the 1-NN results
- *   of both slots, the slot's local-geometry, M3C2 and mesh-distance results and the other slot's M3C2 result; points and normals stay.
+ *   of both slots and the slot's own MME, local-geometry (me_mom with it), M3C2 and mesh-distance results; points and normals stay, and so
+ *   does the OTHER slot's M3C2 result, which is held in that slot's order about unchanged points (me_m3c2_fetch).
  *   ME_ERR_STATE: no cloud, or no normals on the slot.  ME_ERR_ARG: bad parameters.  A cloud that yields no extracted cell is not an
  *   error: zeros.  Device timers "recon_field" and "recon_extract"; the sorts of the lattice build report under "sort".
  * me_isosurface: the same extraction stage on a lattice field the caller supplies: node_ijk int32[n_nodes][3], f[n_nodes],
@@ -1176,7 +1177,15 @@ int me_chamfer(me_ctx *ctx, double *cd);
  *      (map_eval.cpp:1608-1737, 1538-1606, 1438-1535) ------------------------------------------------------------ */
 /* min_k: 10 for the estimated cloud (:1675), 5 for the GT cloud (:1458).  entropies[N] (0.0 where invalid) and
  * valid[N] are in cloud order, nullable.  sum_H / n_valid are shard-local partial sums; the mean entropy is
- * sum_H / n_valid (0 when n_valid == 0, :1720-1724). */
+ * sum_H / n_valid (0 when n_valid == 0, :1720-1724).
+ * INDEX.  A slot whose cell edge is below radius (1 + 2^-20) or above 1.5 times that is re-indexed at `radius` (the rule every
+ * radius pass shares); that discards what a re-sort of the slot discards: the 1-NN results of both slots and the slot's local-geometry,
+ * M3C2 and mesh-distance results.  me_mme ADOPTS its radius as the cell size asked for on the slot (the lazy choice
+ * me_upload_cloud's cell_size <= 0 leaves to it): every later rebuild of the slot's index that uses the requested cell
+ * (me_transform_cloud, the device-side producers, a missing index) builds at `radius`.  So do me_run_suite, through its two me_mme
+ * calls, and me_run_suite_from, which settles both slots' indexes at nn_radius before its lanes start: after either, nn_radius is the
+ * cell size asked for on both slots.  The other radius passes - me_radius_outlier, me_cluster_dbscan, me_local_geometry,
+ * me_radius_normals, me_m3c2 and me_reconstruct - borrow the index: they restore the cell size asked for before. */
 int me_mme(me_ctx *ctx, int slot, double radius, int min_k, double *entropies, uint8_t *valid, double *sum_H,
            int64_t *n_valid);
 /* The per-point arrays of the slot's LAST MME pass (me_mme, me_run_suite, me_run_suite_from), as me_mme returns them: what
