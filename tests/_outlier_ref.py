@@ -3,7 +3,9 @@ PointCloud::RemoveStatisticalOutlier / RemoveRadiusOutlier.
 
 Candidates come from scipy's cKDTree (k + 8 nearest, or the ball at r (1 + 1e-9)); their d2 is then recomputed exactly as the device
 does, ((dx*dx + dy*dy) + dz*dz) in fp64, and re-ranked, so the tree's own rounding never decides anything.  brute_* are the O(n^2)
-definitions the tests hold the restatement to on small clouds."""
+definitions the tests hold the restatement to on small clouds (chunked over rows).  sor_stats is Open3D's serial definition of the
+statistics; sor_stats_device restates the device's fixed summation tree operation for operation, so that mean, std, threshold and
+every keep bit can be compared with ==."""
 from __future__ import annotations
 
 import itertools
@@ -67,6 +69,62 @@ def sor_stats(avg: np.ndarray, std_ratio: float):
     return mean, std, mean + std_ratio * std
 
 
+# ---- the statistics as the device sums them (k_sor_partials / k_sor_final, block_sum_256 and wave_sum of me_internal.hpp) ----
+def sor_launch(n: int):
+    """(nb, per) of statistical_outlier(): nb blocks of 256 threads, block b owns [b * per, min((b + 1) * per, n))."""
+    nb = min(1024, max(1, (n + 255) // 256))
+    per = ((n + nb - 1) // nb + 255) // 256 * 256
+    return nb, per
+
+
+def _block_sum_256(v: np.ndarray) -> np.ndarray:
+    """block_sum_256 over the last axis (256 thread values): each wave's shuffle tree v += shfl_down(v, o) for o = 32 .. 1 as lane 0
+    sees it, then (s0 + s1) + (s2 + s3)."""
+    w = v.reshape(v.shape[:-1] + (4, 64))
+    o = 32
+    while o:
+        w = w[..., :o] + w[..., o:2 * o]
+        o >>= 1
+    w = w[..., 0]
+    return (w[..., 0] + w[..., 1]) + (w[..., 2] + w[..., 3])
+
+
+def device_tree_sum(vals: np.ndarray) -> float:
+    """The sum of vals in the order of k_sor_partials + k_sor_final.  Thread t of block b adds b * per + t, + 256, ... serially from
+    0.0; the four waves of a block are combined by _block_sum_256; one block adds the nb partials in the same pattern.  (An entry the
+    kernel skips is a 0.0 here: s + 0.0 == s for every s >= 0.)"""
+    vals = np.ascontiguousarray(vals, np.float64)
+    n = len(vals)
+    nb, per = sor_launch(n)
+    a = np.zeros(nb * per)
+    a[:n] = vals
+    a = a.reshape(nb, per // 256, 256)
+    s = np.zeros((nb, 256))
+    for j in range(per // 256):
+        s = s + a[:, j, :]
+    part = np.zeros(1024)
+    part[:nb] = _block_sum_256(s)
+    part = part.reshape(4, 256)
+    s = np.zeros(256)
+    for j in range(4):  # (nb <= 1024: thread t adds part[t], part[t + 256], ...)
+        s = s + part[j]
+    return float(_block_sum_256(s))
+
+
+def sor_stats_device(avg: np.ndarray, std_ratio: float):
+    """mean, std, threshold bit for bit as k_sor_partials<0>, k_sor_final<0>, k_sor_partials<1>, k_sor_final<1> compute them."""
+    avg = np.ascontiguousarray(avg, np.float64)
+    n = len(avg)
+    pos = avg > 0
+    with np.errstate(invalid="ignore", divide="ignore"):
+        mean = np.float64(device_tree_sum(np.where(pos, avg, 0.0))) / np.float64(n)
+        d = avg - mean
+        sq = np.float64(device_tree_sum(np.where(pos, d * d, 0.0)))
+        std = np.sqrt(sq / np.float64(n - 1))
+        thr = mean + np.float64(std_ratio) * std
+    return float(mean), float(std), float(thr)
+
+
 def sor_keep(avg: np.ndarray, threshold: float) -> np.ndarray:
     with np.errstate(invalid="ignore"):
         return (avg > 0) & (avg < threshold)
@@ -96,18 +154,28 @@ def ror(xyz: np.ndarray, nb_points: int, radius: float):
 
 
 # ---- O(n^2) definitions ----
+_BRUTE_ROWS = 256  # (rows per chunk: a 4097-point cloud never holds n^2 x 3 doubles at once)
+
+
 def brute_sor_avg(xyz: np.ndarray, k: int) -> np.ndarray:
     xyz = np.asarray(xyz, np.float64)
-    d2 = np.sort(d2_exact(xyz[:, None, :], xyz[None, :, :]), axis=1)[:, :k]
-    out = np.empty(len(xyz))
-    for i in range(len(xyz)):
-        s = 0.0
-        for v in d2[i]:
-            s += float(np.sqrt(v))
-        out[i] = s / len(d2[i])
+    n = len(xyz)
+    kk = min(k, n)
+    out = np.empty(n)
+    for b in range(0, n, _BRUTE_ROWS):
+        d2 = d2_exact(xyz[b:b + _BRUTE_ROWS, None, :], xyz[None, :, :])
+        d2 = np.sort(np.partition(d2, kk - 1, axis=1)[:, :kk], axis=1)  # (the kk smallest of every row, ascending)
+        s = np.zeros(len(d2))
+        for j in range(kk):  # (every row's serial sum from 0.0, ascending d2)
+            s = s + np.sqrt(d2[:, j])
+        out[b:b + _BRUTE_ROWS] = s / kk
     return out
 
 
 def brute_ror_counts(xyz: np.ndarray, radius: float) -> np.ndarray:
     xyz = np.asarray(xyz, np.float64)
-    return np.count_nonzero(d2_exact(xyz[:, None, :], xyz[None, :, :]) < radius * radius, axis=1).astype(np.int32)
+    n = len(xyz)
+    out = np.empty(n, np.int32)
+    for b in range(0, n, _BRUTE_ROWS):
+        out[b:b + _BRUTE_ROWS] = np.count_nonzero(d2_exact(xyz[b:b + _BRUTE_ROWS, None, :], xyz[None, :, :]) < radius * radius, axis=1)
+    return out
