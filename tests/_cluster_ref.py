@@ -32,6 +32,22 @@ def pairs(xyz: np.ndarray, eps: float) -> np.ndarray:
     return pr[ok].astype(np.int64)
 
 
+def brute_pairs(xyz: np.ndarray, eps: float, rows: int = 256) -> np.ndarray:
+    """All i < j with d2_exact < eps^2, (m, 2) int64 as pairs() returns them, from the O(n^2) definition in chunks of rows: no tree and
+    no prefilter, so nothing but d2_exact decides at any coordinate magnitude.  Sorted by (i, j)."""
+    xyz = np.ascontiguousarray(xyz, np.float64)
+    n = len(xyz)
+    r2 = eps * eps
+    out = []
+    for b in range(0, n, rows):
+        near = d2_exact(xyz[b:b + rows, None, :], xyz[None, :, :]) < r2
+        i, j = np.nonzero(near)
+        i += b
+        m = i < j
+        out.append(np.stack([i[m], j[m]], 1))
+    return np.concatenate(out).astype(np.int64) if out else np.zeros((0, 2), np.int64)
+
+
 def dbscan(xyz: np.ndarray, eps: float, min_points: int, pr: np.ndarray | None = None):
     """-> labels (int32, cloud order), counts (int32, the point itself included), n_clusters.  pr: pairs(xyz, eps), when at hand."""
     from scipy.sparse import coo_matrix
