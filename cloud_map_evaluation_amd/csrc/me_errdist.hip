@@ -6,10 +6,8 @@
 //   k_ed_stat    a fixed grid of at most kEdStatBlocks blocks strides over the entries with four loads in flight (k_nn_partial's walk):
 //                the use byte (d2 >= 0 and gate_pass; for the direct entry: the caller's byte and the value inside the contract), the
 //                counts, the smallest and the largest key, the (largest key, smallest original index) pair, the threshold counts and the
-//                two sums; a block's figures by a fixed tree, stored as its partial
-//   k_ed_final   one block: the partials in block order (thread t takes t, t + 256, ...; k_final_sum_d's rule) — no floating-point
-//                atomics, bit-identical from run to run
-//   k_ed_hist    the bin of every used entry by a binary search of the edge table staged in LDS (4096 x 8 B), an LDS histogram of
+//                two sums; the block's partial record and the one-block total over the records are me_reduce.hpp's
+//   k_ed_hist   the bin of every used entry by a binary search of the edge table staged in LDS (4096 x 8 B), an LDS histogram of
 //                integer counts, one integer atomic per non-empty (block, bin)
 // Multi-rank radix select, most significant digit first, eight passes of eight bits, up to 16 ranks at once:
 //   k_rs_start   one slot with an empty prefix that carries every rank; a rank outside [0, count) raises the flag
@@ -24,10 +22,10 @@
 // The file is compiled with -ffp-contract=off like the rest of the library.
 #include <algorithm>
 #include <cmath>
-#include <cstddef>
 #include <cstring>
 
 #include "me_internal.hpp"
+#include "me_reduce.hpp"
 #include "me_stat.hpp"
 
 namespace me {
@@ -44,8 +42,11 @@ constexpr unsigned int kRsHistBlocks = 2048;   // pieces of the list (k_rs_hist,
 constexpr long long kRsCompactMin = 32768;     // a list of fewer entries is not compacted (one read of it costs less than the launches)
 constexpr int kRsCompactDiv = 8;               // compact when the surviving entries are at most 1 / 8 of the list
 constexpr unsigned int kEdStatBlocks = 1024;   // k_ed_stat: above 256 x 1024 entries a block strides over the array
-constexpr int kEdI = 5 + ME_ERRDIST_MAX_THRESHOLDS;  // integer partials per block: n_query, n_used, min key, max key, argmax, n_within[8]
+constexpr int kEdNI = 2 + ME_ERRDIST_MAX_THRESHOLDS;  // integer sums per block: n_query, n_used, n_within[8]
 constexpr int kEdMaxBins = ME_ERRDIST_MAX_BINS;
+// a record: d = sum_d, sum_d2; i = the sums, then the largest key, its argmax and the smallest key
+typedef RedBufs<2, kEdNI, true> EdRed;
+enum { kEdMx = kEdNI, kEdArg, kEdMn };
 
 struct RsList {
     const double *v;
@@ -65,10 +66,7 @@ struct RsBlock {
     RsList cur, src;       // the list the next pass reads; the list a pending k_rs_scatter reads
     double *buf[2];        // the two compacted lists, used in turn
     long long cap[2];
-    // k_ed_final
-    long long n_query, n_used, argmax, n_within[ME_ERRDIST_MAX_THRESHOLDS];
-    u64 mn, mx;
-    double sum_d, sum_d2;
+    EdRed::Totals tot;     // stat_device
     unsigned int err, pad;
     me_rank_stats out;
     long long out_compact[2];  // compactions done, entries of the last list
@@ -87,16 +85,16 @@ template <int MODE>
 __global__ void __launch_bounds__(256)
 k_ed_stat(const double *__restrict__ v, const unsigned char *__restrict__ use_in, const SPoint *__restrict__ sp, long long n, StatParams gp,
           EdThr thr, unsigned char *__restrict__ use_out, long long *__restrict__ pi, double *__restrict__ pd, unsigned int *__restrict__ err) {
-    long long nq = 0, nu = 0, arg = -1, nw[ME_ERRDIST_MAX_THRESHOLDS];
+    long long arg = -1, ci[kEdNI];  // n_query, n_used, n_within[8]
     u64 mn = ~0ull, mx = 0ull;
-    double sd = 0.0, sd2 = 0.0;
+    double sd[2] = {0.0, 0.0};      // sum_d, sum_d2
     bool bad = false;
 #pragma unroll
-    for (int k = 0; k < ME_ERRDIST_MAX_THRESHOLDS; ++k) nw[k] = 0;
+    for (int k = 0; k < kEdNI; ++k) ci[k] = 0;
     auto take = [&](long long i, double d2, unsigned char ub) {
         bool used;
         if (MODE == 0) {
-            if (d2 >= 0.0) nq += 1;
+            if (d2 >= 0.0) ci[0] += 1;
             used = d2 >= 0.0 && gate_pass(gp, d2);
         } else {
             used = ub != 0;
@@ -104,23 +102,23 @@ k_ed_stat(const double *__restrict__ v, const unsigned char *__restrict__ use_in
                 bad = true;
                 used = false;
             }
-            if (used) nq += 1;
+            if (used) ci[0] += 1;
         }
         use_out[i] = used ? 1 : 0;
         if (!used) return;
         const u64 k = key_of(d2);
-        nu += 1;
+        ci[1] += 1;
         mn = k < mn ? k : mn;
         if (k >= mx) {  // (rare once the walk has seen a large value: the index is loaded only then)
             const long long o = MODE == 0 ? sp[i].idx : i;
             if (k > mx || arg < 0 || o < arg) arg = o;
             mx = k;
         }
-        sd += sqrt(d2);
-        sd2 += d2;
+        sd[0] += sqrt(d2);
+        sd[1] += d2;
 #pragma unroll
         for (int q = 0; q < ME_ERRDIST_MAX_THRESHOLDS; ++q)
-            if (q < thr.n && d2 <= thr.t2[q]) nw[q] += 1;
+            if (q < thr.n && d2 <= thr.t2[q]) ci[2 + q] += 1;
     };
     const long long S = (long long) gridDim.x * 256;
     long long i = (long long) blockIdx.x * 256 + threadIdx.x;
@@ -135,97 +133,7 @@ k_ed_stat(const double *__restrict__ v, const unsigned char *__restrict__ use_in
     }
     for (; i < n; i += S) take(i, v[i], (MODE == 1 && use_in) ? use_in[i] : (unsigned char) 1);
     if (bad) atomicOr(err, 1u);
-    // the block's figures: sums by block_sum_256's tree, the extremes through LDS
-    __shared__ double smd[4];
-    __shared__ long long smi[4];
-    __shared__ u64 s_mn[4], s_mx[4];
-    __shared__ long long s_arg[4];
-    long long *bi = pi + (size_t) blockIdx.x * kEdI;
-    double r = block_sum_256(sd, smd);
-    if (threadIdx.x == 0) pd[(size_t) blockIdx.x * 2] = r;
-    r = block_sum_256(sd2, smd);
-    if (threadIdx.x == 0) pd[(size_t) blockIdx.x * 2 + 1] = r;
-    long long c = block_sum_256_ll(nq, smi);
-    if (threadIdx.x == 0) bi[0] = c;
-    c = block_sum_256_ll(nu, smi);
-    if (threadIdx.x == 0) bi[1] = c;
-#pragma unroll
-    for (int q = 0; q < ME_ERRDIST_MAX_THRESHOLDS; ++q) {
-        c = block_sum_256_ll(nw[q], smi);
-        if (threadIdx.x == 0) bi[5 + q] = c;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const u64 omn = (u64) __shfl_down((long long) mn, o, 64), omx = (u64) __shfl_down((long long) mx, o, 64);
-        const long long oa = __shfl_down(arg, o, 64);
-        mn = omn < mn ? omn : mn;
-        if (oa >= 0 && (arg < 0 || omx > mx || (omx == mx && oa < arg))) mx = omx, arg = oa;
-    }
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) s_mn[w] = mn, s_mx[w] = mx, s_arg[w] = arg;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int q = 1; q < 4; ++q) {
-            mn = s_mn[q] < mn ? s_mn[q] : mn;
-            if (s_arg[q] >= 0 && (arg < 0 || s_mx[q] > mx || (s_mx[q] == mx && s_arg[q] < arg))) mx = s_mx[q], arg = s_arg[q];
-        }
-        bi[2] = (long long) mn;
-        bi[3] = (long long) mx;
-        bi[4] = arg;
-    }
-}
-
-__global__ void __launch_bounds__(256) k_ed_final(const long long *__restrict__ pi, const double *__restrict__ pd, int nb, RsBlock *__restrict__ b) {
-    __shared__ double smd[4];
-    __shared__ long long smi[4];
-    __shared__ u64 s_mn[256], s_mx[256];
-    __shared__ long long s_arg[256];
-    double sd = 0.0, sd2 = 0.0;
-    long long ci[kEdI];
-#pragma unroll
-    for (int k = 0; k < kEdI; ++k) ci[k] = 0;
-    u64 mn = ~0ull, mx = 0ull;
-    long long arg = -1;
-    for (int q = threadIdx.x; q < nb; q += 256) {
-        sd += pd[(size_t) q * 2];
-        sd2 += pd[(size_t) q * 2 + 1];
-        const long long *bi = pi + (size_t) q * kEdI;
-        ci[0] += bi[0];
-        ci[1] += bi[1];
-#pragma unroll
-        for (int k = 5; k < kEdI; ++k) ci[k] += bi[k];
-        const u64 omn = (u64) bi[2], omx = (u64) bi[3];
-        const long long oa = bi[4];
-        mn = omn < mn ? omn : mn;
-        if (oa >= 0 && (arg < 0 || omx > mx || (omx == mx && oa < arg))) mx = omx, arg = oa;
-    }
-    double r = block_sum_256(sd, smd);
-    if (threadIdx.x == 0) b->sum_d = r;
-    r = block_sum_256(sd2, smd);
-    if (threadIdx.x == 0) b->sum_d2 = r;
-    long long c = block_sum_256_ll(ci[0], smi);
-    if (threadIdx.x == 0) b->n_query = c;
-    c = block_sum_256_ll(ci[1], smi);
-    if (threadIdx.x == 0) b->n_used = c;
-#pragma unroll
-    for (int k = 5; k < kEdI; ++k) {
-        c = block_sum_256_ll(ci[k], smi);
-        if (threadIdx.x == 0) b->n_within[k - 5] = c;
-    }
-    s_mn[threadIdx.x] = mn;
-    s_mx[threadIdx.x] = mx;
-    s_arg[threadIdx.x] = arg;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int q = 1; q < 256; ++q) {
-            mn = s_mn[q] < mn ? s_mn[q] : mn;
-            if (s_arg[q] >= 0 && (arg < 0 || s_mx[q] > mx || (s_mx[q] == mx && s_arg[q] < arg))) mx = s_mx[q], arg = s_arg[q];
-        }
-        b->mn = mn;
-        b->mx = mx;
-        b->argmax = arg;
-    }
+    red_store_partial<2, kEdNI, true>(sd, ci, mx, arg, mn, pd + (size_t) blockIdx.x * 2, pi + (size_t) blockIdx.x * EdRed::Totals::NR);
 }
 
 // hist[j], j in [0, n_bins]: the used entries with E[j - 1] < d2 <= E[j] (E[-1] = -inf), hist[n_bins] those beyond the last edge.
@@ -261,7 +169,7 @@ __global__ void __launch_bounds__(256)
 k_rs_start(RsBlock *__restrict__ b, const double *values, const unsigned char *use, long long n, int n_ranks, double *buf0, long long cap0,
            double *buf1, long long cap1) {
     for (int t = threadIdx.x; t < kRsMax * kRsBins; t += 256) b->hist[t] = 0ull;
-    const long long count = b->n_used;
+    const long long count = b->tot.i[1];
     if ((int) threadIdx.x < kRsMax) {
         const int j = threadIdx.x;
         long long r = 0;
@@ -500,7 +408,7 @@ __global__ void __launch_bounds__(256) k_rs_scatter(RsBlock *__restrict__ b, u64
 
 __global__ void __launch_bounds__(64) k_rs_out(RsBlock *__restrict__ b) {
     const int j = threadIdx.x;
-    const long long count = b->n_used;
+    const long long count = b->tot.i[1];
     if (j < kRsMax) {
         double v = 0.0;
         if (j < b->n_ranks && count > 0) v = __longlong_as_double((long long) b->prefix[min(max(b->slot_of[j], 0), kRsMax - 1)]);
@@ -508,9 +416,9 @@ __global__ void __launch_bounds__(64) k_rs_out(RsBlock *__restrict__ b) {
     }
     if (j == 0) {
         b->out.count = count;
-        b->out.sum = count > 0 ? b->sum_d2 : 0.0;
-        b->out.min = count > 0 ? __longlong_as_double((long long) b->mn) : 0.0;
-        b->out.max = count > 0 ? __longlong_as_double((long long) b->mx) : 0.0;
+        b->out.sum = count > 0 ? b->tot.d[1] : 0.0;
+        b->out.min = count > 0 ? __longlong_as_double(b->tot.i[kEdMn]) : 0.0;
+        b->out.max = count > 0 ? __longlong_as_double(b->tot.i[kEdMx]) : 0.0;
         b->out_compact[0] = b->n_compact;
         b->out_compact[1] = b->cur.n;
     }
@@ -521,7 +429,7 @@ int ensure_rs(me_ctx *ctx, long long n) {
     ME_CHECK(ctx, ctx->rs_tmp[1].ensure((size_t) (n / kRsCompactDiv + 1) * 8));
     ME_CHECK(ctx, ctx->rs_tmp[2].ensure((size_t) (n / (kRsCompactDiv * kRsCompactDiv) + 1) * 8));
     ME_CHECK(ctx, ctx->rs_tmp[3].ensure((size_t) std::max<long long>(n, 1)));
-    ME_CHECK(ctx, ctx->red.ensure((size_t) kEdStatBlocks * (kEdI + 2) * 8));
+    ME_CHECK(ctx, ctx->red.ensure(EdRed::bytes(kEdStatBlocks)));
     return ME_OK;
 }
 
@@ -530,11 +438,10 @@ template <int MODE>
 void stat_device(me_ctx *ctx, const double *v, const unsigned char *use_in, const SPoint *sp, long long n, const StatParams &gp, const EdThr &thr) {
     RsBlock *blk = ctx->rs_tmp[0].as<RsBlock>();
     const int nb = (int) std::min<long long>(kEdStatBlocks, blocks_of(n));
-    long long *pi = ctx->red.as<long long>();
-    double *pd = reinterpret_cast<double *>(pi + (size_t) kEdStatBlocks * kEdI);
-    hipLaunchKernelGGL(k_ed_stat<MODE>, dim3(nb), dim3(256), 0, ctx->stream, v, use_in, sp, n, gp, thr, ctx->rs_tmp[3].as<unsigned char>(), pi, pd,
-                       &blk->err);
-    hipLaunchKernelGGL(k_ed_final, dim3(1), dim3(256), 0, ctx->stream, (const long long *) pi, (const double *) pd, nb, blk);
+    const EdRed red(ctx, kEdStatBlocks);
+    hipLaunchKernelGGL(k_ed_stat<MODE>, dim3(nb), dim3(256), 0, ctx->stream, v, use_in, sp, n, gp, thr, ctx->rs_tmp[3].as<unsigned char>(), red.pi,
+                       red.pd, &blk->err);
+    red.total(ctx, nb, &blk->tot);
 }
 
 // The select on n (value, use byte) pairs on the device; the state block holds the counts of stat_device and the ranks asked for
@@ -644,43 +551,39 @@ int nn_error_distribution(me_ctx *ctx, int qslot, const me_errdist_params *p, me
                                de.as<double>(), n_bins, dh.as<u64>());
     }
     ME_CHECK(ctx, hipGetLastError());
-    struct {
-        long long n_query, n_used, argmax, n_within[ME_ERRDIST_MAX_THRESHOLDS];
-        u64 mn, mx;
-        double sum_d, sum_d2;
-    } h;
-    static_assert(offsetof(RsBlock, sum_d2) - offsetof(RsBlock, n_query) + 8 == sizeof(h), "the fetched part of the state block");
+    EdRed::Totals h;
     {
         MailGuard mg(ctx);
-        ME_TRY(mail_post(ctx, &h, &blk->n_query, sizeof(h)));
+        ME_TRY(mail_post(ctx, &h, &blk->tot, sizeof(h)));
         ME_TRY(mg.sync());
     }
+    const long long n_used = h.i[1];
     std::memset(out, 0, sizeof(*out));
-    out->n_query = h.n_query;
-    out->n_used = h.n_used;
+    out->n_query = h.i[0];
+    out->n_used = n_used;
     out->argmax = -1;
-    auto as_double = [](u64 k) {
+    auto as_double = [](long long k) {
         double v;
         std::memcpy(&v, &k, 8);
         return v;
     };
-    if (h.n_used > 0) {
-        out->sum_d = h.sum_d;
-        out->sum_d2 = h.sum_d2;
-        out->min_d = std::sqrt(as_double(h.mn));
-        out->max_d = std::sqrt(as_double(h.mx));
-        out->argmax = h.argmax;
+    if (n_used > 0) {
+        out->sum_d = h.d[0];
+        out->sum_d2 = h.d[1];
+        out->min_d = std::sqrt(as_double(h.i[kEdMn]));
+        out->max_d = std::sqrt(as_double(h.i[kEdMx]));
+        out->argmax = h.i[kEdArg];
     }
-    for (int k = 0; k < p->n_thresholds; ++k) out->n_within[k] = h.n_within[k];
+    for (int k = 0; k < p->n_thresholds; ++k) out->n_within[k] = h.i[2 + k];
     long long h_rank[kRsMax] = {0};
     for (int j = 0; j < p->n_quantiles; ++j) {
         // nearest rank: ceil(p n) - 1, one fp64 multiplication, clamped to [0, n_used - 1]
         long long r = -1;
-        if (h.n_used > 0) r = std::min<long long>(h.n_used - 1, std::max<long long>(0, (long long) std::ceil(p->prob[j] * (double) h.n_used) - 1));
+        if (n_used > 0) r = std::min<long long>(n_used - 1, std::max<long long>(0, (long long) std::ceil(p->prob[j] * (double) n_used) - 1));
         out->rank[j] = r;
         h_rank[j] = std::max<long long>(r, 0);
     }
-    if (p->n_quantiles > 0 && h.n_used > 0) {
+    if (p->n_quantiles > 0 && n_used > 0) {
         ME_TRY(copy_h2d(ctx, blk->rank_in, h_rank, sizeof(h_rank)));
         ME_TRY(rank_select_device(ctx, d2, use, n, p->n_quantiles));
         me_rank_stats rs;

@@ -7,8 +7,8 @@
 //                  then C = (sum(d d^T) - sum(d) sum(d)^T / k) / (k - 1), its eigenvalues by jacobi_sym (me_horn.hpp), clamped at 0
 //                  and ordered l1 >= l2 >= l3.  The point is valid iff k >= min_k and l1 > 0; an invalid point stores zeros.
 //                  Per block: the partial sums of l3, linearity, planarity, sphericity, surface variation, k and the valid count.
-//   k_lg_final     the block partials in block order (256 chunks, then one block): a fixed order, bit-identical from run to run, no
-//                  floating-point atomics                                                             (me_local_geometry, "local_geom")
+//                  The rows of block partials are added in block order by me_reduce.hpp's row_sum_device
+//                                                                                                     (me_local_geometry, "local_geom")
 //   k_lg_unpermute the per-point results, kept in SORTED order on the cloud, back in cloud order           (me_local_geometry_fetch)
 //   k_local_geom_normals  the same pass (one body, a template flag) for me_radius_normals ("radius_normals"): it also keeps the column of Jacobi's V that belongs
 //                  to the smallest eigenvalue, scaled to unit length and optionally turned towards a viewpoint, and stores it in the
@@ -19,19 +19,15 @@
 
 #include "me_horn.hpp"
 #include "me_internal.hpp"
+#include "me_reduce.hpp"
 #include "me_wave_stream.hpp"
 
 namespace me {
 
 namespace {
 
-constexpr int kLgSums = 8;  // l3, linearity, planarity, sphericity, surface variation (double); k, valid points (int64); one spare
-constexpr int kLgStage = 256;
-
-union LgWord {
-    double d;
-    long long i;
-};
+constexpr int kLgSums = 7;  // rows of block partials: l3, linearity, planarity, sphericity, surface variation (double); k, valid points (int64)
+constexpr unsigned long long kLgIntRows = 0x60ull;
 
 // what k_local_geom_normals needs beyond the eigenvalues (unused by k_local_geom)
 struct LgNormalArgs {
@@ -48,7 +44,7 @@ struct LgNormalArgs {
 template <bool NORMALS>
 __device__ __forceinline__ void
 local_geom_body(const SPoint *__restrict__ sp, const unsigned long long *__restrict__ codes, long long n, const GridView &g, double r2, int min_k,
-                double *__restrict__ eig_s, int *__restrict__ k_s, unsigned char *__restrict__ valid_s, LgWord *__restrict__ part,
+                double *__restrict__ eig_s, int *__restrict__ k_s, unsigned char *__restrict__ valid_s, RedWord *__restrict__ part,
                 unsigned int nb, const LgNormalArgs &na) {
     __shared__ WaveTile s_tile[4];
     __shared__ int2 s_tab[4][kGroupTab + 1];
@@ -156,7 +152,7 @@ local_geom_body(const SPoint *__restrict__ sp, const unsigned long long *__restr
 
 __global__ void __launch_bounds__(256)
 k_local_geom(const SPoint *__restrict__ sp, const unsigned long long *__restrict__ codes, long long n, GridView g, double r2, int min_k,
-             double *__restrict__ eig_s, int *__restrict__ k_s, unsigned char *__restrict__ valid_s, LgWord *__restrict__ part,
+             double *__restrict__ eig_s, int *__restrict__ k_s, unsigned char *__restrict__ valid_s, RedWord *__restrict__ part,
              unsigned int nb) {
     local_geom_body<false>(sp, codes, n, g, r2, min_k, eig_s, k_s, valid_s, part, nb, LgNormalArgs{});
 }
@@ -165,32 +161,9 @@ k_local_geom(const SPoint *__restrict__ sp, const unsigned long long *__restrict
 // alone is held to six waves per SIMD (80 VGPRs) by the attribute — the resource lines of both are in DESIGN.md section 4.14
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 6)))
 k_local_geom_normals(const SPoint *__restrict__ sp, const unsigned long long *__restrict__ codes, long long n, GridView g, double r2, int min_k,
-                     double *__restrict__ eig_s, int *__restrict__ k_s, unsigned char *__restrict__ valid_s, LgWord *__restrict__ part,
+                     double *__restrict__ eig_s, int *__restrict__ k_s, unsigned char *__restrict__ valid_s, RedWord *__restrict__ part,
                      unsigned int nb, LgNormalArgs na) {
     local_geom_body<true>(sp, codes, n, g, r2, min_k, eig_s, k_s, valid_s, part, nb, na);
-}
-
-// row v of `in` ([kLgSums][nb]) -> out[v * gridDim.x + block]: block b sums the chunk [b chunk, (b + 1) chunk) of the row, thread t
-// taking t, t + 256, ... in order.  Rows 0 - 4 are doubles, 5 - 6 int64.
-__global__ void __launch_bounds__(256)
-k_lg_final(const LgWord *__restrict__ in, long long nb, long long chunk, LgWord *__restrict__ out) {
-    __shared__ double smd[4];
-    __shared__ long long smi[4];
-    const long long b0 = (long long) blockIdx.x * chunk, b1 = b0 + chunk < nb ? b0 + chunk : nb;
-    for (int v = 0; v < 7; ++v) {
-        const LgWord *row = in + (size_t) v * nb;
-        LgWord r;
-        if (v < 5) {
-            double s = 0.0;
-            for (long long b = b0 + threadIdx.x; b < b1; b += 256) s += row[b].d;
-            r.d = block_sum_256(s, smd);
-        } else {
-            long long s = 0;
-            for (long long b = b0 + threadIdx.x; b < b1; b += 256) s += row[b].i;
-            r.i = block_sum_256_ll(s, smi);
-        }
-        if (threadIdx.x == 0) out[(size_t) v * gridDim.x + blockIdx.x] = r;
-    }
 }
 
 __global__ void __launch_bounds__(256)
@@ -214,7 +187,7 @@ k_lg_unpermute(const SPoint *__restrict__ sp, long long n, const double *__restr
 namespace {
 
 // the pass of me_local_geometry (nrm == nullptr) and of me_radius_normals: the per-point results on the slot, the seven totals in h
-int run_local_geom(me_ctx *ctx, int slot, double radius, int min_k, const LgNormalArgs *nrm, const char *who, LgWord h[7]) {
+int run_local_geom(me_ctx *ctx, int slot, double radius, int min_k, const LgNormalArgs *nrm, const char *who, RedWord h[7]) {
     ME_TRY(need_single_gpu_cloud(ctx, slot, who));
     if (!(radius > 0) || !std::isfinite(radius)) return ctx->fail(ME_ERR_ARG, std::string(who) + ": radius must be finite and > 0");
     if (min_k < 2) return ctx->fail(ME_ERR_ARG, std::string(who) + ": min_k must be >= 2 (the covariance divides by k - 1)");
@@ -233,11 +206,8 @@ int run_local_geom(me_ctx *ctx, int slot, double radius, int min_k, const LgNorm
     ME_CHECK(ctx, c.lg_k.ensure((size_t) n * 4));
     ME_CHECK(ctx, c.lg_val.ensure((size_t) n));
     const unsigned int nb = blocks_of(n);
-    // [kLgSums][nb] block partials | [kLgSums][kLgStage] | [kLgSums] totals
-    ME_CHECK(ctx, ctx->red.ensure(((size_t) nb + kLgStage + 1) * kLgSums * 8));
-    LgWord *part = ctx->red.as<LgWord>();
-    LgWord *part2 = part + (size_t) nb * kLgSums;
-    LgWord *tot = part2 + (size_t) kLgStage * kLgSums;
+    ME_CHECK(ctx, ctx->red.ensure(row_sum_bytes(kLgSums, nb)));
+    RedWord *part = row_sum_part(ctx), *tot;
     {
         TimerScope ts(ctx, nrm ? "radius_normals" : "local_geom");
         if (nrm) {
@@ -252,15 +222,12 @@ int run_local_geom(me_ctx *ctx, int slot, double radius, int min_k, const LgNorm
             hipLaunchKernelGGL(k_local_geom, dim3(nb), dim3(256), 0, ctx->stream, c.sp.as<SPoint>(), c.codes.as<unsigned long long>(), n,
                                c.grid, radius * radius, min_k, c.lg_eig.as<double>(), c.lg_k.as<int>(), c.lg_val.as<unsigned char>(), part, nb);
         }
-        const long long chunk = ((long long) nb + kLgStage - 1) / kLgStage;
-        hipLaunchKernelGGL(k_lg_final, dim3(kLgStage), dim3(256), 0, ctx->stream, (const LgWord *) part, (long long) nb, chunk, part2);
-        hipLaunchKernelGGL(k_lg_final, dim3(1), dim3(256), 0, ctx->stream, (const LgWord *) part2, (long long) kLgStage, (long long) kLgStage,
-                           tot);
+        tot = row_sum_device<kLgIntRows>(ctx, kLgSums, nb);
     }
     ME_CHECK(ctx, hipGetLastError());
     {
         MailGuard mg(ctx);
-        ME_TRY(mail_post(ctx, h, tot, 7 * sizeof(LgWord)));
+        ME_TRY(mail_post(ctx, h, tot, kLgSums * sizeof(RedWord)));
         ME_TRY(mg.sync());
     }
     c.lg_have = true;
@@ -271,7 +238,7 @@ int run_local_geom(me_ctx *ctx, int slot, double radius, int min_k, const LgNorm
 }  // namespace
 
 int local_geometry(me_ctx *ctx, int slot, double radius, int min_k, me_local_geom_out *out) {
-    LgWord h[7];
+    RedWord h[7];
     ME_TRY(run_local_geom(ctx, slot, radius, min_k, nullptr, "me_local_geometry", h));
     const long long n = ctx->cloud[slot].n;
     if (out) {
@@ -297,7 +264,7 @@ int radius_normals(me_ctx *ctx, int slot, double radius, int min_k, const double
         na.have_view = 1;
     }
     na.invalid_z = invalid_z != 0;
-    LgWord h[7];
+    RedWord h[7];
     ME_TRY(run_local_geom(ctx, slot, radius, min_k, &na, "me_radius_normals", h));
     Cloud &c = ctx->cloud[slot];
     c.have_normals = true;

@@ -13,9 +13,8 @@
 //                  has no cell of the frame within reach and is settled with n = 0 without streaming.  Masked-out lanes are not pending.
 //   k_m3_final     a fixed grid of at most kM3Blocks blocks strides over the sorted core points: validity, dist, the two variances,
 //                  lod and the significance bit, kept on the slot in SORTED order; counts, sums and the (largest |dist|, smallest
-//                  original index) pair per block by a fixed tree, stored as the block's partial
-//   k_m3_total     one block: the partials in block order (thread t takes t, t + 256, ...; k_sf_final's rule) — no floating-point
-//                  atomics, bit-identical from run to run                                                            (me_m3c2, "m3c2")
+//                  original index) pair per block; the block's partial record and the one-block total over the records are
+//                  me_reduce.hpp's                                                                                   (me_m3c2, "m3c2")
 //   k_m3_unpermute the per-point results back in cloud order                                                         (me_m3c2_fetch)
 // The search visits the ball of radius R, not the cylinder: the work per core point grows like (R / spacing)^2 on a surface.  The
 // remedy for long cylinders on dense clouds is the core mask (M3C2's core points); a stepped walk along the axis is not built.
@@ -24,6 +23,7 @@
 #include <cstring>
 
 #include "me_internal.hpp"
+#include "me_reduce.hpp"
 #include "me_wave_stream.hpp"
 
 namespace me {
@@ -33,18 +33,9 @@ namespace {
 typedef unsigned long long u64;
 
 constexpr unsigned int kM3Blocks = 1024;  // above 256 x 1024 core points a block of k_m3_final strides over the array
-constexpr int kM3D = 4;                   // double partials per block: sum_dist, sum_abs_dist, sum_dist2, sum_lod
-constexpr int kM3I = 8;                   // integer partials: n_core, n_no_normal, n_valid, n_significant, sum_n_own, sum_n_other, max key, argmax
-
-struct M3Totals {
-    double d[kM3D];
-    long long i[kM3I];
-};
-
-// (key, index) pairs: the larger key wins, on equal keys the smaller index; arg < 0 = no entry yet
-__device__ __forceinline__ void m3_take_max(u64 &mx, long long &arg, u64 omx, long long oa) {
-    if (oa >= 0 && (arg < 0 || omx > mx || (omx == mx && oa < arg))) mx = omx, arg = oa;
-}
+constexpr int kM3D = 4;                   // double sums per block: sum_dist, sum_abs_dist, sum_dist2, sum_lod
+constexpr int kM3NI = 6;                  // integer sums: n_core, n_no_normal, n_valid, n_significant, sum_n_own, sum_n_other; then max key, argmax
+typedef RedBufs<kM3D, kM3NI> M3Red;
 
 // qsp / qcodes / nq / qshift: the query cloud's sorted points; ssp / g / fr: the streamed cloud (the query's own when !OTHER).
 // nrm (double[nq][3]) and mask (uint8[nq] or nullptr) are in the query's CLOUD order; cnt_s / S_s / Q_s in its SORTED order.
@@ -109,9 +100,9 @@ __global__ void __launch_bounds__(256)
 k_m3_final(const SPoint *__restrict__ sp, long long n, const double *__restrict__ nrm, const unsigned char *__restrict__ mask,
            int *__restrict__ cnt, const double *__restrict__ mom, int min_points, double reg, double *__restrict__ res,
            unsigned char *__restrict__ flags, double *__restrict__ pd, long long *__restrict__ pi) {
-    long long ncore = 0, nnn = 0, nv = 0, ns = 0, so = 0, st = 0, arg = -1;
+    long long arg = -1, ci[kM3NI] = {0, 0, 0, 0, 0, 0};  // n_core, n_no_normal, n_valid, n_significant, sum_n_own, sum_n_other
     u64 mx = 0ull;
-    double sd = 0.0, sa = 0.0, sd2 = 0.0, sl = 0.0;
+    double sd[kM3D] = {0.0, 0.0, 0.0, 0.0};              // sum_dist, sum_abs_dist, sum_dist2, sum_lod
     const long long stride = (long long) gridDim.x * 256;
     for (long long i = (long long) blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
         const long long o = sp[i].idx;
@@ -120,9 +111,9 @@ k_m3_final(const SPoint *__restrict__ sp, long long n, const double *__restrict_
         double dist = 0.0, lod = 0.0, vo = 0.0, vt = 0.0;
         unsigned char fl = 0;
         if (in) {
-            ncore += 1;
+            ci[0] += 1;
             const bool zero = nrm[3 * o] == 0.0 && nrm[3 * o + 1] == 0.0 && nrm[3 * o + 2] == 0.0;
-            if (zero) nnn += 1;
+            if (zero) ci[1] += 1;
             if (!zero && n_own >= min_points && n_oth >= min_points) {
                 const double no = (double) n_own, nt = (double) n_oth;
                 const double S0 = mom[i], Q0 = mom[n + i], S1 = mom[2 * n + i], Q1 = mom[3 * n + i];
@@ -132,15 +123,15 @@ k_m3_final(const SPoint *__restrict__ sp, long long n, const double *__restrict_
                 lod = 1.96 * (sqrt(vo / no + vt / nt) + reg);
                 const double ad = fabs(dist);
                 fl = 1;
-                if (ad > lod) fl |= 2, ns += 1;
-                nv += 1;
-                sd += dist;
-                sa += ad;
-                sd2 += dist * dist;
-                sl += lod;
-                so += n_own;
-                st += n_oth;
-                m3_take_max(mx, arg, (u64) __double_as_longlong(ad), o);  // (ad >= +0.0: the order of the bit patterns is the numeric order)
+                if (ad > lod) fl |= 2, ci[3] += 1;
+                ci[2] += 1;
+                sd[0] += dist;
+                sd[1] += ad;
+                sd[2] += dist * dist;
+                sd[3] += lod;
+                ci[4] += n_own;
+                ci[5] += n_oth;
+                take_max(mx, arg, (u64) __double_as_longlong(ad), o);  // (ad >= +0.0: the order of the bit patterns is the numeric order)
             }
         } else {
             n_own = n_oth = 0;
@@ -153,89 +144,7 @@ k_m3_final(const SPoint *__restrict__ sp, long long n, const double *__restrict_
         res[3 * n + i] = vt;
         flags[i] = fl;
     }
-    __shared__ double smd[4];
-    __shared__ long long smi[4];
-    __shared__ u64 s_mx[4];
-    __shared__ long long s_arg[4];
-    double *bd = pd + (size_t) blockIdx.x * kM3D;
-    long long *bi = pi + (size_t) blockIdx.x * kM3I;
-    double r = block_sum_256(sd, smd);
-    if (threadIdx.x == 0) bd[0] = r;
-    r = block_sum_256(sa, smd);
-    if (threadIdx.x == 0) bd[1] = r;
-    r = block_sum_256(sd2, smd);
-    if (threadIdx.x == 0) bd[2] = r;
-    r = block_sum_256(sl, smd);
-    if (threadIdx.x == 0) bd[3] = r;
-    long long v = block_sum_256_ll(ncore, smi);
-    if (threadIdx.x == 0) bi[0] = v;
-    v = block_sum_256_ll(nnn, smi);
-    if (threadIdx.x == 0) bi[1] = v;
-    v = block_sum_256_ll(nv, smi);
-    if (threadIdx.x == 0) bi[2] = v;
-    v = block_sum_256_ll(ns, smi);
-    if (threadIdx.x == 0) bi[3] = v;
-    v = block_sum_256_ll(so, smi);
-    if (threadIdx.x == 0) bi[4] = v;
-    v = block_sum_256_ll(st, smi);
-    if (threadIdx.x == 0) bi[5] = v;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const u64 omx = (u64) __shfl_down((long long) mx, o, 64);
-        const long long oa = __shfl_down(arg, o, 64);
-        m3_take_max(mx, arg, omx, oa);
-    }
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) s_mx[w] = mx, s_arg[w] = arg;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int q = 1; q < 4; ++q) m3_take_max(mx, arg, s_mx[q], s_arg[q]);
-        bi[6] = (long long) mx;
-        bi[7] = arg;
-    }
-}
-
-__global__ void __launch_bounds__(256) k_m3_total(const double *__restrict__ pd, const long long *__restrict__ pi, int nb, M3Totals *__restrict__ t) {
-    __shared__ double smd[4];
-    __shared__ long long smi[4];
-    __shared__ u64 s_mx[256];
-    __shared__ long long s_arg[256];
-    double sd[kM3D];
-    long long ci[kM3I];
-#pragma unroll
-    for (int k = 0; k < kM3D; ++k) sd[k] = 0.0;
-#pragma unroll
-    for (int k = 0; k < kM3I; ++k) ci[k] = 0;
-    u64 mx = 0ull;
-    long long arg = -1;
-    for (int q = threadIdx.x; q < nb; q += 256) {
-        const double *bd = pd + (size_t) q * kM3D;
-        const long long *bi = pi + (size_t) q * kM3I;
-#pragma unroll
-        for (int k = 0; k < kM3D; ++k) sd[k] += bd[k];
-#pragma unroll
-        for (int k = 0; k < 6; ++k) ci[k] += bi[k];
-        m3_take_max(mx, arg, (u64) bi[6], bi[7]);
-    }
-#pragma unroll
-    for (int k = 0; k < kM3D; ++k) {
-        const double r = block_sum_256(sd[k], smd);
-        if (threadIdx.x == 0) t->d[k] = r;
-    }
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-        const long long v = block_sum_256_ll(ci[k], smi);
-        if (threadIdx.x == 0) t->i[k] = v;
-    }
-    s_mx[threadIdx.x] = mx;
-    s_arg[threadIdx.x] = arg;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int q = 1; q < 256; ++q) m3_take_max(mx, arg, s_mx[q], s_arg[q]);
-        t->i[6] = (long long) mx;
-        t->i[7] = arg;
-    }
+    red_store_partial<kM3D, kM3NI, false>(sd, ci, mx, arg, 0ull, pd + (size_t) blockIdx.x * kM3D, pi + (size_t) blockIdx.x * M3Red::Totals::NR);
 }
 
 // every output is nullable; cnt_s / res_s / fl_s as k_m3_final leaves them
@@ -298,11 +207,8 @@ int m3c2(me_ctx *ctx, int qslot, const me_m3c2_params *p, const uint8_t *core_ma
         mask = mb.as<unsigned char>();
     }
     const int nb = (int) std::min<long long>(kM3Blocks, blocks_of(n));
-    // [kM3Blocks][kM3D] doubles | [kM3Blocks][kM3I] integers | the totals
-    ME_CHECK(ctx, ctx->red.ensure((size_t) kM3Blocks * (kM3D + kM3I) * 8 + sizeof(M3Totals)));
-    double *pd = ctx->red.as<double>();
-    long long *pi = reinterpret_cast<long long *>(pd + (size_t) kM3Blocks * kM3D);
-    M3Totals *tot = reinterpret_cast<M3Totals *>(pi + (size_t) kM3Blocks * kM3I);
+    ME_CHECK(ctx, ctx->red.ensure(M3Red::bytes(kM3Blocks)));
+    const M3Red red(ctx, kM3Blocks);
     int *cnt = q.m3_cnt.as<int>();
     double *mom = q.m3_mom.as<double>();
     {
@@ -313,14 +219,14 @@ int m3c2(me_ctx *ctx, int qslot, const me_m3c2_params *p, const uint8_t *core_ma
         hipLaunchKernelGGL(k_m3_stream<true>, dim3(blocks_of(n)), dim3(256), 0, ctx->stream, q.sp.as<SPoint>(), q.codes.as<unsigned long long>(), n,
                            q.grid.shift, r.sp.as<SPoint>(), r.grid, fr, q.normals.as<double>(), mask, L, rp * rp, cnt + n, mom + 2 * n, mom + 3 * n);
         hipLaunchKernelGGL(k_m3_final, dim3(nb), dim3(256), 0, ctx->stream, q.sp.as<SPoint>(), n, q.normals.as<double>(), mask, cnt,
-                           (const double *) mom, (int) p->min_points, p->reg_error, q.m3_res.as<double>(), q.m3_flags.as<unsigned char>(), pd, pi);
-        hipLaunchKernelGGL(k_m3_total, dim3(1), dim3(256), 0, ctx->stream, (const double *) pd, (const long long *) pi, nb, tot);
+                           (const double *) mom, (int) p->min_points, p->reg_error, q.m3_res.as<double>(), q.m3_flags.as<unsigned char>(), red.pd, red.pi);
+        red.total(ctx, nb, red.tot);
     }
     ME_CHECK(ctx, hipGetLastError());
-    M3Totals h;
+    M3Red::Totals h;
     {
         MailGuard mg(ctx);
-        ME_TRY(mail_post(ctx, &h, tot, sizeof(h)));
+        ME_TRY(mail_post(ctx, &h, red.tot, sizeof(h)));
         ME_TRY(mg.sync());
     }
     q.m3c2_have = true;
@@ -337,9 +243,8 @@ int m3c2(me_ctx *ctx, int qslot, const me_m3c2_params *p, const uint8_t *core_ma
         out->sum_lod = h.d[3];
         out->sum_n_own = h.i[4];
         out->sum_n_other = h.i[5];
-        const u64 key = (u64) h.i[6];
-        std::memcpy(&out->max_abs_dist, &key, 8);
-        out->argmax = h.i[7];
+        std::memcpy(&out->max_abs_dist, &h.i[kM3NI], 8);
+        out->argmax = h.i[kM3NI + 1];
     }
     return ME_OK;
 }

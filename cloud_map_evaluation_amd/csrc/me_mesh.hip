@@ -10,8 +10,8 @@
 //                  stack: the path is the node index itself (parent = j >> 3) and one byte per level marks the children already taken.
 //                  A child is opened iff its box distance <= bound(best), see mesh_bound; a leaf runs tri_closest on its <= 8 triangles.
 //                  The winner is the lexicographic minimum of (d2, caller index): independent of the order of the walk.
-//   k_mesh_final / k_mesh_total   the gate, the sums and counts: per-block partials by a fixed tree, combined in block order by one block
-//                  (me_m3c2.hip's scheme): no floating-point atomics, bit-identical from run to run
+//   k_mesh_final   the gate, the sums and counts; the block's partial record and the one-block total over the records are
+//                  me_reduce.hpp's
 //   k_mesh_unpermute  the per-point results back in cloud order                                              (me_mesh_distance_fetch)
 //   k_mesh_sample  Philox4x64-10 at counter (i, 0, 0, 0): triangle by binary search in the cumulative areas, point by the square-root
 //                  parametrisation; written into the slot's own buffer, then the normal cloud_finish
@@ -22,20 +22,18 @@
 
 #include "me_internal.hpp"
 #include "me_philox.hpp"
+#include "me_reduce.hpp"
 
 namespace me {
 
 namespace {
 
 constexpr unsigned int kMdBlocks = 1024;
-constexpr int kMdD = 4;   // double partials per block: sum_d, sum_d2, sum_signed, sum_abs_signed
-constexpr int kMdI = 12;  // integer partials: n_matched, n_face, n_within[8], max key, argmax
+constexpr int kMdD = 4;    // double sums per block: sum_d, sum_d2, sum_signed, sum_abs_signed
+constexpr int kMdNI = 2 + ME_MESH_MAX_THRESHOLDS;  // integer sums: n_matched, n_face, n_within[8]; then max key, argmax
+typedef RedBufs<kMdD, kMdNI> MdRed;
 constexpr unsigned int kDegBit = 0x80000000u;  // in the stored caller index: the triangle is degenerate
 
-struct MdTotals {
-    double d[kMdD];
-    long long i[kMdI];
-};
 struct MdGate {
     double max2;  // max_distance * max_distance
     double t2[ME_MESH_MAX_THRESHOLDS];
@@ -276,117 +274,34 @@ k_mesh_dist(const SPoint *__restrict__ sp, long long n, MeshView m, double *__re
     sd_s[i] = sd;
 }
 
-__device__ __forceinline__ void md_take_max(unsigned long long &mx, long long &arg, unsigned long long omx, long long oa) {
-    if (oa >= 0 && (arg < 0 || omx > mx || (omx == mx && oa < arg))) mx = omx, arg = oa;
-}
-
 __global__ void __launch_bounds__(256)
 k_mesh_final(const SPoint *__restrict__ sp, long long n, const double *__restrict__ d2_s, const unsigned char *__restrict__ reg_s,
              const double *__restrict__ sd_s, MdGate g, double *__restrict__ pd, long long *__restrict__ pi) {
-    long long nm = 0, nf = 0, arg = -1, nw[ME_MESH_MAX_THRESHOLDS];
+    long long arg = -1, ci[kMdNI];  // n_matched, n_face, n_within[8]
 #pragma unroll
-    for (int k = 0; k < ME_MESH_MAX_THRESHOLDS; ++k) nw[k] = 0;
+    for (int k = 0; k < kMdNI; ++k) ci[k] = 0;
     unsigned long long mx = 0ull;
-    double sd = 0.0, sd2 = 0.0, ss = 0.0, sa = 0.0;
+    double sd[kMdD] = {0.0, 0.0, 0.0, 0.0};  // sum_d, sum_d2, sum_signed, sum_abs_signed
     const long long stride = (long long) gridDim.x * 256;
     for (long long i = (long long) blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
         const double d2 = d2_s[i];
         if (!(d2 <= g.max2)) continue;
         const double d = sqrt(d2);
-        nm += 1;
-        sd += d;
-        sd2 += d2;
+        ci[0] += 1;
+        sd[0] += d;
+        sd[1] += d2;
 #pragma unroll
         for (int k = 0; k < ME_MESH_MAX_THRESHOLDS; ++k)
-            if (k < g.nt && d2 <= g.t2[k]) nw[k] += 1;
+            if (k < g.nt && d2 <= g.t2[k]) ci[2 + k] += 1;
         if (reg_s[i] == 0) {
             const double s = sd_s[i];
-            nf += 1;
-            ss += s;
-            sa += fabs(s);
+            ci[1] += 1;
+            sd[2] += s;
+            sd[3] += fabs(s);
         }
-        md_take_max(mx, arg, (unsigned long long) __double_as_longlong(d), sp[i].idx);  // (d >= +0.0: bit order = numeric order)
+        take_max(mx, arg, (unsigned long long) __double_as_longlong(d), sp[i].idx);  // (d >= +0.0: bit order = numeric order)
     }
-    __shared__ double smd[4];
-    __shared__ long long smi[4];
-    __shared__ unsigned long long s_mx[4];
-    __shared__ long long s_arg[4];
-    double *bd = pd + (size_t) blockIdx.x * kMdD;
-    long long *bi = pi + (size_t) blockIdx.x * kMdI;
-    double r = block_sum_256(sd, smd);
-    if (threadIdx.x == 0) bd[0] = r;
-    r = block_sum_256(sd2, smd);
-    if (threadIdx.x == 0) bd[1] = r;
-    r = block_sum_256(ss, smd);
-    if (threadIdx.x == 0) bd[2] = r;
-    r = block_sum_256(sa, smd);
-    if (threadIdx.x == 0) bd[3] = r;
-    long long v = block_sum_256_ll(nm, smi);
-    if (threadIdx.x == 0) bi[0] = v;
-    v = block_sum_256_ll(nf, smi);
-    if (threadIdx.x == 0) bi[1] = v;
-#pragma unroll
-    for (int k = 0; k < ME_MESH_MAX_THRESHOLDS; ++k) {
-        v = block_sum_256_ll(nw[k], smi);
-        if (threadIdx.x == 0) bi[2 + k] = v;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long omx = (unsigned long long) __shfl_down((long long) mx, o, 64);
-        const long long oa = __shfl_down(arg, o, 64);
-        md_take_max(mx, arg, omx, oa);
-    }
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) s_mx[w] = mx, s_arg[w] = arg;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int q = 1; q < 4; ++q) md_take_max(mx, arg, s_mx[q], s_arg[q]);
-        bi[10] = (long long) mx;
-        bi[11] = arg;
-    }
-}
-
-__global__ void __launch_bounds__(256) k_mesh_total(const double *__restrict__ pd, const long long *__restrict__ pi, int nb, MdTotals *__restrict__ t) {
-    __shared__ double smd[4];
-    __shared__ long long smi[4];
-    __shared__ unsigned long long s_mx[256];
-    __shared__ long long s_arg[256];
-    double sd[kMdD];
-    long long ci[10];
-#pragma unroll
-    for (int k = 0; k < kMdD; ++k) sd[k] = 0.0;
-#pragma unroll
-    for (int k = 0; k < 10; ++k) ci[k] = 0;
-    unsigned long long mx = 0ull;
-    long long arg = -1;
-    for (int q = threadIdx.x; q < nb; q += 256) {
-        const double *bd = pd + (size_t) q * kMdD;
-        const long long *bi = pi + (size_t) q * kMdI;
-#pragma unroll
-        for (int k = 0; k < kMdD; ++k) sd[k] += bd[k];
-#pragma unroll
-        for (int k = 0; k < 10; ++k) ci[k] += bi[k];
-        md_take_max(mx, arg, (unsigned long long) bi[10], bi[11]);
-    }
-#pragma unroll
-    for (int k = 0; k < kMdD; ++k) {
-        const double r = block_sum_256(sd[k], smd);
-        if (threadIdx.x == 0) t->d[k] = r;
-    }
-#pragma unroll
-    for (int k = 0; k < 10; ++k) {
-        const long long v = block_sum_256_ll(ci[k], smi);
-        if (threadIdx.x == 0) t->i[k] = v;
-    }
-    s_mx[threadIdx.x] = mx;
-    s_arg[threadIdx.x] = arg;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int q = 1; q < 256; ++q) md_take_max(mx, arg, s_mx[q], s_arg[q]);
-        t->i[10] = (long long) mx;
-        t->i[11] = arg;
-    }
+    red_store_partial<kMdD, kMdNI, false>(sd, ci, mx, arg, 0ull, pd + (size_t) blockIdx.x * kMdD, pi + (size_t) blockIdx.x * MdRed::Totals::NR);
 }
 
 // every output is nullable
@@ -588,10 +503,8 @@ int mesh_distance(me_ctx *ctx, int qslot, const me_mesh_params *p, me_mesh_out *
     ME_CHECK(ctx, q.mesh_cp.ensure((size_t) n * 24));
     ME_CHECK(ctx, q.mesh_sd.ensure((size_t) n * 8));
     const int nb = (int) std::min<long long>(kMdBlocks, blocks_of(n));
-    ME_CHECK(ctx, ctx->red.ensure((size_t) kMdBlocks * (kMdD + kMdI) * 8 + sizeof(MdTotals)));
-    double *pd = ctx->red.as<double>();
-    long long *pi = reinterpret_cast<long long *>(pd + (size_t) kMdBlocks * kMdD);
-    MdTotals *tot = reinterpret_cast<MdTotals *>(pi + (size_t) kMdBlocks * kMdI);
+    ME_CHECK(ctx, ctx->red.ensure(MdRed::bytes(kMdBlocks)));
+    const MdRed red(ctx, kMdBlocks);
     MeshView mv{m.tri_s.as<double>(), m.orig.as<unsigned int>(), m.boxes.as<double>(), m.lv.as<int2>(), m.nt, m.n_levels,
                 kMeshDeltaUlps * 0x1p-53 * m.max_abs};
     {
@@ -600,13 +513,13 @@ int mesh_distance(me_ctx *ctx, int qslot, const me_mesh_params *p, me_mesh_out *
                            q.mesh_tri.as<int>(), q.mesh_reg.as<unsigned char>(), q.mesh_cp.as<double>(), q.mesh_sd.as<double>());
     }
     hipLaunchKernelGGL(k_mesh_final, dim3(nb), dim3(256), 0, ctx->stream, q.sp.as<SPoint>(), n, q.mesh_d2.as<double>(),
-                       q.mesh_reg.as<unsigned char>(), q.mesh_sd.as<double>(), g, pd, pi);
-    hipLaunchKernelGGL(k_mesh_total, dim3(1), dim3(256), 0, ctx->stream, (const double *) pd, (const long long *) pi, nb, tot);
+                       q.mesh_reg.as<unsigned char>(), q.mesh_sd.as<double>(), g, red.pd, red.pi);
+    red.total(ctx, nb, red.tot);
     ME_CHECK(ctx, hipGetLastError());
-    MdTotals h;
+    MdRed::Totals h;
     {
         MailGuard mg(ctx);
-        ME_TRY(mail_post(ctx, &h, tot, sizeof(h)));
+        ME_TRY(mail_post(ctx, &h, red.tot, sizeof(h)));
         ME_TRY(mg.sync());
     }
     q.mesh_have = true;
@@ -618,9 +531,8 @@ int mesh_distance(me_ctx *ctx, int qslot, const me_mesh_params *p, me_mesh_out *
     for (int k = 0; k < g.nt; ++k) out->n_within[k] = h.i[2 + k];
     out->argmax = -1;
     if (h.i[0] > 0) {
-        const unsigned long long key = (unsigned long long) h.i[10];
-        std::memcpy(&out->max_d, &key, 8);
-        out->argmax = h.i[11];
+        std::memcpy(&out->max_d, &h.i[kMdNI], 8);
+        out->argmax = h.i[kMdNI + 1];
     }
     return ME_OK;
 }

@@ -5,8 +5,7 @@
 //   k_gs_stat    one tile of kGsTile entries per block: count, smallest and largest key per group through LDS integer atomics and one
 //                integer atomic per (block, group) to memory; the group's sum of the tile by a fixed tree (each thread its eight
 //                entries in order, then block_sum_256), stored as the block's partial.  A group absent from the tile stores 0.0
-//   k_gs_final   the block partials in block order (256 chunks, then one block): a fixed order, bit-identical from run to run, no
-//                floating-point atomics
+//                The rows of block partials are added in block order by me_reduce.hpp's row_sum_device
 //   k_gs_start   per group: live = count > 0, the ranks (count - 1) / 2 and count / 2, an empty prefix
 //   k_gs_hist    THE HOT KERNEL, once per pass (eight passes of eight bits, from the top) and slice of kGsSlice groups: the entries
 //                whose key carries the prefix of a rank found so far add one to the LDS histogram (group, rank slot, digit); a wave whose
@@ -25,6 +24,7 @@
 #include <cstring>
 
 #include "me_internal.hpp"
+#include "me_reduce.hpp"
 
 namespace me {
 
@@ -39,7 +39,6 @@ constexpr int kGsPasses = 64 / kGsBits;
 constexpr int kGsSlice = 16;                 // groups per k_gs_hist launch: 32 KB of LDS, five blocks per CU; 64 groups take four slices
 constexpr int kGsPts = 8;                    // k_gs_stat: entries per thread
 constexpr int kGsTile = 256 * kGsPts;        // ... and per block: the unit of the block-order sum
-constexpr int kGsStage = 256;                // chunks of the first reduction level
 constexpr unsigned int kGsMaxBlocks = 2048;  // k_gs_hist: above it a block strides over the array (fewer global atomics)
 
 struct GsState {
@@ -84,7 +83,7 @@ __global__ void __launch_bounds__(256) k_gs_prep(const double *__restrict__ valu
 
 __global__ void __launch_bounds__(256)
 k_gs_stat(const u64 *__restrict__ keys, const signed char *__restrict__ grp, long long n, int n_groups, GsBlock *__restrict__ b,
-          double *__restrict__ part, unsigned int nb) {
+          RedWord *__restrict__ part, unsigned int nb) {
     __shared__ unsigned int s_cnt[kGsMaxGroups];
     __shared__ u64 s_mn[kGsMaxGroups], s_mx[kGsMaxGroups];
     __shared__ double sm[4];
@@ -123,27 +122,12 @@ k_gs_stat(const u64 *__restrict__ keys, const signed char *__restrict__ grp, lon
             for (int q = 0; q < kGsPts; ++q) s += g[q] == gg ? v[q] : 0.0;
             r = block_sum_256(s, sm);
         }
-        if (threadIdx.x == 0) part[(size_t) gg * nb + blockIdx.x] = r;
+        if (threadIdx.x == 0) part[(size_t) gg * nb + blockIdx.x].d = r;
     }
     if ((int) threadIdx.x < n_groups && s_cnt[threadIdx.x] != 0u) {
         atomicAdd(&b->cnt[threadIdx.x], (u64) s_cnt[threadIdx.x]);
         atomicMin(&b->mn[threadIdx.x], s_mn[threadIdx.x]);
         atomicMax(&b->mx[threadIdx.x], s_mx[threadIdx.x]);
-    }
-}
-
-// row v of `in` ([rows][nb]) -> out[v * gridDim.x + block]: block b sums the chunk [b chunk, (b + 1) chunk) of the row, thread t taking
-// t, t + 256, ... in order (k_lg_final's rule)
-__global__ void __launch_bounds__(256)
-k_gs_final(const double *__restrict__ in, long long nb, long long chunk, int rows, double *__restrict__ out) {
-    __shared__ double sm[4];
-    const long long b0 = (long long) blockIdx.x * chunk, b1 = b0 + chunk < nb ? b0 + chunk : nb;
-    for (int v = 0; v < rows; ++v) {
-        const double *row = in + (size_t) v * nb;
-        double s = 0.0;
-        for (long long b = b0 + threadIdx.x; b < b1; b += 256) s += row[b];
-        const double r = block_sum_256(s, sm);
-        if (threadIdx.x == 0) out[(size_t) v * gridDim.x + blockIdx.x] = r;
     }
 }
 
@@ -285,7 +269,7 @@ int ensure_gs(me_ctx *ctx, long long n, int n_groups, unsigned int *nb_out) {
     ME_CHECK(ctx, ctx->mom_tmp[0].ensure((size_t) std::max<long long>(n, 1) * 8));
     ME_CHECK(ctx, ctx->mom_tmp[1].ensure((size_t) std::max<long long>(n, 1)));
     ME_CHECK(ctx, ctx->mom_tmp[2].ensure(sizeof(GsBlock)));
-    ME_CHECK(ctx, ctx->red.ensure(((size_t) nb + kGsStage) * (size_t) n_groups * 8));  // [n_groups][nb] | [n_groups][kGsStage]
+    ME_CHECK(ctx, ctx->red.ensure(row_sum_bytes(n_groups, nb)));
     *nb_out = nb;
     return ME_OK;
 }
@@ -296,14 +280,10 @@ int group_stats_device(me_ctx *ctx, long long n, int n_groups, unsigned int nb) 
     const u64 *keys = ctx->mom_tmp[0].as<u64>();
     const signed char *grp = ctx->mom_tmp[1].as<signed char>();
     GsBlock *blk = ctx->mom_tmp[2].as<GsBlock>();
-    double *part = ctx->red.as<double>(), *stage = part + (size_t) nb * n_groups;
     TimerScope ts(ctx, "group_select");
     hipLaunchKernelGGL(k_gs_init, dim3(1), dim3(256), 0, ctx->stream, blk);
-    hipLaunchKernelGGL(k_gs_stat, dim3(nb), dim3(256), 0, ctx->stream, keys, grp, n, n_groups, blk, part, nb);
-    const long long chunk = ((long long) nb + kGsStage - 1) / kGsStage;
-    hipLaunchKernelGGL(k_gs_final, dim3(kGsStage), dim3(256), 0, ctx->stream, (const double *) part, (long long) nb, chunk, n_groups, stage);
-    hipLaunchKernelGGL(k_gs_final, dim3(1), dim3(256), 0, ctx->stream, (const double *) stage, (long long) kGsStage, (long long) kGsStage,
-                       n_groups, &blk->tot[0]);
+    hipLaunchKernelGGL(k_gs_stat, dim3(nb), dim3(256), 0, ctx->stream, keys, grp, n, n_groups, blk, row_sum_part(ctx), nb);
+    row_sum_device<0ull>(ctx, n_groups, nb, reinterpret_cast<RedWord *>(blk->tot));
     hipLaunchKernelGGL(k_gs_start, dim3(1), dim3(64), 0, ctx->stream, blk, n_groups);
     const unsigned int gx = std::min(blocks_of(n), kGsMaxBlocks);
     for (int pass = 0; pass < kGsPasses; ++pass) {

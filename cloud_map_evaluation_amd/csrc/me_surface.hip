@@ -4,15 +4,15 @@
 // (map_eval.cpp:1398-1431) with the reference cloud's normals.
 //   k_sf_stat      a fixed grid of at most kSfBlocks blocks strides over the sorted queries: the pair's use, e, t2 and c (kept on the
 //                  slot in SORTED order, -1 where unused), the counts, the sums, the (largest e, smallest original index) pair and the
-//                  threshold counts; a block's figures by a fixed tree, stored as its partial
-//   k_sf_final     one block: the partials in block order (thread t takes t, t + 256, ...; k_ed_final's rule) — no floating-point
-//                  atomics, bit-identical from run to run                                                  (me_nn_surface_error, "surface")
+//                  threshold counts; the block's partial record and the one-block total over the records are me_reduce.hpp's
+//                                                                                                          (me_nn_surface_error, "surface")
 //   k_sf_unpermute e and c back in cloud order                                                             (me_nn_surface_fetch)
 // The file is compiled with -ffp-contract=off: tests/_surface_ref.py restates the three expressions.
 #include <cmath>
 #include <cstring>
 
 #include "me_internal.hpp"
+#include "me_reduce.hpp"
 #include "me_stat.hpp"
 
 namespace me {
@@ -23,24 +23,14 @@ typedef unsigned long long u64;
 
 constexpr int kSfT = ME_ERRDIST_MAX_THRESHOLDS, kSfA = ME_SURFACE_MAX_ANGLES;
 constexpr unsigned int kSfBlocks = 1024;  // above 256 x 1024 queries a block strides over the array
-constexpr int kSfD = 4 + kSfT;            // double partials per block: sum_e, sum_e2, sum_t2, sum_c, sum_e2_within[8]
-constexpr int kSfI = 5 + kSfT + kSfA;     // integer partials: n_query, n_used, n_normal_used, max key, argmax, n_within[8], n_angle[8]
+constexpr int kSfD = 4 + kSfT;            // double sums per block: sum_e, sum_e2, sum_t2, sum_c, sum_e2_within[8]
+constexpr int kSfNI = 3 + kSfT + kSfA;    // integer sums: n_query, n_used, n_normal_used, n_within[8], n_angle[8]; then max key, argmax
+typedef RedBufs<kSfD, kSfNI> SfRed;
 
 struct SfThr {
     double tau[kSfT], cos_min[kSfA];
     int nt, na;
 };
-
-// the totals, in the layout the host reads
-struct SfTotals {
-    double d[kSfD];
-    long long i[kSfI];
-};
-
-// (key, index) pairs: the larger key wins, on equal keys the smaller index; arg < 0 = no entry yet
-__device__ __forceinline__ void sf_take_max(u64 &mx, long long &arg, u64 omx, long long oa) {
-    if (oa >= 0 && (arg < 0 || omx > mx || (omx == mx && oa < arg))) mx = omx, arg = oa;
-}
 
 // ref_xyz / ref_nrm / q_nrm are in CLOUD order (q_nrm may be nullptr); d2s / idxs / e_s / c_s in the query's SORTED order.  Every
 // gather is guarded by 0 <= j < n_ref; the query's original index is a permutation of [0, n).
@@ -48,19 +38,21 @@ __global__ void __launch_bounds__(256)
 k_sf_stat(const SPoint *__restrict__ qsp, const double *__restrict__ d2s, const int *__restrict__ idxs, long long n,
           const double *__restrict__ ref_xyz, const double *__restrict__ ref_nrm, long long n_ref, const double *__restrict__ q_nrm,
           StatParams gp, SfThr thr, double *__restrict__ e_s, double *__restrict__ c_s, double *__restrict__ pd, long long *__restrict__ pi) {
-    long long nq = 0, nu = 0, nn = 0, arg = -1, nw[kSfT], na[kSfA];
+    long long arg = -1, ci[kSfNI];  // n_query, n_used, n_normal_used, n_within[8], n_angle[8]
     u64 mx = 0ull;
-    double se = 0.0, se2 = 0.0, st2 = 0.0, sc = 0.0, sw[kSfT];
+    double sd[kSfD];                // sum_e, sum_e2, sum_t2, sum_c, sum_e2_within[8]
+    long long *const nw = ci + 3, *const na = ci + 3 + kSfT;
+    double *const sw = sd + 4;
 #pragma unroll
-    for (int k = 0; k < kSfT; ++k) nw[k] = 0, sw[k] = 0.0;
+    for (int k = 0; k < kSfNI; ++k) ci[k] = 0;
 #pragma unroll
-    for (int k = 0; k < kSfA; ++k) na[k] = 0;
+    for (int k = 0; k < kSfD; ++k) sd[k] = 0.0;
     const long long S = (long long) gridDim.x * 256;
     for (long long i = (long long) blockIdx.x * 256 + threadIdx.x; i < n; i += S) {
         const double d2 = d2s[i];
         const long long j = idxs[i];
         double e = -1.0, c = -1.0;
-        if (d2 >= 0.0) nq += 1;
+        if (d2 >= 0.0) ci[0] += 1;
         if (d2 >= 0.0 && gate_pass(gp, d2) && j >= 0 && j < n_ref) {
             const double nx = ref_nrm[3 * j], ny = ref_nrm[3 * j + 1], nz = ref_nrm[3 * j + 2];
             if (!(nx == 0.0 && ny == 0.0 && nz == 0.0)) {
@@ -68,12 +60,12 @@ k_sf_stat(const SPoint *__restrict__ qsp, const double *__restrict__ d2s, const 
                 const double dx = p.x - ref_xyz[3 * j], dy = p.y - ref_xyz[3 * j + 1], dz = p.z - ref_xyz[3 * j + 2];
                 e = fabs((nx * dx + ny * dy) + nz * dz);
                 const double e2 = e * e;
-                nu += 1;
-                se += e;
-                se2 += e2;
-                st2 += fmax(d2 - e2, 0.0);
+                ci[1] += 1;
+                sd[0] += e;
+                sd[1] += e2;
+                sd[2] += fmax(d2 - e2, 0.0);
                 const u64 key = (u64) __double_as_longlong(e);  // (e >= +0.0: the order of the bit patterns is the numeric order)
-                sf_take_max(mx, arg, key, p.idx);
+                take_max(mx, arg, key, p.idx);
 #pragma unroll
                 for (int k = 0; k < kSfT; ++k)
                     if (k < thr.nt && e <= thr.tau[k]) nw[k] += 1, sw[k] += e2;
@@ -81,8 +73,8 @@ k_sf_stat(const SPoint *__restrict__ qsp, const double *__restrict__ d2s, const 
                     const double m0 = q_nrm[3 * p.idx], m1 = q_nrm[3 * p.idx + 1], m2 = q_nrm[3 * p.idx + 2];
                     if (!(m0 == 0.0 && m1 == 0.0 && m2 == 0.0)) {
                         c = fabs((m0 * nx + m1 * ny) + m2 * nz);
-                        nn += 1;
-                        sc += c;
+                        ci[2] += 1;
+                        sd[3] += c;
 #pragma unroll
                         for (int k = 0; k < kSfA; ++k)
                             if (k < thr.na && c >= thr.cos_min[k]) na[k] += 1;
@@ -93,100 +85,7 @@ k_sf_stat(const SPoint *__restrict__ qsp, const double *__restrict__ d2s, const 
         e_s[i] = e;
         c_s[i] = c;
     }
-    __shared__ double smd[4];
-    __shared__ long long smi[4];
-    __shared__ u64 s_mx[4];
-    __shared__ long long s_arg[4];
-    double *bd = pd + (size_t) blockIdx.x * kSfD;
-    long long *bi = pi + (size_t) blockIdx.x * kSfI;
-    double r = block_sum_256(se, smd);
-    if (threadIdx.x == 0) bd[0] = r;
-    r = block_sum_256(se2, smd);
-    if (threadIdx.x == 0) bd[1] = r;
-    r = block_sum_256(st2, smd);
-    if (threadIdx.x == 0) bd[2] = r;
-    r = block_sum_256(sc, smd);
-    if (threadIdx.x == 0) bd[3] = r;
-#pragma unroll
-    for (int k = 0; k < kSfT; ++k) {
-        r = block_sum_256(sw[k], smd);
-        if (threadIdx.x == 0) bd[4 + k] = r;
-    }
-    long long v = block_sum_256_ll(nq, smi);
-    if (threadIdx.x == 0) bi[0] = v;
-    v = block_sum_256_ll(nu, smi);
-    if (threadIdx.x == 0) bi[1] = v;
-    v = block_sum_256_ll(nn, smi);
-    if (threadIdx.x == 0) bi[2] = v;
-#pragma unroll
-    for (int k = 0; k < kSfT; ++k) {
-        v = block_sum_256_ll(nw[k], smi);
-        if (threadIdx.x == 0) bi[5 + k] = v;
-    }
-#pragma unroll
-    for (int k = 0; k < kSfA; ++k) {
-        v = block_sum_256_ll(na[k], smi);
-        if (threadIdx.x == 0) bi[5 + kSfT + k] = v;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const u64 omx = (u64) __shfl_down((long long) mx, o, 64);
-        const long long oa = __shfl_down(arg, o, 64);
-        sf_take_max(mx, arg, omx, oa);
-    }
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) s_mx[w] = mx, s_arg[w] = arg;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int q = 1; q < 4; ++q) sf_take_max(mx, arg, s_mx[q], s_arg[q]);
-        bi[3] = (long long) mx;
-        bi[4] = arg;
-    }
-}
-
-__global__ void __launch_bounds__(256) k_sf_final(const double *__restrict__ pd, const long long *__restrict__ pi, int nb, SfTotals *__restrict__ t) {
-    __shared__ double smd[4];
-    __shared__ long long smi[4];
-    __shared__ u64 s_mx[256];
-    __shared__ long long s_arg[256];
-    double sd[kSfD];
-    long long ci[kSfI];
-#pragma unroll
-    for (int k = 0; k < kSfD; ++k) sd[k] = 0.0;
-#pragma unroll
-    for (int k = 0; k < kSfI; ++k) ci[k] = 0;
-    u64 mx = 0ull;
-    long long arg = -1;
-    for (int q = threadIdx.x; q < nb; q += 256) {
-        const double *bd = pd + (size_t) q * kSfD;
-        const long long *bi = pi + (size_t) q * kSfI;
-#pragma unroll
-        for (int k = 0; k < kSfD; ++k) sd[k] += bd[k];
-#pragma unroll
-        for (int k = 0; k < kSfI; ++k)
-            if (k != 3 && k != 4) ci[k] += bi[k];
-        sf_take_max(mx, arg, (u64) bi[3], bi[4]);
-    }
-#pragma unroll
-    for (int k = 0; k < kSfD; ++k) {
-        const double r = block_sum_256(sd[k], smd);
-        if (threadIdx.x == 0) t->d[k] = r;
-    }
-#pragma unroll
-    for (int k = 0; k < kSfI; ++k) {
-        if (k == 3 || k == 4) continue;
-        const long long v = block_sum_256_ll(ci[k], smi);
-        if (threadIdx.x == 0) t->i[k] = v;
-    }
-    s_mx[threadIdx.x] = mx;
-    s_arg[threadIdx.x] = arg;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int q = 1; q < 256; ++q) sf_take_max(mx, arg, s_mx[q], s_arg[q]);
-        t->i[3] = (long long) mx;
-        t->i[4] = arg;
-    }
+    red_store_partial<kSfD, kSfNI, false>(sd, ci, mx, arg, 0ull, pd + (size_t) blockIdx.x * kSfD, pi + (size_t) blockIdx.x * SfRed::Totals::NR);
 }
 
 __global__ void __launch_bounds__(256)
@@ -223,11 +122,8 @@ int nn_surface_error(me_ctx *ctx, int qslot, const me_surface_params *p, me_surf
     ME_CHECK(ctx, q.surf_e.ensure((size_t) n * 8));
     ME_CHECK(ctx, q.surf_c.ensure((size_t) n * 8));
     const int nb = (int) std::min<long long>(kSfBlocks, blocks_of(n));
-    // [kSfBlocks][kSfD] doubles | [kSfBlocks][kSfI] integers | the totals
-    ME_CHECK(ctx, ctx->red.ensure((size_t) kSfBlocks * (kSfD + kSfI) * 8 + sizeof(SfTotals)));
-    double *pd = ctx->red.as<double>();
-    long long *pi = reinterpret_cast<long long *>(pd + (size_t) kSfBlocks * kSfD);
-    SfTotals *tot = reinterpret_cast<SfTotals *>(pi + (size_t) kSfBlocks * kSfI);
+    ME_CHECK(ctx, ctx->red.ensure(SfRed::bytes(kSfBlocks)));
+    const SfRed red(ctx, kSfBlocks);
     SfThr thr{};
     thr.nt = p->n_thresholds;
     thr.na = p->n_angles;
@@ -237,14 +133,14 @@ int nn_surface_error(me_ctx *ctx, int qslot, const me_surface_params *p, me_surf
         TimerScope ts(ctx, "surface");
         hipLaunchKernelGGL(k_sf_stat, dim3(nb), dim3(256), 0, ctx->stream, q.sp.as<SPoint>(), q.nn_d2.as<double>(), q.nn_idx.as<int>(), n,
                            r.xyz.as<double>(), r.normals.as<double>(), r.n, q.have_normals ? q.normals.as<double>() : nullptr,
-                           make_params(p->gate, p->gate_mode, nullptr), thr, q.surf_e.as<double>(), q.surf_c.as<double>(), pd, pi);
-        hipLaunchKernelGGL(k_sf_final, dim3(1), dim3(256), 0, ctx->stream, (const double *) pd, (const long long *) pi, nb, tot);
+                           make_params(p->gate, p->gate_mode, nullptr), thr, q.surf_e.as<double>(), q.surf_c.as<double>(), red.pd, red.pi);
+        red.total(ctx, nb, red.tot);
     }
     ME_CHECK(ctx, hipGetLastError());
-    SfTotals h;
+    SfRed::Totals h;
     {
         MailGuard mg(ctx);
-        ME_TRY(mail_post(ctx, &h, tot, sizeof(h)));
+        ME_TRY(mail_post(ctx, &h, red.tot, sizeof(h)));
         ME_TRY(mg.sync());
     }
     q.surf_have = true;
@@ -258,11 +154,10 @@ int nn_surface_error(me_ctx *ctx, int qslot, const me_surface_params *p, me_surf
         out->sum_e2 = h.d[1];
         out->sum_t2 = h.d[2];
         out->sum_c = h.d[3];
-        const u64 key = (u64) h.i[3];
-        std::memcpy(&out->max_e, &key, 8);
-        out->argmax = h.i[4];
-        for (int k = 0; k < p->n_thresholds; ++k) out->n_within[k] = h.i[5 + k], out->sum_e2_within[k] = h.d[4 + k];
-        for (int k = 0; k < p->n_angles; ++k) out->n_angle[k] = h.i[5 + kSfT + k];
+        std::memcpy(&out->max_e, &h.i[kSfNI], 8);
+        out->argmax = h.i[kSfNI + 1];
+        for (int k = 0; k < p->n_thresholds; ++k) out->n_within[k] = h.i[3 + k], out->sum_e2_within[k] = h.d[4 + k];
+        for (int k = 0; k < p->n_angles; ++k) out->n_angle[k] = h.i[3 + kSfT + k];
     }
     return ME_OK;
 }

@@ -5,7 +5,7 @@ map after the suite's map -> ground-truth search.  Prints one JSON line.
 
 Both clouds of bench.py's workload are uploaded and the map's 1-NN search runs; then, with the device timers on and reps + 1 calls
 each (the first settles the allocations): "rank_select_1_ms" / "rank_select_16_ms": timer "rank_select" of a call with one quantile
-(the median) and with sixteen; "errdist_ms": timer "errdist" (k_ed_stat, k_ed_final, k_ed_hist with 1000 bins) of the same calls;
+(the median) and with sixteen; "errdist_ms": timer "errdist" (k_ed_stat, the one-block total, k_ed_hist with 1000 bins) of the same calls;
 "group_select_ms": timer "group_select" of me_group_order_stats on the same squared distances as one group — the eight-full-pass
 select, on the same box in the same run (its k_gs_prep included, as the upload is not).  "rank_select_direct_ms": timer "rank_select" of me_rank_select on the same array (its stat pass and the
 select: the like-for-like figure beside "group_select").  "compactions" / "last_list": what the

@@ -13,7 +13,7 @@ RANK_MAX = 16
 MAX_THRESHOLDS = 8
 MAX_BINS = 4096
 STAT_BLOCKS = 1024     # blocks of k_ed_stat: up to 256 * STAT_BLOCKS entries one per thread, above it a block strides over the array
-FINAL_THREADS = 256    # k_ed_final: above 256 * FINAL_THREADS entries a thread of the final block adds more than one block partial
+FINAL_THREADS = 256    # the one-block total: above 256 * FINAL_THREADS entries a thread of the final block adds more than one block partial
 IN_FLIGHT = 4          # loads in flight of k_ed_stat's strided walk: taken above IN_FLIGHT * 256 * STAT_BLOCKS entries
 DIGIT_BITS = 8         # radix-select digit: eight passes over the 64-bit key
 HIST_BLOCKS = 2048     # pieces of the list in k_rs_hist / k_rs_scatter
@@ -42,6 +42,49 @@ def rank_select(values, ranks, use=None) -> dict:
     if len(v) == 0:
         return {"count": 0, "sum": 0.0, "min": 0.0, "max": 0.0, "value": np.zeros(len(ranks))}
     return {"count": len(v), "sum": math.fsum(v), "min": float(v[0]), "max": float(v[-1]), "value": v[ranks].copy()}
+
+
+def tree_256(x) -> np.ndarray:
+    """block_sum_256 over the last axis (256 threads): every wave of 64 folds its halves, 64 -> 32 -> ... -> 1, then
+    (w0 + w1) + (w2 + w3)."""
+    w = np.asarray(x, np.float64)
+    w = w.reshape(w.shape[:-1] + (4, 64))
+    for o in (32, 16, 8, 4, 2, 1):
+        w = w[..., :o] + w[..., o:2 * o]
+    w = w[..., 0]
+    return (w[..., 0] + w[..., 1]) + (w[..., 2] + w[..., 3])
+
+
+def block_order_sum(x) -> np.ndarray:
+    """One block over the last axis: thread t adds the entries t, t + 256, ... in order, starting from 0.0, then tree_256.  (A missing
+    entry is a +0.0: adding it to a sum of non-negative terms changes no bit.)"""
+    x = np.asarray(x, np.float64)
+    m = x.shape[-1]
+    rounds = max(1, -(-m // 256))
+    p = np.zeros(x.shape[:-1] + (rounds * 256,))
+    p[..., :m] = x
+    p = p.reshape(x.shape[:-1] + (rounds, 256))
+    acc = np.zeros(x.shape[:-1] + (256,))
+    for k in range(rounds):
+        acc = acc + p[..., k, :]
+    return tree_256(acc)
+
+
+def rank_select_sum_in_order(values, use=None) -> float:
+    """me_rank_select's sum in the order of the device: thread (b, t) of min(STAT_BLOCKS, ceil(n / 256)) blocks adds v[i] for
+    i = 256 b + t, stepping by the grid size (an unused entry adds nothing but keeps its place); a block folds by tree_256; one block
+    adds the block partials by the same rule.  0.0 without a used entry."""
+    v = np.asarray(values, np.float64)
+    n = len(v)
+    if use is not None:
+        v = np.where(np.asarray(use) != 0, v, 0.0)
+    nb = min(STAT_BLOCKS, max(1, -(-n // 256)))
+    grid = 256 * nb
+    rounds = max(1, -(-n // grid))
+    p = np.zeros(rounds * grid)
+    p[:n] = v
+    per_block = p.reshape(rounds, nb, 256).transpose(1, 0, 2).reshape(nb, rounds * 256)  # (b, k, t) = v[k grid + 256 b + t]
+    return float(block_order_sum(block_order_sum(per_block)))
 
 
 def sum_bound(count, total) -> float:

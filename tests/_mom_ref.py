@@ -123,6 +123,27 @@ def order_stats(values, groups, n_groups: int) -> dict:
     return out
 
 
+def group_sums_in_order(values, groups, n_groups: int) -> np.ndarray:
+    """me_group_order_stats' per-group sums in the order of the device: a block holds TILE entries, thread t adds its eight entries
+    t, t + 256, ... in order (an entry of another group adds nothing but keeps its place) and the block tree follows; STAGE chunk
+    blocks add the block partials of their chunk by the same rule, then one block adds the STAGE results."""
+    from _errdist_ref import block_order_sum
+
+    v = np.asarray(values, np.float64) + 0.0
+    g = np.asarray(groups, np.int64)
+    n = len(v)
+    nb = max(1, -(-n // TILE))
+    chunk = -(-nb // STAGE)
+    vp, gp = np.zeros(nb * TILE), np.full(nb * TILE, -1, np.int64)
+    vp[:n], gp[:n] = v, g
+    out = np.zeros(n_groups, np.float64)
+    for k in range(n_groups):
+        part = np.zeros(STAGE * chunk)
+        part[:nb] = block_order_sum(np.where(gp == k, vp, 0.0).reshape(nb, TILE))
+        out[k] = block_order_sum(block_order_sum(part.reshape(STAGE, chunk)))
+    return out
+
+
 def sum_bound(count, total):
     """|sum_device - sum_exact| <= (count - 1) 2^-53 sum: count - 1 additions of non-negative terms, each partial sum <= the total, in
     any order."""

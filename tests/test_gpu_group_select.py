@@ -87,6 +87,20 @@ def test_second_reduction_level_and_striding_blocks(eng, n_groups):
     _check(eng, _values("duplicates", n, rng), g, n_groups)
 
 
+@pytest.mark.parametrize("n", [1, M.TILE - 1, M.TILE, M.TILE + 1, TWO_LEVEL])
+def test_sums_are_added_in_the_fixed_order(eng, n):
+    """Every group's sum, bit for bit, against M.group_sums_in_order: the eight entries of a thread, the block tree, the STAGE chunk
+    blocks (two partials in the first chunk at TWO_LEVEL) and the final block.  The values span 80 binades: another order shows."""
+    rng = np.random.default_rng(9000 + n)
+    for n_groups in GROUPS:
+        v, g = _values("random", n, rng), rng.integers(-1, n_groups, n)
+        assert n < 64 or (g == -1).any()
+        dev = eng.group_order_stats(v, g, n_groups)
+        ref = M.group_sums_in_order(v, g, n_groups)
+        assert np.array_equal(dev["count"], np.bincount(g[g >= 0], minlength=n_groups))
+        assert np.array_equal(M.bits(dev["sum"]), M.bits(ref)), (n, n_groups, dev["sum"], ref)
+
+
 def test_group_shapes_empty_single_even_odd_and_all_ignored(eng):
     rng = np.random.default_rng(5)
     counts = {0: 0, 1: 1, 2: 2, 3: 3, 4: 1000, 5: 1001, 7: 64, 8: 65}  # group 6 and 9 .. 11 stay empty too

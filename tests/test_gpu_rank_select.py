@@ -132,6 +132,19 @@ def test_second_reduction_level_and_striding_blocks(eng, n):
         assert dev["count"] == count
 
 
+@pytest.mark.parametrize("n", [1, 255, 256, 257, TWO_LEVEL, STRIDED, 2 * STRIDED + 77])
+def test_sum_is_added_in_the_fixed_order(eng, n):
+    """The sum, bit for bit, against R.rank_select_sum_in_order: the strided walk (2 * STRIDED + 77 runs the unrolled part twice and its
+    tail), the block tree and the one-block total over the partials.  The values span 80 binades: another order shows."""
+    rng = np.random.default_rng(7000 + n)
+    v = _values("random", n, rng)
+    for use in (None, rng.random(n) < 0.7):
+        dev = eng.rank_select(v, [], use)
+        ref = R.rank_select_sum_in_order(v, use)
+        assert dev["count"] == (n if use is None else int(use.sum()))
+        assert R.bits(dev["sum"])[0] == R.bits(ref)[0], (n, use is not None, dev["sum"], ref)
+
+
 def test_just_past_the_compaction_trigger(eng):
     """COMPACT_MIN + 1 entries over many binades: after the second pass at the latest fewer than 1 / COMPACT_DIV of them carry the prefix
     of the one rank, and the later passes read a compacted list.  One entry fewer than COMPACT_MIN: never compacted.  Same results."""
