@@ -46,7 +46,7 @@ SYMBOLS = [
     "me_set_normals", "me_get_normals", "me_estimate_normals", "me_gicp_covariances", "me_get_covariances", "me_icp_lsq_sums",
     "me_icp_lsq_sums_robust", "me_icp_information",
     "me_nn1", "me_icp_p2p_sums", "me_render_distance", "me_render_entropy", "me_nn_stats", "me_nn_partial_sums", "me_nn_sigma_sums", "me_nn_finalize", "me_chamfer",
-    "me_mme", "me_voxel_gaussians", "me_voxel_metrics", "me_awd_scs", "me_w2_batch", "me_scs_table", "me_run_suite", "me_run_suite_from", "me_mme_fetch",
+    "me_mme", "me_voxel_gaussians", "me_voxel_metrics", "me_voxel_deformation", "me_voxel_deformation_fetch", "me_awd_scs", "me_w2_batch", "me_scs_table", "me_run_suite", "me_run_suite_from", "me_mme_fetch",
     "me_set_voxel_hint", "me_timers_enable", "me_timers_reset", "me_timer_get",
 ]
 
@@ -66,6 +66,30 @@ class NNPartial(C.Structure):
 NN_PARTIAL_DTYPE = np.dtype([("n_query", "<i8"), ("n_corr", "<i8"), ("n_inl", "<i8", (5,)), ("sum_d", "<f8", (5,)), ("sum_d2", "<f8", (5,)),
                              ("sum_sqrt_all", "<f8")])
 assert NN_PARTIAL_DTYPE.itemsize == C.sizeof(NNPartial)
+
+
+# me_voxel_deformation
+ME_DEFORM_FIT, ME_DEFORM_ROT_OK, ME_DEFORM_SUMS = 1, 2, 23
+
+
+class DeformSummary(C.Structure):
+    _fields_ = [
+        ("n_voxels", C.c_int64),
+        ("n_with_pairs", C.c_int64),
+        ("n_fit", C.c_int64),
+        ("n_rot", C.c_int64),
+        ("n_pairs", C.c_int64),
+        ("max_row", C.c_int64),
+        ("max_key", C.c_int32 * 3),
+        ("pad_", C.c_int32),
+        ("sum_n_t0", C.c_double),
+        ("sum_n_t0sq", C.c_double),
+        ("max_t0", C.c_double),
+        ("sum_e0", C.c_double),
+        ("sum_e_t", C.c_double),
+        ("sum_e0_fit", C.c_double),
+        ("sum_e_R", C.c_double),
+    ]
 
 
 class IcpSums(C.Structure):
@@ -640,6 +664,10 @@ def load():
     L.me_voxel_metrics.argtypes = [vp, C.c_int, C.c_double, C.c_double, C.c_int, dp, ip, vp, dp, vp, C.POINTER(C.c_int),
                                    C.POINTER(C.c_int64)]
     L.me_voxel_metrics.restype = C.c_int
+    L.me_voxel_deformation.argtypes = [vp, C.c_int, C.c_double, C.c_double, C.c_int, C.c_double, C.POINTER(DeformSummary)]
+    L.me_voxel_deformation_fetch.argtypes = [vp, C.c_int, ip, vp, vp, dp, dp, dp, dp, dp, C.POINTER(C.c_int64)]
+    for f in ("me_voxel_deformation", "me_voxel_deformation_fetch"):
+        getattr(L, f).restype = C.c_int
     L.me_awd_scs.argtypes = [vp, C.c_double, C.c_int, C.c_int, dp, dp, C.POINTER(C.c_int64), C.POINTER(C.c_double),
                              C.POINTER(C.c_double), dp]
     L.me_run_suite.argtypes = [vp, C.POINTER(SuiteParams), C.POINTER(SuiteOut)]

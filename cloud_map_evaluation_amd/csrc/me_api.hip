@@ -693,6 +693,18 @@ int me_voxel_metrics(me_ctx *ctx, int slot, double voxel_size, double gate, int 
     return me::voxel_metrics(ctx, slot, voxel_size, gate, gate_mode, trunc, keys, nn, sum_H, n_H, have_mme, n_voxels);
 }
 
+int me_voxel_deformation(me_ctx *ctx, int query_slot, double voxel_size, double max_distance, int min_pairs, double min_spread,
+                         me_deform_summary *out) {
+    if (!ctx) return ME_ERR_ARG;
+    return me::voxel_deformation(ctx, query_slot, voxel_size, max_distance, min_pairs, min_spread, out);
+}
+
+int me_voxel_deformation_fetch(me_ctx *ctx, int query_slot, int32_t *keys, int64_t *n_pairs, uint8_t *flags, double *sums, double *t0,
+                               double *u, double *R, double *e, int64_t *n_voxels) {
+    if (!ctx) return ME_ERR_ARG;
+    return me::voxel_deformation_fetch(ctx, query_slot, keys, n_pairs, flags, sums, t0, u, R, e, n_voxels);
+}
+
 int me_voxel_partials(me_ctx *ctx, int slot, double voxel_size, int32_t *keys, int32_t *npts, double *mu, double *m2,
                       int64_t *n_voxels) {
     if (!ctx) return ME_ERR_ARG;

@@ -636,7 +636,7 @@ static int build_grid_table_counted(me_ctx *ctx, Cloud &c, int shift, GridTable 
 // The two lists every reset site shares (tests/_lifetime.py holds the documents' side of them).
 // drop_sorted_results: what is stored in the slot's SORTED order or reads it, gone with every re-sort of the slot — its MME, local
 // geometry (and me_mom's axis bytes, made from its eigenvalues), M3C2 and mesh-distance results, and the 1-NN results of BOTH slots (the
-// other one's holds positions in this slot's sorted array) with the surface errors read from them.
+// other one's holds positions in this slot's sorted array) with the surface errors and the deformation rows read from them.
 void drop_sorted_results(me_ctx *ctx, int slot) {
     Cloud &c = ctx->cloud[slot], &o = ctx->cloud[1 - slot];
     c.mme_have = false;
@@ -646,8 +646,10 @@ void drop_sorted_results(me_ctx *ctx, int slot) {
     c.mesh_have = false;
     c.nn_ref_slot = -1;
     c.surf_have = false;
+    c.dfm_have = false;
     o.nn_ref_slot = -1;
     o.surf_have = false;
+    o.dfm_have = false;
 }
 // drop_point_results: the slot holds other points — the above, and everything kept in cloud order about the old ones: FPFH features,
 // the keep-mask, cluster and plane labels, the orientation bytes, the voxel table and its run records, and the OTHER slot's M3C2

@@ -265,6 +265,12 @@ struct Cloud {
     // normals or points are next replaced (cloud_finish, the normal producers, rotate_attributes)
     DevBuf orient_comp, orient_flip;
     bool orient_have = false;
+    // rows of the last me_voxel_deformation with this cloud as the query, ascending key order (me_deform.hip): keys int32[V][3], pair
+    // counts int64[V], flag bytes, the 23 pair sums double[V][23] and the fit double[V][18] (t0, u, R, e0 / e_t / e_R); current only
+    // while the 1-NN result is (nn_ref_slot >= 0): a new one (nn_search, set_nn_result) clears the flag
+    DevBuf dfm_keys, dfm_n, dfm_flags, dfm_sums, dfm_fit;
+    long long dfm_V = 0;
+    bool dfm_have = false;
 };
 
 // The resident triangle mesh (me_mesh.hip): one per primary context, beside the two clouds and untouched by what happens to them.
@@ -712,6 +718,14 @@ int w2_batch(me_ctx *ctx, const double *mu1, const double *sigma1, const int32_t
 int scs_table(me_ctx *ctx, const int32_t *keys, const double *w, long long n, int scs_radius, double *scs);
 int voxel_metrics(me_ctx *ctx, int slot, double voxel_size, double gate, int gate_mode, const double trunc[5], int32_t *keys,
                   me_nn_partial *nn, double *sum_H, int64_t *n_H, int *have_mme, int64_t *n_voxels);
+// the tail of a one-pass record table, shared with me_deform.hip: the fullest overflow region, and the records' segments per voxel
+int vox_region_fill(me_ctx *ctx, unsigned int *cnt, unsigned int h2[2]);
+int vox_record_segments(me_ctx *ctx, long long cap, const unsigned long long *rec_pos, const unsigned long long *rec_vkey, DevBuf &vkey_d,
+                        DevBuf &seg_d, const unsigned int **perm, long long *n_vox);
+// ---- me_deform.hip ----
+int voxel_deformation(me_ctx *ctx, int qslot, double voxel_size, double max_distance, int min_pairs, double min_spread, me_deform_summary *out);
+int voxel_deformation_fetch(me_ctx *ctx, int qslot, int32_t *keys, int64_t *n_pairs, uint8_t *flags, double *sums, double *t0, double *u,
+                            double *R, double *e, int64_t *n_voxels);
 
 // ---- shared device helpers ----
 #ifdef __HIPCC__

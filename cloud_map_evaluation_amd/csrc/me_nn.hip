@@ -1097,6 +1097,7 @@ int nn_search(me_ctx *ctx, int qslot, int rslot) {
     ME_TRY(cloud_finish_octree(ctx, rslot));  // (an index built with ctx->defer_octree; me_run_suite_from has done this already)
     q.nn_ref_slot = rslot;
     q.surf_have = false;
+    q.dfm_have = false;
     ME_TRACE_POINT(ctx, "nn_search: enter");
     q.n_unres = 0;
     if (q.n == 0) return ME_OK;  // empty slab: nothing to query

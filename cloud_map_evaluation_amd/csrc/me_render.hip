@@ -228,6 +228,7 @@ int set_nn_result(me_ctx *ctx, int qslot, int rslot, const double *d2) {
                        eo.as<double>(), (const unsigned char *) nullptr, q.nn_d2.as<double>(), (unsigned char *) nullptr, q.nn_idx.as<int>());
     ME_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     q.surf_have = false;
+    q.dfm_have = false;
     q.nn_ref_slot = rslot;  // (the neighbour indices are not known here: -1; the renderers and the statistics use d2 only)
     q.n_unres = 0;
     return ME_OK;

@@ -21,6 +21,27 @@ __device__ __host__ __forceinline__ void unpack_key(unsigned long long k, int &k
     kz = (int) (k & 0x1fffff) - kKeyBias;
 }
 
+constexpr unsigned long long kVoxSentinel = 0x7fffffffffffffffULL;  // sorts after every real key
+
+// getVoxelIndex (voxel_calculator.cpp:241-245): floor(x / voxel_size) — IEEE division, not a reciprocal multiply
+__device__ __forceinline__ unsigned long long voxel_key_of(double x, double y, double z, double vs, const SlabView &slab,
+                                                           int *__restrict__ err) {
+    if (!slab_owned(slab, x, y, z)) return kVoxSentinel;  // slab mode: halo points belong to another rank
+    const double fx = floor(x / vs), fy = floor(y / vs), fz = floor(z / vs);
+    const double lim = (double) (kKeyBias - 16);
+    if (!(fabs(fx) < lim && fabs(fy) < lim && fabs(fz) < lim)) {
+        *err = 1;
+        return 0;
+    }
+    return pack_key((int) fx, (int) fy, (int) fz);
+}
+
+// xor butterfly: every lane gets the (fixed-tree) total
+__device__ __forceinline__ double wave_allsum(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
 
 // sum over the lanes of the same (contiguous) segment, delivered to the segment's first lane
 __device__ __forceinline__ double seg_sum_to_head(double v, int seg, int lane) {

@@ -23,23 +23,6 @@
 
 namespace me {
 
-constexpr unsigned long long kVoxSentinel = 0x7fffffffffffffffULL;  // sorts after every real key
-
-__device__ __forceinline__ double wave_allsum(double v);  // xor butterfly: every lane gets the (fixed-tree) total
-
-// getVoxelIndex (voxel_calculator.cpp:241-245): floor(x / voxel_size) — IEEE division, not a reciprocal multiply
-__device__ __forceinline__ unsigned long long voxel_key_of(double x, double y, double z, double vs, const SlabView &slab,
-                                                           int *__restrict__ err) {
-    if (!slab_owned(slab, x, y, z)) return kVoxSentinel;  // slab mode: halo points belong to another rank
-    const double fx = floor(x / vs), fy = floor(y / vs), fz = floor(z / vs);
-    const double lim = (double) (kKeyBias - 16);
-    if (!(fabs(fx) < lim && fabs(fy) < lim && fabs(fz) < lim)) {
-        *err = 1;
-        return 0;
-    }
-    return pack_key((int) fx, (int) fy, (int) fz);
-}
-
 // ---- voxel statistics straight from the Morton-sorted cloud ----------------------------------------------------
 // A voxel is large next to the search cell, so curve-consecutive points mostly share their voxel: every wavefront
 // (64 consecutive sorted points) splits into a few RUNS of equal key.  Pass 1 reduces (n, sum p) per run with a
@@ -209,12 +192,6 @@ __global__ void k_seg_scatter(const unsigned long long *__restrict__ keys, const
     }
 }
 __global__ void k_set_u32v(unsigned int *p, long long i, unsigned int v) { p[i] = v; }
-
-__device__ __forceinline__ double wave_allsum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 __device__ __forceinline__ double det3_rowmajor(const double *m) {
     return m[0] * (m[4] * m[8] - m[5] * m[7]) - m[1] * (m[3] * m[8] - m[5] * m[6]) + m[2] * (m[3] * m[7] - m[4] * m[6]);
@@ -1431,53 +1408,21 @@ k_voxm_reduce(const unsigned int *__restrict__ perm, const unsigned int *__restr
     n_h[v] = c[7];
 }
 
-int voxel_metrics(me_ctx *ctx, int slot, double voxel_size, double gate, int gate_mode, const double trunc[5], int32_t *keys,
-                  me_nn_partial *nn, double *sum_H, int64_t *n_H, int *have_mme, int64_t *n_voxels) {
-    if (slot < 0 || slot > 1 || !trunc || !n_voxels) return ctx->fail(ME_ERR_ARG, "me_voxel_metrics: bad argument");
-    if (!(voxel_size > 0)) return ctx->fail(ME_ERR_ARG, "me_voxel_metrics: voxel_size must be > 0");
-    Cloud &c = ctx->cloud[slot];
-    if (c.slab.axis >= 0 || ctx->shard_world > 1)
-        return ctx->fail(ME_ERR_STATE, "me_voxel_metrics: single GPU only (no slab or shard mode)");
-    if (!c.uploaded) return ctx->fail(ME_ERR_STATE, "me_voxel_metrics: cloud not uploaded");
-    if (c.nn_ref_slot < 0)
-        return ctx->fail(ME_ERR_STATE, "me_voxel_metrics: no me_nn1 with this slot as the query since its last upload or transform");
-    ME_CHECK(ctx, hipSetDevice(ctx->device));
-    const long long n = c.n;
-    const bool mme = c.mme_have;
-    const StatParams st = make_params(gate, gate_mode, trunc);
-    const long long n_rows = (n + 63) / 64;
-    long long rsize = vox_region_size(n), cap = 0;
-    DevBuf &pbuf = ctx->tmp[0], &cbuf = ctx->tmp[1], &dbuf = ctx->tmp[2], &kbuf = ctx->tmp[3], &ibuf = ctx->tmp[4];  // (tmp[5]: sort / scan scratch)
-    ME_CHECK(ctx, ctx->red.ensure(kVoxCounterBytes));
-    unsigned int *cnt = ctx->red.as<unsigned int>();  // [range error, fullest region, the regions' counters]
-    for (int attempt = 0;; ++attempt) {
-        cap = 2 * n_rows + (long long) kVoxRegions * rsize;
-        ME_CHECK(ctx, pbuf.ensure((size_t) cap * 16));  // rec_pos | rec_vkey
-        ME_CHECK(ctx, cbuf.ensure((size_t) cap * 8));
-        ME_CHECK(ctx, dbuf.ensure((size_t) cap * 8 * kVmD));
-        ME_CHECK(ctx, hipMemsetAsync(pbuf.p, 0xFF, (size_t) cap * 8, ctx->stream));  // kVoxEmptySlot
-        ME_CHECK(ctx, hipMemsetAsync(cnt, 0, kVoxCounterBytes, ctx->stream));
-        {
-            TimerScope ts(ctx, "voxel_metrics");
-            hipLaunchKernelGGL(k_voxm_records, dim3(blocks_of(n)), dim3(256), 0, ctx->stream, c.sp.as<SPoint>(), c.nn_d2.as<double>(),
-                               mme ? c.mme_ent.as<double>() : nullptr, mme ? c.mme_val.as<unsigned char>() : nullptr, n, voxel_size, c.slab,
-                               st, pbuf.as<unsigned long long>(), pbuf.as<unsigned long long>() + cap, cbuf.as<uint2>(), dbuf.as<double>(),
-                               cnt + 2, (unsigned int) n_rows, (unsigned int) rsize, reinterpret_cast<int *>(cnt));
-        }
-        hipLaunchKernelGGL(k_vox_region_max, dim3(1), dim3(256), 0, ctx->stream, cnt);
-        unsigned int h2[2] = {0, 0};
-        {
-            MailGuard mg(ctx);
-            ME_TRY(mail_post(ctx, h2, cnt, 8));
-            ME_TRY(mg.sync());
-        }
-        if (h2[0]) return ctx->fail(ME_ERR_ARG, "me_voxel_metrics: voxel index out of range (|floor(p/voxel_size)| must be < 2^20)");
-        if ((long long) h2[1] <= rsize) break;
-        if (attempt > 0) return ctx->fail(ME_ERR_HIP, "me_voxel_metrics: overflow regions still too small");
-        rsize = (long long) h2[1];  // (a region overflowed: once more with regions as large as the fullest one needs; the same records)
-    }
+// the counter block of a record pass (kVoxCounterBytes at `cnt`) -> h2 = [range error, fill of the fullest overflow region]
+int vox_region_fill(me_ctx *ctx, unsigned int *cnt, unsigned int h2[2]) {
+    hipLaunchKernelGGL(k_vox_region_max, dim3(1), dim3(256), 0, ctx->stream, cnt);
+    MailGuard mg(ctx);
+    ME_TRY(mail_post(ctx, h2, cnt, 8));
+    return mg.sync();
+}
+
+// The run records of a one-pass table (k_voxm_records, k_deform_records: `cap` slots, rec_pos = kVoxEmptySlot where unused) -> the
+// voxels' segments: the used slots compacted in slot order, sorted by (row, run) and then stably by voxel key.  *perm (in ctx->tmp[4])
+// lists the record slots in that order, seg_d[v] .. seg_d[v + 1] are voxel v's entries of it, vkey_d its packed key.  Uses tmp[3] - tmp[5].
+int vox_record_segments(me_ctx *ctx, long long cap, const unsigned long long *rec_pos, const unsigned long long *rec_vkey, DevBuf &vkey_d,
+                        DevBuf &seg_d, const unsigned int **perm, long long *n_vox) {
     const long long S = cap;
-    const unsigned long long *rec_pos = pbuf.as<unsigned long long>(), *rec_vkey = rec_pos + cap;
+    DevBuf &kbuf = ctx->tmp[3], &ibuf = ctx->tmp[4];  // (tmp[5]: sort / scan scratch)
     ME_CHECK(ctx, kbuf.ensure((size_t) cap * 16));
     ME_CHECK(ctx, ibuf.ensure((size_t) cap * 20 + 64));
     unsigned long long *ka = kbuf.as<unsigned long long>(), *kb = ka + cap;
@@ -1508,16 +1453,64 @@ int voxel_metrics(me_ctx *ctx, int slot, double voxel_size, double gate, int gat
         ME_TRY(mg.sync());
     }
     const long long V = (long long) last_pos + last_flag;
-    DevBuf vkey_d, seg_d, keys_d, nn_d, sh_d, nh_d;
     ME_CHECK(ctx, vkey_d.ensure((size_t) V * 8));
     ME_CHECK(ctx, seg_d.ensure((size_t) (V + 1) * 4));
+    hipLaunchKernelGGL(k_seg_scatter, dim3(blocks_of(R)), dim3(256), 0, ctx->stream, (const unsigned long long *) kb, (const unsigned int *) flags,
+                       (const unsigned int *) pos, R, vkey_d.as<unsigned long long>(), seg_d.as<unsigned int>());
+    hipLaunchKernelGGL(k_set_u32v, dim3(1), dim3(1), 0, ctx->stream, seg_d.as<unsigned int>(), V, (unsigned int) R);
+    *perm = perm2;
+    *n_vox = V;
+    return ME_OK;
+}
+
+int voxel_metrics(me_ctx *ctx, int slot, double voxel_size, double gate, int gate_mode, const double trunc[5], int32_t *keys,
+                  me_nn_partial *nn, double *sum_H, int64_t *n_H, int *have_mme, int64_t *n_voxels) {
+    if (slot < 0 || slot > 1 || !trunc || !n_voxels) return ctx->fail(ME_ERR_ARG, "me_voxel_metrics: bad argument");
+    if (!(voxel_size > 0)) return ctx->fail(ME_ERR_ARG, "me_voxel_metrics: voxel_size must be > 0");
+    Cloud &c = ctx->cloud[slot];
+    if (c.slab.axis >= 0 || ctx->shard_world > 1)
+        return ctx->fail(ME_ERR_STATE, "me_voxel_metrics: single GPU only (no slab or shard mode)");
+    if (!c.uploaded) return ctx->fail(ME_ERR_STATE, "me_voxel_metrics: cloud not uploaded");
+    if (c.nn_ref_slot < 0)
+        return ctx->fail(ME_ERR_STATE, "me_voxel_metrics: no me_nn1 with this slot as the query since its last upload or transform");
+    ME_CHECK(ctx, hipSetDevice(ctx->device));
+    const long long n = c.n;
+    const bool mme = c.mme_have;
+    const StatParams st = make_params(gate, gate_mode, trunc);
+    const long long n_rows = (n + 63) / 64;
+    long long rsize = vox_region_size(n), cap = 0;
+    DevBuf &pbuf = ctx->tmp[0], &cbuf = ctx->tmp[1], &dbuf = ctx->tmp[2];  // (tmp[3] - tmp[5]: vox_record_segments)
+    ME_CHECK(ctx, ctx->red.ensure(kVoxCounterBytes));
+    unsigned int *cnt = ctx->red.as<unsigned int>();  // [range error, fullest region, the regions' counters]
+    for (int attempt = 0;; ++attempt) {
+        cap = 2 * n_rows + (long long) kVoxRegions * rsize;
+        ME_CHECK(ctx, pbuf.ensure((size_t) cap * 16));  // rec_pos | rec_vkey
+        ME_CHECK(ctx, cbuf.ensure((size_t) cap * 8));
+        ME_CHECK(ctx, dbuf.ensure((size_t) cap * 8 * kVmD));
+        ME_CHECK(ctx, hipMemsetAsync(pbuf.p, 0xFF, (size_t) cap * 8, ctx->stream));  // kVoxEmptySlot
+        ME_CHECK(ctx, hipMemsetAsync(cnt, 0, kVoxCounterBytes, ctx->stream));
+        {
+            TimerScope ts(ctx, "voxel_metrics");
+            hipLaunchKernelGGL(k_voxm_records, dim3(blocks_of(n)), dim3(256), 0, ctx->stream, c.sp.as<SPoint>(), c.nn_d2.as<double>(),
+                               mme ? c.mme_ent.as<double>() : nullptr, mme ? c.mme_val.as<unsigned char>() : nullptr, n, voxel_size, c.slab,
+                               st, pbuf.as<unsigned long long>(), pbuf.as<unsigned long long>() + cap, cbuf.as<uint2>(), dbuf.as<double>(),
+                               cnt + 2, (unsigned int) n_rows, (unsigned int) rsize, reinterpret_cast<int *>(cnt));
+        }
+        unsigned int h2[2] = {0, 0};
+        ME_TRY(vox_region_fill(ctx, cnt, h2));
+        if (h2[0]) return ctx->fail(ME_ERR_ARG, "me_voxel_metrics: voxel index out of range (|floor(p/voxel_size)| must be < 2^20)");
+        if ((long long) h2[1] <= rsize) break;
+        if (attempt > 0) return ctx->fail(ME_ERR_HIP, "me_voxel_metrics: overflow regions still too small");
+        rsize = (long long) h2[1];  // (a region overflowed: once more with regions as large as the fullest one needs; the same records)
+    }
+    DevBuf vkey_d, seg_d, keys_d, nn_d, sh_d, nh_d;
+    const unsigned int *perm2 = nullptr;
+    long long V = 0;
+    ME_TRY(vox_record_segments(ctx, cap, pbuf.as<unsigned long long>(), pbuf.as<unsigned long long>() + cap, vkey_d, seg_d, &perm2, &V));
     ME_CHECK(ctx, keys_d.ensure((size_t) V * 12));
     ME_CHECK(ctx, nn_d.ensure((size_t) V * sizeof(me_nn_partial)));
     ME_CHECK(ctx, sh_d.ensure((size_t) V * 8));
     ME_CHECK(ctx, nh_d.ensure((size_t) V * 8));
-    hipLaunchKernelGGL(k_seg_scatter, dim3(blocks_of(R)), dim3(256), 0, ctx->stream, (const unsigned long long *) kb, (const unsigned int *) flags,
-                       (const unsigned int *) pos, R, vkey_d.as<unsigned long long>(), seg_d.as<unsigned int>());
-    hipLaunchKernelGGL(k_set_u32v, dim3(1), dim3(1), 0, ctx->stream, seg_d.as<unsigned int>(), V, (unsigned int) R);
     {
         TimerScope ts(ctx, "voxel_metrics");
         hipLaunchKernelGGL(k_voxm_reduce, dim3((unsigned int) ((V + 3) / 4)), dim3(256), 0, ctx->stream, (const unsigned int *) perm2,

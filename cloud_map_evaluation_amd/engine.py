@@ -54,6 +54,16 @@ class RegStats:
         return RegStats(o.n_src, o.n_corr, f(o.mean), f(o.rmse), f(o.fitness), f(o.sigma), f(o.number), o.mean_nn_dist)
 
 
+def rotation_angle(R) -> np.ndarray:
+    """The angle of rotation matrices (.., 9) or (.., 3, 3), radians in [0, pi]: atan2(s, c) with
+    s = sqrt((R21 - R12)^2 + (R02 - R20)^2 + (R10 - R01)^2) / 2 and c = (tr R - 1) / 2 (deformation_field; the C++ host's formula)."""
+    R = np.asarray(R, np.float64)
+    R = R.reshape(R.shape[:-2] + (9,)) if R.shape[-2:] == (3, 3) else R
+    a, b, c = R[..., 7] - R[..., 5], R[..., 2] - R[..., 6], R[..., 3] - R[..., 1]
+    s = 0.5 * np.sqrt(a * a + b * b + c * c)
+    return np.arctan2(s, 0.5 * (R[..., 0] + R[..., 4] + R[..., 8] - 1.0))
+
+
 def _addr(a) -> int:
     """Raw address of a numpy array (host) or a torch tensor (host or device)."""
     if a is None:
@@ -1236,6 +1246,44 @@ class Engine:
         out = {f: np.ascontiguousarray(nn[f]) for f in _lib.NN_PARTIAL_DTYPE.names}
         out.update(keys=keys, sum_H=sum_h, n_H=n_h, have_mme=bool(hm.value))
         return out
+
+    def deformation_field(self, query_slot: int, voxel_size: float, max_distance: float, min_pairs: int = 30,
+                          min_spread: Optional[float] = None, fetch: bool = True) -> dict:
+        """me_voxel_deformation: the rigid deformation of every voxel of the query cloud against the reference of the last
+        nn1(query_slot, ..), on the lattice of voxel_gaussians(query_slot, voxel_size); min_spread None = voxel_size / 20.
+        -> the totals of me_deform_summary (its n_pairs as n_pairs_total) and, computed here: mean_disp = sum n|t0| / sum n, rms_disp = sqrt(sum n|t0|^2 / sum n),
+        max_disp and max_key (None without a fitted voxel), share_translation = 1 - sum e_t / sum e0 and share_rigid =
+        1 - sum e_R / sum e0_fit (NaN when the denominator is 0).  With fetch also the rows: keys (V, 3), n_pairs, flags, sums (V, 23),
+        t0, u (V, 3), R (V, 3, 3), e0, e_t, e_R and angle = rotation_angle(R) in radians."""
+        ms = float(voxel_size) / 20.0 if min_spread is None else float(min_spread)
+        o = _lib.DeformSummary()
+        self._ck(self._L.me_voxel_deformation(self._ctx, query_slot, float(voxel_size), float(max_distance), int(min_pairs), ms, C.byref(o)))
+        res = {f: getattr(o, f) for f in ("n_voxels", "n_with_pairs", "n_fit", "n_rot", "max_row", "sum_n_t0", "sum_n_t0sq",
+                                          "sum_e0", "sum_e_t", "sum_e0_fit", "sum_e_R")}
+        res["n_pairs_total"] = o.n_pairs  # (n_pairs is the per-voxel array of the rows)
+        nan = float("nan")
+        res["mean_disp"] = o.sum_n_t0 / o.n_pairs if o.n_pairs > 0 else nan
+        res["rms_disp"] = math.sqrt(o.sum_n_t0sq / o.n_pairs) if o.n_pairs > 0 else nan
+        res["max_disp"] = o.max_t0
+        res["max_key"] = tuple(int(k) for k in o.max_key) if o.max_row >= 0 else None
+        res["share_translation"] = 1.0 - o.sum_e_t / o.sum_e0 if o.sum_e0 != 0 else nan
+        res["share_rigid"] = 1.0 - o.sum_e_R / o.sum_e0_fit if o.sum_e0_fit != 0 else nan
+        if fetch:
+            res.update(self.deformation_fetch(query_slot))
+        return res
+
+    def deformation_fetch(self, query_slot: int) -> dict:
+        """me_voxel_deformation_fetch: the rows of the last deformation_field(query_slot, ..)."""
+        nv = C.c_int64(0)
+        self._ck(self._L.me_voxel_deformation_fetch(self._ctx, query_slot, 0, 0, 0, 0, 0, 0, 0, 0, C.byref(nv)))
+        v = nv.value
+        keys, n, fl = np.empty((v, 3), np.int32), np.empty(v, np.int64), np.empty(v, np.uint8)
+        sums, t0, u = np.empty((v, _lib.ME_DEFORM_SUMS), np.float64), np.empty((v, 3), np.float64), np.empty((v, 3), np.float64)
+        R, e = np.empty((v, 9), np.float64), np.empty((v, 3), np.float64)
+        self._ck(self._L.me_voxel_deformation_fetch(self._ctx, query_slot, _addr(keys), _addr(n), _addr(fl), _addr(sums), _addr(t0), _addr(u),
+                                                    _addr(R), _addr(e), C.byref(nv)))
+        return dict(keys=keys, n_pairs=n, flags=fl, sums=sums, t0=t0, u=u, R=R.reshape(v, 3, 3), e0=np.ascontiguousarray(e[:, 0]),
+                    e_t=np.ascontiguousarray(e[:, 1]), e_R=np.ascontiguousarray(e[:, 2]), angle=rotation_angle(R))
 
     def voxel_metrics_table(self, voxel_size: float, gate: float, gate_mode: int, trunc, min_pts: int = 100,
                             scs_radius: int = 5) -> np.ndarray:

@@ -417,6 +417,20 @@ Param loadParametersFromYAML(const std::string &yaml_file_path) {
         if (param.evaluate_noised_gt_) throw std::runtime_error("evaluate_m3c2: not with evaluate_noised_gt");
         if (param.num_gpus > 1) throw std::runtime_error("evaluate_m3c2: single GPU only (num_gpus must be 1)");
     }
+    // per-voxel rigid deformation field (me_voxel_deformation; no reference counterpart)
+    if (config.has("evaluate_deformation")) param.evaluate_deformation = config.as_bool("evaluate_deformation");
+    param.deformation_voxel_size = config.has("deformation_voxel_size") ? config.as_double("deformation_voxel_size") : param.vmd_voxel_size_;
+    param.deformation_max_distance = config.has("deformation_max_distance") ? config.as_double("deformation_max_distance")
+                                     : (param.icp_max_distance_ > 0 ? std::sqrt(param.icp_max_distance_) : INFINITY);
+    if (config.has("deformation_min_pairs")) param.deformation_min_pairs = (int) config.as_double("deformation_min_pairs");
+    param.deformation_min_spread = config.has("deformation_min_spread") ? config.as_double("deformation_min_spread") : param.deformation_voxel_size / 20.0;
+    if (param.evaluate_deformation) {
+        if (!(param.deformation_voxel_size > 0) || !std::isfinite(param.deformation_voxel_size)) throw std::runtime_error("deformation_voxel_size: must be > 0");
+        if (!(param.deformation_max_distance > 0)) throw std::runtime_error("deformation_max_distance: must be > 0");
+        if (param.deformation_min_pairs < 3) throw std::runtime_error("deformation_min_pairs: must be >= 3");
+        if (!(param.deformation_min_spread >= 0)) throw std::runtime_error("deformation_min_spread: must be >= 0");
+        if (param.num_gpus > 1) throw std::runtime_error("evaluate_deformation: single GPU only (num_gpus must be 1)");
+    }
     // cloud-to-mesh distance (the role of the reference's mesh branch, with a supplied mesh)
     if (config.has("evaluate_mesh_distance")) param.evaluate_mesh_distance = config.as_bool("evaluate_mesh_distance");
     if (config.has("gt_mesh_path")) param.gt_mesh_path = config.as_string("gt_mesh_path");
@@ -547,7 +561,7 @@ std::string paramToJson(const Param &p) {
     for (size_t i = 0; i < p.surface_thresholds.size(); ++i) o << (i ? ", " : "") << p.surface_thresholds[i];
     o << "], \"surface_angles_deg\": [";
     for (size_t i = 0; i < p.surface_angles_deg.size(); ++i) o << (i ? ", " : "") << p.surface_angles_deg[i];
-    o << "], \"surface_gated\": " << b(p.surface_gated) << ", \"evaluate_m3c2\": " << b(p.evaluate_m3c2)
+    o << "], \"surface_gated\": " << b(p.surface_gated) << ", \"evaluate_m3c2\": " << b(p.evaluate_m3c2) << ", \"evaluate_deformation\": " << b(p.evaluate_deformation)
       << ", \"m3c2_normal_radius\": " << p.m3c2_normal_radius << ", \"m3c2_projection_radius\": " << p.m3c2_projection_radius
       << ", \"m3c2_max_depth\": " << p.m3c2_max_depth << ", \"m3c2_min_points\": " << p.m3c2_min_points
       << ", \"m3c2_reg_error\": " << p.m3c2_reg_error << ", \"m3c2_core_every\": " << p.m3c2_core_every
@@ -803,6 +817,7 @@ int MapEval::process() {
 
     calculateVMD();
     if (!last_error.empty()) return -1;
+    if (param_.evaluate_deformation && computeDeformation() != 0) return -1;
     if (param_.save_voxel_metrics) {  // (only the registration path gets here on one GPU: the initial-matrix one is processOneCall)
         // the transforms of the registration discarded the map's MME result on the device: hand back the entropies computeMME
         // fetched (those of map_entropy.txt), and the ground truth's with them
@@ -1237,6 +1252,7 @@ int MapEval::processOneCall(bool from_host, double t_loaded) {
     // ---- calculateVMD (:240-390): the voxel tables are cached on the clouds, AWD / CDF / SCS are O(voxels) ----
     calculateVMD();
     if (!last_error.empty()) return -1;
+    if (param_.evaluate_deformation && computeDeformation() != 0) return -1;
     if (param_.save_voxel_metrics) {
         saveVoxelMetrics(ME_GATE_LE_UNSQUARED);  // the gate of the statistics above (:1219)
         if (!last_error.empty()) return -1;
@@ -1835,6 +1851,61 @@ void MapEval::saveM3C2() {
     if (std::fclose(f) != 0) fail("writing " + path + " failed");
 }
 
+// evaluate_deformation: the per-voxel rigid deformation field of the map against the ground truth, from the resident 1-NN result with
+// the map as the query (the one the statistics above were taken from), where the map stands now: me_voxel_deformation.
+int MapEval::computeDeformation() {
+    if (me_voxel_deformation(ctx_, ME_SLOT_EST, param_.deformation_voxel_size, param_.deformation_max_distance, param_.deformation_min_pairs,
+                             param_.deformation_min_spread, &deform_out) != ME_OK)
+        return fail(std::string("evaluate_deformation: ") + me_last_error(ctx_));
+    return 0;
+}
+
+// The result line `Deformation mean-rms-max share_t-share_R:` (mean = sum n|t0| / sum n, rms = sqrt(sum n|t0|^2 / sum n), the largest |t0|
+// of a fitted voxel, 1 - sum e_t / sum e0, 1 - sum e_R / sum e0_fit; nan on a zero denominator) and deformation_field.txt: the
+// parameters ("name value"), then one row per voxel WITH pairs
+//   ix iy iz n flags t0x t0y t0z ux uy uz angle e0 e_t e_R          (doubles as %.17g; angle = atan2(s, c) in radians,
+// s = sqrt((R21 - R12)^2 + (R02 - R20)^2 + (R10 - R01)^2) / 2, c = (tr R - 1) / 2: Engine.deformation_field's formula)
+void MapEval::saveDeformation() {
+    const me_deform_summary &o = deform_out;
+    const double nan = std::nan("");
+    const double sn = (double) o.n_pairs;
+    file_result << std::fixed << std::setprecision(15) << "Deformation mean-rms-max share_t-share_R: " << (o.n_pairs > 0 ? o.sum_n_t0 / sn : nan) << " "
+                << (o.n_pairs > 0 ? std::sqrt(o.sum_n_t0sq / sn) : nan) << " " << o.max_t0 << " "
+                << (o.sum_e0 != 0 ? 1.0 - o.sum_e_t / o.sum_e0 : nan) << " " << (o.sum_e0_fit != 0 ? 1.0 - o.sum_e_R / o.sum_e0_fit : nan) << std::endl;
+    int64_t V = 0;
+    if (me_voxel_deformation_fetch(ctx_, ME_SLOT_EST, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &V) != ME_OK) {
+        fail(std::string("evaluate_deformation: ") + me_last_error(ctx_));
+        return;
+    }
+    std::vector<int32_t> keys((size_t) V * 3);
+    std::vector<int64_t> n((size_t) V);
+    std::vector<uint8_t> flags((size_t) V);
+    std::vector<double> t0((size_t) V * 3), u((size_t) V * 3), R((size_t) V * 9), e((size_t) V * 3);
+    if (V > 0 && me_voxel_deformation_fetch(ctx_, ME_SLOT_EST, keys.data(), n.data(), flags.data(), nullptr, t0.data(), u.data(), R.data(), e.data(),
+                                            &V) != ME_OK) {
+        fail(std::string("evaluate_deformation: ") + me_last_error(ctx_));
+        return;
+    }
+    const std::string path = results_subfolder + "deformation_field.txt";
+    FILE *f = std::fopen(path.c_str(), "w");
+    if (!f) {
+        fail("cannot write " + path);
+        return;
+    }
+    std::fprintf(f, "voxel_size %.17g\nmax_distance %.17g\nmin_pairs %d\nmin_spread %.17g\n", param_.deformation_voxel_size,
+                 param_.deformation_max_distance, param_.deformation_min_pairs, param_.deformation_min_spread);
+    for (int64_t v = 0; v < V; ++v) {
+        if (n[v] <= 0) continue;
+        const double *r = &R[(size_t) v * 9];
+        const double a = r[7] - r[5], b = r[2] - r[6], c = r[3] - r[1];
+        const double angle = std::atan2(0.5 * std::sqrt(a * a + b * b + c * c), 0.5 * (r[0] + r[4] + r[8] - 1.0));
+        std::fprintf(f, "%d %d %d %lld %d %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g\n", keys[3 * v], keys[3 * v + 1], keys[3 * v + 2],
+                     (long long) n[v], (int) flags[v], t0[3 * v], t0[3 * v + 1], t0[3 * v + 2], u[3 * v], u[3 * v + 1], u[3 * v + 2], angle,
+                     e[3 * v], e[3 * v + 1], e[3 * v + 2]);
+    }
+    if (std::fclose(f) != 0) fail("writing " + path + " failed");
+}
+
 // evaluate_mesh_distance: the mesh of gt_mesh_path as it is in the file (like the ground-truth cloud it is not moved), the map where
 // initial_matrix puts it (me_transform_cloud; the host's copy stays as loaded), me_mesh_distance with the map as the query, the exact
 // nearest-rank quantiles of d over the matched points (error_quantiles; me_rank_select on the fetched values) and, with
@@ -2093,6 +2164,7 @@ void MapEval::saveRegistrationResults() {
     if (param_.evaluate_m3c2) saveM3C2();
     if (param_.evaluate_mesh_distance) saveMeshDistance();
     if (param_.evaluate_mesh) saveReconstruction();
+    if (param_.evaluate_deformation) saveDeformation();
     file_result << std::fixed << std::setprecision(5) << "VMD: " << vmd << std::endl;
     file_result << std::fixed << std::setprecision(5) << "SCS: " << scs_overall << std::endl;
     if (param_.evaluate_using_initial_)

@@ -146,6 +146,12 @@ struct Param {
     // initial_matrix, before every other stage — me_radius_normals on both clouds, me_m3c2 in both directions — after which both clouds
     // are uploaded again as loaded (single GPU, with evaluate_using_initial); one line before `VMD`, and m3c2.txt
     bool evaluate_m3c2 = false;                // `evaluate_m3c2:`
+    bool evaluate_deformation = false;         // `evaluate_deformation:` true = the per-voxel rigid deformation field of the map against the
+                                               // ground truth (me_voxel_deformation; single GPU only): a result line and deformation_field.txt
+    double deformation_voxel_size = 0;         // `deformation_voxel_size:` (default vmd_voxel_size)
+    double deformation_max_distance = 0;       // `deformation_max_distance:` a DISTANCE (d2 < max^2); default sqrt(icp_max_distance) when that is > 0, else inf
+    int deformation_min_pairs = 30;            // `deformation_min_pairs:` (>= 3)
+    double deformation_min_spread = 0;         // `deformation_min_spread:` (default deformation_voxel_size / 20)
     double m3c2_normal_radius = 0.0;           // `m3c2_normal_radius:` > 0 (default: nn_radius)
     double m3c2_projection_radius = 0.0;       // `m3c2_projection_radius:` the cylinder's radius, > 0 (default: nn_radius)
     double m3c2_max_depth = 0.0;               // `m3c2_max_depth:` the cylinder's half-length, > 0 (default: 4 nn_radius)
@@ -223,6 +229,8 @@ public:
     void saveSurfaceError();                                // its three result lines and surface_error.txt
     int computeM3C2();                                      // evaluate_m3c2: normals and me_m3c2 on both clouds, the map moved (no reference counterpart)
     void saveM3C2();                                        // its result line and m3c2.txt
+    int computeDeformation();                               // evaluate_deformation: me_voxel_deformation with the map as the query (no reference counterpart)
+    void saveDeformation();                                 // its result line and deformation_field.txt
     int computeMeshDistance();                              // evaluate_mesh_distance: me_mesh_distance of the moved map (no reference counterpart)
     void saveMeshDistance();                                // its two result lines and mesh_distance.txt
     int computeReconstruction();                            // evaluate_mesh: radius normals + me_reconstruct on both clouds as loaded
@@ -253,6 +261,7 @@ public:
     me_surface_out surface_out[2] = {};         // ... [ME_SLOT_EST], [ME_SLOT_GT]
     me_radius_normals_out surface_normals[2] = {};
     me_m3c2_out m3c2_out[2] = {};               // evaluate_m3c2: [ME_SLOT_EST], [ME_SLOT_GT] as the query
+    me_deform_summary deform_out = {};          // evaluate_deformation
     me_radius_normals_out m3c2_normals[2] = {};
     me_mesh_info_out mesh_info = {};            // evaluate_mesh_distance: the mesh, the totals, the quantiles of d, the sampled block
     me_mesh_out mesh_out = {};

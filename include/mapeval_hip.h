@@ -1219,6 +1219,56 @@ int me_voxel_metrics(me_ctx *ctx, int slot, double voxel_size, double gate, int 
                      int32_t *keys /*V x 3*/, me_nn_partial *nn /*V*/, double *sum_H /*V*/, int64_t *n_H /*V*/,
                      int *have_mme, int64_t *n_voxels);
 
+/* ---- per-voxel rigid deformation field from the resident 1-NN pairs (no reference counterpart: map_eval.cpp reports scalars only) -- */
+/* (DESIGN.md section 4.22).  Which way, and by how much, has each voxel of the query cloud moved against the reference cloud: the pair
+ * moments of the last me_nn1(query_slot, ..) per voxel of the lattice of me_voxel_gaussians(query_slot, voxel_size) (same keys, same
+ * row order, a row for EVERY voxel of the query cloud), a rigid fit per voxel (Horn's closed form) and the share of the squared error
+ * that fit explains.  Nothing resident is changed but the result itself.
+ *   PAIRS   point i of the voxel is a pair iff d2_i >= 0, d2_i < max_distance^2 (strict: Open3D's SearchHybrid, as me_icp_p2p_sums;
+ *           max_distance = +inf takes every d2 >= 0) and nn_idx_i names a reference point (a result placed by me_set_nn_result has
+ *           no neighbour indices: none of its pairs is used).  p = the query point, q = the reference point, both in CURRENT
+ *           coordinates; o = (double(k) * voxel_size + 0.5 * voxel_size) per axis, the voxel's centre; a = p - o, b = q - o.
+ *   SUMS    23 doubles per voxel: sum a (3), sum b (3), sum a b^T (9, row-major), sum a a^T (6: xx, xy, xz, yy, yz, zz), sum |b|^2,
+ *           sum d2 (the resident values).  Fixed-order sums, no floating-point atomics, added in the POINTS' OWN order (by voxel,
+ *           inside a voxel by original point index): bit-identical from call to call and after any re-index of the same points.
+ *   FIT     with n the voxel's pair count: abar = sum a / n, bbar = sum b / n, t0 = bbar - abar (the mean displacement);
+ *           S = sum a b^T - (sum a)(sum b)^T / n, C = sum a a^T - (sum a)(sum a)^T / n.  ME_DEFORM_FIT: n >= min_pairs.
+ *           ME_DEFORM_ROT_OK: FIT and the middle eigenvalue of C >= n * min_spread^2 (a collinear or single-point source has no
+ *           rotation).  With ROT_OK R = horn_rotation(S), the least-squares rotation a - abar -> b - bbar, and u = bbar - R abar,
+ *           the fit's displacement at the voxel centre; otherwise R = I and u = t0.  e0 = sum d2; e_t = max(0, sum d2 - n |t0|^2),
+ *           what is left after the mean displacement; e_R = max(0, tr C + (sum |b|^2 - |sum b|^2 / n) - 2 sum_rc R_rc S_cr), the
+ *           sum of |R (a - abar) - (b - bbar)|^2 over the pairs: what is left after the rigid fit, with ROT_OK, else e_R = e_t.  n = 0: t0 = u = 0, R = I, every residual 0.
+ *   out     the totals over the rows in key order, added in the fixed order of the per-cloud totals.
+ * me_voxel_deformation_fetch: the rows of the last me_voxel_deformation(query_slot, ..): every array may be NULL; *n_voxels in:
+ * capacity, out: count (all-NULL arrays: count only; ME_ERR_CAPACITY if too small).  Host pointers.  e = [e0, e_t, e_R] per row.
+ * The rows stay on the query cloud exactly as long as its 1-NN result: a new search (me_nn1, me_set_nn_result, the suite), an upload
+ * or a transform of either slot, or an index rebuild of either slot discards them (ME_ERR_STATE from the fetch).
+ * ME_ERR_STATE: slot not uploaded, no me_nn1 with this slot as the query since the last upload or transform of either slot, or slab
+ * / shard mode.  ME_ERR_ARG: voxel_size <= 0, max_distance <= 0 or NaN, min_pairs < 3, min_spread < 0 or NaN, or a voxel index
+ * outside |floor(p / voxel_size)| < 2^20.  A sort of n (key, position) pairs, one pass over the cloud and a sort of ~n / 60 run records (device timer
+ * "voxel_deformation": the kernels; the sorts are under "sort").
+ * LIMITATION: 1-NN pairs under-report motion tangential to a surface; on a single plane u is reliable along the normal only, and the
+ * rigid share 1 - sum e_R / sum e0_fit is a lower bound of the drift share. */
+#define ME_DEFORM_FIT 1
+#define ME_DEFORM_ROT_OK 2
+#define ME_DEFORM_SUMS 23
+typedef struct {
+    int64_t n_voxels, n_with_pairs, n_fit, n_rot; /* rows, rows with n > 0, with FIT, with ROT_OK */
+    int64_t n_pairs;                              /* sum n = me_icp_p2p_sums(query_slot, max_distance).n_corr for a searched result */
+    int64_t max_row;                              /* row of max_t0 (ties: the smallest row); -1 without a FIT row */
+    int32_t max_key[3];                           /* its voxel key */
+    int32_t pad_;
+    double sum_n_t0, sum_n_t0sq;                  /* sum n |t0|, sum n |t0|^2 over all rows */
+    double max_t0;                                /* the largest |t0| of a FIT row (0 without one) */
+    double sum_e0, sum_e_t;                       /* over all rows */
+    double sum_e0_fit, sum_e_R;                   /* over the FIT rows */
+} me_deform_summary;
+int me_voxel_deformation(me_ctx *ctx, int query_slot, double voxel_size, double max_distance, int min_pairs, double min_spread,
+                         me_deform_summary *out);
+int me_voxel_deformation_fetch(me_ctx *ctx, int query_slot, int32_t *keys /*V x 3*/, int64_t *n_pairs /*V*/, uint8_t *flags /*V*/,
+                               double *sums /*V x 23*/, double *t0 /*V x 3*/, double *u /*V x 3*/, double *R /*V x 9*/,
+                               double *e /*V x 3*/, int64_t *n_voxels);
+
 /* ---- AWD + CDF + SCS: MapEval::calculateVMD (map_eval.cpp:240-390) with updateVoxelMap (voxel_calculator.cpp:
  *      142-172) and computeWassersteinDistanceGaussian (:115-140) ------------------------------------------------ */
 /* rows: n x 27 doubles in the column order of voxel_errors.txt (map_eval.cpp:292-302), ascending key order;
@@ -1304,7 +1354,7 @@ int me_run_suite_from(me_ctx *ctx, const double *est, int64_t n_est, const doubl
 
 /* ---- instrumentation (bench.py roofline leg) ------------------------------------------------------------- */
 /* Average device time (ms, HIP events on the context's stream) and launch count of a named kernel family since
- * the last me_timers_reset: "nn_grid", "nn1", "mme", "sort", "morton", "gather", "cells" (the cell tables), "octree", "nn_stats", "voxel", "voxel_metrics", "w2", "scs", "slab_filter", "halo_pack", "perturb", "fpfh", "fpfh_match", "ransac", "ransac_validate", "plane", "plane_score", "mom", "group_select".  Enabled by me_timers_enable(1).
+ * the last me_timers_reset: "nn_grid", "nn1", "mme", "sort", "morton", "gather", "cells" (the cell tables), "octree", "nn_stats", "voxel", "voxel_metrics", "voxel_deformation", "w2", "scs", "slab_filter", "halo_pack", "perturb", "fpfh", "fpfh_match", "ransac", "ransac_validate", "plane", "plane_score", "mom", "group_select".  Enabled by me_timers_enable(1).
  * Counters (total_ms = 0, value in *launches): "mme_pairs" (accepted (query, neighbour) pairs of the MME launches: the useful work of
  * the VALU-bound kernel, bench.py's roofline.valu), "mme_refined" (queries whose thin neighbourhood — smallest covariance eigenvalue below ~1.8e-6 cell^2 — the MME pass
  * recomputed two-pass about the query itself; counted whether or not timers are on), "nn_queries" / "nn_fallback_queries" (1-NN queries, and those that needed the
