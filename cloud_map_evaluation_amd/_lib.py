@@ -37,6 +37,7 @@ SYMBOLS = [
     "me_local_geometry", "me_local_geometry_fetch", "me_radius_normals", "me_nn_surface_error", "me_nn_surface_fetch",
     "me_m3c2", "me_m3c2_fetch",
     "me_mesh_upload", "me_mesh_clear", "me_mesh_info", "me_mesh_distance", "me_mesh_distance_fetch", "me_mesh_sample",
+    "me_mesh_topology", "me_mesh_topology_fetch", "me_mesh_signed_distance", "me_mesh_signed_fetch",
     "me_reconstruct", "me_isosurface", "me_reconstruct_fetch", "me_reconstruct_nodes_fetch", "me_reconstruct_install",
     "me_orient_normals", "me_orient_fetch",
     "me_knn_search", "me_hybrid_search", "me_radius_search", "me_search_sort_tile",
@@ -433,6 +434,35 @@ class MeshOut(C.Structure):
     ]
 
 
+# flags of me_mesh_topology_fetch (edges and vertices) and of me_mesh_signed_fetch (points)
+MESH_TOPO_BOUNDARY, MESH_TOPO_NONMANIFOLD, MESH_TOPO_INCONSISTENT, MESH_TOPO_ZERO, MESH_TOPO_TAINTED = 1, 2, 4, 8, 16
+MESH_SIGN_ON, MESH_SIGN_UNSIGNED, MESH_SIGN_UNRELIABLE = 1, 2, 4
+
+
+class MeshTopoOut(C.Structure):
+    _fields_ = [(k, C.c_int64) for k in (
+        "n_edges", "n_boundary_edges", "n_nonmanifold_edges", "n_inconsistent_edges", "n_zero_edges", "n_zero_vertices",
+        "n_tainted_vertices", "n_unreferenced_vertices", "closed", "oriented_manifold")]
+
+
+class MeshSignParams(C.Structure):
+    _fields_ = [("max_distance", C.c_double)]
+
+
+class MeshSignOut(C.Structure):
+    _fields_ = [(k, C.c_int64) for k in (
+        "n_query", "n_matched", "n_signed", "n_inside", "n_outside", "n_on", "n_unsigned", "n_unreliable")] + [
+        ("n_by_region", C.c_int64 * 3),
+        ("sum_signed", C.c_double),
+        ("sum_abs_signed", C.c_double),
+        ("sum_signed2", C.c_double),
+        ("min_signed", C.c_double),
+        ("argmin", C.c_int64),
+        ("max_signed", C.c_double),
+        ("argmax", C.c_int64),
+    ]
+
+
 class MeshInfoOut(C.Structure):
     _fields_ = [
         ("n_vertices", C.c_int64),
@@ -590,7 +620,12 @@ def load():
     L.me_mesh_distance.argtypes = [vp, C.c_int, C.POINTER(MeshParams), C.POINTER(MeshOut)]
     L.me_mesh_distance_fetch.argtypes = [vp, C.c_int, dp, ip, vp, dp, dp]
     L.me_mesh_sample.argtypes = [vp, C.c_int, C.c_int64, C.c_uint64]
-    for f in ("me_mesh_upload", "me_mesh_clear", "me_mesh_info", "me_mesh_distance", "me_mesh_distance_fetch", "me_mesh_sample"):
+    L.me_mesh_topology.argtypes = [vp, C.POINTER(MeshTopoOut)]
+    L.me_mesh_topology_fetch.argtypes = [vp, dp, vp, dp, vp]
+    L.me_mesh_signed_distance.argtypes = [vp, C.c_int, C.POINTER(MeshSignParams), C.POINTER(MeshSignOut)]
+    L.me_mesh_signed_fetch.argtypes = [vp, C.c_int, dp, vp]
+    for f in ("me_mesh_upload", "me_mesh_clear", "me_mesh_info", "me_mesh_distance", "me_mesh_distance_fetch", "me_mesh_sample",
+              "me_mesh_topology", "me_mesh_topology_fetch", "me_mesh_signed_distance", "me_mesh_signed_fetch"):
         getattr(L, f).restype = C.c_int
     L.me_reconstruct.argtypes = [vp, C.c_int, C.POINTER(ReconParams), C.POINTER(ReconOut)]
     L.me_isosurface.argtypes = [vp, ip, dp, vp, C.c_int64, C.c_double, C.POINTER(ReconOut)]

@@ -422,6 +422,26 @@ int me_mesh_sample(me_ctx *ctx, int dst_slot, int64_t n_points, uint64_t seed) {
     return me::mesh_sample(ctx, dst_slot, n_points, seed);
 }
 
+int me_mesh_topology(me_ctx *ctx, me_mesh_topo_out *out) {
+    if (!ctx) return ME_ERR_ARG;
+    return me::mesh_topology(ctx, out);
+}
+
+int me_mesh_topology_fetch(me_ctx *ctx, double *vertex_normal, uint8_t *vertex_flags, double *edge_normal, uint8_t *edge_flags) {
+    if (!ctx) return ME_ERR_ARG;
+    return me::mesh_topology_fetch(ctx, vertex_normal, vertex_flags, edge_normal, edge_flags);
+}
+
+int me_mesh_signed_distance(me_ctx *ctx, int query_slot, const me_mesh_sign_params *p, me_mesh_sign_out *out) {
+    if (!ctx) return ME_ERR_ARG;
+    return me::mesh_signed_distance(ctx, query_slot, p, out);
+}
+
+int me_mesh_signed_fetch(me_ctx *ctx, int query_slot, double *signed_d, uint8_t *flags) {
+    if (!ctx) return ME_ERR_ARG;
+    return me::mesh_signed_fetch(ctx, query_slot, signed_d, flags);
+}
+
 int me_reconstruct(me_ctx *ctx, int slot, const me_recon_params *p, me_recon_out *out) {
     if (!ctx) return ME_ERR_ARG;
     return me::reconstruct(ctx, slot, p, out);

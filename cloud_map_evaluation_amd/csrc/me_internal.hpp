@@ -261,6 +261,10 @@ struct Cloud {
     // (cloud_build_index), with the points, and with the mesh (me_mesh_upload, me_mesh_clear)
     DevBuf mesh_d2, mesh_tri, mesh_reg, mesh_cp, mesh_sd;
     bool mesh_have = false;
+    // last me_mesh_signed_distance over that result, SORTED order (me_meshsign.hip): signed distance double[n], flag byte; current only
+    // while mesh_have is, and cleared by a new me_mesh_distance on the slot
+    DevBuf mesh_ssd, mesh_sfl;
+    bool mesh_sign_have = false;
     // component (int32[n]) and flip byte per point of the last me_orient_normals, CLOUD order (me_orient.hip); dropped when the slot's
     // normals or points are next replaced (cloud_finish, the normal producers, rotate_attributes)
     DevBuf orient_comp, orient_flip;
@@ -289,6 +293,14 @@ struct Mesh {
     DevBuf cum;     // double[nt] cumulative area, caller's order
     DevBuf boxes;   // double[nodes][6] of all levels
     DevBuf lv;      // int2[kMeshMaxLevels] (offset, count) per level
+    DevBuf idx;     // int32[nt][3] the caller's vertex indices (the mesh's connectivity)
+    // topology and pseudo-normals (me_meshsign.hip), built on first use, dropped with the mesh: the edge id int32[nt][3] per
+    // (triangle, local edge AB BC CA), -1 for a triangle without edges; N_e double[n_edges][3] and the edge flags; N_v double[nv][3]
+    // and the vertex flags; the build's counters
+    bool topo_have = false;
+    long long n_edges = 0;
+    DevBuf eid, e_n, e_fl, v_n, v_fl, topo_cnt;
+    me_mesh_topo_out topo{};
 };
 
 // The last reconstruction (me_recon.hip): one per primary context, like the mesh; held until the next me_reconstruct / me_isosurface
@@ -607,6 +619,11 @@ int mesh_distance(me_ctx *ctx, int qslot, const me_mesh_params *p, me_mesh_out *
 int mesh_distance_fetch(me_ctx *ctx, int qslot, double *d2_host, int32_t *tri_host, uint8_t *region_host, double *closest_host,
                         double *signed_host);
 int mesh_sample(me_ctx *ctx, int dst_slot, long long n_points, unsigned long long seed);
+// ---- me_meshsign.hip ----
+int mesh_topology(me_ctx *ctx, me_mesh_topo_out *out);
+int mesh_topology_fetch(me_ctx *ctx, double *vertex_normal_host, uint8_t *vertex_flags_host, double *edge_normal_host, uint8_t *edge_flags_host);
+int mesh_signed_distance(me_ctx *ctx, int qslot, const me_mesh_sign_params *p, me_mesh_sign_out *out);
+int mesh_signed_fetch(me_ctx *ctx, int qslot, double *signed_host, uint8_t *flags_host);
 // ---- me_recon.hip ----
 int reconstruct(me_ctx *ctx, int slot, const me_recon_params *p, me_recon_out *out);
 int isosurface(me_ctx *ctx, const int32_t *node_ijk_host, const double *f_host, const uint8_t *valid_host, long long n_nodes, double voxel,

@@ -344,6 +344,9 @@ __global__ void __launch_bounds__(256) k_mesh_sample(const double *__restrict__ 
 void mesh_drop_results(me_ctx *ctx) {
     ctx->cloud[0].mesh_have = false;
     ctx->cloud[1].mesh_have = false;
+    ctx->cloud[0].mesh_sign_have = false;
+    ctx->cloud[1].mesh_sign_have = false;
+    ctx->mesh->topo_have = false;  // (the topology and the pseudo-normals go with the mesh they were built from: me_meshsign.hip)
 }
 
 }  // namespace
@@ -408,6 +411,7 @@ int mesh_upload(me_ctx *ctx, const double *vertices, long long nv, const int32_t
     ME_CHECK(ctx, m.tri_s.ensure((size_t) nt * 72));
     ME_CHECK(ctx, m.orig.ensure((size_t) nt * 4));
     ME_CHECK(ctx, m.cum.ensure((size_t) nt * 8));
+    ME_CHECK(ctx, m.idx.ensure((size_t) nt * 12));
     ME_CHECK(ctx, m.boxes.ensure((size_t) off * 48));
     ME_CHECK(ctx, m.lv.ensure(sizeof(int2) * kMeshMaxLevels));
     int2 lv[kMeshMaxLevels] = {};
@@ -420,6 +424,7 @@ int mesh_upload(me_ctx *ctx, const double *vertices, long long nv, const int32_t
     ME_CHECK(ctx, degd.ensure((size_t) nt));
     ME_TRY(copy_h2d(ctx, m.tri_in.p, tri.data(), (size_t) nt * 72));
     ME_TRY(copy_h2d(ctx, m.cum.p, cum.data(), (size_t) nt * 8));
+    ME_TRY(copy_h2d(ctx, m.idx.p, triangles, (size_t) nt * 12));
     ME_TRY(copy_h2d(ctx, degd.p, deg.data(), (size_t) nt));
     ME_TRY(copy_h2d(ctx, m.lv.p, lv, sizeof(lv)));
     double extent = 0.0;
@@ -460,6 +465,7 @@ int mesh_clear(me_ctx *ctx) {
     m.have = false;
     mesh_drop_results(ctx);
     m.tri_in.release(), m.tri_s.release(), m.orig.release(), m.cum.release(), m.boxes.release(), m.lv.release();
+    m.idx.release(), m.eid.release(), m.e_n.release(), m.e_fl.release(), m.v_n.release(), m.v_fl.release(), m.topo_cnt.release();
     reconstruct_drop(ctx);  // (the last reconstruction goes with the mesh it may have become: me_recon.hip)
     return ME_OK;
 }
@@ -495,6 +501,7 @@ int mesh_distance(me_ctx *ctx, int qslot, const me_mesh_params *p, me_mesh_out *
     Cloud &q = ctx->cloud[qslot];
     ME_CHECK(ctx, hipSetDevice(ctx->device));
     q.mesh_have = false;
+    q.mesh_sign_have = false;  // (the sign pass reads this result: me_meshsign.hip)
     if (!q.index_valid) ME_TRY(cloud_build_index(ctx, qslot, q.cell_size_req));  // (a slot whose points a device pass has just replaced)
     const long long n = q.n;
     ME_CHECK(ctx, q.mesh_d2.ensure((size_t) n * 8));

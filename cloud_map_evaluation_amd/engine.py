@@ -1091,8 +1091,73 @@ class Engine:
         self._held.pop(dst_slot, None)
         return self.size(dst_slot)
 
+    # ---- the sign of that distance at edges and vertices: connectivity, pseudo-normals, the sign pass (me_meshsign.hip) ----
+    @staticmethod
+    def mesh_weld(vertices, triangles):
+        """Merge vertices of equal value (-0.0 == 0.0), keeping the first occurrence and the order of the kept ones -> (vertices,
+        triangles, map) with map[i] the new index of old vertex i.  Plain numpy, for STL-style triangle soup: the topology identifies
+        a vertex by its index, so unwelded soup is all boundary edges."""
+        v = np.ascontiguousarray(vertices, dtype=np.float64).reshape(-1, 3)
+        t = np.ascontiguousarray(triangles, dtype=np.int32).reshape(-1, 3)
+        if v.shape[0] == 0:
+            return v.copy(), t.copy(), np.zeros(0, np.int64)
+        _, first, inv = np.unique(v + 0.0, axis=0, return_index=True, return_inverse=True)  # (+ 0.0 turns -0.0 into +0.0)
+        inv = np.asarray(inv).reshape(-1)
+        keep = np.sort(first)  # first occurrences, in the caller's order
+        new_of_group = np.empty(first.shape[0], np.int64)
+        new_of_group[np.argsort(first, kind="stable")] = np.arange(first.shape[0])
+        vmap = new_of_group[inv]
+        return v[keep].copy(), vmap[t].astype(np.int32), vmap
+
+    def mesh_topology(self, fetch: bool = False):
+        """me_mesh_topology: the resident mesh's connectivity by the caller's vertex indices -> n_edges, n_boundary_edges,
+        n_nonmanifold_edges, n_inconsistent_edges, n_zero_edges, n_zero_vertices, n_tainted_vertices, n_unreferenced_vertices, closed,
+        oriented_manifold.  Built on first use and kept with the mesh.  With fetch=True also the dict of me_mesh_topology_fetch:
+        vertex_normal (V,3), vertex_flags (V,), edge_normal (F,3,3) and edge_flags (F,3) per (triangle, local edge AB BC CA)."""
+        o = _lib.MeshTopoOut()
+        self._ck(self._L.me_mesh_topology(self._ctx, C.byref(o)))
+        res = {k: int(getattr(o, k)) for k, _ in _lib.MeshTopoOut._fields_}
+        res["closed"], res["oriented_manifold"] = bool(res["closed"]), bool(res["oriented_manifold"])
+        if not fetch:
+            return res
+        info = self.mesh_info()
+        nv, nt = info["vertices"], info["triangles"]
+        d = {"vertex_normal": np.empty((nv, 3), np.float64), "vertex_flags": np.empty(nv, np.uint8),
+             "edge_normal": np.empty((nt, 3, 3), np.float64), "edge_flags": np.empty((nt, 3), np.uint8)}
+        self._ck(self._L.me_mesh_topology_fetch(self._ctx, _addr(d["vertex_normal"]), _addr(d["vertex_flags"]), _addr(d["edge_normal"]),
+                                                _addr(d["edge_flags"])))
+        return res, d
+
+    def mesh_signed_distance(self, query_slot: int, max_distance: float = math.inf, fetch: bool = False):
+        """me_mesh_signed_distance over the slot's current mesh_distance result: the sign from the face normal, the edge pseudo-normal
+        or the angle-weighted vertex pseudo-normal of the feature the closest point lies on (signed_d > 0 outside).  Returns the totals
+        over the matched points plus mean_signed, mean_abs (over the signed points), inside_share (inside / signed) and
+        unreliable_share (unreliable / matched); zeros where the denominator is.  With fetch=True also the dict of mesh_signed_fetch."""
+        p = _lib.MeshSignParams()
+        p.max_distance = float(max_distance)
+        o = _lib.MeshSignOut()
+        self._ck(self._L.me_mesh_signed_distance(self._ctx, int(query_slot), C.byref(p), C.byref(o)))
+        res = {k: int(getattr(o, k)) for k in ("n_query", "n_matched", "n_signed", "n_inside", "n_outside", "n_on", "n_unsigned",
+                                                "n_unreliable", "argmin", "argmax")}
+        res["n_by_region"] = np.array(list(o.n_by_region), np.int64)
+        for k in ("sum_signed", "sum_abs_signed", "sum_signed2", "min_signed", "max_signed"):
+            res[k] = float(getattr(o, k))
+        ns, nm = res["n_signed"], res["n_matched"]
+        res["mean_signed"] = o.sum_signed / ns if ns > 0 else 0.0
+        res["mean_abs"] = o.sum_abs_signed / ns if ns > 0 else 0.0
+        res["inside_share"] = res["n_inside"] / ns if ns > 0 else 0.0
+        res["unreliable_share"] = res["n_unreliable"] / nm if nm > 0 else 0.0
+        return (res, self.mesh_signed_fetch(query_slot)) if fetch else res
+
+    def mesh_signed_fetch(self, query_slot: int) -> dict:
+        """me_mesh_signed_fetch -> signed_d (float64, NaN where unsigned) and flags (uint8: 1 ON, 2 UNSIGNED, 4 UNRELIABLE), cloud order."""
+        n = self.size(query_slot)
+        d = {"signed_d": np.empty(n, np.float64), "flags": np.empty(n, np.uint8)}
+        self._ck(self._L.me_mesh_signed_fetch(self._ctx, int(query_slot), _addr(d["signed_d"]), _addr(d["flags"])))
+        return d
+
     def mesh_report(self, thresholds, quantiles=(0.5, 0.9, 0.95, 0.99), sample_points: int = 0, seed: int = 0,
-                    max_distance: float = math.inf) -> dict:
+                    max_distance: float = math.inf, signed: bool = False) -> dict:
         """The cloud-to-mesh figures of slot 0 (mesh_distance) plus prob / rank / quantile_d: exact nearest-rank quantiles of d over the
         matched points (rank_select on the fetched values).  With sample_points > 0 the mesh is then sampled into slot 1, nn1 runs both
         ways and "sampled" holds error_report(thresholds, quantiles): completeness (recall) and F-score per threshold."""
@@ -1107,6 +1172,29 @@ class Engine:
             rep["quantile_d"] = self.rank_select(d, ranks, use=pts["d2"] <= float(max_distance) * float(max_distance))["value"]
         else:
             rep["quantile_d"] = np.zeros(len(probs), np.float64)
+        if signed:  # the sign everywhere (mesh_signed_distance) and exact nearest-rank quantiles of signed_d over the signed matched points
+            srep, spts = self.mesh_signed_distance(ME_SLOT_EST, max_distance, fetch=True)
+            srep["topology"] = self.mesh_topology()
+            ns = srep["n_signed"]
+            sranks = [min(ns - 1, max(0, int(math.ceil(pr * float(ns))) - 1)) if ns > 0 else -1 for pr in probs]
+            srep["prob"], srep["rank"] = np.array(probs, np.float64), np.array(sranks, np.int64)
+            if probs and ns > 0:
+                # rank_select takes values >= 0: the ni negative ones come first in ascending order, by descending |s|
+                sd = spts["signed_d"]
+                use = (pts["d2"] <= float(max_distance) * float(max_distance)) & ~np.isnan(sd)
+                neg = use & (sd < 0)
+                ni = int(np.count_nonzero(neg))
+                q = np.zeros(len(probs), np.float64)
+                lo = [j for j, r in enumerate(sranks) if r < ni]
+                hi = [j for j, r in enumerate(sranks) if r >= ni]
+                if lo:
+                    q[lo] = -self.rank_select(np.where(neg, -sd, 0.0), [ni - 1 - sranks[j] for j in lo], use=neg)["value"]
+                if hi:
+                    q[hi] = self.rank_select(np.where(use & ~neg, sd, 0.0), [sranks[j] - ni for j in hi], use=use & ~neg)["value"]
+                srep["quantile_signed"] = q
+            else:
+                srep["quantile_signed"] = np.zeros(len(probs), np.float64)
+            rep["signed"] = srep
         if sample_points > 0:
             self.mesh_sample(ME_SLOT_GT, sample_points, seed)
             self.nn1(ME_SLOT_EST, ME_SLOT_GT, fetch=False)

@@ -459,6 +459,8 @@ Param loadParametersFromYAML(const std::string &yaml_file_path) {
         param.mesh_sample_points = (int64_t) n;
     }
     if (config.has("mesh_seed")) as_u64("mesh_seed", param.mesh_seed);
+    if (config.has("mesh_signed")) param.mesh_signed = config.as_bool("mesh_signed");
+    if (param.mesh_signed && !param.evaluate_mesh_distance) throw std::runtime_error("mesh_signed: requires evaluate_mesh_distance: true");
     if (param.evaluate_mesh_distance) {
         if (mesh_not_a_list) throw std::runtime_error("mesh_thresholds: must be a list [a, b, ...]");
         if (param.gt_mesh_path.empty() && !(config.has("evaluate_mesh") && config.as_bool("evaluate_mesh")))
@@ -576,7 +578,8 @@ std::string paramToJson(const Param &p) {
     o << "], \"mesh_max_distance\": ";
     if (std::isinf(p.mesh_max_distance)) o << "Infinity";  // (what Python's json reads as inf)
     else o << p.mesh_max_distance;
-    o << ", \"mesh_sample_points\": " << p.mesh_sample_points << ", \"mesh_seed\": " << p.mesh_seed;
+    o << ", \"mesh_sample_points\": " << p.mesh_sample_points << ", \"mesh_seed\": " << p.mesh_seed
+      << ", \"mesh_signed\": " << b(p.mesh_signed);
     o << ", \"evaluate_mesh\": " << b(p.evaluate_mesh) << ", \"mesh_voxel_size\": " << p.mesh_voxel_size << ", \"mesh_radius\": " << p.mesh_radius
       << ", \"mesh_min_points\": " << p.mesh_min_points << ", \"mesh_band\": " << p.mesh_band << ", \"mesh_normal_radius\": "
       << p.mesh_normal_radius << ", \"mesh_viewpoint\": ";
@@ -1950,6 +1953,12 @@ int MapEval::computeMeshDistance() {
         if (me_rank_select(ctx_, d.data(), use.data(), (int64_t) n, mesh_rank.data(), (int32_t) nq, &rs) != ME_OK) return bad(me_last_error(ctx_));
         for (size_t j = 0; j < nq; ++j) mesh_quantile[j] = rs.value[j];
     }
+    if (param_.mesh_signed) {  // the sign everywhere, over the result above and under the same gate
+        me_mesh_sign_params sp{};
+        sp.max_distance = param_.mesh_max_distance;
+        if (me_mesh_topology(ctx_, &mesh_topo) != ME_OK || me_mesh_signed_distance(ctx_, ME_SLOT_EST, &sp, &mesh_sign) != ME_OK)
+            return fail(std::string("mesh_signed: ") + me_last_error(ctx_));
+    }
     if (param_.mesh_sample_points > 0) {
         if (me_mesh_sample(ctx_, ME_SLOT_GT, param_.mesh_sample_points, param_.mesh_seed) != ME_OK ||
             me_nn1(ctx_, ME_SLOT_EST, ME_SLOT_GT, nullptr, nullptr) != ME_OK || me_nn1(ctx_, ME_SLOT_GT, ME_SLOT_EST, nullptr, nullptr) != ME_OK)
@@ -2061,6 +2070,14 @@ void MapEval::saveMeshDistance() {
     for (size_t k = 0; k < param_.mesh_thresholds.size(); ++k)
         file_result << " " << param_.mesh_thresholds[k] << " " << (o.n_matched > 0 ? (double) o.n_within[k] / nm : 0.0);
     file_result << std::endl;
+    const me_mesh_sign_out &sg = mesh_sign;
+    if (param_.mesh_signed) {  // over the signed points: mean, mean |.|, inside share; over the matched ones: the unreliable share
+        const double ns = (double) sg.n_signed, nsm = (double) sg.n_matched;
+        file_result << std::fixed << std::setprecision(5) << "MeshSigned mean-meanabs-inside-unreliable: "
+                    << (sg.n_signed > 0 ? sg.sum_signed / ns : 0.0) << " " << (sg.n_signed > 0 ? sg.sum_abs_signed / ns : 0.0) << " "
+                    << (sg.n_signed > 0 ? (double) sg.n_inside / ns : 0.0) << " " << (sg.n_matched > 0 ? (double) sg.n_unreliable / nsm : 0.0)
+                    << std::endl;
+    }
     // mesh_distance.txt: the info block ("name value ..."), the parameters, the totals row
     //   totals n_query n_matched n_face sum_d sum_d2 max_d argmax
     // the signed bias over the face region `signed sum_signed sum_abs_signed mean mean_abs`, the rows `t threshold n_within`,
@@ -2092,6 +2109,27 @@ void MapEval::saveMeshDistance() {
                          (long long) mesh_sampled[s].n_used, mesh_sampled[s].sum_d, mesh_sampled[s].sum_d2, mesh_sampled[s].max_d);
         for (size_t k = 0; k < param_.mesh_thresholds.size(); ++k)
             std::fprintf(f, "f %.17g %.17g %.17g %.17g\n", param_.mesh_thresholds[k], mesh_prf[k][0], mesh_prf[k][1], mesh_prf[k][2]);
+    }
+    if (param_.mesh_signed) {
+        // with mesh_signed the topology block `topology <name> <count>` (me_mesh_topo_out's members in order) and the signed block:
+        //   sign counts n_matched n_signed n_inside n_outside n_on n_unsigned n_unreliable
+        //   sign regions n_face n_edge n_vertex
+        //   sign sums sum_signed sum_abs_signed sum_signed2
+        //   sign extremes min_signed argmin max_signed argmax
+        const me_mesh_topo_out &tp = mesh_topo;
+        std::fprintf(f, "topology n_edges %lld\ntopology n_boundary_edges %lld\ntopology n_nonmanifold_edges %lld\n"
+                        "topology n_inconsistent_edges %lld\ntopology n_zero_edges %lld\ntopology n_zero_vertices %lld\n"
+                        "topology n_tainted_vertices %lld\ntopology n_unreferenced_vertices %lld\ntopology closed %lld\n"
+                        "topology oriented_manifold %lld\n",
+                     (long long) tp.n_edges, (long long) tp.n_boundary_edges, (long long) tp.n_nonmanifold_edges,
+                     (long long) tp.n_inconsistent_edges, (long long) tp.n_zero_edges, (long long) tp.n_zero_vertices,
+                     (long long) tp.n_tainted_vertices, (long long) tp.n_unreferenced_vertices, (long long) tp.closed,
+                     (long long) tp.oriented_manifold);
+        std::fprintf(f, "sign counts %lld %lld %lld %lld %lld %lld %lld\n", (long long) sg.n_matched, (long long) sg.n_signed,
+                     (long long) sg.n_inside, (long long) sg.n_outside, (long long) sg.n_on, (long long) sg.n_unsigned, (long long) sg.n_unreliable);
+        std::fprintf(f, "sign regions %lld %lld %lld\n", (long long) sg.n_by_region[0], (long long) sg.n_by_region[1], (long long) sg.n_by_region[2]);
+        std::fprintf(f, "sign sums %.17g %.17g %.17g\n", sg.sum_signed, sg.sum_abs_signed, sg.sum_signed2);
+        std::fprintf(f, "sign extremes %.17g %lld %.17g %lld\n", sg.min_signed, (long long) sg.argmin, sg.max_signed, (long long) sg.argmax);
     }
     if (std::fclose(f) != 0) fail("writing " + path + " failed");
 }

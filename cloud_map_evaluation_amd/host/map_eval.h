@@ -168,6 +168,7 @@ struct Param {
     double mesh_max_distance = INFINITY;       // `mesh_max_distance:` matched iff d <= this; <= 0 or absent: every point
     int64_t mesh_sample_points = 0;            // `mesh_sample_points:` > 0: also the mesh sampled into the ground-truth slot, 1-NN both ways
     uint64_t mesh_seed = 0;                    // `mesh_seed:` the sampler's seed
+    bool mesh_signed = false;                  // `mesh_signed:` also the sign at edges and vertices (me_mesh_signed_distance; needs evaluate_mesh_distance)
     // surface reconstruction of both clouds (optional keys; the reference's createMeshFromPCD, map_eval.cpp:777-826, with the library's
     // IMLS field + marching tetrahedra instead of Poisson): radius normals turned towards a viewpoint on each cloud as loaded,
     // me_reconstruct, gt_mesh.ply / est_mesh.ply (the reference's names) and reconstruction.txt in the results folder (single GPU).
@@ -265,6 +266,8 @@ public:
     me_radius_normals_out m3c2_normals[2] = {};
     me_mesh_info_out mesh_info = {};            // evaluate_mesh_distance: the mesh, the totals, the quantiles of d, the sampled block
     me_mesh_out mesh_out = {};
+    me_mesh_topo_out mesh_topo = {};            // ... with mesh_signed: the mesh's connectivity and the signed totals
+    me_mesh_sign_out mesh_sign = {};
     std::vector<int64_t> mesh_rank;
     std::vector<double> mesh_quantile;
     me_errdist_out mesh_sampled[2] = {};        // ... with mesh_sample_points: 1-NN error of the map in the sample and the reverse

@@ -842,8 +842,9 @@ int me_m3c2_fetch(me_ctx *ctx, int query_slot, double *dist, double *lod, double
  *   Per query: the minimal d2; the triangle = the smallest caller index among the bitwise-minimal d2; that triangle's region and c.
  *   The search is unbounded and exact in this arithmetic (the tree only prunes what cannot win or tie).  Device timer "mesh_dist".
  *   SIGN.  Only in the face region: s = dot(p - c, n) / sqrt(dot(n, n)), n = (B-A) x (C-A) by the triangle's winding.  At an edge or a
- *   vertex a single face normal can name the wrong side of a non-convex mesh; angle-weighted pseudo-normals are not built: signed_d is
- *   NaN there and such points enter neither sum_signed nor sum_abs_signed.
+ *   vertex a single face normal can name the wrong side of a non-convex mesh: signed_d is NaN there and such points enter neither
+ *   sum_signed nor sum_abs_signed.  The sign at edges and vertices is me_mesh_signed_distance's (pseudo-normals, below); this call and
+ *   its fetch are unchanged by it.
  *   GATE.  A point is MATCHED iff d2 <= max_distance * max_distance (+inf: every point); only matched points enter the totals.
  *   n_within[k] counts the matched points with d2 <= thresholds[k] * thresholds[k].  max_d = the largest matched d = sqrt(d2), argmax its
  *   cloud-order index (ties -> the smaller index; -1 without a matched point).  n_face, sum_signed, sum_abs_signed over the matched points
@@ -883,6 +884,79 @@ int me_mesh_info(me_ctx *ctx, me_mesh_info_out *out);
 int me_mesh_distance(me_ctx *ctx, int query_slot, const me_mesh_params *p, me_mesh_out *out);
 int me_mesh_distance_fetch(me_ctx *ctx, int query_slot, double *d2, int32_t *tri, uint8_t *region, double *closest, double *signed_d);
 int me_mesh_sample(me_ctx *ctx, int dst_slot, int64_t n_points, uint64_t seed);
+
+/* ---- signed cloud-to-mesh distance everywhere: mesh connectivity, pseudo-normals at edges and vertices, the sign pass ------------------ */
+/*   Baerentzen and Aanaes (2005): for a closed, orientable, manifold mesh the sign of dot(p - c, N) is that of
+ * the side p lies on when N is chosen by the feature the closest point c lies on: the face normal in a face, the sum of the two incident
+ * face normals on an edge, the angle-weighted sum of the incident face normals at a vertex.  me_mesh_upload (and me_reconstruct_install,
+ * which is one) keeps the caller's int32 [n_triangles][3] index array on the device, 12 B per triangle.  VERTEX IDENTITY IS THE
+ * CALLER'S INDEX: two indices with equal coordinates are two vertices (weld triangle soup first).  Everything below is formed from the
+ * resident corners (after the upload's T) in fp64 without contraction, dot(u, v) = (u0*v0 + u1*v1) + u2*v2.  Single GPU only.
+ *
+ * me_mesh_topology: built on the device on first use and kept with the mesh; me_mesh_upload, me_mesh_clear and me_reconstruct_install
+ *   drop it.  Needs 3 * n_triangles < 2^32 (ME_ERR_ARG otherwise).  ME_ERR_STATE: no mesh.
+ *   FACE.  n = (B-A) x (C-A), each component u1*v2 - u2*v1; len = sqrt((nx*nx + ny*ny) + nz*nz); n^ = n / len per component.  A
+ *     degenerate triangle (n exactly zero, as the upload flags it) has no n^ and contributes nothing to any sum.
+ *   CORNER ANGLES.  ang_A = atan2(len, dot(B-A, C-A)), ang_B = atan2(len, dot(C-B, A-B)), ang_C = atan2(len, dot(A-C, B-C)).
+ *   EDGE {lo, hi} (undirected, by vertex index).  N_e = sum of n^ over the incident non-degenerate triangles in ascending caller triangle
+ *     index, a left-to-right fp64 sum.  m counts ALL incident triangles, degenerate ones included, except a triangle that names the same
+ *     vertex twice: such a triangle has no edges.  Flags: BOUNDARY m == 1; NONMANIFOLD m > 2; INCONSISTENT m == 2 and both triangles
+ *     traverse the edge in the same direction; ZERO N_e is exactly the zero vector or no incident triangle is non-degenerate.
+ *   VERTEX v.  N_v = sum of ang * n^ (each term ang * n^x, ang * n^y, ang * n^z) over the incident non-degenerate (triangle, corner) pairs
+ *     in ascending triangle index, then corner; a left-to-right sum.  Flags: ZERO as for edges; TAINTED any edge of an incident triangle
+ *     that ends in v carries BOUNDARY, NONMANIFOLD or INCONSISTENT.  A vertex no triangle names: zero normal, ZERO.
+ *   The 3T edge records (key lo, hi) and the 3T corner records (key v) are emitted in triangle order and sorted by the library's stable
+ *   radix sort ("sort" timer); one lane walks each run of equal keys serially.  Device timer "mesh_topology" covers the build's kernels.
+ *   me_mesh_topo_out: n_edges (unique), the edges per flag, n_zero_vertices (every vertex that carries ZERO, unreferenced ones included),
+ *   n_tainted_vertices, n_unreferenced_vertices, closed (no boundary edge), oriented_manifold (none of the three edge flags anywhere).
+ * me_mesh_topology_fetch: every pointer nullable.  vertex_normal [n_vertices][3], vertex_flags [n_vertices], edge_normal
+ *   [n_triangles][3][3] and edge_flags [n_triangles][3] per (triangle, local edge AB BC CA); a triangle without edges: zeros and ZERO.
+ *
+ * me_mesh_signed_distance: needs the slot's current me_mesh_distance result (ME_ERR_STATE otherwise, and without a mesh); builds the
+ *   topology if it is absent.  Per point, from the resident (d2, triangle, region, c): N = n (NOT normalised) of the winning triangle
+ *   for region 0, N_e of that triangle's edge for regions 1-3, N_v of that corner for regions 4-6; g = dot(p - c, N), p - c per component.
+ *       d2 == 0                        -> signed_d = +0.0, flag ON
+ *       the winning triangle is degenerate, or the feature carries ZERO -> NaN, flag UNSIGNED
+ *       g > 0 -> +sqrt(d2)    g < 0 -> -sqrt(d2)    else (g == 0 or NaN) -> NaN, flag UNSIGNED
+ *   UNRELIABLE: the feature carries BOUNDARY, NONMANIFOLD, INCONSISTENT or TAINTED (the theorem's preconditions fail there).  The
+ *   magnitude is the same sqrt(d2) in every region; across a shared edge N is the same vector whichever tied triangle won.
+ *   signed_d > 0 outside, as in me_mesh_distance.  Per-point values exist for every point; the TOTALS are over the MATCHED points,
+ *   d2 <= max_distance * max_distance (+inf: every point): n_signed = n_inside (signed_d < 0) + n_outside (> 0) + n_on; n_unsigned;
+ *   n_unreliable; n_by_region face / edge / vertex; sum_signed, sum_abs_signed, sum_signed2 = sum of signed_d * signed_d, over the signed
+ *   points; min_signed / argmin (the deepest inside point) and max_signed / argmax over the signed points, ties -> the smaller cloud
+ *   index, -1 (and 0.0) without one.  Sums as in me_mesh_distance: fixed tree, identical from run to run.  Device timer "mesh_sign".
+ *   ME_ERR_ARG: bad slot, NULL, max_distance negative or NaN, slab or shard mode.
+ * me_mesh_signed_fetch: signed_d[N] and flags[N] in cloud order, both nullable.  The result is discarded with the mesh-distance result
+ *   (a changed cloud, a new index, me_mesh_upload, me_mesh_clear, me_reconstruct_install) and by a new me_mesh_distance on the slot. */
+#define ME_MESH_TOPO_BOUNDARY 1
+#define ME_MESH_TOPO_NONMANIFOLD 2
+#define ME_MESH_TOPO_INCONSISTENT 4
+#define ME_MESH_TOPO_ZERO 8
+#define ME_MESH_TOPO_TAINTED 16
+#define ME_MESH_SIGN_ON 1
+#define ME_MESH_SIGN_UNSIGNED 2
+#define ME_MESH_SIGN_UNRELIABLE 4
+typedef struct me_mesh_topo_out {
+    int64_t n_edges, n_boundary_edges, n_nonmanifold_edges, n_inconsistent_edges, n_zero_edges;
+    int64_t n_zero_vertices, n_tainted_vertices, n_unreferenced_vertices;
+    int64_t closed, oriented_manifold;
+} me_mesh_topo_out;
+typedef struct me_mesh_sign_params {
+    double max_distance; /* >= 0, +inf allowed */
+} me_mesh_sign_params;
+typedef struct me_mesh_sign_out {
+    int64_t n_query, n_matched, n_signed, n_inside, n_outside, n_on, n_unsigned, n_unreliable;
+    int64_t n_by_region[3];
+    double sum_signed, sum_abs_signed, sum_signed2;
+    double min_signed;
+    int64_t argmin;
+    double max_signed;
+    int64_t argmax;
+} me_mesh_sign_out;
+int me_mesh_topology(me_ctx *ctx, me_mesh_topo_out *out);
+int me_mesh_topology_fetch(me_ctx *ctx, double *vertex_normal, uint8_t *vertex_flags, double *edge_normal, uint8_t *edge_flags);
+int me_mesh_signed_distance(me_ctx *ctx, int query_slot, const me_mesh_sign_params *p, me_mesh_sign_out *out);
+int me_mesh_signed_fetch(me_ctx *ctx, int query_slot, double *signed_d, uint8_t *flags);
 
 /* ---- surface reconstruction of a resident cloud into a triangle mesh ------------------------------------------------------------------ */
 /*   Stands in for the reference's createMeshFromPCD (map_eval.cpp:777-826, called at :194-205), a Poisson
