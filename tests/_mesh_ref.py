@@ -137,3 +137,34 @@ def sample(vertices, triangles, n_points, seed):
     r1, r2 = np.sqrt(P.u01(w[1])), P.u01(w[2])
     wa, wb, wc = (1.0 - r1)[:, None], (r1 * (1.0 - r2))[:, None], (r1 * r2)[:, None]
     return (wa * v[t, 0] + wb * v[t, 1]) + wc * v[t, 2], t
+
+
+MORTON_BITS = 21
+
+
+def _spread21(x):
+    out = np.zeros(len(x), np.uint64)
+    for b in range(MORTON_BITS):
+        out |= ((x >> np.uint64(b)) & np.uint64(1)) << np.uint64(3 * b)
+    return out
+
+
+def morton_codes(vertices, triangles):
+    """k_mesh_codes with the origin and the cell edge me_mesh_upload passes it: the Morton code of every triangle's centroid on the
+    2^21 lattice over the bounding box of the referenced vertices."""
+    v = np.asarray(vertices, np.float64)[np.asarray(triangles)]
+    corners = v.reshape(-1, 3)
+    lo, hi = corners.min(0), corners.max(0)
+    extent = float((hi - lo).max())
+    h = math.ldexp(extent, -MORTON_BITS) * (1.0 + 2.0 ** -20) if extent > 0 else 1.0
+    c = ((v[:, 0] + v[:, 1]) + v[:, 2]) / 3.0
+    g = np.fmin(np.fmax(np.floor((c - lo) / h), 0.0), 2097151.0).astype(np.uint64)
+    return _spread21(g[:, 0]) | (_spread21(g[:, 1]) << np.uint64(1)) | (_spread21(g[:, 2]) << np.uint64(2))
+
+
+def morton_rank(vertices, triangles):
+    """rank[t]: where the caller's triangle t stands after the upload's stable sort by Morton code (a leaf is 8 consecutive ranks)."""
+    order = np.argsort(morton_codes(vertices, triangles), kind="stable")
+    rank = np.empty(len(order), np.int64)
+    rank[order] = np.arange(len(order))
+    return rank

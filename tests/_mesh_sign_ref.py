@@ -297,3 +297,101 @@ def queries(vertices, triangles, n, seed, inflate=0.5):
     lo, hi = v.min(0), v.max(0)
     pad = inflate * float(np.linalg.norm(hi - lo))
     return np.random.default_rng(seed).uniform(lo - pad, hi + pad, size=(n, 3))
+
+
+# ---- the record lists of the topology build: k_topo_face's keys, the stable sorts, the serial walks of k_topo_edges / k_topo_verts ----
+def key_bits(nv):
+    """topo_build's `bits`: the smallest value with nv < 2^bits"""
+    bits = 1
+    while (1 << bits) <= nv:
+        bits += 1
+    return bits
+
+
+def edge_records(triangles, nv):
+    """(sorted keys, sorted values 3 t + e, no_edge, bits): the edge records of k_topo_face (key = lo << bits | hi, no_edge for a
+    triangle that names a vertex twice) after the stable sort over the low 2 * bits bits."""
+    tri = np.asarray(triangles, np.int64)
+    bits = key_bits(nv)
+    no_edge = (nv << bits) | nv
+    a, b = tri, np.roll(tri, -1, axis=1)
+    twice = (tri[:, 0] == tri[:, 1]) | (tri[:, 1] == tri[:, 2]) | (tri[:, 2] == tri[:, 0])
+    key = np.where(twice[:, None], no_edge, (np.minimum(a, b) << bits) | np.maximum(a, b)).reshape(-1)
+    order = np.argsort(key & ((1 << (2 * bits)) - 1), kind="stable")
+    return key[order], order, no_edge, bits
+
+
+def corner_records(triangles, nv):
+    """(sorted keys, sorted values 3 t + c): the corner records (key = vertex) after the stable sort over the low `bits` bits."""
+    key = np.asarray(triangles, np.int64).reshape(-1)
+    order = np.argsort(key & ((1 << key_bits(nv)) - 1), kind="stable")
+    return key[order], order
+
+
+def record_topology(vertices, triangles):
+    """me_mesh_topology the way the device builds it: from the sorted records, the head of every run walking its run.  The same dict
+    as topology() plus edge_runs / vertex_runs: (position of the head in the sorted list, run length, key) per run."""
+    tri = np.asarray(triangles, np.int64)
+    nv, nt = len(vertices), len(tri)
+    n3 = 3 * nt
+    n, nhat, ang, deg = faces(vertices, tri)
+    key, val, no_edge, _ = edge_records(tri, nv)
+    head = np.array([key[i] != no_edge and (i == 0 or key[i - 1] != key[i]) for i in range(n3)])
+    rank = np.cumsum(head) - head  # (the exclusive scan: the edge id)
+    n_edges = int(head.sum())
+    e_n, e_fl = np.zeros((max(n_edges, 1), 3)), np.zeros(max(n_edges, 1), np.uint8)
+    eid = -np.ones((nt, 3), np.int64)
+    edge_runs = []
+    for i in np.flatnonzero(head):
+        s, m, nf, dir0, same, j = np.zeros(3), 0, 0, False, False, int(i)
+        while j < n3 and key[j] == key[i]:
+            t, e = divmod(int(val[j]), 3)
+            d = bool(tri[t, e] < tri[t, (e + 1) % 3])
+            if m == 0:
+                dir0 = d
+            elif m == 1:
+                same = d == dir0
+            m += 1
+            if not deg[t]:
+                nf += 1
+                s = s + nhat[t]
+            eid[t, e] = rank[i]
+            j += 1
+        f = (BOUNDARY if m == 1 else 0) | (NONMANIFOLD if m > 2 else 0) | (INCONSISTENT if m == 2 and same else 0)
+        if nf == 0 or (s == 0.0).all():
+            f |= ZERO
+        e_n[rank[i]], e_fl[rank[i]] = s, f
+        edge_runs.append((int(i), m, int(key[i])))
+    vkey, vval = corner_records(tri, nv)
+    v_n, v_fl = np.zeros((nv, 3)), np.full(nv, ZERO, np.uint8)
+    referenced = np.zeros(nv, bool)
+    vertex_runs = []
+    for i in range(n3):
+        if i and vkey[i - 1] == vkey[i]:
+            continue
+        s, nf, bad, j = np.zeros(3), 0, 0, i
+        while j < n3 and vkey[j] == vkey[i]:
+            t, c = divmod(int(vval[j]), 3)
+            if not deg[t]:
+                nf += 1
+                s = s + ang[t, c] * nhat[t]
+            for e in (eid[t, c], eid[t, (c + 2) % 3]):
+                if e >= 0:
+                    bad |= int(e_fl[e])
+            j += 1
+        f = (ZERO if nf == 0 or (s == 0.0).all() else 0) | (TAINTED if bad & EDGE_BAD else 0)
+        v_n[vkey[i]], v_fl[vkey[i]], referenced[vkey[i]] = s, f, True
+        vertex_runs.append((i, j - i, int(vkey[i])))
+    fl = e_fl[:n_edges]
+    cnt = {
+        "n_edges": n_edges, "n_boundary_edges": int(((fl & BOUNDARY) != 0).sum()), "n_nonmanifold_edges": int(((fl & NONMANIFOLD) != 0).sum()),
+        "n_inconsistent_edges": int(((fl & INCONSISTENT) != 0).sum()), "n_zero_edges": int(((fl & ZERO) != 0).sum()),
+        "n_zero_vertices": int(((v_fl & ZERO) != 0).sum()), "n_tainted_vertices": int(((v_fl & TAINTED) != 0).sum()),
+        "n_unreferenced_vertices": int((~referenced).sum()),
+    }
+    cnt["closed"] = cnt["n_boundary_edges"] == 0
+    cnt["oriented_manifold"] = not (fl & EDGE_BAD).any()
+    te_n = np.where((eid >= 0)[..., None], e_n[np.maximum(eid, 0)], 0.0)
+    te_fl = np.where(eid >= 0, e_fl[np.maximum(eid, 0)], ZERO).astype(np.uint8)
+    return {"counts": cnt, "n": n, "deg": deg, "eid": eid, "edge_normal": te_n, "edge_flags": te_fl, "vertex_normal": v_n, "vertex_flags": v_fl,
+            "edge_runs": edge_runs, "vertex_runs": vertex_runs}
