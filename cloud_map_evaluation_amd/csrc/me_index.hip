@@ -963,7 +963,7 @@ int cloud_build_index(me_ctx *ctx, int slot, double cell_size) {
     ME_TRACE_POINT(ctx, slot == 0 ? "cloud_build_index(est): enter" : "cloud_build_index(gt): enter");
     if (!c.uploaded) return ctx->fail(ME_ERR_STATE, "cloud not uploaded");
     ME_CHECK(ctx, hipSetDevice(ctx->device));
-    c.cell_size_req = cell_size;
+    const double cell_size_asked = cell_size;
     const long long n = c.n;
     double extent = 0;
     for (int d = 0; d < 3; ++d) extent = std::fmax(extent, c.bbox_hi[d] - c.bbox_lo[d]);
@@ -973,14 +973,19 @@ int cloud_build_index(me_ctx *ctx, int slot, double cell_size) {
     // origin snapped to the global cell lattice: two clouds built with the same cell size get ALIGNED grids, so the
     // points of one cell of the query cloud fall into one cell of the reference cloud (the 1-NN grid pass groups
     // lanes by reference cell; with a common lattice a wave of curve-consecutive queries touches few of them)
-    for (int d = 0; d < 3; ++d) c.origin[d] = std::floor(c.bbox_lo[d] / cell_h) * cell_h;
+    double origin[3];
+    for (int d = 0; d < 3; ++d) origin[d] = std::floor(c.bbox_lo[d] / cell_h) * cell_h;
     extent = 0;
-    for (int d = 0; d < 3; ++d) extent = std::fmax(extent, c.bbox_hi[d] - c.origin[d]);
+    for (int d = 0; d < 3; ++d) extent = std::fmax(extent, c.bbox_hi[d] - origin[d]);
     const double ncell = std::floor(extent / cell_h) + 1.0;
     int bits_cell = 1;
     while ((double) (1LL << bits_cell) < ncell && bits_cell <= kMortonBits) ++bits_cell;
+    // a refused cell size touches nothing: the slot keeps its index, the frame (origin) that index was built in, and the cell size
+    // it was asked for, so that every pass and every later lazy rebuild works as before the call
     if (bits_cell > kMortonBits)
         return ctx->fail(ME_ERR_ARG, "cell size too small for the cloud extent (needs > 2^21 cells per axis)");
+    c.cell_size_req = cell_size_asked;
+    for (int d = 0; d < 3; ++d) c.origin[d] = origin[d];
     c.shift = kMortonBits - bits_cell;
     c.cell_h = cell_h;
     c.fine_h = std::ldexp(cell_h, -c.shift);

@@ -182,18 +182,21 @@ int m3c2(me_ctx *ctx, int qslot, const me_m3c2_params *p, const uint8_t *core_ma
     if (!q.have_normals)
         return ctx->fail(ME_ERR_STATE, "me_m3c2: the query cloud has no normals (me_set_normals / me_estimate_normals / me_radius_normals)");
     ME_CHECK(ctx, hipSetDevice(ctx->device));
-    q.m3c2_have = false;
     // both indexes at the level of the cylinder's bounding ball (run_local_geom's test): the 27-cell stencil is exact when the cell
     // edge is >= R.  A rebuild re-sorts the slot and drops the 1-NN results of both slots and the slot's local-geometry result.
+    // A refused R (more than 2^21 cells per axis) leaves that slot's index and everything resident on it as they were: the cell size
+    // asked for at the upload is put back before the error returns, and the query's earlier result is discarded only below.
     const double want_h = R * (1.0 + 0x1p-20);
     for (int s = 0; s < 2; ++s) {
         Cloud &c = ctx->cloud[s];
         if (!c.index_valid || c.cell_h < want_h || c.cell_h > 1.5 * want_h) {
             const double req = c.cell_size_req;
-            ME_TRY(cloud_build_index(ctx, s, R));
+            const int rc = cloud_build_index(ctx, s, R);
             c.cell_size_req = req;
+            if (rc != ME_OK) return rc;
         }
     }
+    q.m3c2_have = false;  // (from here on the slot's result buffers are rewritten)
     const long long n = q.n;
     ME_CHECK(ctx, q.m3_cnt.ensure((size_t) n * 2 * 4));
     ME_CHECK(ctx, q.m3_mom.ensure((size_t) n * 4 * 8));
