@@ -48,7 +48,7 @@ SYMBOLS = [
     "me_icp_lsq_sums_robust", "me_icp_information",
     "me_nn1", "me_icp_p2p_sums", "me_render_distance", "me_render_entropy", "me_nn_stats", "me_nn_partial_sums", "me_nn_sigma_sums", "me_nn_finalize", "me_chamfer",
     "me_mme", "me_voxel_gaussians", "me_voxel_metrics", "me_voxel_deformation", "me_voxel_deformation_fetch", "me_awd_scs", "me_w2_batch", "me_scs_table", "me_run_suite", "me_run_suite_from", "me_mme_fetch",
-    "me_set_voxel_hint", "me_timers_enable", "me_timers_reset", "me_timer_get",
+    "me_set_voxel_hint", "me_cell_table_fetch", "me_timers_enable", "me_timers_reset", "me_timer_get",
 ]
 
 
@@ -710,6 +710,8 @@ def load():
     L.me_mme_fetch.argtypes = [vp, C.c_int, dp, dp]
     L.me_w2_batch.argtypes = [vp, dp, dp, ip, dp, dp, ip, C.c_int64, dp]
     L.me_scs_table.argtypes = [vp, ip, dp, C.c_int64, C.c_int, C.POINTER(C.c_double)]
+    L.me_cell_table_fetch.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64), vp, vp, vp, vp]
+    L.me_cell_table_fetch.restype = C.c_int
     L.me_timers_enable.argtypes = [vp, C.c_int]
     L.me_timers_reset.argtypes = [vp]
     L.me_timer_get.argtypes = [vp, C.c_char_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]

@@ -924,6 +924,16 @@ int me_timers_enable(me_ctx *ctx, int on) {
     return ME_OK;
 }
 
+int me_cell_table_fetch(me_ctx *ctx, int slot, int which, int64_t *n_slots, int64_t *n_cells, uint64_t *hkeys, uint32_t *hvals,
+                        uint32_t *cell_start, void *entries) {
+    if (!ctx) return ME_ERR_ARG;
+    long long ns = 0, nc = 0;
+    const int rc = me::cell_table_fetch(ctx, slot, which, &ns, &nc, reinterpret_cast<unsigned long long *>(hkeys), hvals, cell_start, entries);
+    if (n_slots) *n_slots = ns;
+    if (n_cells) *n_cells = nc;
+    return rc;
+}
+
 int me_timers_reset(me_ctx *ctx) {
     if (!ctx) return ME_ERR_ARG;
     ctx->timers_collect();

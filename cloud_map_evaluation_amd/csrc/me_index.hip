@@ -545,7 +545,12 @@ k_block_counts(const unsigned int *__restrict__ block_hist, int nb, int level, u
 __global__ void __launch_bounds__(256)
 k_cell_fill(const unsigned long long *__restrict__ codes, long long n, int shift3, const unsigned int *__restrict__ block_off,
             long long n_cells, unsigned long long *__restrict__ cell_code, unsigned int *__restrict__ cell_start,
-            unsigned long long *__restrict__ hkeys, unsigned int *__restrict__ hvals, unsigned int hmask) {
+            unsigned long long *__restrict__ hkeys, unsigned int *__restrict__ hvals, unsigned int hmask, CellEntry *__restrict__ hent) {
+    // hent: the 16-byte record {key, start, count} of the cell in the slot its key won (wave_group_table<.., ENT> probes these alone).  The
+    // lane that finds a cell's start knows its END from the wave's own start flags (the next one, in its row or a later one); only the LAST
+    // cell of a wave's 512 points ends outside them, and that end is found once per wave, wave-uniformly (scalar loads): the codes are sorted,
+    // so the first point past the chunk with another cell code is found by doubling steps and bisection — a handful of loads for a cell of
+    // a few dozen points, log2(n) when one cell holds the cloud.
     static_assert(kCellChunk == 2048, "four wavefronts x eight rows of 64 points");
     __shared__ unsigned int s_w[4];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -569,6 +574,32 @@ k_cell_fill(const unsigned long long *__restrict__ codes, long long n, int shift
         wave_total += (unsigned int) __popcll(m[k]);
     }
     if (lane == 0) s_w[wv] = wave_total;
+    // end of the cell that starts in row k and has no later start in that row: nxt[k] (chunk-relative; 512 = the wave's last cell)
+    int nxt[8];
+    nxt[7] = 512;
+#pragma unroll
+    for (int k = 6; k >= 0; --k) nxt[k] = m[k + 1] ? 64 * (k + 1) + __ffsll((long long) m[k + 1]) - 1 : nxt[k + 1];
+    long long tail_end = n;  // where the wave's last cell ends
+    if (wave_total && w0 + 512 < n) {  // (wave-uniform; w0 + 512 < n: the chunk is full and the block's, so its last point is w0 + 511)
+        const long long ws = i0 + (long long) __builtin_amdgcn_readfirstlane(wv) * 512;  // (= w0, known to be wave-uniform)
+        const unsigned long long ct = codes[ws + 511] >> shift3;
+        long long lo = ws + 512, hi = n, step = 1;  // [.., lo) is the cell's, hi is not (or is n)
+        while (lo < hi) {
+            const long long p = lo + step - 1 < hi - 1 ? lo + step - 1 : hi - 1;
+            if ((codes[p] >> shift3) != ct) {
+                hi = p;
+                break;
+            }
+            lo = p + 1;
+            step <<= 1;
+        }
+        while (lo < hi) {
+            const long long mid = lo + ((hi - lo) >> 1);
+            if ((codes[mid] >> shift3) == ct) lo = mid + 1;
+            else hi = mid;
+        }
+        tail_end = lo;
+    }
     __syncthreads();
     unsigned int pos0 = block_off[blockIdx.x];
 #pragma unroll
@@ -579,12 +610,21 @@ k_cell_fill(const unsigned long long *__restrict__ codes, long long n, int shift
         if ((m[k] >> lane) & 1ULL) {
             const unsigned int pos = pos0 + (unsigned int) __popcll(m[k] & ((1ULL << lane) - 1ULL));
             cell_code[pos] = c[k];
-            cell_start[pos] = (unsigned int) (w0 + 64 * k + lane);
+            const unsigned int start = (unsigned int) (w0 + 64 * k + lane);
+            cell_start[pos] = start;
+            const unsigned long long above = m[k] & ~((2ULL << lane) - 1ULL);  // (lane 63: 2 << 63 wraps to 0, nothing above)
+            const int e = above ? 64 * k + __ffsll((long long) above) - 1 : nxt[k];
+            const unsigned int end = e < 512 ? (unsigned int) (w0 + e) : (unsigned int) tail_end;
             unsigned int sl = (unsigned int) hash_u64(c[k]) & hmask;  // (open addressing, linear probe: first free slot)
             for (;;) {
                 const unsigned long long prev = atomicCAS(&hkeys[sl], kEmptyKey, c[k]);
                 if (prev == kEmptyKey || prev == c[k]) {
                     hvals[sl] = pos;
+                    CellEntry ce;
+                    ce.key = c[k];
+                    ce.start = start;
+                    ce.count = end - start;
+                    hent[sl] = ce;
                     break;
                 }
                 sl = (sl + 1) & hmask;
@@ -613,18 +653,21 @@ static int build_grid_table_counted(me_ctx *ctx, Cloud &c, int shift, GridTable 
     ME_CHECK(ctx, t.cell_start.ensure((size_t) (n_cells + 1) * 4));
     unsigned long long hsize = 64;
     while (hsize < 2ULL * (unsigned long long) n_cells) hsize <<= 1;
-    ME_CHECK(ctx, t.hkeys.ensure((size_t) hsize * 8));
+    // (keys, then the 16-byte records of the same slots — hsize >= 64 keeps them 16-byte aligned: one buffer, ONE fill with the empty key)
+    ME_CHECK(ctx, t.hkeys.ensure((size_t) hsize * (8 + sizeof(CellEntry))));
     ME_CHECK(ctx, t.hvals.ensure((size_t) hsize * 4));
-    ME_CHECK(ctx, hipMemsetAsync(t.hkeys.p, 0xFF, (size_t) hsize * 8, ctx->stream));
+    ME_CHECK(ctx, hipMemsetAsync(t.hkeys.p, 0xFF, (size_t) hsize * (8 + sizeof(CellEntry)), ctx->stream));
+    CellEntry *hent = reinterpret_cast<CellEntry *>(t.hkeys.as<unsigned long long>() + hsize);
     hipLaunchKernelGGL(k_cell_fill, dim3((unsigned int) nblk), dim3(256), 0, ctx->stream, c.codes.as<unsigned long long>(), n, 3 * shift,
                        block_off, n_cells, t.cell_code.as<unsigned long long>(), t.cell_start.as<unsigned int>(), t.hkeys.as<unsigned long long>(),
-                       t.hvals.as<unsigned int>(), (unsigned int) (hsize - 1));
+                       t.hvals.as<unsigned int>(), (unsigned int) (hsize - 1), hent);
     t.shift = shift;
     g.cell_code = t.cell_code.as<unsigned long long>();
     g.cell_start = t.cell_start.as<unsigned int>();
     g.hkeys = t.hkeys.as<unsigned long long>();
     g.hvals = t.hvals.as<unsigned int>();
     g.hmask = (unsigned int) (hsize - 1);
+    g.hent = hent;
     g.n_cells = n_cells;
     g.shift = shift;
     return ME_OK;
@@ -1174,6 +1217,27 @@ int cloud_build_index(me_ctx *ctx, int slot, double cell_size) {
     ME_TRY(tail.end());
     c.index_valid = true;
     ME_TRACE_POINT(ctx, "cloud_build_index: done (host side)");
+    return ME_OK;
+}
+
+// me_cell_table_fetch (debug): one cell table of an indexed slot as it lies on the device — the hash slots of hkeys / hvals, the run starts
+// and the 16-byte records of the same slots.  which: 0 the radius grid, 1 the 1-NN grid.  Arrays may be NULL (sizes only).
+int cell_table_fetch(me_ctx *ctx, int slot, int which, long long *n_slots, long long *n_cells, unsigned long long *hkeys, unsigned int *hvals,
+                     unsigned int *cell_start, void *entries) {
+    if (slot < 0 || slot > 1 || which < 0 || which > 1) return ctx->fail(ME_ERR_ARG, "me_cell_table_fetch: bad slot or table");
+    Cloud &c = ctx->cloud[slot];
+    if (!c.uploaded || !c.index_valid) return ctx->fail(ME_ERR_STATE, "me_cell_table_fetch: the slot has no index");
+    const GridView &g = which == 0 ? c.grid : c.nn_grid;
+    if (!g.hent) return ctx->fail(ME_ERR_STATE, "me_cell_table_fetch: the slot has no cell table");
+    const size_t ns = (size_t) g.hmask + 1, nc = (size_t) g.n_cells;
+    if (n_slots) *n_slots = (long long) ns;
+    if (n_cells) *n_cells = (long long) nc;
+    ME_CHECK(ctx, hipSetDevice(ctx->device));
+    ME_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    if (hkeys) ME_CHECK(ctx, hipMemcpy(hkeys, g.hkeys, ns * 8, hipMemcpyDeviceToHost));
+    if (hvals) ME_CHECK(ctx, hipMemcpy(hvals, g.hvals, ns * 4, hipMemcpyDeviceToHost));
+    if (cell_start) ME_CHECK(ctx, hipMemcpy(cell_start, g.cell_start, (nc + 1) * 4, hipMemcpyDeviceToHost));
+    if (entries) ME_CHECK(ctx, hipMemcpy(entries, g.hent, ns * sizeof(CellEntry), hipMemcpyDeviceToHost));
     return ME_OK;
 }
 

@@ -105,10 +105,18 @@ struct GridView {
     unsigned int hmask;
     long long n_cells;
     int shift;                            // fine Morton code >> (3*shift) = cell code
+    const struct CellEntry *hent;         // the same table, slot for slot, as one 16-byte record per occupied cell
 };
+// One slot of GridView::hent: everything a probe of wave_group_table wants from hkeys[s] -> hvals[s] -> cell_start[ci], cell_start[ci + 1]
+// in ONE 16-byte load.  Same slot function, same linear probing, same empty key (an empty slot is all ones) as hkeys / hvals.
+struct alignas(16) CellEntry {
+    unsigned long long key;
+    unsigned int start, count;  // the cell's run of the sorted points
+};
+static_assert(sizeof(CellEntry) == 16, "one global_load_dwordx4 per probe");
 
 struct GridTable {
-    DevBuf cell_code, cell_start, hkeys, hvals;
+    DevBuf cell_code, cell_start, hkeys, hvals;  // (hkeys: the keys, then — 16-byte aligned — the CellEntry table: one fill for both)
     int shift = -1;
 };
 
@@ -577,6 +585,8 @@ int cloud_upload(me_ctx *ctx, int slot, const double *src, bool src_on_device, l
                  double cell_size, bool prefiltered = false);
 int cloud_build_index(me_ctx *ctx, int slot, double cell_size);
 int cloud_finish_octree(me_ctx *ctx, int slot);
+int cell_table_fetch(me_ctx *ctx, int slot, int which, long long *n_slots, long long *n_cells, unsigned long long *hkeys, unsigned int *hvals,
+                     unsigned int *cell_start, void *entries);
 int cloud_finish(me_ctx *ctx, int slot, bool bbox_ready = false);
 // the two lists of "this result is current" flags that every reset site clears: what goes with the slot's sorted order (every index
 // rebuild), and what goes with its points (the former included); normals and covariances stay with the caller
@@ -1004,7 +1014,63 @@ constexpr int kGroupTab2 = (2 * kGroupR + 5) * (2 * kGroupR + 5) * (2 * kGroupR 
 // passes of the MME kernel (a (2R+1+2H)^3 = 125-entry table).
 // `tabc` / `cell_aux` (optional, both or neither): tabc[slot] = cell_aux[cell index] for every non-empty slot — a second per-cell
 // array looked up with the same probe (the matrix-pipe MME kernel keeps the first feature chunk of every cell there).
-template <int H = 1, bool CULL = false, int R = kGroupR, bool MLP = false>
+// ENT (the two stream kernels, k_mme3 and k_nn_grid; needs H = 1, R <= 2, CULL, no tabc): the same table, slot for slot — same box, same
+// slot order t = tx + nx * (ty + ny * tz), same runs — from fewer vector instructions.  What a slot cost before (two integer divisions and
+// a modulo by the box extents, three spread21 of 64-bit values, six bounds compares, then hkeys[s] -> hvals[s] -> cell_start[ci],
+// cell_start[ci + 1]) is moved to where it is paid once per ROUND or not at all:
+//   * t / nx and q / ny are multiply-shifts with ceil(2^14 / n), n <= 7 (exact for every t < 5461: recip14_exact below);
+//   * the lanes that dilate the cull's row masks (one per (ty, tz) row of the box, <= 49) also store their row's part of the key,
+//     spread21(y) << 1 | spread21(z) << 2, and clear the mask bits of cells outside the lattice (the whole row when y or z is);
+//     nx lanes store spread21(x).  A slot's key is then two LDS reads and an OR, its bounds test the cull bit it tested anyway;
+//   * the probe reads GridView::hent: one 16-byte load per slot gives key, start and count.
+// PRECONDITION of ENT: the cell (cx, cy, cz) of every PENDING lane lies inside the lattice, 0 <= c < cell_lim per axis (both callers
+// derive it from a code of the grid or skip queries outside it), so that x0 >= -1 and x0 + nx <= cell_lim + 1 and the shifts of the
+// bounds mask are in range; the other path tolerates cells outside the lattice through its per-slot compares, this one does not.
+// `rows` must hold kGroupRowsEnt ints.  hash_u64 stays (it decides where every cell lives): its two 64 x 64 multiplies by constants
+// compile to v_mul_lo_u32 / v_mul_hi_u32 / v_mad_u64_u32 chains of three to four instructions each.
+__host__ __device__ constexpr unsigned int recip14(int n) {  // ceil(2^14 / n), 1 <= n <= 7, from two packed constants (scalar shifts, no table)
+    return (unsigned int) (((n < 4 ? 0x1556200040000000ULL : 0x09250AAB0CCD1000ULL) >> (16 * (n & 3))) & 0xffffULL);
+}
+constexpr bool recip14_exact() {
+    for (int n = 1; n <= 7; ++n)
+        for (unsigned int t = 0; t < 5461; ++t)
+            if (((t * recip14(n)) >> 14) != t / (unsigned int) n) return false;
+    return true;
+}
+static_assert(recip14_exact(), "t / n as (t * recip14(n)) >> 14");
+// spread21 from two 32-bit halves (bits 0..9 and 10..20): the same value from 32-bit shifts and masks, a third of the instructions and
+// half the registers of the 64-bit ladder
+__host__ __device__ constexpr unsigned int spread11_32(unsigned int x) {  // bit i of the low 11 -> bit 3 i
+    x = (x | x << 16) & 0x070000ffu;
+    x = (x | x << 8) & 0x0700f00fu;
+    x = (x | x << 4) & 0x430c30c3u;
+    x = (x | x << 2) & 0x49249249u;
+    return x;
+}
+__host__ __device__ constexpr unsigned long long spread21_halves(unsigned int x) {
+    return (unsigned long long) spread11_32(x & 0x3ffu) | ((unsigned long long) spread11_32((x >> 10) & 0x7ffu) << 30);
+}
+constexpr unsigned long long spread21_ladder(unsigned long long x) {  // (spread21 above, as a constant expression)
+    x &= 0x1fffffULL;
+    x = (x | x << 32) & 0x1f00000000ffffULL;
+    x = (x | x << 16) & 0x1f0000ff0000ffULL;
+    x = (x | x << 8) & 0x100f00f00f00f00fULL;
+    x = (x | x << 4) & 0x10c30c30c30c30c3ULL;
+    x = (x | x << 2) & 0x1249249249249249ULL;
+    return x;
+}
+constexpr bool spread21_halves_exact() {  // every single bit, every run of ones from bit 0 and to bit 20, and a stride through the rest
+    for (unsigned int i = 0; i < 21; ++i) {
+        const unsigned int a = 1u << i, b = (2u << i) - 1u, c = 0x1fffffu & ~(a - 1u);
+        if (spread21_halves(a) != spread21_ladder(a) || spread21_halves(b) != spread21_ladder(b) || spread21_halves(c) != spread21_ladder(c)) return false;
+    }
+    for (unsigned int x = 0; x < 0x200000u; x += 4099u)
+        if (spread21_halves(x) != spread21_ladder(x)) return false;
+    return true;
+}
+static_assert(spread21_halves_exact(), "spread21 from 32-bit halves");
+constexpr int kGroupRowsEnt = 240;  // LDS ints per wave with ENT: the 128 of the cull, 49 row keys and 7 x keys of 8 bytes
+template <int H = 1, bool CULL = false, int R = kGroupR, bool MLP = false, bool ENT = false>
 __device__ __forceinline__ bool wave_group_table(bool pending, int cx, int cy, int cz, const GridView &g, int cell_lim,
                                                  int lane, int2 *tab, GroupBox &box, int *n_keys_out = nullptr,
                                                  unsigned int *rows = nullptr, unsigned short *tcell = nullptr,
@@ -1065,6 +1131,9 @@ __device__ __forceinline__ bool wave_group_table(bool pending, int cx, int cy, i
     box.z0 = z0;
     box.nx = nx;
     box.ny = ny;
+    static_assert(!ENT || (H == 1 && R <= 2 && CULL && !MLP), "ENT: the <= 7 x 7 x 7 box of the stream kernels, with the cull");
+    const unsigned int mx = ENT ? recip14(nx) : 0u, my = ENT ? recip14(ny) : 0u;  // (scalar)
+    unsigned long long *ykey = ENT ? reinterpret_cast<unsigned long long *>(rows + 128) : nullptr, *xkey = ENT ? ykey + 49 : nullptr;
     if (CULL) {
         const int n_rows = ny * nz;  // <= 49 (H = 1)
         if (lane < n_rows) rows[lane] = 0u;
@@ -1074,7 +1143,7 @@ __device__ __forceinline__ bool wave_group_table(bool pending, int cx, int cy, i
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         __builtin_amdgcn_wave_barrier();
         if (lane < n_rows) {
-            const int ry = lane % ny, rz = lane / ny;
+            const int rz = ENT ? (int) (((unsigned int) lane * my) >> 14) : lane / ny, ry = lane - rz * ny;
             unsigned int m = 0;
             for (int dz = -H; dz <= H; ++dz)
                 for (int dy = -H; dy <= H; ++dy) {
@@ -1084,8 +1153,17 @@ __device__ __forceinline__ bool wave_group_table(bool pending, int cx, int cy, i
             unsigned int d = m;
 #pragma unroll
             for (int s = 1; s <= H; ++s) d |= (m << s) | (m >> s);
+            if (ENT) {
+                // cells outside the lattice [0, cell_lim)^3 are dropped here, once per row, not per slot: x by a wave-uniform bit mask
+                // (x0 >= -1 and x0 + nx <= cell_lim + 1: both shifts are in range), y and z by the row
+                const int iy = y0 + ry, iz = z0 + rz;
+                const unsigned int okx = ((1u << (cell_lim - x0 < nx ? cell_lim - x0 : nx)) - 1u) & ~((1u << (x0 < 0 ? -x0 : 0)) - 1u);
+                d = (iy >= 0 && iy < cell_lim && iz >= 0 && iz < cell_lim) ? d & okx : 0u;
+                ykey[lane] = (spread21_halves((unsigned int) iy & 0x1fffffu) << 1) | (spread21_halves((unsigned int) iz & 0x1fffffu) << 2);
+            }
             rows[64 + lane] = d;
         }
+        if (ENT && lane < nx) xkey[lane] = spread21_halves((unsigned int) (x0 + lane) & 0x1fffffu);  // (a column outside the lattice: never read)
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         __builtin_amdgcn_wave_barrier();
     }
@@ -1141,6 +1219,31 @@ __device__ __forceinline__ bool wave_group_table(bool pending, int cx, int cy, i
             if (t < n_keys) {
                 tab[t] = make_int2((int) cs0[i], (int) (cs1[i] - cs0[i]));
                 if (tabc) tabc[t] = ax[i];
+            }
+        }
+    } else if (ENT) {
+        for (int t = lane; t < n_keys; t += 64) {
+            const unsigned int q = ((unsigned int) t * mx) >> 14, tx = (unsigned int) t - q * (unsigned int) nx;  // q = ty + ny * tz: the slot's row
+            int2 run = make_int2(0, 0);
+            if ((rows[64 + q] >> tx) & 1u) {
+                const unsigned long long key = ykey[q] | xkey[tx];
+                unsigned int s = (unsigned int) hash_u64(key) & g.hmask;
+                for (;;) {  // (collisions: linear probing, rare)
+                    uint4 e = *reinterpret_cast<const uint4 *>(g.hent + s);
+                    asm volatile("" : "+v"(e.x), "+v"(e.y), "+v"(e.z), "+v"(e.w));  // (ONE 16-byte load, not the key first and the run after it)
+                    const unsigned long long k = ((unsigned long long) e.y << 32) | e.x;
+                    if (k == key) {
+                        run = make_int2((int) e.z, (int) e.w);
+                        break;
+                    }
+                    if (k == kEmptyKey) break;
+                    s = (s + 1) & g.hmask;
+                }
+            }
+            tab[t] = run;
+            if (tcell) {
+                const unsigned int tz = (q * my) >> 14, ty = q - tz * (unsigned int) ny;
+                tcell[t] = (unsigned short) (tx | (ty << 3) | (tz << 6));
             }
         }
     } else

@@ -14,7 +14,9 @@
 //     k, sum(u), sum(u u^T) accumulated straight from the tile (the covariance is translation-invariant; the sums start at minus
 //     the lane's own contribution: the element the reference erases at :1672-1673).
 // The kernel is bound by vector instruction issue (96 % busy: profiles/r04_mme3_c4_sq_per_wave.json): 57 VGPRs, eight waves per
-// SIMD, no scratch; per step on the 50 M + 50 M pair (ME_MME_DBG builds, round 6) table + prologue + epilogue 3.3 ms, staging 4.7
+// SIMD, no scratch (59 VGPRs since the round's table reads the 16-byte cell records: ~362 vector instructions per 343-slot table
+// instead of ~1 065, profiles/EXPERIMENTS.md "Round 8"; `make resources` prints the figures); per step on the 50 M + 50 M pair
+// (ME_MME_DBG builds, round 6, with the table as it was then) table + prologue + epilogue 3.3 ms, staging 4.7
 // (hidden by the other waves in the full kernel: prefetching the next chunk made it slower), the pre-test 6.7, the accumulation —
 // nine fp64 instructions for every candidate SOME lane accepts, at 12 - 17 % lane efficiency — 8.4.  What was measured and dropped
 // (a per-lane walk, half-radius cells, sub-wave groups, scalar-cache delivery, readlane broadcasts, per-lane compaction, streaming
@@ -111,7 +113,7 @@ k_mme3(const SPoint *__restrict__ sp, const unsigned long long *__restrict__ cod
     // cell_h = edge of a radius-grid cell; thr_lo / thr_hi = r^2 -+ E in FP32 (E = 2^-12 cell_h^2): kernel arguments, i.e.
     // scalar registers for the whole kernel (computed in the kernel they lived in VGPRs and were spilled around the loop).
     // dbg: profiling switches (profiles/README.md) — 1: no candidate streaming at all, 2: pre-test only, nothing accepted, 3: staging only.
-    static_assert(TILE * 16 >= kGroupRows * 4, "the row masks of the cull alias the tile");
+    static_assert(TILE * sizeof(MmeTileRec) >= kGroupRowsEnt * 4, "the row masks and keys of the round's table alias the tile");
     (void) fr;
     (void) cell_h;
     const unsigned int vb = xcd_virtual_block(blockIdx.x, gridDim.x, xcd_chunk);
@@ -164,7 +166,7 @@ k_mme3(const SPoint *__restrict__ sp, const unsigned long long *__restrict__ cod
         GroupBox bx;
         int nk = 0, leader = 0;
         const int cx = (int) compact21(mycell), cy = (int) compact21(mycell >> 1), cz = (int) compact21(mycell >> 2);
-        const bool in = wave_group_table<1, true>(!done, cx, cy, cz, g, cell_lim, lane, tab, bx, &nk, reinterpret_cast<unsigned int *>(trec),
+        const bool in = wave_group_table<1, true, kGroupR, false, true>(!done, cx, cy, cz, g, cell_lim, lane, tab, bx, &nk, reinterpret_cast<unsigned int *>(trec),
                                                   nullptr, nullptr, nullptr, &leader);
         // Round origin o = the group LEADER'S POINT, wave-uniform in scalar registers.  Both the FP32 record and the fp64
         // coordinates of a staged candidate are taken relative to it ONCE, by the lane that loads the candidate: u = p - o.  The

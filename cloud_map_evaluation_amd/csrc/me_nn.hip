@@ -119,6 +119,7 @@ k_nn_grid(const SPoint *__restrict__ qsp, long long q_begin, long long q_end, co
     const int cell_lim = 1 << cell_bits;
     const double cell_h = ldexp(fr.fine_h, g.shift);
     __shared__ float4 s_tile[4][64];  // (doubles as the row masks of the adjacency cull while a round's table is built)
+    static_assert(sizeof(s_tile[0]) >= kGroupRowsEnt * 4, "the row masks and keys of the round's table alias the wave's tile");
     __shared__ int2 s_tab[4][kGroupTab + 1];
     // (list positions and the offsets of a pass are 32-bit — a cloud holds < 2^31 points —: the 64-bit forms cost the list pass, whose
     // loop keeps them alive across a whole round, 12 bytes of scratch per lane)
@@ -139,13 +140,15 @@ k_nn_grid(const SPoint *__restrict__ qsp, long long q_begin, long long q_end, co
     int mcx = 0, mcy = 0, mcz = 0;  // the query's cell in the REFERENCE cloud's grid
     bool in_grid = false;
     if (active) {
-        const SPoint q = qsp[q_begin + (long long) qoff];
+        unsigned int qo = qoff;
+        asm volatile("" : "+v"(qo));  // (the 64-bit index is rebuilt at every use, here too: carried, it is spilled across the kernel)
+        const SPoint q = qsp[q_begin + (long long) qo];
         qx = q.x;
         qy = q.y;
         qz = q.z;
         if (!FROM_LIST && !slab_owned(slab, qx, qy, qz)) {  // halo point: a reference for others, not a query of this rank
-            d2_out[q_begin + (long long) qoff] = -1.0;                 // skip marker for the statistics kernels
-            idx_out[q_begin + (long long) qoff] = -1;
+            d2_out[q_begin + (long long) qo] = -1.0;                   // skip marker for the statistics kernels
+            idx_out[q_begin + (long long) qo] = -1;
             active = false;
         }
     }
@@ -289,7 +292,7 @@ k_nn_grid(const SPoint *__restrict__ qsp, long long q_begin, long long q_end, co
         GroupBox bx;
         int nk = 0;
         // (cull: a run adjacent to no lane of the group is in nobody's 3x3x3 block, so nobody's resolution test needs it)
-        const bool in = wave_group_table<1, true>(!done, mcx, mcy, mcz, g, cell_lim, lane, tab, bx, &nk,
+        const bool in = wave_group_table<1, true, kGroupR, false, true>(!done, mcx, mcy, mcz, g, cell_lim, lane, tab, bx, &nk,
                                                   reinterpret_cast<unsigned int *>(tile));
         ox = uniform_f64(fr.ox + (double) bx.x0 * cell_h);  // (scalar registers: wave-uniform)
         oy = uniform_f64(fr.oy + (double) bx.y0 * cell_h);
@@ -404,8 +407,10 @@ k_nn_grid(const SPoint *__restrict__ qsp, long long q_begin, long long q_end, co
             gmin *= (1.0 - 1e-9);  // rounding slack of the cell assignment
             unresolved = !(gmin > 0.0 && best_x < gmin * gmin);
         }
-        d2_out[q_begin + (long long) qoff] = best_x;  // final if resolved, initial bound otherwise
-        idx_out[q_begin + (long long) qoff] = (j1 >= 0) ? (int) best_i : -1;
+        unsigned int qo = qoff;
+        asm volatile("" : "+v"(qo));
+        d2_out[q_begin + (long long) qo] = best_x;  // final if resolved, initial bound otherwise
+        idx_out[q_begin + (long long) qo] = (j1 >= 0) ? (int) best_i : -1;
     }
     if (ME_NN_DBG) unresolved = false;  // (measurement builds: nothing goes to the octree pass)
     if (!FROM_LIST && flag_out) {

@@ -1749,6 +1749,19 @@ class Engine:
         self._ck(self._L.me_mme_fetch(self._ctx, slot, _addr(ent), _addr(val)))
         return ent, val
 
+    def cell_table(self, slot: int, which: int):
+        """me_cell_table_fetch (debug): (hkeys[S], hvals[S], cell_start[C + 1], entries[S]) of the slot's radius (which = 0) or 1-NN
+        (which = 1) cell table; entries is a record array with fields key, start, count."""
+        ns, nc = C.c_int64(), C.c_int64()
+        self._ck(self._L.me_cell_table_fetch(self._ctx, slot, which, C.byref(ns), C.byref(nc), None, None, None, None))
+        hkeys = np.zeros(ns.value, np.uint64)
+        hvals = np.zeros(ns.value, np.uint32)
+        cell_start = np.zeros(nc.value + 1, np.uint32)
+        ent = np.zeros(ns.value, np.dtype([("key", "<u8"), ("start", "<u4"), ("count", "<u4")]))
+        self._ck(self._L.me_cell_table_fetch(self._ctx, slot, which, C.byref(ns), C.byref(nc), _addr(hkeys), _addr(hvals), _addr(cell_start),
+                                              _addr(ent)))
+        return hkeys, hvals, cell_start, ent
+
     # ---- instrumentation ----
     def timers_enable(self, on: bool = True):
         self._ck(self._L.me_timers_enable(self._ctx, int(on)))

@@ -1434,6 +1434,13 @@ int me_run_suite_from(me_ctx *ctx, const double *est, int64_t n_est, const doubl
  * recomputed two-pass about the query itself; counted whether or not timers are on), "nn_queries" / "nn_fallback_queries" (1-NN queries, and those that needed the
  * octree pass), "nn1_opened" / "nn1_scans" / "nn1_points" / "nn1_max_opened" (octree walk: nodes opened, leaf cells and points
  * scanned, the longest chain of one query in the octet walk), "nn1_far" (walks handed over to the wave-per-query kernel). */
+/* Debug: one cell table of an indexed slot as it lies on the device (which: 0 the radius grid, 1 the 1-NN grid).  *n_slots = size of the
+ * open-addressing table, *n_cells = occupied cells; hkeys[n_slots] (empty = all ones), hvals[n_slots] (cell index; undefined in empty
+ * slots), cell_start[n_cells + 1] (runs of the sorted points) and entries[n_slots] x 16 bytes {uint64 key; uint32 start; uint32 count}:
+ * the record of the same slot that the per-round tables of the radius and 1-NN kernels probe.  Any array may be NULL (sizes only).
+ * ME_ERR_STATE without an index. */
+int me_cell_table_fetch(me_ctx *ctx, int slot, int which, int64_t *n_slots, int64_t *n_cells, uint64_t *hkeys, uint32_t *hvals,
+                        uint32_t *cell_start, void *entries);
 int me_timers_enable(me_ctx *ctx, int on);
 int me_timers_reset(me_ctx *ctx);
 int me_timer_get(me_ctx *ctx, const char *name, double *total_ms, int64_t *launches);
