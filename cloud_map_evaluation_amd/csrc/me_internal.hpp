@@ -1304,6 +1304,46 @@ __device__ __forceinline__ void wave_for_each_run(const int2 *tab, int n_keys, i
         }
     }
 }
+
+// inclusive prefix sum over the 64 lanes of a wave: four DPP row shifts (zero fill) sum every row of 16 lanes, three readlanes and
+// scalar additions give the rows their bases; *total (wave-uniform, scalar) = the sum over all lanes
+__device__ __forceinline__ int wave_incl_scan_i(int v, int lane, int *total) {
+    v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xF, 0xF, true);  // row_shr:1
+    v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xF, 0xF, true);  // row_shr:2
+    v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xF, 0xF, true);  // row_shr:4
+    v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xF, 0xF, true);  // row_shr:8
+    const int t0 = __builtin_amdgcn_readlane(v, 15), t1 = t0 + __builtin_amdgcn_readlane(v, 31), t2 = t1 + __builtin_amdgcn_readlane(v, 47);
+    *total = t2 + __builtin_amdgcn_readlane(v, 63);
+    return v + (lane < 32 ? (lane < 16 ? 0 : t0) : (lane < 48 ? t1 : t2));
+}
+
+// The round's table as a RUN LIST, in place: the non-empty slots of tab[0 .. n_keys) compacted in slot order — the order in which
+// wave_for_each_run hands them out — into tab[i] = {start of run i in the sorted array, offset of run i in the round's candidate
+// stream} (an exclusive prefix of the counts), i < *n_runs, closed by tab[*n_runs] = {0, stream length}: `tab` holds kGroupTab + 1
+// entries.  Batch by batch: all 64 slots of a batch are read before any is written, and the writes go to indices no higher than the
+// slots read so far.  Returns the stream's length; it and *n_runs are wave-uniform (scalar).
+__device__ __forceinline__ int wave_run_list(int2 *tab, int n_keys, int lane, int *n_runs) {
+    int nr = 0, total = 0;
+    for (int base = 0; base < n_keys; base += 64) {
+        const int t = base + lane;
+        int2 run = make_int2(0, 0);
+        if (t < n_keys) run = tab[t];
+        const unsigned long long m = __ballot(run.y > 0);
+        int batch = 0;
+        const int incl = wave_incl_scan_i(run.y, lane, &batch);  // (empty and culled slots count 0)
+        const int rank = (int) __builtin_amdgcn_mbcnt_hi((unsigned int) (m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned int) m, 0u));
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        if (run.y > 0) tab[nr + rank] = make_int2(run.x, total + incl - run.y);  // nr + rank <= t
+        nr += __popcll(m);
+        total += batch;
+    }
+    if (lane == 0) tab[nr] = make_int2(0, total);  // nr <= n_keys <= kGroupTab
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    *n_runs = nr;
+    return total;
+}
 #endif
 
 }  // namespace me

@@ -8,14 +8,16 @@
 //   * groups the lanes whose cell is within Chebyshev distance 2 of a leader's (the best of five candidates along the pending
 //     stretch; normally the whole wave) and resolves the group's cell box grown by one with one hash probe per (lane, slot) into a
 //     wave-private LDS run table, runs adjacent to no lane of the group culled (wave_group_table<1, true>),
-//   * stages every run ONCE through a wave-private LDS tile — one coalesced vector load per 32 points, the staging lane storing an
+//   * stages the runs, flattened into ONE candidate stream (wave_run_list; chunks of 48 positions whatever run they fall into), ONCE
+//     through a wave-private LDS tile — one vector load per 48 candidates, the staging lane storing an
 //     FP32 record (p', |p'|^2) and u = p - o in fp64, o = the leader's point — and reads it back with broadcast ds_reads, every
 //     group lane testing the candidate against its own query: an FP32 pre-test with an exact fp64 band (k_mme3 below), then
 //     k, sum(u), sum(u u^T) accumulated straight from the tile (the covariance is translation-invariant; the sums start at minus
 //     the lane's own contribution: the element the reference erases at :1672-1673).
 // The kernel is bound by vector instruction issue (96 % busy: profiles/r04_mme3_c4_sq_per_wave.json): 57 VGPRs, eight waves per
 // SIMD, no scratch (59 VGPRs since the round's table reads the 16-byte cell records: ~362 vector instructions per 343-slot table
-// instead of ~1 065, profiles/EXPERIMENTS.md "Round 8"; `make resources` prints the figures); per step on the 50 M + 50 M pair
+// instead of ~1 065, profiles/EXPERIMENTS.md "Round 8"; 64 with the flattened stream of "Round 9"; `make resources` prints the
+// figures); per step on the 50 M + 50 M pair
 // (ME_MME_DBG builds, round 6, with the table as it was then) table + prologue + epilogue 3.3 ms, staging 4.7
 // (hidden by the other waves in the full kernel: prefetching the next chunk made it slower), the pre-test 6.7, the accumulation —
 // nine fp64 instructions for every candidate SOME lane accepts, at 12 - 17 % lane efficiency — 8.4.  What was measured and dropped
@@ -59,7 +61,8 @@ struct alignas(16) MmeTileRec {
     float4 f;    // (p'x, p'y, p'z, |p'|^2) in FP32, p' = p - o
     double2 xy;  // u = p - o in fp64
     double z;
-    double pad;
+    int gi;      // the candidate's position in `sp` (the exact band test loads the point from there)
+    int pad;
 };
 static_assert(sizeof(MmeTileRec) == 48, "tile record layout");
 // LDS load through a 32-bit LDS byte address held in a vector register
@@ -150,6 +153,8 @@ k_mme3(const SPoint *__restrict__ sp, const unsigned long long *__restrict__ cod
     const int wv = __builtin_amdgcn_readfirstlane((int) (threadIdx.x >> 6));  // scalar: the wave's LDS bases stay out of VGPRs
     int2 *tab = s_tab[wv];
     MmeTileRec *trec = s_rec[wv];
+    __shared__ unsigned int s_head[4][2];  // per wave: which positions of the chunk being staged begin a run (bit d: position d + 1)
+    unsigned int *head = s_head[wv];
     const unsigned int trec_lds = (unsigned int) (size_t) trec;  // LDS byte address of the wave's tile (flat -> local: the low 32 bits)
     const int lane = threadIdx.x & 63;
 
@@ -206,7 +211,7 @@ k_mme3(const SPoint *__restrict__ sp, const unsigned long long *__restrict__ cod
 #ifdef ME_MME_STATS
         int st_cand = 0;
 #endif
-        auto test = [&](const float4 &c, unsigned int ra, int gj) {  // ra: LDS address of the tile record, gj: the candidate's position in `sp`
+        auto test = [&](const float4 &c, unsigned int ra) {  // ra: LDS address of the tile record
             const float u = fmaf(c.x, ax, fmaf(c.y, ay, fmaf(c.z, az, c.w)));
             const bool hi = u < t_hi;
             const unsigned long long mh = __ballot(hi);
@@ -220,7 +225,7 @@ k_mme3(const SPoint *__restrict__ sp, const unsigned long long *__restrict__ cod
                     unsigned int loc_b = loc;
                     asm volatile("" : "+v"(loc_b));
                     const SPoint qe = sp[i_begin + (long long) loc_b];
-                    const SPoint pe = sp[gj];
+                    const SPoint pe = sp[lds_load<int>(ra + 40)];  // MmeTileRec::gi
                     const double ex = pe.x - qe.x, ey = pe.y - qe.y, ez = pe.z - qe.z;
                     const double d2 = (ex * ex + ey * ey) + ez * ez;
                     acc = acc || (hi && d2 < r2);                        // strict, nanoflann RadiusResultSet [upstream]
@@ -241,14 +246,40 @@ k_mme3(const SPoint *__restrict__ sp, const unsigned long long *__restrict__ cod
                 }
             }
         };
-        if (dbg != 1) wave_for_each_run(tab, nk, lane, [&](int cs, int ce, int) {
-            for (int base = cs; base < ce; base += TILE) {
-                const int n = min(TILE, ce - base);
+        // The round's candidate stream, staged TILE wide ACROSS the cell runs (round 9): the table's non-empty slots become a run list
+        // {start, stream offset} (wave_run_list: slot order, the order wave_for_each_run hands them out), and the stream is cut into
+        // chunks of TILE positions whatever run they fall into — a radius cell holds ~25 points, so a run staged on its own filled
+        // 22 of 64 lanes and a round paid ~20 times for the run pick, the fences and the tail of the read loop.  The candidates
+        // come in the same order, so every lane accepts the same sequence and its sums are bit for bit what they were.
+        // Which run holds stream position base + l: s_r0 (scalar) = the run that holds `base`; the lanes read the offsets of the
+        // next 64 runs, those that begin at base + 1 .. base + TILE (at most TILE <= 64 of them: a run holds a point) set bit
+        // (offset - base - 1) of the chunk's head mask in LDS, and lane l's run is s_r0 + the bits below l (v_mbcnt); the mask's
+        // population advances s_r0 to the run that holds base + TILE.  No bound on a run's or the stream's length, no search.
+        static_assert(TILE <= 64, "a chunk is staged by one wave, its head mask is two words");
+        if (dbg != 1) {
+            int n_runs = 0;
+            const int total = wave_run_list(tab, nk, lane, &n_runs);
+            int s_r0 = 0;
+            for (int base = 0; base < total; base += TILE) {
+                const int n = min(TILE, total - base);
 #ifdef ME_MME_STATS
                 st_cand += n;
 #endif
+                if (lane < 2) head[lane] = 0u;
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                if (s_r0 + 1 + lane < n_runs) {
+                    const int d = tab[s_r0 + 1 + lane].y - base - 1;  // >= 0: run s_r0 + 1 begins after `base`
+                    if (d < TILE) atomicOr(&head[d >> 5], 1u << (d & 31));
+                }
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                const unsigned int h0 = (unsigned int) __builtin_amdgcn_readfirstlane((int) head[0]);
+                const unsigned int h1 = (unsigned int) __builtin_amdgcn_readfirstlane((int) head[1]);
                 if (lane < n) {
-                    const SPoint p = sp[base + lane];
+                    const int2 run = tab[s_r0 + (int) __builtin_amdgcn_mbcnt_hi(h1, __builtin_amdgcn_mbcnt_lo(h0, 0u))];
+                    const int gi = run.x + (base + lane - run.y);  // inside its run: inside the cloud
+                    const SPoint p = sp[gi];
                     const double px = p.x - ox, py = p.y - oy, pz = p.z - oz;
                     const float fx = (float) px, fy = (float) py, fz = (float) pz;
                     // |p'|^2 of the ROUNDED coordinates (the error bound is stated for them), rounded once
@@ -256,7 +287,9 @@ k_mme3(const SPoint *__restrict__ sp, const unsigned long long *__restrict__ cod
                     trec[lane].f = make_float4(fx, fy, fz, (float) w);
                     trec[lane].xy = make_double2(px, py);
                     trec[lane].z = pz;
+                    trec[lane].gi = gi;
                 }
+                s_r0 += __popc(h0) + __popc(h1);
                 __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
                 __builtin_amdgcn_wave_barrier();
                 int j = (dbg == 3) ? n : 0;
@@ -266,21 +299,21 @@ k_mme3(const SPoint *__restrict__ sp, const unsigned long long *__restrict__ cod
                 asm volatile("" : "+v"(ra));  // the record address lives in a VECTOR register: reads below use it + an immediate
                 for (; j + 2 <= n; j += 2) {
                     const float4 c0 = lds_load<float4>(ra), c1 = lds_load<float4>(ra + (unsigned int) sizeof(MmeTileRec));
-                    test(c0, ra, base + j);
-                    test(c1, ra + (unsigned int) sizeof(MmeTileRec), base + j + 1);
+                    test(c0, ra);
+                    test(c1, ra + (unsigned int) sizeof(MmeTileRec));
                     ra += 2u * (unsigned int) sizeof(MmeTileRec);
                     asm volatile("" : "+v"(ra));
                 }
                 for (; j < n; ++j) {
                     const float4 c0 = lds_load<float4>(ra);
-                    test(c0, ra, base + j);
+                    test(c0, ra);
                     ra += (unsigned int) sizeof(MmeTileRec);
                     asm volatile("" : "+v"(ra));
                 }
                 __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
                 __builtin_amdgcn_wave_barrier();  // the tile is overwritten by the next chunk
             }
-        });
+        }
 #ifdef ME_MME_STATS
         {
             int ka = in ? k : 0;
@@ -724,7 +757,7 @@ int mme_run(me_ctx *ctx, int slot, double radius, int min_k, double *entropies, 
 #ifdef ME_AB
 #include "me_mme_dispatch_ab.inc"
 #else
-        ME_LAUNCH_MME3(32, ME_TUNE_MME_WAVES, ME_MME_DBG);
+        ME_LAUNCH_MME3(48, ME_TUNE_MME_WAVES, ME_MME_DBG);
 #endif
 #undef ME_LAUNCH_MME3
         ts.end();
