@@ -47,7 +47,7 @@ SYMBOLS = [
     "me_set_normals", "me_get_normals", "me_estimate_normals", "me_gicp_covariances", "me_get_covariances", "me_icp_lsq_sums",
     "me_icp_lsq_sums_robust", "me_icp_information",
     "me_nn1", "me_icp_p2p_sums", "me_render_distance", "me_render_entropy", "me_nn_stats", "me_nn_partial_sums", "me_nn_sigma_sums", "me_nn_finalize", "me_chamfer",
-    "me_mme", "me_voxel_gaussians", "me_voxel_metrics", "me_voxel_deformation", "me_voxel_deformation_fetch", "me_awd_scs", "me_w2_batch", "me_scs_table", "me_run_suite", "me_run_suite_from", "me_mme_fetch",
+    "me_mme", "me_voxel_gaussians", "me_voxel_metrics", "me_voxel_deformation", "me_voxel_deformation_fetch", "me_voxel_distances", "me_awd_scs", "me_w2_batch", "me_scs_table", "me_run_suite", "me_run_suite_from", "me_mme_fetch",
     "me_set_voxel_hint", "me_cell_table_fetch", "me_timers_enable", "me_timers_reset", "me_timer_get",
 ]
 
@@ -92,6 +92,27 @@ class DeformSummary(C.Structure):
         ("sum_e_R", C.c_double),
     ]
 
+
+class VoxDistParams(C.Structure):
+    _fields_ = [
+        ("voxel_size", C.c_double),
+        ("min_pts", C.c_int32),
+        ("n_sigma", C.c_int32),
+        ("sigma", C.c_double * 4),
+        ("max_points", C.c_int64),
+        ("eig_floor", C.c_double),
+    ]
+
+
+class VoxDistOut(C.Structure):
+    _fields_ = [
+        ("n_rows", C.c_int64),
+        ("n_rows_subsampled", C.c_int64),
+        ("n_pairs", C.c_int64),
+        ("mean_mmd", C.c_double * 4),
+        ("mean_mmd2_u", C.c_double * 4),
+        ("mean_gauss", C.c_double * 4),
+    ]
 
 class IcpSums(C.Structure):
     _fields_ = [
@@ -703,6 +724,8 @@ def load():
     L.me_voxel_deformation_fetch.argtypes = [vp, C.c_int, ip, vp, vp, dp, dp, dp, dp, dp, C.POINTER(C.c_int64)]
     for f in ("me_voxel_deformation", "me_voxel_deformation_fetch"):
         getattr(L, f).restype = C.c_int
+    L.me_voxel_distances.argtypes = [vp, C.POINTER(VoxDistParams), ip, ip, ip, dp, dp, dp, C.POINTER(C.c_int64), C.POINTER(VoxDistOut)]
+    L.me_voxel_distances.restype = C.c_int
     L.me_awd_scs.argtypes = [vp, C.c_double, C.c_int, C.c_int, dp, dp, C.POINTER(C.c_int64), C.POINTER(C.c_double),
                              C.POINTER(C.c_double), dp]
     L.me_run_suite.argtypes = [vp, C.POINTER(SuiteParams), C.POINTER(SuiteOut)]

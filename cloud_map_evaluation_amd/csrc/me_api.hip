@@ -725,6 +725,12 @@ int me_voxel_deformation_fetch(me_ctx *ctx, int query_slot, int32_t *keys, int64
     return me::voxel_deformation_fetch(ctx, query_slot, keys, n_pairs, flags, sums, t0, u, R, e, n_voxels);
 }
 
+int me_voxel_distances(me_ctx *ctx, const me_voxdist_params *p, int32_t *keys, int32_t *n_pop, int32_t *n_used, double *ksum, double *mmd2,
+                       double *gauss, int64_t *n_rows, me_voxdist_out *out) {
+    if (!ctx) return ME_ERR_ARG;
+    return me::voxel_distances(ctx, p, keys, n_pop, n_used, ksum, mmd2, gauss, n_rows, out);
+}
+
 int me_voxel_partials(me_ctx *ctx, int slot, double voxel_size, int32_t *keys, int32_t *npts, double *mu, double *m2,
                       int64_t *n_voxels) {
     if (!ctx) return ME_ERR_ARG;

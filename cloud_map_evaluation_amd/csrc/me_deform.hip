@@ -4,7 +4,7 @@
 // Which way has this part of the map moved, and by how much: the pair moments me_icp_p2p_sums forms for the whole cloud, formed per
 // voxel of the AWD lattice (the rows of me_voxel_gaussians: voxel_key_of, ascending keys), a rigid fit per voxel (me_horn.hpp) and
 // what the fit leaves of the squared error.
-//   pass 0  k_deform_order     THE ORDER OF THE SUMS IS THE POINTS' OWN: every point's voxel key, filed under its ORIGINAL index, and a
+//   pass 0  k_point_order      THE ORDER OF THE SUMS IS THE POINTS' OWN: every point's voxel key, filed under its ORIGINAL index, and a
 //                              stable sort by key: the points grouped by voxel, inside a voxel in ascending original index.  The
 //                              sorted (Hilbert) order of the cloud, which changes with the index's cell size, decides nothing:
 //                              the rows are bit-identical after any re-sort of the same points.
@@ -24,6 +24,7 @@
 
 #include "me_horn.hpp"
 #include "me_internal.hpp"
+#include "me_point_order.hpp"
 #include "me_reduce.hpp"
 #include "me_vox_rows.hpp"
 
@@ -58,21 +59,6 @@ __device__ __forceinline__ void deform_sum_store(const double (&a)[3], const dou
     v = ONE ? wave_sum_to_lane0(v) : seg_sum_to_head(v, seg, lane);
     if (store) dst[K] = v;
     if constexpr (K + 1 < kDfD) deform_sum_store<K + 1, ONE>(a, b, d2, seg, lane, store, dst);
-}
-
-// okey[o] = the voxel key of the point with original index o, opos[o] = its position in the sorted cloud
-__global__ void __launch_bounds__(256)
-k_deform_order(const SPoint *__restrict__ sp, long long n, double vs, SlabView slab, unsigned long long *__restrict__ okey,
-               unsigned int *__restrict__ opos, int *__restrict__ err) {
-    const long long s = (long long) blockIdx.x * blockDim.x + threadIdx.x;
-    if (s >= n) return;
-    const SPoint p = sp[s];
-    if (p.idx < 0 || p.idx >= n) {  // (never: the sorted cloud is a permutation of the uploaded one)
-        *err = 1;
-        return;
-    }
-    okey[p.idx] = voxel_key_of(p.x, p.y, p.z, vs, slab, err);
-    opos[p.idx] = (unsigned int) s;
 }
 
 // lane = entry i of the points' own order: skey[i] its voxel key, spos[i] its position in the sorted cloud (where d2 and idx lie)
@@ -301,27 +287,9 @@ int voxel_deformation(me_ctx *ctx, int qslot, double voxel_size, double max_dist
     unsigned int *cnt = ctx->red.as<unsigned int>();  // [range error, fullest region, the regions' counters]
     // the points' own order: by voxel key, inside a voxel by original index (a stable sort of the keys filed by original index)
     DevBuf okey_d, opos_d, skey_d, spos_d;
-    ME_CHECK(ctx, okey_d.ensure((size_t) n * 8));
-    ME_CHECK(ctx, opos_d.ensure((size_t) n * 4));
-    ME_CHECK(ctx, skey_d.ensure((size_t) n * 8));
-    ME_CHECK(ctx, spos_d.ensure((size_t) n * 4));
     ME_CHECK(ctx, hipMemsetAsync(cnt, 0, kVoxCounterBytes, ctx->stream));
-    ME_CHECK(ctx, hipMemsetAsync(opos_d.p, 0xFF, (size_t) n * 4, ctx->stream));  // (an entry no point files: no position, no pair)
-    ME_CHECK(ctx, hipMemsetAsync(okey_d.p, 0, (size_t) n * 8, ctx->stream));
-    {
-        TimerScope ts(ctx, "voxel_deformation");
-        hipLaunchKernelGGL(k_deform_order, dim3(blocks_of(n)), dim3(256), 0, ctx->stream, q.sp.as<SPoint>(), n, voxel_size, q.slab,
-                           okey_d.as<unsigned long long>(), opos_d.as<unsigned int>(), reinterpret_cast<int *>(cnt));
-    }
-    {
-        unsigned int h_err = 0;
-        MailGuard mg(ctx);
-        ME_TRY(mail_post(ctx, &h_err, cnt, 4));
-        ME_TRY(mg.sync());
-        if (h_err) return ctx->fail(ME_ERR_ARG, "me_voxel_deformation: voxel index out of range (|floor(p/voxel_size)| must be < 2^20)");
-    }
-    ME_TRY(sort_pairs_u64_u32(ctx, okey_d.as<unsigned long long>(), skey_d.as<unsigned long long>(), opos_d.as<unsigned int>(),
-                              spos_d.as<unsigned int>(), n, 0, 64));  // (a radix sort: stable)
+    ME_TRY(points_own_order(ctx, q, voxel_size, reinterpret_cast<int *>(cnt), "voxel_deformation", "me_voxel_deformation", okey_d, opos_d,
+                            skey_d, spos_d));  // (me_point_order.hpp)
     for (int attempt = 0;; ++attempt) {
         cap = 2 * n_rows + (long long) kVoxRegions * rsize;
         ME_CHECK(ctx, pbuf.ensure((size_t) cap * 16));  // rec_pos | rec_vkey

@@ -753,6 +753,9 @@ int vox_record_segments(me_ctx *ctx, long long cap, const unsigned long long *re
 int voxel_deformation(me_ctx *ctx, int qslot, double voxel_size, double max_distance, int min_pairs, double min_spread, me_deform_summary *out);
 int voxel_deformation_fetch(me_ctx *ctx, int qslot, int32_t *keys, int64_t *n_pairs, uint8_t *flags, double *sums, double *t0, double *u,
                             double *R, double *e, int64_t *n_voxels);
+// ---- me_voxdist.hip ----
+int voxel_distances(me_ctx *ctx, const me_voxdist_params *p, int32_t *keys, int32_t *n_pop, int32_t *n_used, double *ksum, double *mmd2,
+                    double *gauss, int64_t *n_rows, me_voxdist_out *out);
 
 // ---- shared device helpers ----
 #ifdef __HIPCC__

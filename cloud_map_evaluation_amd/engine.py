@@ -1373,6 +1373,45 @@ class Engine:
         return dict(keys=keys, n_pairs=n, flags=fl, sums=sums, t0=t0, u=u, R=R.reshape(v, 3, 3), e0=np.ascontiguousarray(e[:, 0]),
                     e_t=np.ascontiguousarray(e[:, 1]), e_R=np.ascontiguousarray(e[:, 2]), angle=rotation_angle(R))
 
+    def voxel_distances(self, voxel_size: float, sigmas, min_pts: int = 100, max_points: int = 2048, eig_floor: float = 1e-6,
+                        fetch: bool = True) -> dict:
+        """me_voxel_distances: per row of calculateVMD(voxel_size, min_pts) the point-set MMD of the two clouds' points in the voxel
+        at 1 - 4 kernel bandwidths `sigmas`, and the Gaussian closed forms KL(est || gt), KL(gt || est), Bhattacharyya and the textbook
+        W2 (definitions: include/mapeval_hip.h).  max_points: a fuller voxel is sub-sampled by a stride (0: never).
+        -> the summary: n_rows, n_rows_subsampled, n_pairs_total, mean_mmd, mean_mmd2_u (one per bandwidth) and mean_kl_est_gt,
+        mean_kl_gt_est, mean_bhattacharyya, mean_w2 (NaN without rows).  With fetch also the rows: keys (V, 3), n_pop, n_used (V, 2),
+        ksum (V, n_sigma, 3: Sxx, Syy, Sxy), mmd2_u, mmd2_b, mmd (V, n_sigma), kl_est_gt, kl_gt_est, bhattacharyya, w2 (V)."""
+        sg = np.atleast_1d(np.asarray(sigmas, dtype=np.float64)).ravel()
+        if not 1 <= sg.shape[0] <= 4:
+            raise ValueError("voxel_distances: 1 to 4 bandwidths")
+        ns = int(sg.shape[0])
+        p = _lib.VoxDistParams()
+        p.voxel_size, p.min_pts, p.n_sigma, p.max_points, p.eig_floor = float(voxel_size), int(min_pts), ns, int(max_points), float(eig_floor)
+        for b in range(ns):
+            p.sigma[b] = float(sg[b])
+        o = _lib.VoxDistOut()
+        nr = C.c_int64(0)
+        arrays = {}
+        if fetch:
+            self._ck(self._L.me_voxel_distances(self._ctx, C.byref(p), 0, 0, 0, 0, 0, 0, C.byref(nr), None))
+            v = nr.value
+            keys, pop, used = np.empty((v, 3), np.int32), np.empty((v, 2), np.int32), np.empty((v, 2), np.int32)
+            ksum, mmd2, gauss = np.empty((v, ns, 3), np.float64), np.empty((v, ns, 2), np.float64), np.empty((v, 4), np.float64)
+            self._ck(self._L.me_voxel_distances(self._ctx, C.byref(p), _addr(keys), _addr(pop), _addr(used), _addr(ksum), _addr(mmd2),
+                                                _addr(gauss), C.byref(nr), C.byref(o)))
+            mb = np.ascontiguousarray(mmd2[:, :, 1])
+            arrays = dict(keys=keys, n_pop=pop, n_used=used, ksum=ksum, mmd2_u=np.ascontiguousarray(mmd2[:, :, 0]), mmd2_b=mb,
+                          mmd=np.sqrt(np.maximum(0.0, mb)), kl_est_gt=np.ascontiguousarray(gauss[:, 0]),
+                          kl_gt_est=np.ascontiguousarray(gauss[:, 1]), bhattacharyya=np.ascontiguousarray(gauss[:, 2]),
+                          w2=np.ascontiguousarray(gauss[:, 3]))
+        else:
+            self._ck(self._L.me_voxel_distances(self._ctx, C.byref(p), 0, 0, 0, 0, 0, 0, C.byref(nr), C.byref(o)))
+        res = dict(n_rows=o.n_rows, n_rows_subsampled=o.n_rows_subsampled, n_pairs_total=o.n_pairs, sigmas=sg.copy(),
+                   mean_mmd=np.array(o.mean_mmd[:ns]), mean_mmd2_u=np.array(o.mean_mmd2_u[:ns]), mean_kl_est_gt=o.mean_gauss[0],
+                   mean_kl_gt_est=o.mean_gauss[1], mean_bhattacharyya=o.mean_gauss[2], mean_w2=o.mean_gauss[3])
+        res.update(arrays)
+        return res
+
     def voxel_metrics_table(self, voxel_size: float, gate: float, gate_mode: int, trunc, min_pts: int = 100,
                             scs_radius: int = 5) -> np.ndarray:
         """The joined per-voxel table of a finished suite — what the C++ host writes to voxel_metrics.txt: one row per voxel of

@@ -6,6 +6,7 @@
 #include <chrono>
 #include <climits>
 #include <cstdio>
+#include <cstring>
 #include <cmath>
 #include <ctime>
 #include <filesystem>
@@ -431,6 +432,26 @@ Param loadParametersFromYAML(const std::string &yaml_file_path) {
         if (!(param.deformation_min_spread >= 0)) throw std::runtime_error("deformation_min_spread: must be >= 0");
         if (param.num_gpus > 1) throw std::runtime_error("evaluate_deformation: single GPU only (num_gpus must be 1)");
     }
+    // per-voxel distribution distances on the AWD lattice (me_voxel_distances; no reference counterpart)
+    if (config.has("evaluate_voxel_distances")) param.evaluate_voxel_distances = config.as_bool("evaluate_voxel_distances");
+    if (config.has("mmd_sigmas")) {
+        if (!config.at("mmd_sigmas").scalar.empty() || !config.at("mmd_sigmas").rows.empty()) throw std::runtime_error("mmd_sigmas: must be a list of 1 to 4 numbers");
+        for (const auto &v : config.at("mmd_sigmas").seq) param.mmd_sigmas.push_back(yaml_lite::Document::to_double(v, "mmd_sigmas"));
+    } else {
+        param.mmd_sigmas.assign(1, param.nn_radius_);
+    }
+    if (config.has("mmd_max_points")) param.mmd_max_points = (long long) config.as_double("mmd_max_points");
+    if (config.has("voxel_distance_eig_floor")) param.voxel_distance_eig_floor = config.as_double("voxel_distance_eig_floor");
+    if (param.evaluate_voxel_distances) {
+        if (param.mmd_sigmas.empty() || param.mmd_sigmas.size() > 4) throw std::runtime_error("mmd_sigmas: must be a list of 1 to 4 numbers");
+        for (const double sg : param.mmd_sigmas)
+            if (!(sg > 0) || !std::isfinite(sg)) throw std::runtime_error("mmd_sigmas: every bandwidth must be > 0");
+        if (param.mmd_max_points < 0 || (param.mmd_max_points >= 1 && param.mmd_max_points <= 10))
+            throw std::runtime_error("mmd_max_points: must be 0 (all points) or >= 11");
+        if (!(param.voxel_distance_eig_floor > 0) || !std::isfinite(param.voxel_distance_eig_floor))
+            throw std::runtime_error("voxel_distance_eig_floor: must be > 0");
+        if (param.num_gpus > 1) throw std::runtime_error("evaluate_voxel_distances: single GPU only (num_gpus must be 1)");
+    }
     // cloud-to-mesh distance (the role of the reference's mesh branch, with a supplied mesh)
     if (config.has("evaluate_mesh_distance")) param.evaluate_mesh_distance = config.as_bool("evaluate_mesh_distance");
     if (config.has("gt_mesh_path")) param.gt_mesh_path = config.as_string("gt_mesh_path");
@@ -592,6 +613,9 @@ std::string paramToJson(const Param &p) {
         else o << c;
     }
     o << "\", \"mesh_orient_k\": " << p.mesh_orient_k << ", \"mesh_orient_inward\": " << b(p.mesh_orient_inward);
+    o << ", \"evaluate_voxel_distances\": " << b(p.evaluate_voxel_distances) << ", \"mmd_sigmas\": [";
+    for (size_t i = 0; i < p.mmd_sigmas.size(); ++i) o << (i ? ", " : "") << p.mmd_sigmas[i];
+    o << "], \"mmd_max_points\": " << p.mmd_max_points << ", \"voxel_distance_eig_floor\": " << p.voxel_distance_eig_floor;
     o << "}";
     return o.str();
 }
@@ -821,6 +845,7 @@ int MapEval::process() {
     calculateVMD();
     if (!last_error.empty()) return -1;
     if (param_.evaluate_deformation && computeDeformation() != 0) return -1;
+    if (param_.evaluate_voxel_distances && computeVoxelDistances() != 0) return -1;
     if (param_.save_voxel_metrics) {  // (only the registration path gets here on one GPU: the initial-matrix one is processOneCall)
         // the transforms of the registration discarded the map's MME result on the device: hand back the entropies computeMME
         // fetched (those of map_entropy.txt), and the ground truth's with them
@@ -1256,6 +1281,7 @@ int MapEval::processOneCall(bool from_host, double t_loaded) {
     calculateVMD();
     if (!last_error.empty()) return -1;
     if (param_.evaluate_deformation && computeDeformation() != 0) return -1;
+    if (param_.evaluate_voxel_distances && computeVoxelDistances() != 0) return -1;
     if (param_.save_voxel_metrics) {
         saveVoxelMetrics(ME_GATE_LE_UNSQUARED);  // the gate of the statistics above (:1219)
         if (!last_error.empty()) return -1;
@@ -1909,6 +1935,69 @@ void MapEval::saveDeformation() {
     if (std::fclose(f) != 0) fail("writing " + path + " failed");
 }
 
+// evaluate_voxel_distances: per row of the AWD table (vmd_voxel_size, 100 points in both clouds, as calculateVMD) the point-set MMD at
+// the bandwidths mmd_sigmas and the Gaussian closed forms, where both clouds stand now: me_voxel_distances.
+int MapEval::computeVoxelDistances() {
+    me_voxdist_params p;
+    std::memset(&p, 0, sizeof(p));
+    p.voxel_size = param_.vmd_voxel_size_;
+    p.min_pts = 100;
+    p.n_sigma = (int32_t) param_.mmd_sigmas.size();
+    for (int b = 0; b < p.n_sigma; ++b) p.sigma[b] = param_.mmd_sigmas[(size_t) b];
+    p.max_points = param_.mmd_max_points;
+    p.eig_floor = param_.voxel_distance_eig_floor;
+    int64_t V = 0;
+    if (me_voxel_distances(ctx_, &p, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &V, nullptr) != ME_OK)
+        return fail(std::string("evaluate_voxel_distances: ") + me_last_error(ctx_));
+    const size_t v = (size_t) V, ns = (size_t) p.n_sigma;
+    voxdist_keys.assign(v * 3, 0);
+    voxdist_pop.assign(v * 2, 0);
+    voxdist_used.assign(v * 2, 0);
+    voxdist_ksum.assign(v * ns * 3, 0.0);
+    voxdist_mmd2.assign(v * ns * 2, 0.0);
+    voxdist_gauss.assign(v * 4, 0.0);
+    if (me_voxel_distances(ctx_, &p, voxdist_keys.data(), voxdist_pop.data(), voxdist_used.data(), voxdist_ksum.data(), voxdist_mmd2.data(),
+                           voxdist_gauss.data(), &V, &voxdist_out) != ME_OK)
+        return fail(std::string("evaluate_voxel_distances: ") + me_last_error(ctx_));
+    return 0;
+}
+
+// The result lines `VoxelMMD @s1,s2,..:` (the bandwidths, then per bandwidth "mean_mmd mean_mmd2_u", the means over the rows) and `VoxelKL-BD-W2:` (the means of
+// KL(est || gt), KL(gt || est), Bhattacharyya and W2), and voxel_distances.txt: the parameters ("name value"), then one row per voxel
+//   ix iy iz n_est n_gt used_est used_gt kl_est_gt kl_gt_est bhattacharyya w2 { Sxx Syy Sxy mmd2_u mmd2_b } per bandwidth   (doubles as %.17g)
+void MapEval::saveVoxelDistances() {
+    const me_voxdist_out &o = voxdist_out;
+    const size_t ns = param_.mmd_sigmas.size();
+    file_result << std::fixed << std::setprecision(15) << "VoxelMMD @";
+    for (size_t b = 0; b < ns; ++b) file_result << (b ? "," : "") << param_.mmd_sigmas[b];
+    file_result << ":";
+    for (size_t b = 0; b < ns; ++b) file_result << " " << o.mean_mmd[b] << " " << o.mean_mmd2_u[b];
+    file_result << std::endl;
+    file_result << std::fixed << std::setprecision(15) << "VoxelKL-BD-W2: " << o.mean_gauss[0] << " " << o.mean_gauss[1] << " " << o.mean_gauss[2] << " "
+                << o.mean_gauss[3] << std::endl;
+    const std::string path = results_subfolder + "voxel_distances.txt";
+    FILE *f = std::fopen(path.c_str(), "w");
+    if (!f) {
+        fail("cannot write " + path);
+        return;
+    }
+    std::fprintf(f, "voxel_size %.17g\nmin_pts %d\nmax_points %lld\neig_floor %.17g\nn_sigma %d\n", param_.vmd_voxel_size_, 100, param_.mmd_max_points,
+                 param_.voxel_distance_eig_floor, (int) ns);
+    for (size_t b = 0; b < ns; ++b) std::fprintf(f, "sigma %.17g\n", param_.mmd_sigmas[b]);
+    std::fprintf(f, "n_rows %lld\nn_rows_subsampled %lld\nn_pairs %lld\n", (long long) o.n_rows, (long long) o.n_rows_subsampled, (long long) o.n_pairs);
+    for (size_t v = 0; v < (size_t) o.n_rows; ++v) {
+        std::fprintf(f, "%d %d %d %d %d %d %d %.17g %.17g %.17g %.17g", voxdist_keys[3 * v], voxdist_keys[3 * v + 1], voxdist_keys[3 * v + 2],
+                     voxdist_pop[2 * v], voxdist_pop[2 * v + 1], voxdist_used[2 * v], voxdist_used[2 * v + 1], voxdist_gauss[4 * v],
+                     voxdist_gauss[4 * v + 1], voxdist_gauss[4 * v + 2], voxdist_gauss[4 * v + 3]);
+        for (size_t b = 0; b < ns; ++b) {
+            const double *k = &voxdist_ksum[(v * ns + b) * 3], *m = &voxdist_mmd2[(v * ns + b) * 2];
+            std::fprintf(f, " %.17g %.17g %.17g %.17g %.17g", k[0], k[1], k[2], m[0], m[1]);
+        }
+        std::fprintf(f, "\n");
+    }
+    if (std::fclose(f) != 0) fail("writing " + path + " failed");
+}
+
 // evaluate_mesh_distance: the mesh of gt_mesh_path as it is in the file (like the ground-truth cloud it is not moved), the map where
 // initial_matrix puts it (me_transform_cloud; the host's copy stays as loaded), me_mesh_distance with the map as the query, the exact
 // nearest-rank quantiles of d over the matched points (error_quantiles; me_rank_select on the fetched values) and, with
@@ -2203,6 +2292,7 @@ void MapEval::saveRegistrationResults() {
     if (param_.evaluate_mesh_distance) saveMeshDistance();
     if (param_.evaluate_mesh) saveReconstruction();
     if (param_.evaluate_deformation) saveDeformation();
+    if (param_.evaluate_voxel_distances) saveVoxelDistances();
     file_result << std::fixed << std::setprecision(5) << "VMD: " << vmd << std::endl;
     file_result << std::fixed << std::setprecision(5) << "SCS: " << scs_overall << std::endl;
     if (param_.evaluate_using_initial_)

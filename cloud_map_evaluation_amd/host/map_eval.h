@@ -152,6 +152,11 @@ struct Param {
     double deformation_max_distance = 0;       // `deformation_max_distance:` a DISTANCE (d2 < max^2); default sqrt(icp_max_distance) when that is > 0, else inf
     int deformation_min_pairs = 30;            // `deformation_min_pairs:` (>= 3)
     double deformation_min_spread = 0;         // `deformation_min_spread:` (default deformation_voxel_size / 20)
+    bool evaluate_voxel_distances = false;     // `evaluate_voxel_distances:` true = per AWD voxel the point-set MMD and the Gaussian KL / Bhattacharyya /
+                                               // textbook W2 of the two clouds (me_voxel_distances; single GPU only): two result lines and voxel_distances.txt
+    std::vector<double> mmd_sigmas;            // `mmd_sigmas:` 1 - 4 kernel bandwidths (default [nn_radius])
+    long long mmd_max_points = 2048;           // `mmd_max_points:` a fuller voxel is sub-sampled by a stride (0: never; else >= 11)
+    double voxel_distance_eig_floor = 1e-6;    // `voxel_distance_eig_floor:` the eigenvalue floor of the closed forms (> 0)
     double m3c2_normal_radius = 0.0;           // `m3c2_normal_radius:` > 0 (default: nn_radius)
     double m3c2_projection_radius = 0.0;       // `m3c2_projection_radius:` the cylinder's radius, > 0 (default: nn_radius)
     double m3c2_max_depth = 0.0;               // `m3c2_max_depth:` the cylinder's half-length, > 0 (default: 4 nn_radius)
@@ -231,7 +236,9 @@ public:
     int computeM3C2();                                      // evaluate_m3c2: normals and me_m3c2 on both clouds, the map moved (no reference counterpart)
     void saveM3C2();                                        // its result line and m3c2.txt
     int computeDeformation();                               // evaluate_deformation: me_voxel_deformation with the map as the query (no reference counterpart)
+    int computeVoxelDistances();                            // evaluate_voxel_distances: me_voxel_distances on the AWD lattice (no reference counterpart)
     void saveDeformation();                                 // its result line and deformation_field.txt
+    void saveVoxelDistances();                              // its two result lines and voxel_distances.txt
     int computeMeshDistance();                              // evaluate_mesh_distance: me_mesh_distance of the moved map (no reference counterpart)
     void saveMeshDistance();                                // its two result lines and mesh_distance.txt
     int computeReconstruction();                            // evaluate_mesh: radius normals + me_reconstruct on both clouds as loaded
@@ -263,6 +270,9 @@ public:
     me_radius_normals_out surface_normals[2] = {};
     me_m3c2_out m3c2_out[2] = {};               // evaluate_m3c2: [ME_SLOT_EST], [ME_SLOT_GT] as the query
     me_deform_summary deform_out = {};          // evaluate_deformation
+    me_voxdist_out voxdist_out = {};            // evaluate_voxel_distances: the summary and the rows (keys | n_pop | n_used | ksum | mmd2 | gauss)
+    std::vector<int32_t> voxdist_keys, voxdist_pop, voxdist_used;
+    std::vector<double> voxdist_ksum, voxdist_mmd2, voxdist_gauss;
     me_radius_normals_out m3c2_normals[2] = {};
     me_mesh_info_out mesh_info = {};            // evaluate_mesh_distance: the mesh, the totals, the quantiles of d, the sampled block
     me_mesh_out mesh_out = {};

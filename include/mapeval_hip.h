@@ -1343,6 +1343,63 @@ int me_voxel_deformation_fetch(me_ctx *ctx, int query_slot, int32_t *keys /*V x 
                                double *sums /*V x 23*/, double *t0 /*V x 3*/, double *u /*V x 3*/, double *R /*V x 9*/,
                                double *e /*V x 3*/, int64_t *n_voxels);
 
+/* ---- per-voxel distribution distances on the AWD lattice: point-set MMD, KL, Bhattacharyya and the textbook W2 (the reference
+ *      declares computeKLDivergenceGaussian, computeGaussianKernel, computeGaussianBhattacharyya and computeMMD at
+ *      voxel_calculator.hpp:71-79 and defines none of them) ---------------------------------------------------------------------- */
+/* (DESIGN.md section 4.24).  AWD's W is close to the offset of two centroids wherever the reference's formula clamps the eigenvalues;
+ * these columns compare the SHAPES of what the two clouds hold in a voxel.  Both resident clouds, single GPU.
+ *   ROWS    exactly the voxels for which me_awd_scs(voxel_size, min_pts, ..) emits a row: the keys present in both clouds with both
+ *           populations >= min_pts, ascending (ix, iy, iz), on the lattice of me_voxel_gaussians (floor(p / voxel_size), CURRENT
+ *           coordinates).  n_pop[v] = the two populations (est, gt).
+ *   POINTS  X = the map's points in the voxel, Y = the ground truth's, each in ascending ORIGINAL point index.  With max_points > 0
+ *           and a population n > max_points only every s-th point of that list is used, starting at the first, s = ceil(n /
+ *           max_points): ceil(n / s) points.  max_points = 0: all points.  n_used[v] = the used counts (n, m); the min_pts gate
+ *           always looks at the full population.
+ *   MMD     per bandwidth sigma_b, b < n_sigma: g_b = 1.0 / (2.0 * sigma_b * sigma_b) (host), d2 = ((dx dx) + (dy dy)) + (dz dz)
+ *           from the coordinates as stored (no recentring, no FMA: the d2 of every other kernel), k_b(x, y) = exp(-(d2 * g_b)) in
+ *           fp64.  ksum[v][b] = Sxx, Syy, Sxy with Sxx = sum_{i<j} k(x_i, x_j), Syy likewise, Sxy = sum_i sum_j k(x_i, y_j).
+ *           mmd2[v][b] = u, b:  u = 2 Sxx / (n (n - 1)) + 2 Syy / (m (m - 1)) - 2 Sxy / (n m)   (the unbiased estimate),
+ *                               b = (n + 2 Sxx) / n^2 + (m + 2 Syy) / m^2 - 2 Sxy / (n m)        (the biased one);
+ *           mmd = sqrt(max(0, b)).  Fixed-order sums in the points' own order, no floating-point atomics: bit-identical from call
+ *           to call and after any re-index of the same points (the sorted order of a cloud decides nothing).
+ *   GAUSS   from both voxels' n, mu and sigma AS me_voxel_gaussians REPORTS THEM (min_pts >= 11, so sigma is M2 / (n - 1)^2): the
+ *           sample covariance C = sigma * (n - 1) elementwise, its symmetric part, jacobi_sym, the eigenvalues raised to eig_floor:
+ *           S~ = V diag(l~) V^T, ln det = sum ln l~.  d = mu_gt - mu_est.  gauss[v] =
+ *             KL(est || gt) = 1/2 [tr(S~g^-1 S~e) + d^T S~g^-1 d - 3 + ln det S~g - ln det S~e],
+ *             KL(gt || est), the same with the roles swapped,
+ *             Bhattacharyya = 1/8 d^T S^-1 d + 1/2 [ln det S - 1/2 (ln det S~e + ln det S~g)], S = (S~e + S~g) / 2 decomposed the
+ *               same way,
+ *             W2 = sqrt(max(0, |d|^2 + tr S~e + tr S~g - 2 tr (S~e^1/2 S~g S~e^1/2)^1/2)), both square roots by jacobi_sym: the textbook
+ *               2-Wasserstein distance, which the reference's W is not (SURVEY finding 2).
+ *           A function of the two voxel tables alone: bit-identical from call to call, and across every re-sort, because a slot keeps
+ *           its table until its points are replaced (a table built afresh under another sorted order sums in that order and may
+ *           differ in the last bits, as me_voxel_gaussians' own output does).
+ *   out     n_rows; n_rows_subsampled = rows with s > 1 on either side; n_pairs = sum over the rows of n (n - 1) / 2 + m (m - 1) / 2
+ *           + n m; mean_mmd[b], mean_mmd2_u[b] (b < n_sigma, NaN past it) and mean_gauss[4], the means over the rows, added in the
+ *           fixed order of the per-cloud totals; NaN with no rows, as AWD is.
+ * Host pointers; every array and `out` may be NULL.  *n_rows in: capacity, out: count (ME_ERR_CAPACITY if an array is passed and the
+ * capacity is too small).  All arrays and `out` NULL: the row count alone, no pass over the points; all arrays NULL with `out`: the
+ * summary.  Nothing resident changes but the two slots' cached voxel tables, which are (re)built at voxel_size exactly as me_awd_scs
+ * and me_voxel_gaussians build them; the 1-NN, MME and every other per-point result stay.
+ * ME_ERR_ARG: voxel_size <= 0, min_pts < 11, n_sigma outside 1 .. 4, a sigma that is <= 0 or NaN, max_points < 0 or in 1 .. 10,
+ * eig_floor <= 0 or NaN, or a voxel index outside |floor(p / voxel_size)| < 2^20.  ME_ERR_STATE: a slot not uploaded, or slab / shard
+ * mode.  A refused call changes nothing.  Cost: a sort of (key, position) pairs per cloud and one exp per pair and bandwidth (device
+ * timer "voxel_distances": the kernels; the sorts are under "sort"). */
+typedef struct {
+    double voxel_size;
+    int32_t min_pts, n_sigma;
+    double sigma[4];
+    int64_t max_points;
+    double eig_floor;
+} me_voxdist_params;
+typedef struct {
+    int64_t n_rows, n_rows_subsampled, n_pairs;
+    double mean_mmd[4], mean_mmd2_u[4], mean_gauss[4];
+} me_voxdist_out;
+int me_voxel_distances(me_ctx *ctx, const me_voxdist_params *p, int32_t *keys /*V x 3*/, int32_t *n_pop /*V x 2*/, int32_t *n_used /*V x 2*/,
+                       double *ksum /*V x n_sigma x 3*/, double *mmd2 /*V x n_sigma x 2*/, double *gauss /*V x 4*/,
+                       int64_t *n_rows /*in: capacity, out: count*/, me_voxdist_out *out);
+
 /* ---- AWD + CDF + SCS: MapEval::calculateVMD (map_eval.cpp:240-390) with updateVoxelMap (voxel_calculator.cpp:
  *      142-172) and computeWassersteinDistanceGaussian (:115-140) ------------------------------------------------ */
 /* rows: n x 27 doubles in the column order of voxel_errors.txt (map_eval.cpp:292-302), ascending key order;
