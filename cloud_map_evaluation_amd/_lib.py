@@ -38,6 +38,7 @@ SYMBOLS = [
     "me_m3c2", "me_m3c2_fetch",
     "me_mesh_upload", "me_mesh_clear", "me_mesh_info", "me_mesh_distance", "me_mesh_distance_fetch", "me_mesh_sample",
     "me_mesh_topology", "me_mesh_topology_fetch", "me_mesh_signed_distance", "me_mesh_signed_fetch",
+    "me_mesh_raycast", "me_mesh_scan", "me_mesh_scan_fetch", "me_cloud_visibility", "me_cloud_visibility_fetch",
     "me_reconstruct", "me_isosurface", "me_reconstruct_fetch", "me_reconstruct_nodes_fetch", "me_reconstruct_install",
     "me_orient_normals", "me_orient_fetch",
     "me_knn_search", "me_hybrid_search", "me_radius_search", "me_search_sort_tile",
@@ -496,6 +497,33 @@ class MeshInfoOut(C.Structure):
     ]
 
 
+# me_mesh_raycast: modes, per-ray flags
+ME_RAY_CLOSEST, ME_RAY_ANY = 0, 1
+RAY_HIT, RAY_BACKFACE, RAY_INVALID = 1, 2, 4
+ME_VIS_MAX_ORIGINS = 65536
+
+
+class RayOut(C.Structure):
+    _fields_ = [("n_rays", C.c_int64), ("n_hit", C.c_int64), ("n_backface", C.c_int64), ("n_invalid", C.c_int64),
+                ("min_t", C.c_double), ("max_t", C.c_double)]
+
+
+class ScanParams(C.Structure):
+    _fields_ = [("min_range", C.c_double), ("max_range", C.c_double), ("noise_std", C.c_double), ("seed", C.c_uint64)]
+
+
+class ScanOut(C.Structure):
+    _fields_ = [("n_rays", C.c_int64), ("n_hit", C.c_int64), ("n_backface", C.c_int64)]
+
+
+class VisParams(C.Structure):
+    _fields_ = [("min_range", C.c_double), ("max_range", C.c_double), ("tolerance", C.c_double), ("first_only", C.c_int64)]
+
+
+class VisOut(C.Structure):
+    _fields_ = [("n_points", C.c_int64), ("n_visible", C.c_int64), ("n_in_range", C.c_int64), ("n_tests", C.c_int64)]
+
+
 class ReconParams(C.Structure):
     _fields_ = [("voxel", C.c_double), ("radius", C.c_double), ("min_k", C.c_int32), ("band", C.c_int32)]
 
@@ -647,6 +675,13 @@ def load():
     L.me_mesh_signed_fetch.argtypes = [vp, C.c_int, dp, vp]
     for f in ("me_mesh_upload", "me_mesh_clear", "me_mesh_info", "me_mesh_distance", "me_mesh_distance_fetch", "me_mesh_sample",
               "me_mesh_topology", "me_mesh_topology_fetch", "me_mesh_signed_distance", "me_mesh_signed_fetch"):
+        getattr(L, f).restype = C.c_int
+    L.me_mesh_raycast.argtypes = [vp, dp, dp, C.c_int64, C.c_double, C.c_double, C.c_int, dp, ip, dp, dp, vp, C.POINTER(RayOut)]
+    L.me_mesh_scan.argtypes = [vp, C.c_int, dp, C.c_int64, dp, C.c_int64, C.POINTER(ScanParams), vp, C.POINTER(ScanOut)]
+    L.me_mesh_scan_fetch.argtypes = [vp, C.c_int, vp]
+    L.me_cloud_visibility.argtypes = [vp, C.c_int, dp, C.c_int64, C.POINTER(VisParams), C.POINTER(VisOut)]
+    L.me_cloud_visibility_fetch.argtypes = [vp, C.c_int, ip, ip]
+    for f in ("me_mesh_raycast", "me_mesh_scan", "me_mesh_scan_fetch", "me_cloud_visibility", "me_cloud_visibility_fetch"):
         getattr(L, f).restype = C.c_int
     L.me_reconstruct.argtypes = [vp, C.c_int, C.POINTER(ReconParams), C.POINTER(ReconOut)]
     L.me_isosurface.argtypes = [vp, ip, dp, vp, C.c_int64, C.c_double, C.POINTER(ReconOut)]

@@ -126,6 +126,8 @@ int need_single_gpu_cloud(me_ctx *ctx, int slot, const char *who) {
     if (ctx->shard_world != 1 || ctx->slab.axis >= 0 || c.slab.axis >= 0)
         return ctx->fail(ME_ERR_ARG, std::string(who) + ": single GPU only (no slab or shard mode)");
     if (!c.uploaded) return ctx->fail(ME_ERR_STATE, std::string(who) + ": cloud not uploaded");
+    if (c.n == 0)  // (outside slab mode only a me_mesh_scan without a hit leaves this: no pass indexes or launches over nothing)
+        return ctx->fail(ME_ERR_STATE, std::string(who) + ": the slot's cloud is empty");
     return ME_OK;
 }
 }  // namespace me
@@ -440,6 +442,33 @@ int me_mesh_signed_distance(me_ctx *ctx, int query_slot, const me_mesh_sign_para
 int me_mesh_signed_fetch(me_ctx *ctx, int query_slot, double *signed_d, uint8_t *flags) {
     if (!ctx) return ME_ERR_ARG;
     return me::mesh_signed_fetch(ctx, query_slot, signed_d, flags);
+}
+
+int me_mesh_raycast(me_ctx *ctx, const double *origins, const double *dirs, int64_t n_rays, double t_min, double t_max, int mode, double *t,
+                    int32_t *tri, double *u, double *v, uint8_t *flags, me_ray_out *out) {
+    if (!ctx) return ME_ERR_ARG;
+    return me::mesh_raycast(ctx, origins, dirs, n_rays, t_min, t_max, mode, t, tri, u, v, flags, out);
+}
+
+int me_mesh_scan(me_ctx *ctx, int dst_slot, const double *poses, int64_t n_poses, const double *dirs, int64_t n_dirs,
+                 const me_scan_params *p, int64_t *pose_hits, me_scan_out *out) {
+    if (!ctx) return ME_ERR_ARG;
+    return me::mesh_scan(ctx, dst_slot, poses, n_poses, dirs, n_dirs, p, pose_hits, out);
+}
+
+int me_mesh_scan_fetch(me_ctx *ctx, int slot, int64_t *ray_id) {
+    if (!ctx) return ME_ERR_ARG;
+    return me::mesh_scan_fetch(ctx, slot, ray_id);
+}
+
+int me_cloud_visibility(me_ctx *ctx, int slot, const double *origins, int64_t n_origins, const me_vis_params *p, me_vis_out *out) {
+    if (!ctx) return ME_ERR_ARG;
+    return me::cloud_visibility(ctx, slot, origins, n_origins, p, out);
+}
+
+int me_cloud_visibility_fetch(me_ctx *ctx, int slot, int32_t *n_seen, int32_t *first_seen) {
+    if (!ctx) return ME_ERR_ARG;
+    return me::cloud_visibility_fetch(ctx, slot, n_seen, first_seen);
 }
 
 int me_reconstruct(me_ctx *ctx, int slot, const me_recon_params *p, me_recon_out *out) {

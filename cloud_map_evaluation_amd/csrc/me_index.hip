@@ -687,6 +687,7 @@ void drop_sorted_results(me_ctx *ctx, int slot) {
     c.mom_have = false;
     c.m3c2_have = false;
     c.mesh_have = false;
+    c.vis_have = false;
     c.nn_ref_slot = -1;
     c.surf_have = false;
     c.dfm_have = false;
@@ -703,6 +704,7 @@ void drop_point_results(me_ctx *ctx, int slot) {
     c.fpfh_valid = false;
     c.orient_have = false;
     c.outlier_keep_valid = false;  // (the mask belongs to the points it was computed on)
+    c.scan_have = false;
     c.cluster_valid = false;
     c.plane_valid = false;
     c.vox_valid = false;

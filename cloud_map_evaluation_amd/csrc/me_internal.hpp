@@ -283,6 +283,13 @@ struct Cloud {
     DevBuf dfm_keys, dfm_n, dfm_flags, dfm_sums, dfm_fit;
     long long dfm_V = 0;
     bool dfm_have = false;
+    // ray id int64[n] of every point, CLOUD order, while the slot holds the result of me_mesh_scan (me_ray.hip); dropped with the points
+    DevBuf scan_ray;
+    bool scan_have = false;
+    // last me_cloud_visibility of this cloud, SORTED order (me_ray.hip): origins that see the point int32[n], the first of them int32[n]
+    // (-1: none); dropped with the sorted order (cloud_build_index), with the points, and with the mesh (me_mesh_upload, me_mesh_clear)
+    DevBuf vis_n, vis_first;
+    bool vis_have = false;
 };
 
 // The resident triangle mesh (me_mesh.hip): one per primary context, beside the two clouds and untouched by what happens to them.
@@ -634,6 +641,19 @@ int mesh_topology(me_ctx *ctx, me_mesh_topo_out *out);
 int mesh_topology_fetch(me_ctx *ctx, double *vertex_normal_host, uint8_t *vertex_flags_host, double *edge_normal_host, uint8_t *edge_flags_host);
 int mesh_signed_distance(me_ctx *ctx, int qslot, const me_mesh_sign_params *p, me_mesh_sign_out *out);
 int mesh_signed_fetch(me_ctx *ctx, int qslot, double *signed_host, uint8_t *flags_host);
+// ---- me_ray.hip: per triangle the watertight test of Woop, Benthin and Wald in fp64, one fixed operation order (include/mapeval_hip.h);
+// winner = lexicographic minimum of (t, caller index); the tree only culls what cannot be a computed hit ----
+int mesh_raycast(me_ctx *ctx, const double *origins_host, const double *dirs_host, long long n_rays, double t_min, double t_max, int mode,
+                 double *t_host, int32_t *tri_host, double *u_host, double *v_host, uint8_t *flags_host, me_ray_out *out);
+// ray p * n_dirs + b: o = translation of pose p, d_w[k] = (R[k][0] dx + R[k][1] dy) + R[k][2] dz, closest hit with t in
+// [min_range, max_range] / sqrt(dot(d_w, d_w)); hits compacted in ray order into dst_slot, then cloud_finish
+int mesh_scan(me_ctx *ctx, int dst_slot, const double *poses_host, long long n_poses, const double *dirs_host, long long n_dirs,
+              const me_scan_params *p, int64_t *pose_hits_host, me_scan_out *out);
+int mesh_scan_fetch(me_ctx *ctx, int slot, int64_t *ray_id_host);
+// point p, origin o: d = p - o, len = sqrt(dot(d, d)); seen iff min_range <= len <= max_range and (len <= tolerance or no any-hit of
+// the ray (o, d) with t in [0, (len - tolerance) / len]); writes the slot's keep mask (outlier_keep)
+int cloud_visibility(me_ctx *ctx, int slot, const double *origins_host, long long n_origins, const me_vis_params *p, me_vis_out *out);
+int cloud_visibility_fetch(me_ctx *ctx, int slot, int32_t *n_seen_host, int32_t *first_seen_host);
 // ---- me_recon.hip ----
 int reconstruct(me_ctx *ctx, int slot, const me_recon_params *p, me_recon_out *out);
 int isosurface(me_ctx *ctx, const int32_t *node_ijk_host, const double *f_host, const uint8_t *valid_host, long long n_nodes, double voxel,

@@ -346,6 +346,8 @@ void mesh_drop_results(me_ctx *ctx) {
     ctx->cloud[1].mesh_have = false;
     ctx->cloud[0].mesh_sign_have = false;
     ctx->cloud[1].mesh_sign_have = false;
+    ctx->cloud[0].vis_have = false;  // (the visibility of a slot's points was cast against this mesh: me_ray.hip)
+    ctx->cloud[1].vis_have = false;
     ctx->mesh->topo_have = false;  // (the topology and the pseudo-normals go with the mesh they were built from: me_meshsign.hip)
 }
 

@@ -1,6 +1,6 @@
 // me_philox.hpp — counter-based randomness shared by the device passes: Philox4x64-10 (Salmon et al., SC'11; Random123
 // philox4x64_R with R = 10), key (seed, 0).  Counter word 1 names the user (include/mapeval_hip.h): 1-3 me_perturb_cloud,
-// 4 me_global_register, 5 me_segment_planes.
+// 4 me_global_register, 5 me_segment_planes, 6 me_mesh_scan (range noise).
 #pragma once
 
 #include <hip/hip_runtime.h>

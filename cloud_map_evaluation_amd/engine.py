@@ -1202,6 +1202,98 @@ class Engine:
             rep["sampled"] = self.error_report(thresholds, quantiles)
         return rep
 
+    # ---- rays against the resident mesh: casts, the simulated sensor, observability (me_ray.hip) ----
+    def mesh_raycast(self, origins, directions, t_min: float = 0.0, t_max: float = math.inf, any_hit: bool = False) -> dict:
+        """me_mesh_raycast: rays (origins[i], directions[i]) against the resident mesh, t in units of |direction| within [t_min, t_max].
+        Returns per ray t (+inf on a miss), tri (the caller's triangle index, -1 on a miss), u, v (barycentric weights of B and C) and
+        flags (RAY_HIT, RAY_BACKFACE, RAY_INVALID), plus the totals n_rays, n_hit, n_backface, n_invalid, min_t, max_t.  The closest hit
+        is the smallest (t, triangle index); any_hit=True only answers whether a hit exists (flags; t, tri, u, v carry the miss values)."""
+        o = np.ascontiguousarray(origins, dtype=np.float64)
+        d = np.ascontiguousarray(directions, dtype=np.float64)
+        if o.ndim != 2 or o.shape[1] != 3 or d.shape != o.shape:
+            raise ValueError("expected (N,3) origins and directions of the same shape")
+        n = int(o.shape[0])
+        res = {"t": np.empty(n, np.float64), "tri": np.empty(n, np.int32), "u": np.empty(n, np.float64), "v": np.empty(n, np.float64),
+               "flags": np.empty(n, np.uint8)}
+        out = _lib.RayOut()
+        self._ck(self._L.me_mesh_raycast(self._ctx, _addr(o), _addr(d), n, float(t_min), float(t_max),
+                                         _lib.ME_RAY_ANY if any_hit else _lib.ME_RAY_CLOSEST, _addr(res["t"]), _addr(res["tri"]),
+                                         _addr(res["u"]), _addr(res["v"]), _addr(res["flags"]), C.byref(out)))
+        res.update({f: getattr(out, f) for f, _ in out._fields_})
+        return res
+
+    def mesh_scan(self, dst_slot: int, poses, directions, min_range: float = 0.0, max_range: float = math.inf, noise_std: float = 0.0,
+                  seed: int = 0, fetch: bool = False) -> dict:
+        """me_mesh_scan: a range sensor with the beam table `directions` (D,3, sensor frame) at every pose (M,4,4 sensor -> world) scans the
+        resident mesh; the hits, in ray order (ray = pose * D + beam), become the cloud of dst_slot.  Returns n_rays, n_hit, n_backface,
+        pose_hits (M,) and with fetch=True ray_id (int64 per point of the slot)."""
+        P = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 16)
+        d = np.ascontiguousarray(directions, dtype=np.float64)
+        if d.ndim != 2 or d.shape[1] != 3:
+            raise ValueError("expected (D,3) directions")
+        p = _lib.ScanParams()
+        p.min_range, p.max_range, p.noise_std, p.seed = float(min_range), float(max_range), float(noise_std), int(seed) & ((1 << 64) - 1)
+        out = _lib.ScanOut()
+        hits = np.zeros(P.shape[0], np.int64)
+        self._ck(self._L.me_mesh_scan(self._ctx, int(dst_slot), _addr(P), int(P.shape[0]), _addr(d), int(d.shape[0]), C.byref(p), _addr(hits),
+                                      C.byref(out)))
+        self._held.pop(int(dst_slot), None)
+        res = {"n_rays": int(out.n_rays), "n_hit": int(out.n_hit), "n_backface": int(out.n_backface), "pose_hits": hits}
+        if fetch:
+            res["ray_id"] = self.mesh_scan_fetch(dst_slot) if res["n_hit"] > 0 else np.zeros(0, np.int64)
+        return res
+
+    def mesh_scan_fetch(self, slot: int) -> np.ndarray:
+        """me_mesh_scan_fetch: the ray id of every point of a scanned slot, cloud order (pose = ray_id // D)."""
+        ids = np.empty(self.size(slot), np.int64)
+        self._ck(self._L.me_mesh_scan_fetch(self._ctx, int(slot), _addr(ids)))
+        return ids
+
+    def cloud_visibility(self, slot: int, origins, max_range: float = math.inf, min_range: float = 0.0, tolerance: float = 0.0,
+                         first_only: bool = False, fetch: bool = False):
+        """me_cloud_visibility: which points of the slot some origin (M,3) sees past the resident mesh — in range, and no triangle on the
+        segment origin -> point short of `tolerance` metres before the point.  Returns n_points, n_visible, n_in_range, n_tests and
+        visible_share; the slot's keep mask becomes "visible" (select_kept_into copies the observable points).  With fetch=True also
+        the dict of visibility_fetch."""
+        o = np.ascontiguousarray(origins, dtype=np.float64)
+        if o.ndim != 2 or o.shape[1] != 3:
+            raise ValueError("expected (M,3) origins")
+        p = _lib.VisParams()
+        p.min_range, p.max_range, p.tolerance, p.first_only = float(min_range), float(max_range), float(tolerance), 1 if first_only else 0
+        out = _lib.VisOut()
+        self._ck(self._L.me_cloud_visibility(self._ctx, int(slot), _addr(o), int(o.shape[0]), C.byref(p), C.byref(out)))
+        res = {f: int(getattr(out, f)) for f, _ in out._fields_}
+        res["visible_share"] = res["n_visible"] / res["n_points"] if res["n_points"] > 0 else 0.0
+        return (res, self.visibility_fetch(slot)) if fetch else res
+
+    def visibility_fetch(self, slot: int) -> dict:
+        """me_cloud_visibility_fetch -> n_seen (int32, origins that see the point) and first_seen (int32, the first of them, -1), cloud order."""
+        n = self.size(slot)
+        d = {"n_seen": np.empty(n, np.int32), "first_seen": np.empty(n, np.int32)}
+        self._ck(self._L.me_cloud_visibility_fetch(self._ctx, int(slot), _addr(d["n_seen"]), _addr(d["first_seen"])))
+        return d
+
+    def observable_report(self, origins, thresholds, tolerance: float = 0.05, max_range: float = math.inf, min_range: float = 0.0,
+                          quantiles=(0.5, 0.9, 0.95, 0.99)) -> dict:
+        """Completeness against the ground truth a sensor at `origins` could have seen.  In order: visibility of the ground-truth slot
+        (first_only), its visible points into a private engine beside a copy of the map, nn1 both ways there and here, error_report
+        on both.  Returns "all" (every ground-truth point), "observable" (the visible ones), "visibility" (the totals) and
+        visible_share.  This engine's clouds are left as they were (their 1-NN results are renewed, the ground truth's keep mask is
+        the visibility's)."""
+        vis = self.cloud_visibility(ME_SLOT_GT, origins, max_range=max_range, min_range=min_range, tolerance=tolerance, first_only=True)
+        self.nn1(ME_SLOT_EST, ME_SLOT_GT, fetch=False)
+        self.nn1(ME_SLOT_GT, ME_SLOT_EST, fetch=False)
+        rep_all = self.error_report(thresholds, quantiles)
+        if vis["n_visible"] == 0:
+            raise MapEvalError("[-3] observable_report: no ground-truth point is visible from the origins")
+        with Engine(self.device) as priv:
+            self.select_kept_into(ME_SLOT_GT, priv, ME_SLOT_GT)
+            priv.upload(ME_SLOT_EST, self.download(ME_SLOT_EST))
+            priv.nn1(ME_SLOT_EST, ME_SLOT_GT, fetch=False)
+            priv.nn1(ME_SLOT_GT, ME_SLOT_EST, fetch=False)
+            rep_obs = priv.error_report(thresholds, quantiles)
+        return {"all": rep_all, "observable": rep_obs, "visibility": vis, "visible_share": vis["visible_share"]}
+
     # ---- neighbour lists between the resident clouds (me_search.hip) ----
     def _query_mask(self, query_slot: int, mask):
         if mask is None:

@@ -19,6 +19,7 @@
 #include <cerrno>
 
 #include "pcd_io.hpp"
+#include "tum_io.hpp"
 #include "yaml_lite.hpp"
 
 namespace fs = std::filesystem;
@@ -527,6 +528,36 @@ Param loadParametersFromYAML(const std::string &yaml_file_path) {
         if (param.evaluate_noised_gt_) throw std::runtime_error("evaluate_mesh: not with evaluate_noised_gt");
         if (param.num_gpus > 1) throw std::runtime_error("evaluate_mesh: single GPU only (num_gpus must be 1)");
     }
+    // completeness against the observable ground truth (me_cloud_visibility from the poses of a trajectory)
+    if (config.has("evaluate_observable")) param.evaluate_observable = config.as_bool("evaluate_observable");
+    if (config.has("trajectory_path")) param.trajectory_path = config.as_string("trajectory_path");
+    const double obs_stride = config.has("observable_pose_stride") ? config.as_double("observable_pose_stride") : 1.0;
+    const bool obs_stride_ok = obs_stride >= 1.0 && obs_stride <= 2147483647.0 && obs_stride == std::floor(obs_stride);
+    if (obs_stride_ok) param.observable_pose_stride = (int) obs_stride;  // (judged below, with the stage on)
+    if (config.has("observable_max_range")) param.observable_max_range = config.as_double("observable_max_range");
+    if (!(param.observable_max_range > 0)) param.observable_max_range = INFINITY;
+    if (config.has("observable_tolerance")) param.observable_tolerance = config.as_double("observable_tolerance");
+    const bool obs_not_a_list =
+        config.has("observable_thresholds") && (!config.at("observable_thresholds").scalar.empty() || !config.at("observable_thresholds").rows.empty());
+    if (config.has("observable_thresholds")) {
+        for (const auto &v : config.at("observable_thresholds").seq)
+            param.observable_thresholds.push_back(yaml_lite::Document::to_double(v, "observable_thresholds"));
+    } else {
+        param.observable_thresholds.assign(param.trunc_dist_.begin(), param.trunc_dist_.end());
+    }
+    if (param.evaluate_observable) {
+        if (param.num_gpus > 1) throw std::runtime_error("evaluate_observable: single GPU only (num_gpus must be 1)");
+        if (param.trajectory_path.empty()) throw std::runtime_error("trajectory_path: required with evaluate_observable");
+        if (param.gt_mesh_path.empty() && !param.evaluate_mesh)
+            throw std::runtime_error("evaluate_observable: needs a mesh (gt_mesh_path, or evaluate_mesh: true for the reconstructed ground-truth mesh)");
+        if (!obs_stride_ok) throw std::runtime_error("observable_pose_stride: must be an integer >= 1");
+        if (!(param.observable_tolerance >= 0) || !std::isfinite(param.observable_tolerance))
+            throw std::runtime_error("observable_tolerance: must be finite and >= 0");
+        if (obs_not_a_list) throw std::runtime_error("observable_thresholds: must be a list [a, b, ...]");
+        if (param.observable_thresholds.size() > ME_ERRDIST_MAX_THRESHOLDS) throw std::runtime_error("observable_thresholds: at most 8 values");
+        for (const double t : param.observable_thresholds)
+            if (!(t >= 0.0) || !std::isfinite(t)) throw std::runtime_error("observable_thresholds: every value must be finite and >= 0");
+    }
     return param;
 }
 
@@ -616,6 +647,18 @@ std::string paramToJson(const Param &p) {
     o << ", \"evaluate_voxel_distances\": " << b(p.evaluate_voxel_distances) << ", \"mmd_sigmas\": [";
     for (size_t i = 0; i < p.mmd_sigmas.size(); ++i) o << (i ? ", " : "") << p.mmd_sigmas[i];
     o << "], \"mmd_max_points\": " << p.mmd_max_points << ", \"voxel_distance_eig_floor\": " << p.voxel_distance_eig_floor;
+    o << ", \"evaluate_observable\": " << b(p.evaluate_observable) << ", \"trajectory_path\": \"";
+    for (const char c : p.trajectory_path) {
+        if (c == '"' || c == '\\') o << '\\' << c;
+        else if ((unsigned char) c < 0x20) o << ' ';
+        else o << c;
+    }
+    o << "\", \"observable_pose_stride\": " << p.observable_pose_stride << ", \"observable_max_range\": ";
+    if (std::isinf(p.observable_max_range)) o << "Infinity";
+    else o << p.observable_max_range;
+    o << ", \"observable_tolerance\": " << p.observable_tolerance << ", \"observable_thresholds\": [";
+    for (size_t i = 0; i < p.observable_thresholds.size(); ++i) o << (i ? ", " : "") << p.observable_thresholds[i];
+    o << "]";
     o << "}";
     return o.str();
 }
@@ -710,7 +753,9 @@ int MapEval::process() {
     if (mesh && comm_) return fail("evaluate_mesh_distance: single GPU only (num_gpus must be 1)");
     const bool recon = param_.evaluate_mesh;  // (on resident clouds as loaded, first of all)
     if (recon && (comm_ || noised)) return fail("evaluate_mesh: single GPU only (num_gpus must be 1), and not with evaluate_noised_gt");
-    if (one_call && !noised && !filter && !mpv && !planes && !mom && !surf && !m3c2 && !mesh && !recon && !(param_.downsample_size > 0)) {
+    const bool obs = param_.evaluate_observable;  // (on resident clouds, the map moved by initial_matrix for it alone, like the mesh stage)
+    if (obs && comm_) return fail("evaluate_observable: single GPU only (num_gpus must be 1)");
+    if (one_call && !noised && !filter && !mpv && !planes && !mom && !surf && !m3c2 && !mesh && !obs && !recon && !(param_.downsample_size > 0)) {
         file_result << std::fixed << std::setprecision(15) << "Estimated-Ground Truth point count: " << map_3d_->size() << " / "
                     << gt_3d_->size() << std::endl;
         if (param_.enable_debug)
@@ -768,7 +813,7 @@ int MapEval::process() {
                 return fail(me_last_error(ctx_));
         }
     }
-    if (m3c2 || mesh) {
+    if (m3c2 || mesh || obs) {
         // (the mesh stage, like M3C2, moves the map and may replace the ground-truth slot by the mesh's sample: same restoration)
         // FIRST of the stages on the resident clouds: it moves the map, replaces both clouds' normals and re-indexes both at the
         // cylinder's bounding radius.  Both clouds are then uploaded again from the host's copies (the clouds as loaded: the map's is
@@ -779,6 +824,13 @@ int MapEval::process() {
             me_upload_cloud(ctx_, ME_SLOT_EST, map_3d_->points_.data(), (int64_t) map_3d_->size(), nullptr, param_.nn_radius_) != ME_OK)
             return fail(me_last_error(ctx_));
         if (mesh && computeMeshDistance() != 0) return -1;
+        if (obs) {  // (after the stages above, from the clouds as loaded: they moved the map and may have replaced the ground-truth slot)
+            if ((m3c2 || mesh) &&
+                (me_upload_cloud(ctx_, ME_SLOT_GT, gt_3d_->points_.data(), (int64_t) gt_3d_->size(), nullptr, param_.nn_radius_) != ME_OK ||
+                 me_upload_cloud(ctx_, ME_SLOT_EST, map_3d_->points_.data(), (int64_t) map_3d_->size(), nullptr, param_.nn_radius_) != ME_OK))
+                return fail(me_last_error(ctx_));
+            if (computeObservable() != 0) return -1;
+        }
         if (me_upload_cloud(ctx_, ME_SLOT_GT, gt_3d_->points_.data(), (int64_t) gt_3d_->size(), nullptr, param_.nn_radius_) != ME_OK ||
             me_upload_cloud(ctx_, ME_SLOT_EST, map_3d_->points_.data(), (int64_t) map_3d_->size(), nullptr, param_.nn_radius_) != ME_OK)
             return fail(me_last_error(ctx_));
@@ -2065,6 +2117,92 @@ int MapEval::computeMeshDistance() {
     return 0;
 }
 
+// evaluate_observable: the ground-truth mesh (gt_mesh_path as it is in the file, or the ground truth's reconstruction), the positions of
+// trajectory_path (every observable_pose_stride-th), the map where initial_matrix puts it; me_cloud_visibility of the ground truth
+// (first_only), me_nn1 both ways and the ground truth's error distribution at the thresholds (all points); the visible points into a
+// private context beside a copy of the moved map (me_outlier_select_into), the same there (observable points).
+int MapEval::computeObservable() {
+    auto bad = [&](const std::string &m) { return fail("evaluate_observable: " + m); };
+    std::vector<double> vx, traj, org;
+    std::vector<int32_t> tri;
+    std::string err;
+    if (param_.gt_mesh_path.empty()) {  // the ground truth's own reconstruction (computeReconstruction ran before)
+        vx = recon_vertices[ME_SLOT_GT];
+        tri = recon_triangles[ME_SLOT_GT];
+        if (tri.empty()) return bad("the reconstruction of the ground truth has no triangle (mesh_voxel_size, mesh_min_points)");
+    } else if (!pcio::read_ply_mesh(param_.gt_mesh_path, vx, tri, &err)) {
+        return bad(err);
+    }
+    if (!tumio::read_tum_positions(param_.trajectory_path, traj, &err)) return bad(err);
+    obs_poses_file = (int64_t) (traj.size() / 3);
+    for (size_t i = 0; i < traj.size() / 3; i += (size_t) param_.observable_pose_stride) org.insert(org.end(), traj.begin() + 3 * i, traj.begin() + 3 * i + 3);
+    obs_poses = (int64_t) (org.size() / 3);
+    if (obs_poses > ME_VIS_MAX_ORIGINS)
+        return bad("the trajectory holds " + std::to_string(obs_poses) + " poses after the stride, at most 65536 are cast (observable_pose_stride)");
+    if (me_mesh_upload(ctx_, vx.data(), (int64_t) (vx.size() / 3), tri.data(), (int64_t) (tri.size() / 3), nullptr) != ME_OK)
+        return bad(me_last_error(ctx_));
+    const double *T = param_.initial_matrix_.data();
+    bool identity = true;
+    for (int i = 0; i < 16; ++i) identity = identity && (T[i] == ((i % 5 == 0) ? 1.0 : 0.0));
+    if (!identity && me_transform_cloud(ctx_, ME_SLOT_EST, T) != ME_OK) return bad(me_last_error(ctx_));
+    me_vis_params vp{};
+    vp.min_range = 0.0, vp.max_range = param_.observable_max_range, vp.tolerance = param_.observable_tolerance, vp.first_only = 1;
+    if (me_cloud_visibility(ctx_, ME_SLOT_GT, org.data(), obs_poses, &vp, &obs_vis) != ME_OK) return bad(me_last_error(ctx_));
+    if (obs_vis.n_visible == 0) return bad("no ground-truth point is visible from the trajectory");
+    me_errdist_params ep{};
+    ep.gate = -1.0;
+    ep.n_thresholds = (int32_t) param_.observable_thresholds.size();
+    for (int k = 0; k < ep.n_thresholds; ++k) ep.tau[k] = param_.observable_thresholds[(size_t) k];
+    if (me_nn1(ctx_, ME_SLOT_EST, ME_SLOT_GT, nullptr, nullptr) != ME_OK || me_nn1(ctx_, ME_SLOT_GT, ME_SLOT_EST, nullptr, nullptr) != ME_OK ||
+        me_nn_error_distribution(ctx_, ME_SLOT_GT, &ep, &obs_gt[0], nullptr) != ME_OK)
+        return bad(me_last_error(ctx_));
+    std::vector<double> moved((size_t) me_cloud_size(ctx_, ME_SLOT_EST) * 3);
+    if (me_download_cloud(ctx_, ME_SLOT_EST, moved.data()) != ME_OK) return bad(me_last_error(ctx_));
+    me_ctx *priv = me_create(param_.gpu_device, 0);
+    if (!priv) return bad(me_last_error(nullptr));
+    int64_t kept = 0;
+    const bool ok = me_outlier_select_into(ctx_, ME_SLOT_GT, priv, ME_SLOT_GT, &kept) == ME_OK &&
+                    me_upload_cloud(priv, ME_SLOT_EST, moved.data(), (int64_t) (moved.size() / 3), nullptr, param_.nn_radius_) == ME_OK &&
+                    me_nn1(priv, ME_SLOT_EST, ME_SLOT_GT, nullptr, nullptr) == ME_OK && me_nn1(priv, ME_SLOT_GT, ME_SLOT_EST, nullptr, nullptr) == ME_OK &&
+                    me_nn_error_distribution(priv, ME_SLOT_GT, &ep, &obs_gt[1], nullptr) == ME_OK;
+    const std::string perr = ok ? "" : me_last_error(priv);
+    me_destroy(priv);
+    if (!ok) return bad(perr);
+    if (me_mesh_clear(ctx_) != ME_OK) return bad(me_last_error(ctx_));
+    if (param_.dist_rank == 0)
+        std::cout << "INFO: Observable ground truth: " << obs_vis.n_visible << " of " << obs_vis.n_points << " points from " << obs_poses << " poses"
+                  << std::endl;
+    return 0;
+}
+
+// `Observable visible-share COM@t: <share> then per threshold <t> <recall over all> <recall over the observable>`; observable.txt: the
+// parameters and totals as "name value" lines, then one row per threshold: t, n_within and recall for all, the same for the observable
+void MapEval::saveObservable() {
+    const double share = obs_vis.n_points > 0 ? (double) obs_vis.n_visible / (double) obs_vis.n_points : 0.0;
+    auto recall = [](const me_errdist_out &o, size_t k) { return o.n_used > 0 ? (double) o.n_within[k] / (double) o.n_used : 0.0; };
+    file_result << std::fixed << std::setprecision(5) << "Observable visible-share COM@t: " << share;
+    for (size_t k = 0; k < param_.observable_thresholds.size(); ++k)
+        file_result << " " << param_.observable_thresholds[k] << " " << recall(obs_gt[0], k) << " " << recall(obs_gt[1], k);
+    file_result << std::endl;
+    const std::string path = results_subfolder + "observable.txt";
+    FILE *f = std::fopen(path.c_str(), "w");
+    if (!f) {
+        fail("cannot write " + path);
+        return;
+    }
+    std::fprintf(f, "trajectory_path %s\nposes_in_file %lld\npose_stride %d\nposes_used %lld\n", param_.trajectory_path.c_str(),
+                 (long long) obs_poses_file, param_.observable_pose_stride, (long long) obs_poses);
+    std::fprintf(f, "max_range %.17g\ntolerance %.17g\n", param_.observable_max_range, param_.observable_tolerance);
+    std::fprintf(f, "n_points %lld\nn_visible %lld\nn_in_range %lld\nn_tests %lld\nvisible_share %.17g\n", (long long) obs_vis.n_points,
+                 (long long) obs_vis.n_visible, (long long) obs_vis.n_in_range, (long long) obs_vis.n_tests, share);
+    std::fprintf(f, "n_used_all %lld\nn_used_observable %lld\n", (long long) obs_gt[0].n_used, (long long) obs_gt[1].n_used);
+    std::fprintf(f, "# threshold n_within_all recall_all n_within_observable recall_observable\n");
+    for (size_t k = 0; k < param_.observable_thresholds.size(); ++k)
+        std::fprintf(f, "%.17g %lld %.17g %lld %.17g\n", param_.observable_thresholds[k], (long long) obs_gt[0].n_within[k], recall(obs_gt[0], k),
+                     (long long) obs_gt[1].n_within[k], recall(obs_gt[1], k));
+    if (std::fclose(f) != 0) fail("writing " + path + " failed");
+}
+
 // evaluate_mesh: on each cloud as loaded, me_radius_normals at mesh_normal_radius (normal_min_points neighbours) turned towards
 // mesh_viewpoint, or towards the centre of the cloud's bounding box, then me_reconstruct; the meshes are kept on the host for the writers
 // and for computeMeshDistance.  With mesh_orient: propagate the radius normals are left unoriented (no viewpoint) and me_orient_normals
@@ -2291,6 +2429,7 @@ void MapEval::saveRegistrationResults() {
     if (param_.evaluate_m3c2) saveM3C2();
     if (param_.evaluate_mesh_distance) saveMeshDistance();
     if (param_.evaluate_mesh) saveReconstruction();
+    if (param_.evaluate_observable) saveObservable();
     if (param_.evaluate_deformation) saveDeformation();
     if (param_.evaluate_voxel_distances) saveVoxelDistances();
     file_result << std::fixed << std::setprecision(5) << "VMD: " << vmd << std::endl;

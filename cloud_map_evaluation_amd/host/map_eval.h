@@ -188,6 +188,16 @@ struct Param {
     std::string mesh_orient = "viewpoint";     // `mesh_orient: viewpoint | propagate`: propagate = me_orient_normals after unoriented radius normals
     int mesh_orient_k = 12;                    // `mesh_orient_k`: neighbours of the orientation graph, 1 .. 39
     bool mesh_orient_inward = false;           // `mesh_orient_inward`: the roots are turned against +z instead of towards it
+    // completeness against the OBSERVABLE ground truth (optional keys; no reference counterpart): the ground-truth points that some pose
+    // of `trajectory_path` sees past the ground-truth mesh (gt_mesh_path, or the reconstruction of evaluate_mesh) by me_cloud_visibility,
+    // and the recall of the map (moved by initial_matrix) over all and over the observable ground-truth points; afterwards both clouds are
+    // uploaded again as loaded (single GPU); one line before `VMD`, and observable.txt
+    bool evaluate_observable = false;          // `evaluate_observable:`
+    std::string trajectory_path;               // `trajectory_path:` TUM text `t x y z qx qy qz qw` (required with evaluate_observable; positions only)
+    int observable_pose_stride = 1;            // `observable_pose_stride:` every k-th pose, >= 1
+    double observable_max_range = INFINITY;    // `observable_max_range:` metres (absent or <= 0: inf)
+    double observable_tolerance = 0.05;        // `observable_tolerance:` metres short of the point at which the segment ends, >= 0
+    std::vector<double> observable_thresholds; // `observable_thresholds: [..]` recall thresholds, at most 8 (default: accuracy_level)
     int dist_rank = 0;              // (set by the launcher, not a YAML key)
     void printParam() const;
 };
@@ -241,6 +251,8 @@ public:
     void saveVoxelDistances();                              // its two result lines and voxel_distances.txt
     int computeMeshDistance();                              // evaluate_mesh_distance: me_mesh_distance of the moved map (no reference counterpart)
     void saveMeshDistance();                                // its two result lines and mesh_distance.txt
+    int computeObservable();                                // evaluate_observable: me_cloud_visibility of the ground truth, recall for all / observable points
+    void saveObservable();                                  // its result line and observable.txt
     int computeReconstruction();                            // evaluate_mesh: radius normals + me_reconstruct on both clouds as loaded
     void saveReconstruction();                              // gt_mesh.ply, est_mesh.ply, reconstruction.txt
     void saveErrorDistribution();                           // its three result lines and error_distribution.txt
@@ -282,6 +294,9 @@ public:
     std::vector<double> mesh_quantile;
     me_errdist_out mesh_sampled[2] = {};        // ... with mesh_sample_points: 1-NN error of the map in the sample and the reverse
     double mesh_prf[ME_MESH_MAX_THRESHOLDS][3] = {};
+    me_vis_out obs_vis = {};                    // evaluate_observable: the visibility totals, the poses used, the ground truth's error
+    int64_t obs_poses = 0, obs_poses_file = 0;  // distribution at the thresholds over all points [0] and over the observable ones [1]
+    me_errdist_out obs_gt[2] = {};
     me_recon_out recon_out[2] = {};             // evaluate_mesh: per slot the counts, the normals' info, the viewpoint used and the mesh
     me_radius_normals_out recon_normals[2] = {};
     double recon_viewpoint[2][3] = {};

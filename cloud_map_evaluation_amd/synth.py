@@ -274,3 +274,23 @@ def heightfield_mesh(nx: int, ny: int, step: float, amplitude: float, seed: int 
     v10, v01, v11 = v00 + ny, v00 + 1, v00 + ny + 1
     triangles = np.stack([np.stack([v00, v10, v11], -1), np.stack([v00, v11, v01], -1)], 1).reshape(-1, 3).astype(np.int32)
     return np.ascontiguousarray(vertices), np.ascontiguousarray(triangles)
+
+
+def lidar_directions(n_beams: int, n_azimuth: int, fov_lo_deg: float, fov_hi_deg: float):
+    """The beam table of a spinning LiDAR in its own frame (x forward, z up) for Engine.mesh_scan: (n_beams * n_azimuth, 3) float64 unit
+    vectors, row a * n_beams + b = azimuth step a (2 pi a / n_azimuth about z, from +x towards +y), beam b at the elevation of fov_lo_deg
+    ... fov_hi_deg in n_beams equal steps (one beam: their mean).  Unit length to one ulp (normalised after the trigonometry)."""
+    import numpy as np
+
+    if n_beams < 1 or n_azimuth < 1:
+        raise ValueError("lidar_directions needs n_beams >= 1 and n_azimuth >= 1")
+    if n_beams > 1:
+        el = np.deg2rad(np.linspace(float(fov_lo_deg), float(fov_hi_deg), n_beams))
+    else:
+        el = np.deg2rad(np.array([0.5 * (float(fov_lo_deg) + float(fov_hi_deg))]))
+    az = (2.0 * np.pi / n_azimuth) * np.arange(n_azimuth, dtype=np.float64)
+    ce, se = np.cos(el)[None, :], np.sin(el)[None, :]
+    d = np.stack([ce * np.cos(az)[:, None], ce * np.sin(az)[:, None], np.broadcast_to(se, (n_azimuth, n_beams))], -1).reshape(-1, 3)
+    for _ in range(2):
+        d = d / np.sqrt((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2])[:, None]
+    return np.ascontiguousarray(d)

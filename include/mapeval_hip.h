@@ -958,6 +958,94 @@ int me_mesh_topology_fetch(me_ctx *ctx, double *vertex_normal, uint8_t *vertex_f
 int me_mesh_signed_distance(me_ctx *ctx, int query_slot, const me_mesh_sign_params *p, me_mesh_sign_out *out);
 int me_mesh_signed_fetch(me_ctx *ctx, int query_slot, double *signed_d, uint8_t *flags);
 
+/* ---- rays against the resident mesh: closest hit, any hit, a simulated range sensor, observability of a cloud's points --------------- */
+/* (DESIGN.md section 4.25.  No reference counterpart: the reference has no ray.)  All against the resident mesh of the primary context
+ * (a twin sees it); ME_ERR_STATE without one.  fp64, single GPU only (slab or shard mode: ME_ERR_ARG).
+ *
+ * The ray-triangle routine is the watertight test of Woop, Benthin and Wald (2013) as ONE fixed sequence of fp64 operations, none
+ * contracted.  Per ray (o, d), INVALID (hits nothing) unless every component of o and d is finite and d is not the zero vector:
+ *   kz = argmax |d[k]| (ties: lowest k); kx = (kz+1)%3; ky = (kz+2)%3; if d[kz] < 0: swap(kx, ky)
+ *   Sx = d[kx]/d[kz]   Sy = d[ky]/d[kz]   Sz = 1/d[kz]   dd = (d0*d0 + d1*d1) + d2*d2
+ * Per triangle (A, B, C) in the caller's winding; a triangle flagged degenerate at upload never hits:
+ *   grazing gate: u = B - A, v = C - A, n = (u1*v2 - u2*v1, u2*v0 - u0*v2, u0*v1 - u1*v0), c = (n0*d0 + n1*d1) + n2*d2,
+ *     nn = (n0*n0 + n1*n1) + n2*n2; a miss if c*c < 0x1p-40 * (nn * dd)        (an incidence within ~1e-6 rad of the plane)
+ *   A' = A - o per component (likewise B', C');  Ax = A'[kx] - Sx*A'[kz]   Ay = A'[ky] - Sy*A'[kz]   (same for B, C)
+ *   U = Cx*By - Cy*Bx   V = Ax*Cy - Ay*Cx   W = Bx*Ay - By*Ax
+ *   a miss if (U < 0 || V < 0 || W < 0) && (U > 0 || V > 0 || W > 0);  det = (U + V) + W;  a miss if det == 0
+ *   T = (U*(Sz*A'[kz]) + V*(Sz*B'[kz])) + W*(Sz*C'[kz]);  t = T / det;  a hit iff t_min <= t && t <= t_max
+ *   u = V / det (weight of B), v = W / det (weight of C), BACKFACE iff det < 0.  The point is o + t d: t is in units of |d|.
+ * The edge functions are exactly antisymmetric (Qx*Py - Qy*Px of edge P->Q is the exact negative of the neighbour's): a ray across
+ * the shared edge of two consistently wound triangles hits at least one of them, unless the grazing gate drops it.
+ * Closest hit: the lexicographic minimum of (t, caller's triangle index) over the hits.  Any hit: whether a hit exists.  Neither depends
+ * on the order of the walk: the tree culls a box only when no triangle inside it can be a computed hit in the interval.
+ * (Stated limit of that cull, DESIGN.md 4.25 "Pruning": a triangle whose smallest altitude is below 2^-29 of its lateral distance from the
+ * ray may be a hit of an exhaustive loop over the routine, far off the ray, and be culled.)
+ *
+ * me_mesh_raycast: origins / dirs = host fp64 [n_rays][3], 0 <= t_min (finite) <= t_max (+inf allowed), mode ME_RAY_CLOSEST or
+ *   ME_RAY_ANY.  Every per-ray output is nullable, caller's order: t (+inf on a miss), tri (caller's index, -1 on a miss), u, v, flags
+ *   (ME_RAY_HIT, ME_RAY_BACKFACE, ME_RAY_INVALID).  ME_RAY_ANY reports ME_RAY_HIT / ME_RAY_INVALID only: t = +inf, tri = -1, u = v = 0
+ *   (the triangle the walk met first is not a result).  Totals: n_rays, n_hit, n_backface, n_invalid, min_t / max_t over the hits
+ *   (+inf / -inf without a hit and in mode ME_RAY_ANY).  Device timers "ray_cast" (closest) and "ray_occl" (any).
+ *   ME_ERR_ARG: a NULL input, n_rays outside [1, 2^31), t_min negative or not finite, t_max < t_min or NaN, an unknown mode.
+ *
+ * me_mesh_scan: the simulated sensor; no trigonometry in the library.  poses = host [n_poses][16] row-major 4x4 sensor -> world, dirs =
+ *   host [n_dirs][3] beams in the sensor frame; n_poses * n_dirs < 2^31.  Ray r = p * n_dirs + b: o = (P[3], P[7], P[11]),
+ *   d_w[k] = (P[4k]*dx + P[4k+1]*dy) + P[4k+2]*dz, len = sqrt((d_w0*d_w0 + d_w1*d_w1) + d_w2*d_w2), the closest hit with t in
+ *   [min_range / len, max_range / len].  With noise_std > 0 the hit parameter becomes t + (noise_std * z) / len, z =
+ *   sqrt(-2 ln u1) cos(2 pi u2) of Philox4x64-10 at counter (r, 6, 0, 0), key (seed, 0), u1 = ((w0 >> 11) + 1) 2^-53, u2 =
+ *   (w1 >> 11) 2^-53 (counter word 1 = 6 names this user; 0 me_mesh_sample, 1-3 me_perturb_cloud, 4 me_global_register,
+ *   5 me_segment_planes); the range gate is on the hit, not on the noised value.  Point x[k] = o[k] + t * d_w[k].  The hits become the
+ *   cloud of dst_slot IN RAY ORDER (a prefix sum of the hit flags; no atomic decides an order), as me_mesh_sample leaves a slot (the
+ *   other slot's cell size).  No hit at all: dst_slot is left holding an empty cloud (me_cloud_size 0).  pose_hits = nullable
+ *   int64[n_poses].  Device timer "scan".  ME_ERR_ARG: a NULL input, bad counts, min_range negative or not finite, max_range <
+ *   min_range, noise_std negative or not finite.
+ * me_mesh_scan_fetch: ray_id int64[N] of every point of the slot, cloud order (pose = ray / n_dirs).  ME_ERR_STATE once the slot's
+ *   points are no longer that scan's.
+ *
+ * me_cloud_visibility: origins = host [n_origins][3], n_origins <= ME_VIS_MAX_ORIGINS.  Point p, origin o_j: d = p - o_j per
+ *   component, len = sqrt((d0*d0 + d1*d1) + d2*d2).  p is IN RANGE of j iff min_range <= len <= max_range, and SEEN from j iff in range
+ *   and (len <= tolerance, or no any-hit of the ray (o_j, d) with t in [0, (len - tolerance) / len]); a non-finite p or o_j sees nothing.
+ *   Per point: n_seen (origins that see it) and first_seen (the smallest such j, -1: none); first_only = 1 stops at the first origin
+ *   that sees the point (n_seen is 0 or 1, first_seen the same).  Totals: n_points, n_visible (n_seen > 0), n_in_range (of some
+ *   origin), n_tests (segments cast; an integer sum).  The call writes the slot's keep mask (kept = visible) exactly as me_plane_keep
+ *   does: me_outlier_select_into then copies the observable points anywhere.  Device timer "ray_occl".
+ *   ME_ERR_STATE: no mesh, or no cloud in the slot.  ME_ERR_ARG: bad slot, n_origins outside [1, 65536], min_range negative or not
+ *   finite, max_range < min_range, tolerance negative or not finite, first_only not 0 or 1.
+ * me_cloud_visibility_fetch: n_seen[N], first_seen[N] in cloud order, both nullable.  The result is discarded when the slot's points
+ *   change or the slot is re-indexed, and by me_mesh_upload / me_mesh_clear / me_reconstruct_install. */
+#define ME_RAY_CLOSEST 0
+#define ME_RAY_ANY 1
+#define ME_RAY_HIT 1
+#define ME_RAY_BACKFACE 2
+#define ME_RAY_INVALID 4
+#define ME_VIS_MAX_ORIGINS 65536
+typedef struct me_ray_out {
+    int64_t n_rays, n_hit, n_backface, n_invalid;
+    double min_t, max_t;
+} me_ray_out;
+typedef struct me_scan_params {
+    double min_range, max_range; /* metres along the beam; max_range = +inf: unbounded */
+    double noise_std;            /* metres; 0 = off */
+    uint64_t seed;               /* Philox key word 0 */
+} me_scan_params;
+typedef struct me_scan_out {
+    int64_t n_rays, n_hit, n_backface;
+} me_scan_out;
+typedef struct me_vis_params {
+    double min_range, max_range, tolerance; /* metres */
+    int64_t first_only;
+} me_vis_params;
+typedef struct me_vis_out {
+    int64_t n_points, n_visible, n_in_range, n_tests;
+} me_vis_out;
+int me_mesh_raycast(me_ctx *ctx, const double *origins, const double *dirs, int64_t n_rays, double t_min, double t_max, int mode, double *t,
+                    int32_t *tri, double *u, double *v, uint8_t *flags, me_ray_out *out);
+int me_mesh_scan(me_ctx *ctx, int dst_slot, const double *poses, int64_t n_poses, const double *dirs, int64_t n_dirs,
+                 const me_scan_params *p, int64_t *pose_hits, me_scan_out *out);
+int me_mesh_scan_fetch(me_ctx *ctx, int slot, int64_t *ray_id);
+int me_cloud_visibility(me_ctx *ctx, int slot, const double *origins, int64_t n_origins, const me_vis_params *p, me_vis_out *out);
+int me_cloud_visibility_fetch(me_ctx *ctx, int slot, int32_t *n_seen, int32_t *first_seen);
+
 /* ---- surface reconstruction of a resident cloud into a triangle mesh ------------------------------------------------------------------ */
 /*   Stands in for the reference's createMeshFromPCD (map_eval.cpp:777-826, called at :194-205), a Poisson
  * solve, with a LOCAL, deterministic reconstruction whose every number has a stated definition: an implicit-moving-least-squares
