@@ -48,7 +48,7 @@ SYMBOLS = [
     "me_set_normals", "me_get_normals", "me_estimate_normals", "me_gicp_covariances", "me_get_covariances", "me_icp_lsq_sums",
     "me_icp_lsq_sums_robust", "me_icp_information",
     "me_nn1", "me_icp_p2p_sums", "me_render_distance", "me_render_entropy", "me_nn_stats", "me_nn_partial_sums", "me_nn_sigma_sums", "me_nn_finalize", "me_chamfer",
-    "me_mme", "me_voxel_gaussians", "me_voxel_metrics", "me_voxel_deformation", "me_voxel_deformation_fetch", "me_voxel_distances", "me_awd_scs", "me_w2_batch", "me_scs_table", "me_run_suite", "me_run_suite_from", "me_mme_fetch",
+    "me_mme", "me_voxel_gaussians", "me_voxel_metrics", "me_voxel_deformation", "me_voxel_deformation_fetch", "me_voxel_distances", "me_voxel_transport", "me_awd_scs", "me_w2_batch", "me_scs_table", "me_run_suite", "me_run_suite_from", "me_mme_fetch",
     "me_set_voxel_hint", "me_cell_table_fetch", "me_timers_enable", "me_timers_reset", "me_timer_get",
 ]
 
@@ -113,6 +113,34 @@ class VoxDistOut(C.Structure):
         ("mean_mmd", C.c_double * 4),
         ("mean_mmd2_u", C.c_double * 4),
         ("mean_gauss", C.c_double * 4),
+    ]
+
+
+class VoxTransParams(C.Structure):
+    _fields_ = [
+        ("voxel_size", C.c_double),
+        ("min_pts", C.c_int32),
+        ("n_dir", C.c_int32),
+        ("n_eps", C.c_int32),
+        ("reserved", C.c_int32),
+        ("max_points", C.c_int64),
+    ]
+
+
+class VoxTransOut(C.Structure):
+    _fields_ = [
+        ("n_rows", C.c_int64),
+        ("n_rows_subsampled", C.c_int64),
+        ("n_pairs", C.c_int64),
+        ("n_used_est", C.c_int64),
+        ("n_used_gt", C.c_int64),
+        ("max_marginal_row", C.c_int64),
+        ("mean_sw2", C.c_double),
+        ("mean_max_sw2", C.c_double),
+        ("mean_s", C.c_double),
+        ("mean_sinkhorn", C.c_double),
+        ("mean_marginal_err", C.c_double),
+        ("max_marginal_err", C.c_double),
     ]
 
 class IcpSums(C.Structure):
@@ -761,6 +789,8 @@ def load():
         getattr(L, f).restype = C.c_int
     L.me_voxel_distances.argtypes = [vp, C.POINTER(VoxDistParams), ip, ip, ip, dp, dp, dp, C.POINTER(C.c_int64), C.POINTER(VoxDistOut)]
     L.me_voxel_distances.restype = C.c_int
+    L.me_voxel_transport.argtypes = [vp, C.POINTER(VoxTransParams), dp, dp, ip, ip, ip, dp, dp, dp, dp, C.POINTER(C.c_int64), C.POINTER(VoxTransOut)]
+    L.me_voxel_transport.restype = C.c_int
     L.me_awd_scs.argtypes = [vp, C.c_double, C.c_int, C.c_int, dp, dp, C.POINTER(C.c_int64), C.POINTER(C.c_double),
                              C.POINTER(C.c_double), dp]
     L.me_run_suite.argtypes = [vp, C.POINTER(SuiteParams), C.POINTER(SuiteOut)]

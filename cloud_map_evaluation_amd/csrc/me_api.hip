@@ -760,6 +760,13 @@ int me_voxel_distances(me_ctx *ctx, const me_voxdist_params *p, int32_t *keys, i
     return me::voxel_distances(ctx, p, keys, n_pop, n_used, ksum, mmd2, gauss, n_rows, out);
 }
 
+int me_voxel_transport(me_ctx *ctx, const me_voxtrans_params *p, const double *directions, const double *eps_schedule, int32_t *keys,
+                       int32_t *n_pop, int32_t *n_used, double *sliced, double *sinkhorn, double *per_direction, double *potentials,
+                       int64_t *n_rows, me_voxtrans_out *out) {
+    if (!ctx) return ME_ERR_ARG;
+    return me::voxel_transport(ctx, p, directions, eps_schedule, keys, n_pop, n_used, sliced, sinkhorn, per_direction, potentials, n_rows, out);
+}
+
 int me_voxel_partials(me_ctx *ctx, int slot, double voxel_size, int32_t *keys, int32_t *npts, double *mu, double *m2,
                       int64_t *n_voxels) {
     if (!ctx) return ME_ERR_ARG;

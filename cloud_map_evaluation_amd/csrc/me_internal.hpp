@@ -776,6 +776,10 @@ int voxel_deformation_fetch(me_ctx *ctx, int qslot, int32_t *keys, int64_t *n_pa
 // ---- me_voxdist.hip ----
 int voxel_distances(me_ctx *ctx, const me_voxdist_params *p, int32_t *keys, int32_t *n_pop, int32_t *n_used, double *ksum, double *mmd2,
                     double *gauss, int64_t *n_rows, me_voxdist_out *out);
+// ---- me_transport.hip ----
+int voxel_transport(me_ctx *ctx, const me_voxtrans_params *p, const double *directions, const double *eps_schedule, int32_t *keys,
+                    int32_t *n_pop, int32_t *n_used, double *sliced, double *sinkhorn, double *per_direction, double *potentials,
+                    int64_t *n_rows, me_voxtrans_out *out);
 
 // ---- shared device helpers ----
 #ifdef __HIPCC__

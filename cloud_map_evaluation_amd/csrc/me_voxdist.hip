@@ -26,19 +26,12 @@
 
 #include "me_horn.hpp"
 #include "me_internal.hpp"
-#include "me_point_order.hpp"
 #include "me_reduce.hpp"
-#include "me_vox_rows.hpp"
-
-#ifndef ME_TUNE_VOXDIST_TILE
-#define ME_TUNE_VOXDIST_TILE 256  // points per side of a pair tile = lanes of its workgroup (a multiple of 64)
-#endif
+#include "me_vd_rows.hpp"  // passes 0 - 2, shared with me_transport.hip
 
 namespace me {
 namespace {
 
-constexpr int kVdT = ME_TUNE_VOXDIST_TILE;
-static_assert(kVdT % 64 == 0 && kVdT >= 64 && kVdT <= 1024, "a tile is a whole number of wavefronts of one workgroup");
 constexpr int kVdBlocks = 1024;       // blocks of the totals pass at most; part of the order
 constexpr int kVdND = 12, kVdNI = 2;  // totals: mmd [4], mmd2_u [4], gauss [4] | rows sub-sampled, pairs
 typedef RedBufs<kVdND, kVdNI> VdRed;
@@ -46,146 +39,6 @@ typedef RedBufs<kVdND, kVdNI> VdRed;
 struct VdGamma {
     double g[4];
 };
-
-// per row: what the later passes read
-struct VdRows {
-    int *ei, *gi;            // the row's voxel in either table
-    unsigned int *start;     // [M][2] first entry of the voxel in the cloud's own order (est, gt)
-    int *stride;             // [M][2]
-    int *pop, *used;         // [M][2] each
-    long long *pairs;        // [M]
-    long long *cnt;          // [3][M + 1]: used est, used gt, tiles -> (in place) their exclusive prefix sums, the totals at [M]
-};
-
-__device__ __forceinline__ long long vd_tri(long long t) { return t * (t + 1) / 2; }
-
-// match[i] = 1 iff est voxel i has a ground-truth voxel of the same key and both populations are >= min_pts (k_join of me_voxel.hip)
-__global__ void __launch_bounds__(256)
-k_vd_join(const unsigned long long *__restrict__ ekey, const int *__restrict__ en, long long Ve, const unsigned long long *__restrict__ gkey,
-          const int *__restrict__ gn, long long Vg, int min_pts, int *__restrict__ gi_out, unsigned int *__restrict__ match) {
-    const long long i = (long long) blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= Ve) return;
-    const unsigned long long k = ekey[i];
-    long long lo = 0, hi = Vg;
-    while (lo < hi) {
-        const long long mid = (lo + hi) >> 1;
-        if (gkey[mid] < k) lo = mid + 1;
-        else hi = mid;
-    }
-    const bool found = lo < Vg && gkey[lo] == k;
-    gi_out[i] = found ? (int) lo : -1;
-    match[i] = (found && en[i] >= min_pts && gn[lo] >= min_pts) ? 1u : 0u;
-}
-
-__device__ __forceinline__ unsigned int vd_lower_bound(const unsigned long long *__restrict__ a, long long n, unsigned long long k) {
-    long long lo = 0, hi = n;
-    while (lo < hi) {
-        const long long mid = (lo + hi) >> 1;
-        if (a[mid] < k) lo = mid + 1;
-        else hi = mid;
-    }
-    return (unsigned int) lo;
-}
-
-// the stride rule: every s-th point of the voxel's list, s = ceil(n / max_points), ceil(n / s) of them
-__device__ __forceinline__ void vd_stride(int n, long long max_points, int &s, int &used) {
-    s = 1;
-    if (max_points > 0 && (long long) n > max_points) s = (int) (((long long) n + max_points - 1) / max_points);
-    used = (n + s - 1) / s;
-}
-
-__global__ void __launch_bounds__(256)
-k_vd_rows(const unsigned int *__restrict__ match, const unsigned int *__restrict__ mpos, const int *__restrict__ gi, long long Ve,
-          const unsigned long long *__restrict__ ekey, const int *__restrict__ en, const int *__restrict__ gn,
-          const unsigned long long *__restrict__ skey_e, long long n_e, const unsigned long long *__restrict__ skey_g, long long n_g,
-          long long max_points, long long M, VdRows R, int *__restrict__ keys3) {
-    const long long i = (long long) blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= Ve || !match[i]) return;
-    const long long r = mpos[i];
-    const int g = gi[i];
-    const unsigned long long key = ekey[i];
-    int kx, ky, kz;
-    unpack_key(key, kx, ky, kz);
-    keys3[3 * r] = kx, keys3[3 * r + 1] = ky, keys3[3 * r + 2] = kz;
-    R.ei[r] = (int) i;
-    R.gi[r] = g;
-    const int pe = en[i], pg = gn[g];
-    int se, sg, ue, ug;
-    vd_stride(pe, max_points, se, ue);
-    vd_stride(pg, max_points, sg, ug);
-    R.start[2 * r] = vd_lower_bound(skey_e, n_e, key);
-    R.start[2 * r + 1] = vd_lower_bound(skey_g, n_g, key);
-    R.stride[2 * r] = se, R.stride[2 * r + 1] = sg;
-    R.pop[2 * r] = pe, R.pop[2 * r + 1] = pg;
-    R.used[2 * r] = ue, R.used[2 * r + 1] = ug;
-    const long long n = ue, m = ug;
-    R.pairs[r] = (n * (n - 1) / 2 + m * (m - 1) / 2) + n * m;
-    const long long ti = (n + kVdT - 1) / kVdT, tj = (m + kVdT - 1) / kVdT;
-    R.cnt[r] = n;
-    R.cnt[(M + 1) + r] = m;
-    R.cnt[2 * (M + 1) + r] = (vd_tri(ti) + vd_tri(tj)) + ti * tj;
-}
-
-// ONE block: the three rows of cnt ([3][M + 1]) -> their exclusive prefix sums in place, the totals in entry M.  Thread t scans the
-// chunk [t c, (t + 1) c), thread 0 the 256 chunk totals.
-__global__ void __launch_bounds__(256)
-k_vd_scan(long long *__restrict__ cnt, long long M) {
-    __shared__ long long s_tot[256];
-    const long long c = (M + 255) / 256;
-    const long long b = (long long) threadIdx.x * c, e = b + c < M ? b + c : M;
-    for (int q = 0; q < 3; ++q) {
-        long long *a = cnt + (size_t) q * (M + 1);
-        long long s = 0;
-        for (long long k = b; k < e; ++k) s += a[k];
-        s_tot[threadIdx.x] = s;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            long long run = 0;
-            for (int t = 0; t < 256; ++t) {
-                const long long v = s_tot[t];
-                s_tot[t] = run;
-                run += v;
-            }
-            a[M] = run;
-        }
-        __syncthreads();
-        long long run = s_tot[threadIdx.x];
-        for (long long k = b; k < e; ++k) {
-            const long long v = a[k];
-            a[k] = run;
-            run += v;
-        }
-        __syncthreads();
-    }
-}
-
-// block (r, side): the used points of row r in cloud `side`, in the cloud's own order -> dst[side][off[r] ..][3]
-__global__ void __launch_bounds__(256)
-k_vd_gather(VdRows R, long long M, const unsigned int *__restrict__ spos_e, const SPoint *__restrict__ sp_e, long long n_e,
-            const unsigned int *__restrict__ spos_g, const SPoint *__restrict__ sp_g, long long n_g, double *__restrict__ X,
-            double *__restrict__ Y) {
-    const long long r = blockIdx.x;
-    const int side = blockIdx.y;
-    if (r >= M) return;
-    const unsigned int *spos = side ? spos_g : spos_e;
-    const SPoint *sp = side ? sp_g : sp_e;
-    const long long n_c = side ? n_g : n_e;
-    double *dst = (side ? Y : X) + 3 * R.cnt[(size_t) side * (M + 1) + r];
-    const long long start = R.start[2 * r + side], stride = R.stride[2 * r + side];
-    const int used = R.used[2 * r + side];
-    for (int u = threadIdx.x; u < used; u += 256) {
-        const long long i = start + (long long) u * stride;
-        double x = 0.0, y = 0.0, z = 0.0;
-        if (i < n_c) {  // (always: the voxel's list holds its population)
-            const long long s = spos[i];
-            if (s < n_c) {
-                const SPoint p = sp[s];
-                x = p.x, y = p.y, z = p.z;
-            }
-        }
-        dst[3 * u] = x, dst[3 * u + 1] = y, dst[3 * u + 2] = z;
-    }
-}
 
 // entry q of the upper triangle of a t x t tile grid, row by row: (i, j), i <= j
 __device__ __forceinline__ void vd_tri_decode(long long q, long long t, int &i_out, int &j_out) {
@@ -468,28 +321,10 @@ int voxel_distances(me_ctx *ctx, const me_voxdist_params *p, int32_t *keys, int3
     const int ns = p->n_sigma;
     const bool arrays = keys || n_pop || n_used || ksum || mmd2 || gauss;
     // the voxel tables me_awd_scs joins (the slots' cached tables; built here when a slot holds none of this size)
-    ME_TRY(voxel_build(ctx, ME_SLOT_GT, vs, false));
-    ME_TRY(voxel_build(ctx, ME_SLOT_EST, vs, false));
-    const long long Ve = E.n_vox, Vg = G.n_vox;
     const long long capacity = *n_rows;
     const double nan = std::nan("");
     long long M = 0;
-    DevBuf &gi_d = ctx->tmp[0], &match_d = ctx->tmp[1], &mpos_d = ctx->tmp[2];
-    if (Ve > 0 && Vg > 0) {
-        ME_CHECK(ctx, gi_d.ensure((size_t) Ve * 4));
-        ME_CHECK(ctx, match_d.ensure((size_t) Ve * 4));
-        ME_CHECK(ctx, mpos_d.ensure((size_t) Ve * 4));
-        hipLaunchKernelGGL(k_vd_join, dim3(blocks_of(Ve)), dim3(256), 0, ctx->stream, (const unsigned long long *) E.vox_key.as<unsigned long long>(),
-                           (const int *) E.vox_n.as<int>(), Ve, (const unsigned long long *) G.vox_key.as<unsigned long long>(),
-                           (const int *) G.vox_n.as<int>(), Vg, (int) p->min_pts, gi_d.as<int>(), match_d.as<unsigned int>());
-        ME_TRY(exclusive_scan_u32(ctx, match_d.as<unsigned int>(), mpos_d.as<unsigned int>(), Ve));
-        unsigned int last_pos = 0, last_flag = 0;
-        MailGuard mg(ctx);
-        ME_TRY(mail_post(ctx, &last_pos, mpos_d.as<unsigned int>() + (Ve - 1), 4));
-        ME_TRY(mail_post(ctx, &last_flag, match_d.as<unsigned int>() + (Ve - 1), 4));
-        ME_TRY(mg.sync());
-        M = (long long) last_pos + last_flag;
-    }
+    ME_TRY(vd_rows_count(ctx, vs, (int) p->min_pts, M));
     *n_rows = M;
     if (out) {
         std::memset(out, 0, sizeof(*out));
@@ -501,42 +336,11 @@ int voxel_distances(me_ctx *ctx, const me_voxdist_params *p, int32_t *keys, int3
     if (M == 0) return ME_OK;
     // ---- pass 0: the clouds' own orders and the rows ----
     ME_CHECK(ctx, ctx->red.ensure(std::max<size_t>(VdRed::bytes(kVdBlocks), 64)));
-    int *err = ctx->red.as<int>();
-    ME_CHECK(ctx, hipMemsetAsync(err, 0, 8, ctx->stream));
-    DevBuf okey_d, opos_d, skey_e, spos_e, skey_g, spos_g;
-    ME_TRY(points_own_order(ctx, E, vs, err, "voxel_distances", "me_voxel_distances", okey_d, opos_d, skey_e, spos_e));
-    ME_TRY(points_own_order(ctx, G, vs, err + 1, "voxel_distances", "me_voxel_distances", okey_d, opos_d, skey_g, spos_g));
-    DevBuf &rows_d = ctx->tmp[3];
-    // [M] ei | gi | [M][2] start | stride | pop | used | [M][3] keys | [M] pairs | [3][M + 1] cnt   (8-byte words last)
-    const size_t w4 = (size_t) M * (2 + 4 * 2 + 3);
-    const size_t off8 = (w4 * 4 + 7) & ~(size_t) 7;
-    ME_CHECK(ctx, rows_d.ensure(off8 + (size_t) M * 8 + (size_t) 3 * (M + 1) * 8));
-    VdRows R;
-    R.ei = rows_d.as<int>();
-    R.gi = R.ei + M;
-    R.start = reinterpret_cast<unsigned int *>(R.gi + M);
-    R.stride = reinterpret_cast<int *>(R.start + 2 * M);
-    R.pop = R.stride + 2 * M;
-    R.used = R.pop + 2 * M;
-    int *keys3 = R.used + 2 * M;
-    R.pairs = reinterpret_cast<long long *>(reinterpret_cast<char *>(rows_d.p) + off8);
-    R.cnt = R.pairs + M;
-    long long tot[3] = {0, 0, 0};
-    {
-        TimerScope ts(ctx, "voxel_distances");
-        hipLaunchKernelGGL(k_vd_rows, dim3(blocks_of(Ve)), dim3(256), 0, ctx->stream, (const unsigned int *) match_d.as<unsigned int>(),
-                           (const unsigned int *) mpos_d.as<unsigned int>(), (const int *) gi_d.as<int>(), Ve,
-                           (const unsigned long long *) E.vox_key.as<unsigned long long>(), (const int *) E.vox_n.as<int>(),
-                           (const int *) G.vox_n.as<int>(), (const unsigned long long *) skey_e.as<unsigned long long>(), E.n,
-                           (const unsigned long long *) skey_g.as<unsigned long long>(), G.n, (long long) p->max_points, M, R, keys3);
-        hipLaunchKernelGGL(k_vd_scan, dim3(1), dim3(256), 0, ctx->stream, R.cnt, M);
-    }
-    {
-        MailGuard mg(ctx);
-        for (int q = 0; q < 3; ++q) ME_TRY(mail_post(ctx, &tot[q], R.cnt + (size_t) q * (M + 1) + M, 8));
-        ME_TRY(mg.sync());
-    }
-    const long long nx = tot[0], ny = tot[1], n_tiles = tot[2];
+    VdBuilt B;
+    ME_TRY(vd_rows_build(ctx, vs, (long long) p->max_points, M, "voxel_distances", "me_voxel_distances", B));
+    const VdRows &R = B.R;
+    const int *keys3 = B.keys3;
+    const long long nx = B.tot[0], ny = B.tot[1], n_tiles = B.tot[2];
     if (n_tiles > 0x7fffffffLL)
         return ctx->fail(ME_ERR_ARG, "me_voxel_distances: more than 2^31 - 1 pair tiles (set max_points to sub-sample the fullest voxels)");
     // ---- passes 2 - 7 ----
@@ -554,9 +358,7 @@ int voxel_distances(me_ctx *ctx, const me_voxdist_params *p, int32_t *keys, int3
     const VdRed red(ctx, kVdBlocks);
     {
         TimerScope ts(ctx, "voxel_distances");
-        hipLaunchKernelGGL(k_vd_gather, dim3((unsigned int) M, 2), dim3(256), 0, ctx->stream, R, M, (const unsigned int *) spos_e.as<unsigned int>(),
-                           (const SPoint *) E.sp.as<SPoint>(), E.n, (const unsigned int *) spos_g.as<unsigned int>(),
-                           (const SPoint *) G.sp.as<SPoint>(), G.n, X, Y);
+        vd_gather_launch(ctx, B, M, X, Y);
         hipLaunchKernelGGL(k_vd_tiles, dim3((unsigned int) M), dim3(256), 0, ctx->stream, R, M, tiles_d.as<int4>());
         const int4 *tl = tiles_d.as<int4>();
         double *pt = part_d.as<double>();

@@ -64,6 +64,25 @@ def rotation_angle(R) -> np.ndarray:
     return np.arctan2(s, 0.5 * (R[..., 0] + R[..., 4] + R[..., 8] - 1.0))
 
 
+TRANSPORT_N_FINAL = 128  # iterations at blur^2 after the descent: chosen on the numpy model's marginal_err
+
+
+def transport_schedule(voxel_size: float, blur: float, scaling: float = 0.5, n_final: int = TRANSPORT_N_FINAL) -> np.ndarray:
+    """The default eps schedule of Engine.voxel_transport, host arithmetic in float64: eps_0 = 3 voxel_size^2 (the squared diameter of a
+    voxel), eps_{t+1} = max(blur^2, eps_t scaling^2) down to blur^2 (once), then n_final further iterations at blur^2."""
+    vs, b, sc = float(voxel_size), float(blur), float(scaling)
+    if not (vs > 0 and b > 0 and 0 < sc < 1 and n_final >= 0):
+        raise ValueError("transport_schedule: voxel_size > 0, blur > 0, 0 < scaling < 1 and n_final >= 0")
+    b2, s2 = b * b, sc * sc
+    eps = [max(b2, 3.0 * (vs * vs))]
+    while eps[-1] > b2:
+        eps.append(max(b2, eps[-1] * s2))
+    eps.extend([b2] * int(n_final))
+    if len(eps) > 512:
+        raise ValueError("transport_schedule: more than 512 iterations")
+    return np.array(eps, np.float64)
+
+
 def _addr(a) -> int:
     """Raw address of a numpy array (host) or a torch tensor (host or device)."""
     if a is None:
@@ -1501,6 +1520,64 @@ class Engine:
         res = dict(n_rows=o.n_rows, n_rows_subsampled=o.n_rows_subsampled, n_pairs_total=o.n_pairs, sigmas=sg.copy(),
                    mean_mmd=np.array(o.mean_mmd[:ns]), mean_mmd2_u=np.array(o.mean_mmd2_u[:ns]), mean_kl_est_gt=o.mean_gauss[0],
                    mean_kl_gt_est=o.mean_gauss[1], mean_bhattacharyya=o.mean_gauss[2], mean_w2=o.mean_gauss[3])
+        res.update(arrays)
+        return res
+
+    def voxel_transport(self, voxel_size: float, blur=None, directions=32, min_pts: int = 100, max_points: int = 512, scaling: float = 0.5,
+                        n_final: int = TRANSPORT_N_FINAL, eps_schedule=None, fetch: bool = True) -> dict:
+        """me_voxel_transport: per row of calculateVMD(voxel_size, min_pts) the sliced 2-Wasserstein distance of the two clouds' points
+        in the voxel (exact per direction) and the debiased Sinkhorn divergence on a fixed eps schedule (definitions:
+        include/mapeval_hip.h).  directions: a count (the table synth.fibonacci_directions(count); 0: no sliced part) or an (L, 3) array
+        used as given.  The schedule: eps_schedule as given (empty: no Sinkhorn part), else transport_schedule(voxel_size, blur, scaling,
+        n_final) with `blur` in metres, which has no default.  max_points (11 .. 1024): a fuller voxel is sub-sampled by a stride.
+        -> the summary: n_rows, n_rows_subsampled, n_pairs_total, n_used_est, n_used_gt, mean_sw2, mean_max_sw2, mean_s, mean_sinkhorn,
+        mean_marginal_err, max_marginal_err, max_marginal_row (NaN / -1 for a part that did not run or without rows), and `directions`
+        and `eps_schedule` as used, so that the call can be replayed.  With fetch also the rows: keys (V, 3), n_pop, n_used (V, 2),
+        sw2_sq, sw2, max_sw2_sq (V), max_dir (V, int), per_direction (V, L), ot_xy, ot_xx, ot_yy, s, sinkhorn, marginal_err (V), and f, g:
+        lists of V arrays, the cross problem's final potentials per used point."""
+        if isinstance(directions, (int, np.integer)):
+            from . import synth
+
+            dirs = synth.fibonacci_directions(int(directions)) if int(directions) > 0 else np.empty((0, 3), np.float64)
+        else:
+            dirs = np.ascontiguousarray(np.asarray(directions, dtype=np.float64).reshape(-1, 3))
+        if eps_schedule is None:
+            if blur is None:
+                raise ValueError("voxel_transport: blur (metres) is required when no eps_schedule is given")
+            eps = transport_schedule(voxel_size, blur, scaling, n_final)
+        else:
+            eps = np.ascontiguousarray(np.asarray(eps_schedule, dtype=np.float64).ravel())
+        nl, nt = int(dirs.shape[0]), int(eps.shape[0])
+        p = _lib.VoxTransParams()
+        p.voxel_size, p.min_pts, p.n_dir, p.n_eps, p.reserved, p.max_points = float(voxel_size), int(min_pts), nl, nt, 0, int(max_points)
+        da, ea = (_addr(dirs) if nl else 0), (_addr(eps) if nt else 0)
+        o = _lib.VoxTransOut()
+        nr = C.c_int64(0)
+        call = self._L.me_voxel_transport
+        arrays = {}
+        if fetch:
+            self._ck(call(self._ctx, C.byref(p), da, ea, 0, 0, 0, 0, 0, 0, 0, C.byref(nr), None))
+            v = nr.value
+            keys, pop, used = np.empty((v, 3), np.int32), np.empty((v, 2), np.int32), np.empty((v, 2), np.int32)
+            self._ck(call(self._ctx, C.byref(p), da, ea, 0, 0, _addr(used), 0, 0, 0, 0, C.byref(nr), None))  # (the rows alone: the sizes)
+            nx, ny = int(used[:, 0].sum()), int(used[:, 1].sum())
+            sl, sk = np.full((v, 4), np.nan), np.full((v, 6), np.nan)
+            per, pot = np.empty((v, nl), np.float64), np.empty(nx + ny if nt else 0, np.float64)
+            self._ck(call(self._ctx, C.byref(p), da, ea, _addr(keys), _addr(pop), _addr(used), _addr(sl), _addr(sk), _addr(per),
+                          _addr(pot) if nt else 0, C.byref(nr), C.byref(o)))
+            ox, oy = np.concatenate([[0], np.cumsum(used[:, 0])]), nx + np.concatenate([[0], np.cumsum(used[:, 1])])
+            col = lambda a, k: np.ascontiguousarray(a[:, k])  # noqa: E731
+            arrays = dict(keys=keys, n_pop=pop, n_used=used, sw2_sq=col(sl, 0), sw2=col(sl, 1), max_sw2_sq=col(sl, 2),
+                          max_dir=(col(sl, 3).astype(np.int32) if nl else np.full(v, -1, np.int32)), per_direction=per,
+                          ot_xy=col(sk, 0), ot_xx=col(sk, 1), ot_yy=col(sk, 2), s=col(sk, 3), sinkhorn=col(sk, 4), marginal_err=col(sk, 5),
+                          f=[pot[ox[r]:ox[r + 1]].copy() for r in range(v)] if nt else [],
+                          g=[pot[oy[r]:oy[r + 1]].copy() for r in range(v)] if nt else [])
+        else:
+            self._ck(call(self._ctx, C.byref(p), da, ea, 0, 0, 0, 0, 0, 0, 0, C.byref(nr), C.byref(o)))
+        res = dict(n_rows=o.n_rows, n_rows_subsampled=o.n_rows_subsampled, n_pairs_total=o.n_pairs, n_used_est=o.n_used_est,
+                   n_used_gt=o.n_used_gt, mean_sw2=o.mean_sw2, mean_max_sw2=o.mean_max_sw2, mean_s=o.mean_s, mean_sinkhorn=o.mean_sinkhorn,
+                   mean_marginal_err=o.mean_marginal_err, max_marginal_err=o.max_marginal_err, max_marginal_row=o.max_marginal_row,
+                   directions=dirs.copy(), eps_schedule=eps.copy())
         res.update(arrays)
         return res
 

@@ -453,6 +453,19 @@ Param loadParametersFromYAML(const std::string &yaml_file_path) {
             throw std::runtime_error("voxel_distance_eig_floor: must be > 0");
         if (param.num_gpus > 1) throw std::runtime_error("evaluate_voxel_distances: single GPU only (num_gpus must be 1)");
     }
+    // per-voxel point-set Wasserstein distances on the AWD lattice (me_voxel_transport; no reference counterpart)
+    if (config.has("evaluate_voxel_transport")) param.evaluate_voxel_transport = config.as_bool("evaluate_voxel_transport");
+    param.transport_blur = config.has("transport_blur") ? config.as_double("transport_blur") : param.nn_radius_;
+    if (config.has("transport_directions")) param.transport_directions = (int) config.as_double("transport_directions");
+    if (config.has("transport_max_points")) param.transport_max_points = (long long) config.as_double("transport_max_points");
+    if (config.has("transport_scaling")) param.transport_scaling = config.as_double("transport_scaling");
+    if (param.evaluate_voxel_transport) {
+        if (!(param.transport_blur > 0) || !std::isfinite(param.transport_blur)) throw std::runtime_error("transport_blur: must be > 0");
+        if (param.transport_directions < 0 || param.transport_directions > 64) throw std::runtime_error("transport_directions: must be in 0 .. 64");
+        if (param.transport_max_points < 11 || param.transport_max_points > 1024) throw std::runtime_error("transport_max_points: must be in 11 .. 1024");
+        if (!(param.transport_scaling > 0 && param.transport_scaling < 1)) throw std::runtime_error("transport_scaling: must be in (0, 1)");
+        if (param.num_gpus > 1) throw std::runtime_error("evaluate_voxel_transport: single GPU only (num_gpus must be 1)");
+    }
     // cloud-to-mesh distance (the role of the reference's mesh branch, with a supplied mesh)
     if (config.has("evaluate_mesh_distance")) param.evaluate_mesh_distance = config.as_bool("evaluate_mesh_distance");
     if (config.has("gt_mesh_path")) param.gt_mesh_path = config.as_string("gt_mesh_path");
@@ -647,6 +660,9 @@ std::string paramToJson(const Param &p) {
     o << ", \"evaluate_voxel_distances\": " << b(p.evaluate_voxel_distances) << ", \"mmd_sigmas\": [";
     for (size_t i = 0; i < p.mmd_sigmas.size(); ++i) o << (i ? ", " : "") << p.mmd_sigmas[i];
     o << "], \"mmd_max_points\": " << p.mmd_max_points << ", \"voxel_distance_eig_floor\": " << p.voxel_distance_eig_floor;
+    o << ", \"evaluate_voxel_transport\": " << b(p.evaluate_voxel_transport) << ", \"transport_blur\": " << p.transport_blur
+      << ", \"transport_directions\": " << p.transport_directions << ", \"transport_max_points\": " << p.transport_max_points
+      << ", \"transport_scaling\": " << p.transport_scaling;
     o << ", \"evaluate_observable\": " << b(p.evaluate_observable) << ", \"trajectory_path\": \"";
     for (const char c : p.trajectory_path) {
         if (c == '"' || c == '\\') o << '\\' << c;
@@ -898,6 +914,7 @@ int MapEval::process() {
     if (!last_error.empty()) return -1;
     if (param_.evaluate_deformation && computeDeformation() != 0) return -1;
     if (param_.evaluate_voxel_distances && computeVoxelDistances() != 0) return -1;
+    if (param_.evaluate_voxel_transport && computeVoxelTransport() != 0) return -1;
     if (param_.save_voxel_metrics) {  // (only the registration path gets here on one GPU: the initial-matrix one is processOneCall)
         // the transforms of the registration discarded the map's MME result on the device: hand back the entropies computeMME
         // fetched (those of map_entropy.txt), and the ground truth's with them
@@ -1334,6 +1351,7 @@ int MapEval::processOneCall(bool from_host, double t_loaded) {
     if (!last_error.empty()) return -1;
     if (param_.evaluate_deformation && computeDeformation() != 0) return -1;
     if (param_.evaluate_voxel_distances && computeVoxelDistances() != 0) return -1;
+    if (param_.evaluate_voxel_transport && computeVoxelTransport() != 0) return -1;
     if (param_.save_voxel_metrics) {
         saveVoxelMetrics(ME_GATE_LE_UNSQUARED);  // the gate of the statistics above (:1219)
         if (!last_error.empty()) return -1;
@@ -2050,6 +2068,81 @@ void MapEval::saveVoxelDistances() {
     if (std::fclose(f) != 0) fail("writing " + path + " failed");
 }
 
+// evaluate_voxel_transport: per row of the AWD table (vmd_voxel_size, 100 points in both clouds, as calculateVMD) the sliced 2-Wasserstein
+// distance over transport_directions directions of a Fibonacci half sphere (z_k = (k + 0.5) / L, azimuth k times the golden angle,
+// normalised twice) and the debiased Sinkhorn divergence on the schedule eps_0 = max(blur^2, 3 voxel_size^2), eps_{t+1} = max(blur^2,
+// eps_t scaling^2) down to blur^2, then 128 further iterations at blur^2, where both clouds stand now: me_voxel_transport.
+int MapEval::computeVoxelTransport() {
+    const int L = param_.transport_directions;
+    voxtrans_dirs.assign((size_t) L * 3, 0.0);
+    for (int k = 0; k < L; ++k) {
+        const double z = ((double) k + 0.5) / (double) L, rho = std::sqrt(1.0 - z * z), phi = (double) k * (M_PI * (3.0 - std::sqrt(5.0)));
+        double d[3] = {rho * std::cos(phi), rho * std::sin(phi), z};
+        for (int pass = 0; pass < 2; ++pass) {
+            const double len = std::sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
+            for (int c = 0; c < 3; ++c) d[c] /= len;
+        }
+        for (int c = 0; c < 3; ++c) voxtrans_dirs[(size_t) 3 * k + c] = d[c];
+    }
+    const double vs = param_.vmd_voxel_size_, b2 = param_.transport_blur * param_.transport_blur, s2 = param_.transport_scaling * param_.transport_scaling;
+    voxtrans_eps.assign(1, std::max(b2, 3.0 * (vs * vs)));
+    while (voxtrans_eps.back() > b2) voxtrans_eps.push_back(std::max(b2, voxtrans_eps.back() * s2));
+    voxtrans_eps.insert(voxtrans_eps.end(), 128, b2);
+    if (voxtrans_eps.size() > 512) return fail("evaluate_voxel_transport: the schedule has more than 512 iterations (raise transport_blur or lower transport_scaling)");
+    me_voxtrans_params p;
+    std::memset(&p, 0, sizeof(p));
+    p.voxel_size = vs;
+    p.min_pts = 100;
+    p.n_dir = L;
+    p.n_eps = (int32_t) voxtrans_eps.size();
+    p.max_points = param_.transport_max_points;
+    const double *dirs = L > 0 ? voxtrans_dirs.data() : nullptr;
+    int64_t V = 0;
+    if (me_voxel_transport(ctx_, &p, dirs, voxtrans_eps.data(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &V, nullptr) != ME_OK)
+        return fail(std::string("evaluate_voxel_transport: ") + me_last_error(ctx_));
+    const size_t v = (size_t) V;
+    voxtrans_keys.assign(v * 3, 0);
+    voxtrans_pop.assign(v * 2, 0);
+    voxtrans_used.assign(v * 2, 0);
+    voxtrans_sliced.assign(v * 4, std::nan(""));
+    voxtrans_sinkhorn.assign(v * 6, 0.0);
+    if (me_voxel_transport(ctx_, &p, dirs, voxtrans_eps.data(), voxtrans_keys.data(), voxtrans_pop.data(), voxtrans_used.data(), voxtrans_sliced.data(),
+                           voxtrans_sinkhorn.data(), nullptr, nullptr, &V, &voxtrans_out) != ME_OK)
+        return fail(std::string("evaluate_voxel_transport: ") + me_last_error(ctx_));
+    return 0;
+}
+
+// The result lines `VoxelSW2 mean-max:` (the means over the rows of sw2 and of sqrt(max_sw2_sq)) and `VoxelSinkhorn @blur:` (the means of S,
+// sqrt(max(0, S)) and marginal_err), and voxel_transport.txt: the parameters ("name value"), one "direction ux uy uz" line per direction, one
+// "eps value" line per iteration, then one row per voxel
+//   ix iy iz n_est n_gt used_est used_gt sw2_sq sw2 max_sw2_sq max_dir ot_xy ot_xx ot_yy S sinkhorn marginal_err   (doubles as %.17g)
+void MapEval::saveVoxelTransport() {
+    const me_voxtrans_out &o = voxtrans_out;
+    file_result << std::fixed << std::setprecision(15) << "VoxelSW2 mean-max: " << o.mean_sw2 << " " << o.mean_max_sw2 << std::endl;
+    file_result << std::fixed << std::setprecision(15) << "VoxelSinkhorn @" << param_.transport_blur << ": " << o.mean_s << " " << o.mean_sinkhorn << " "
+                << o.mean_marginal_err << std::endl;
+    const std::string path = results_subfolder + "voxel_transport.txt";
+    FILE *f = std::fopen(path.c_str(), "w");
+    if (!f) {
+        fail("cannot write " + path);
+        return;
+    }
+    const size_t L = voxtrans_dirs.size() / 3;
+    std::fprintf(f, "voxel_size %.17g\nmin_pts %d\nmax_points %lld\nblur %.17g\nscaling %.17g\nn_final %d\nn_dir %d\nn_eps %d\n", param_.vmd_voxel_size_, 100,
+                 param_.transport_max_points, param_.transport_blur, param_.transport_scaling, 128, (int) L, (int) voxtrans_eps.size());
+    for (size_t k = 0; k < L; ++k) std::fprintf(f, "direction %.17g %.17g %.17g\n", voxtrans_dirs[3 * k], voxtrans_dirs[3 * k + 1], voxtrans_dirs[3 * k + 2]);
+    for (const double e : voxtrans_eps) std::fprintf(f, "eps %.17g\n", e);
+    std::fprintf(f, "n_rows %lld\nn_rows_subsampled %lld\nn_pairs %lld\nmax_marginal_err %.17g\nmax_marginal_row %lld\n", (long long) o.n_rows,
+                 (long long) o.n_rows_subsampled, (long long) o.n_pairs, o.max_marginal_err, (long long) o.max_marginal_row);
+    for (size_t v = 0; v < (size_t) o.n_rows; ++v) {
+        const double *s = &voxtrans_sliced[4 * v], *k = &voxtrans_sinkhorn[6 * v];
+        std::fprintf(f, "%d %d %d %d %d %d %d %.17g %.17g %.17g %d %.17g %.17g %.17g %.17g %.17g %.17g\n", voxtrans_keys[3 * v], voxtrans_keys[3 * v + 1],
+                     voxtrans_keys[3 * v + 2], voxtrans_pop[2 * v], voxtrans_pop[2 * v + 1], voxtrans_used[2 * v], voxtrans_used[2 * v + 1], s[0], s[1], s[2],
+                     L > 0 ? (int) s[3] : -1, k[0], k[1], k[2], k[3], k[4], k[5]);
+    }
+    if (std::fclose(f) != 0) fail("writing " + path + " failed");
+}
+
 // evaluate_mesh_distance: the mesh of gt_mesh_path as it is in the file (like the ground-truth cloud it is not moved), the map where
 // initial_matrix puts it (me_transform_cloud; the host's copy stays as loaded), me_mesh_distance with the map as the query, the exact
 // nearest-rank quantiles of d over the matched points (error_quantiles; me_rank_select on the fetched values) and, with
@@ -2432,6 +2525,7 @@ void MapEval::saveRegistrationResults() {
     if (param_.evaluate_observable) saveObservable();
     if (param_.evaluate_deformation) saveDeformation();
     if (param_.evaluate_voxel_distances) saveVoxelDistances();
+    if (param_.evaluate_voxel_transport) saveVoxelTransport();
     file_result << std::fixed << std::setprecision(5) << "VMD: " << vmd << std::endl;
     file_result << std::fixed << std::setprecision(5) << "SCS: " << scs_overall << std::endl;
     if (param_.evaluate_using_initial_)

@@ -157,6 +157,12 @@ struct Param {
     std::vector<double> mmd_sigmas;            // `mmd_sigmas:` 1 - 4 kernel bandwidths (default [nn_radius])
     long long mmd_max_points = 2048;           // `mmd_max_points:` a fuller voxel is sub-sampled by a stride (0: never; else >= 11)
     double voxel_distance_eig_floor = 1e-6;    // `voxel_distance_eig_floor:` the eigenvalue floor of the closed forms (> 0)
+    bool evaluate_voxel_transport = false;     // `evaluate_voxel_transport:` true = per AWD voxel the sliced 2-Wasserstein distance and the debiased Sinkhorn
+                                               // divergence of the two clouds' points (me_voxel_transport; single GPU only): two result lines and voxel_transport.txt
+    double transport_blur = 0;                 // `transport_blur:` metres, > 0 (default nn_radius): the schedule ends at blur^2
+    int transport_directions = 32;             // `transport_directions:` 0 .. 64 directions of a Fibonacci half sphere (0: no sliced part)
+    long long transport_max_points = 512;      // `transport_max_points:` 11 .. 1024: a fuller voxel is sub-sampled by a stride
+    double transport_scaling = 0.5;            // `transport_scaling:` in (0, 1): eps shrinks by its square per iteration down to blur^2
     double m3c2_normal_radius = 0.0;           // `m3c2_normal_radius:` > 0 (default: nn_radius)
     double m3c2_projection_radius = 0.0;       // `m3c2_projection_radius:` the cylinder's radius, > 0 (default: nn_radius)
     double m3c2_max_depth = 0.0;               // `m3c2_max_depth:` the cylinder's half-length, > 0 (default: 4 nn_radius)
@@ -249,6 +255,8 @@ public:
     int computeVoxelDistances();                            // evaluate_voxel_distances: me_voxel_distances on the AWD lattice (no reference counterpart)
     void saveDeformation();                                 // its result line and deformation_field.txt
     void saveVoxelDistances();                              // its two result lines and voxel_distances.txt
+    int computeVoxelTransport();                            // evaluate_voxel_transport: me_voxel_transport on the AWD lattice (no reference counterpart)
+    void saveVoxelTransport();                              // its two result lines and voxel_transport.txt
     int computeMeshDistance();                              // evaluate_mesh_distance: me_mesh_distance of the moved map (no reference counterpart)
     void saveMeshDistance();                                // its two result lines and mesh_distance.txt
     int computeObservable();                                // evaluate_observable: me_cloud_visibility of the ground truth, recall for all / observable points
@@ -285,6 +293,9 @@ public:
     me_voxdist_out voxdist_out = {};            // evaluate_voxel_distances: the summary and the rows (keys | n_pop | n_used | ksum | mmd2 | gauss)
     std::vector<int32_t> voxdist_keys, voxdist_pop, voxdist_used;
     std::vector<double> voxdist_ksum, voxdist_mmd2, voxdist_gauss;
+    me_voxtrans_out voxtrans_out = {};          // evaluate_voxel_transport: the summary, the directions and the schedule as used, and the rows
+    std::vector<int32_t> voxtrans_keys, voxtrans_pop, voxtrans_used;
+    std::vector<double> voxtrans_dirs, voxtrans_eps, voxtrans_sliced, voxtrans_sinkhorn;
     me_radius_normals_out m3c2_normals[2] = {};
     me_mesh_info_out mesh_info = {};            // evaluate_mesh_distance: the mesh, the totals, the quantiles of d, the sampled block
     me_mesh_out mesh_out = {};

@@ -294,3 +294,45 @@ def lidar_directions(n_beams: int, n_azimuth: int, fov_lo_deg: float, fov_hi_deg
     for _ in range(2):
         d = d / np.sqrt((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2])[:, None]
     return np.ascontiguousarray(d)
+
+
+def fibonacci_directions(n_dir: int):
+    """The default direction table of Engine.voxel_transport: (n_dir, 3) float64 unit vectors on the half sphere z > 0 (a direction and
+    its opposite give the same sliced distance), a Fibonacci lattice: z_k = (k + 0.5) / n_dir, azimuth k times the golden angle
+    pi (3 - sqrt 5).  Unit length to one ulp (normalised after the trigonometry)."""
+    import numpy as np
+
+    if not 1 <= int(n_dir) <= 64:
+        raise ValueError("fibonacci_directions needs 1 <= n_dir <= 64")
+    k = np.arange(int(n_dir), dtype=np.float64)
+    z = (k + 0.5) / float(n_dir)
+    rho = np.sqrt(1.0 - z * z)
+    phi = k * (np.pi * (3.0 - np.sqrt(5.0)))
+    d = np.stack([rho * np.cos(phi), rho * np.sin(phi), z], -1)
+    for _ in range(2):
+        d = d / np.sqrt((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2])[:, None]
+    return np.ascontiguousarray(d)
+
+
+def doubled_wall_voxel(n_est: int, n_gt: int, voxel_size: float = 1.0, gap: float = 0.05, seed: int = 0, origin=(0.0, 0.0, 0.0)):
+    """One voxel of side voxel_size at `origin` that a Gaussian model cannot tell apart: the ground truth (n_gt, 3) is ONE wall, the plane
+    x = voxel_size / 2 sampled uniformly over the middle 90 % of the voxel; the map (n_est, 3) holds the same wall TWICE, alternately
+    `gap` before and behind it, so that its centroid stays where the ground truth's is.  -> (est, gt) float64."""
+    import numpy as np
+
+    if n_est < 2 or n_gt < 1 or not 0.0 < gap < 0.45 * voxel_size:
+        raise ValueError("doubled_wall_voxel needs n_est >= 2, n_gt >= 1 and 0 < gap < 0.45 voxel_size")
+    rng = np.random.default_rng(seed)
+    o = np.asarray(origin, np.float64)
+    vs = float(voxel_size)
+
+    def wall(n):
+        p = np.empty((n, 3))
+        p[:, 0] = 0.5 * vs
+        p[:, 1:] = vs * (0.05 + 0.9 * rng.random((n, 2)))
+        return p
+
+    gt, est = wall(int(n_gt)), wall(int(n_est))
+    est[0::2, 0] -= gap
+    est[1::2, 0] += gap
+    return np.ascontiguousarray(est + o), np.ascontiguousarray(gt + o)

@@ -1488,6 +1488,57 @@ int me_voxel_distances(me_ctx *ctx, const me_voxdist_params *p, int32_t *keys /*
                        double *ksum /*V x n_sigma x 3*/, double *mmd2 /*V x n_sigma x 2*/, double *gauss /*V x 4*/,
                        int64_t *n_rows /*in: capacity, out: count*/, me_voxdist_out *out);
 
+/* ---- per-voxel point-set Wasserstein distances on the AWD lattice: sliced W2 and the debiased Sinkhorn divergence (no reference
+ *      counterpart: AWD is called a Wasserstein distance and computes none between the points of a voxel).  DESIGN.md 4.26 --------
+ * The rows, the gate, the points X (map) and Y (ground truth) of a row and the stride rule are those of me_voxel_distances, with
+ * max_points in 11 .. 1024 (both used point sets of a row stay in one workgroup's LDS).  n = |X used|, m = |Y used|.
+ *   SLICED  n_dir = L directions u_l (fp64 triples, used AS GIVEN: not normalised).  Per row and direction the projections
+ *           p = ((x ux) + (y uy)) + (z uz) (no FMA, coordinates as stored) of both sides are sorted ascending (a_i, b_j) and
+ *             W2^2_l = (sum w_ij ((a_i - b_j) (a_i - b_j))) / (n m),
+ *           w_ij the INTEGER overlap of [i m, (i + 1) m) and [j n, (j + 1) n): the exact squared 2-Wasserstein distance of the two
+ *           empirical measures on the line, n + m - gcd(n, m) terms.  ORDER: lane t of 256 takes i = t, t + 256, ... ascending, for each i
+ *           the overlapping j ascending, one fp64 accumulator; the lanes fold by wave_sum (shuffle down 32 .. 1), the four waves as
+ *           (s0 + s1) + (s2 + s3); then one division by (double) n * (double) m.  A function of n, m and the points alone.
+ *           sliced[v] = sw2_sq (the sum over l ascending, divided by (double) L), sw2 = sqrt(sw2_sq), max_sw2_sq = the largest
+ *           W2^2_l, and the index l that attains it as a double (the smallest on ties).  per_direction[v][l] = W2^2_l.
+ *   SINKHORN  cost C_ij = ((dx dx) + (dy dy)) + (dz dz), weights 1 / n and 1 / m, n_eps = T iterations, iteration t at eps[t], no
+ *           convergence test.  From f = g = 0, per iteration
+ *             f_i <- -eps (M_i + log sum_j exp(t_ij - M_i)),  t_ij = lb + (g_j - C_ij) / eps,  M_i = max_j t_ij,  lb = -log((double) m),
+ *           the sum in ascending j (two passes over j: the maximum, then the sum; t_ij is formed the same way in both, so the sum is
+ *           >= 1), then g_j likewise from the new f with la = -log((double) n).  The symmetric problems (X, X) and (Y, Y) iterate
+ *           f_i <- 0.5 (f_i + T(f)_i), every T(f)_i from the f of the iteration before.  OT(X, Y) = (sum f_i) / n + (sum g_j) / m,
+ *           OT(X, X) = (sum f_i) / n + (sum f_i) / n; each sum: lane t takes t, t + 256, ... ascending, then the fold above.
+ *           S = (OT(X, Y) - 0.5 OT(X, X)) - 0.5 OT(Y, Y).  marginal_err = sum_i | sum_j exp((la + lb) + ((f_i + g_j) - C_ij) / eps) - 1 / n |
+ *           at eps[T - 1] with the final f and g (j ascending, the i as the sums above): the L1 distance of the plan's first marginal
+ *           from 1 / n, which tells whether T was enough (the second marginal is exact after the g update).
+ *           sinkhorn[v] = OT(X, Y), OT(X, X), OT(Y, Y), S, sqrt(max(0, S)), marginal_err.  potentials: the final f of the cross
+ *           problem of all rows, row after row (sum of n_used[v][0] doubles), then the final g (sum of n_used[v][1]): out->n_used_est
+ *           and out->n_used_gt are those sums, and a call with n_used alone (no solver runs) tells them beforehand.
+ *   out     n_rows; n_rows_subsampled; n_pairs = sum n m; n_used_est, n_used_gt; mean_sw2 and mean_max_sw2 (of sqrt(max_sw2_sq)),
+ *           mean_s, mean_sinkhorn, mean_marginal_err over the rows in the fixed order of the per-cloud totals; max_marginal_err and
+ *           its row (-1 without rows).  NaN for a part that did not run (n_dir = 0 or n_eps = 0) and with no rows.
+ * No floating-point atomics: bit-identical from call to call and after any re-index of the same points.  n_dir = 0 skips the sliced
+ * part (sliced and per_direction are not written), n_eps = 0 the Sinkhorn part; the other part's bytes do not change.
+ * Host pointers; every array and `out` may be NULL.  *n_rows in: capacity, out: count (ME_ERR_CAPACITY if an array is passed and the
+ * capacity is too small).  All arrays and `out` NULL: the row count alone; only keys / n_pop / n_used: the rows, no solver.
+ * ME_ERR_ARG: voxel_size <= 0, min_pts < 11, n_dir outside 0 .. 64, n_eps outside 0 .. 512, n_dir = n_eps = 0, directions NULL with
+ * n_dir > 0, eps_schedule NULL with n_eps > 0 or not positive and non-increasing (NaN included), max_points outside 11 .. 1024, or a
+ * voxel index out of range.  ME_ERR_STATE: a slot not uploaded, or slab / shard mode.  A refused call changes nothing.
+ * Cost: one exp per pair, half-update and iteration (device timer "voxel_transport"). */
+typedef struct {
+    double voxel_size;
+    int32_t min_pts, n_dir, n_eps, reserved;
+    int64_t max_points;
+} me_voxtrans_params;
+typedef struct {
+    int64_t n_rows, n_rows_subsampled, n_pairs, n_used_est, n_used_gt, max_marginal_row;
+    double mean_sw2, mean_max_sw2, mean_s, mean_sinkhorn, mean_marginal_err, max_marginal_err;
+} me_voxtrans_out;
+int me_voxel_transport(me_ctx *ctx, const me_voxtrans_params *p, const double *directions /*n_dir x 3*/, const double *eps_schedule /*n_eps*/,
+                       int32_t *keys /*V x 3*/, int32_t *n_pop /*V x 2*/, int32_t *n_used /*V x 2*/, double *sliced /*V x 4*/,
+                       double *sinkhorn /*V x 6*/, double *per_direction /*V x n_dir*/, double *potentials /*n_used_est + n_used_gt*/,
+                       int64_t *n_rows /*in: capacity, out: count*/, me_voxtrans_out *out);
+
 /* ---- AWD + CDF + SCS: MapEval::calculateVMD (map_eval.cpp:240-390) with updateVoxelMap (voxel_calculator.cpp:
  *      142-172) and computeWassersteinDistanceGaussian (:115-140) ------------------------------------------------ */
 /* rows: n x 27 doubles in the column order of voxel_errors.txt (map_eval.cpp:292-302), ascending key order;
