@@ -19,10 +19,18 @@
 #include "me_stat.hpp"
 
 #ifndef ME_NN_DBG
-#define ME_NN_DBG 0  // measurement builds of k_nn_grid (profiles/EXPERIMENTS.md "Round 6"): 1 no ranking loop, 2 no staging either, 3 no exact epilogue loads, 4 ranking without note()
+#define ME_NN_DBG 0  // measurement builds of k_nn_grid (profiles/EXPERIMENTS.md "Round 6", "Round 10"): 1 no ranking loop, 2 no staging either (run lookup, load, record), 3 no exact evaluation of the kept groups, 4 ranking without note(), 5 staging from a cache-resident stretch
 #endif
 
 namespace me {
+
+#ifdef ME_NN_STATS
+// build with -DME_NN_STATS (profiles/README.md): per launch of k_nn_grid, [0] wave rounds, [1] staged chunks, [2] candidates (= active
+// lanes summed over the chunk loads), [3] ranked records, padding included, [4] note() calls on groups of eight, [5] on groups of
+// four (none since round 10), [6] lanes served; [8..] the same for the list passes — printed to stderr by nn_search.  Two lanes that
+// search at the same time share the counters: run with --no-overlap for per-launch figures.
+__device__ unsigned long long g_nn_stat[16];
+#endif
 
 // v_min_f64 without the NaN canonicalisation the compiler wraps around fmin() (squared distances are never NaN)
 __device__ __forceinline__ double vmin_f64(double a, double b) {
@@ -89,10 +97,12 @@ __device__ __forceinline__ double box_upper_bound(const float *__restrict__ b, d
 // ------------------------------------------------------------------------------------------------------------
 // Fast path: uniform-grid 1-NN.  A wavefront owns 64 consecutive (curve-ordered) queries.  The lanes whose
 // reference-grid cell lies within Chebyshev distance 2 of the leader's form a group (normally the whole wave); the
-// group's cell box grown by one is resolved with one hash probe per (lane, slot) into a wave-private LDS table, and
-// every non-empty run is streamed ONCE through a wave-private LDS tile (one coalesced load per run, broadcast reads), every
-// lane ranking the candidates in FP32 and settling the winner exactly in fp64 afterwards (see "Ranking" below).  The grid
-// level is the finest whose occupied cells hold >= 6 points.
+// group's cell box grown by one is resolved with one hash probe per (lane, slot) into a wave-private LDS table, the
+// table's non-empty runs are flattened into ONE candidate stream (wave_run_list) and the stream goes ONCE through a
+// wave-private LDS tile, 64 positions at a time whatever run they fall into (one coalesced load per chunk, broadcast
+// reads), every lane of the group ranking the candidates in FP32 in groups of eight stream positions and settling the
+// winner exactly in fp64 at the end of its round, its two best groups translated back through the run list (see "Ranking"
+// and "Candidate delivery" below).  The grid level is the finest whose occupied cells hold >= 6 points.
 // A lane is RESOLVED when its best distance is below its distance to the faces of its own 3x3x3 block: every
 // reference point outside the block is farther, so the minimum is the exact global minimum.  Unresolved lanes
 // (no neighbour within about one cell edge: outliers, non-overlapping map regions, queries outside the reference
@@ -163,129 +173,54 @@ k_nn_grid(const SPoint *__restrict__ qsp, long long q_begin, long long q_end, co
             mcz = (int) ((unsigned int) fz >> g.shift);
         }
     }
-    float b1 = INFINITY, b2 = INFINITY, b3 = INFINITY;  // the three smallest group ranks seen (see below)
-    int j1 = -1, j2 = -1;  // positions (in the sorted reference array) of the groups that produced b1 and b2
     bool done = !active || !in_grid;
+    // A lane's answer is written at the end of ITS round (below); only this bit is carried to the append after the loop.  A lane that
+    // never joins a round (outside the reference's lattice) goes to the list with +inf / -1.
+    bool unresolved = active;
+    if (active && !in_grid) {
+        unsigned int qo = qoff;
+        asm volatile("" : "+v"(qo));
+        d2_out[q_begin + (long long) qo] = INFINITY;
+        idx_out[q_begin + (long long) qo] = -1;
+    }
 
     // Ranking.  argmin_p |p - q|^2 = argmin_p (|p|^2 - 2 p.q).  With the candidates shifted to a wave-local origin o (the
     // corner of the round's cell box, |p - o| and |q - o| < 8 cells) the rank
     //     r = fma(p'x, ax, fma(p'y, ay, fma(p'z, az, |p'|^2))),   p' = p - o,  a = -2 (q - o)
     // is accurate enough in FP32 to ORDER candidates down to ~1e-6 (cell edge 0.1 m) of squared distance: p' and |p'|^2
-    // are computed in fp64 ONCE per candidate when its run is staged and stored as one float4, so a candidate costs one
+    // are computed in fp64 ONCE per candidate when its chunk is staged and stored as one float4, so a candidate costs one
     // 16-byte broadcast LDS read and 3 fp32 FMAs per lane (the fp64 variant of this loop was bound by LDS bandwidth:
-    // 32 bytes per candidate broadcast to 64 lanes).  The loop keeps the two best GROUPS of <= 8 stream-consecutive
-    // candidates (rank + position) and the third-best rank.  The epilogue evaluates both groups EXACTLY in fp64
-    // ((dx*dx + dy*dy) + dz*dz, the CPU path's value; ties -> smallest original index, as the CPU path) — every
-    // candidate outside them ranks at least b3, so the exact minimum over the two groups is the answer whenever
-    // b3 - b1 exceeds twice the rank error (rank_tol).  The few lanes where it does not (about 0.05 %: three near-equal
-    // neighbours, or duplicates spread over three groups) go to the octree kernel, which is exact.
-    // Only the lanes of the current round's group rank its candidates (in_round: the exec mask of the ranking loop): a lane ranks
-    // candidates in exactly one round (one origin) and never sees a candidate twice.
-    float ax = 0, ay = 0, az = 0;
-    bool in_round = false;  // this lane belongs to the current round's group
+    // 32 bytes per candidate broadcast to 64 lanes).  The loop keeps the two best GROUPS of eight stream-consecutive
+    // candidates (rank + position IN THE ROUND'S STREAM) and the third-best rank.  At the end of the round both groups are
+    // evaluated EXACTLY in fp64 ((dx*dx + dy*dy) + dz*dz, the CPU path's value; ties -> smallest original index, as the CPU
+    // path) — every candidate outside them ranks at least b3, whatever the partition into groups, so the exact minimum over the
+    // two groups is the answer whenever b3 - b1 exceeds twice the rank error (rank_tol).  The few lanes where it does not (about
+    // 0.05 %: three near-equal neighbours, or duplicates spread over three groups) go to the octree kernel, which is exact.
+    // Only the lanes of the current round's group rank its candidates (`in`: the exec mask of the ranking loop): a lane ranks
+    // candidates in exactly one round (one origin) and never sees a candidate twice, so the ranking state and the exact result
+    // live INSIDE the round: nothing of them is alive while the next round's table is built.
     // rank error: the cell box spans <= 7 cells per axis, so |p'| <= 12 h, |a| <= 24 h, every term of r is below ~150 h^2
     // and carries a few 2^-24 relative: E < 1.2e-4 h^2 in the worst case (typically 10x less); the check uses 2E with margin
     const float rank_tol = (float) (1e-3 * cell_h * cell_h);
-    // (b1 <= b2 <= b3 are the three smallest ranks seen: the new second is the median of {b1, b2, m}, the new third the
-    // median of {b2, b3, m} — one v_med3_f32 each; fminf/fmaxf chains cost three times as many instructions, most of them
-    // NaN canonicalisations of values that are never NaN)
-#if ME_TUNE_NN_SGPR_MASKS
-    // The two compare masks go to SCALAR register pairs and the selects read them from there (VOP3 encodings, written out: the
-    // compiler puts both masks through vcc).  A v_cndmask_b32 that takes its mask from vcc right after the v_cmp that wrote it
-    // costs ~11 issue cycles on gfx950, 4.2 with the mask in an SGPR pair (profiles/r04_issue_rates.txt) — four of them per
-    // group of four candidates; b1 needs no select at all (ranks are never NaN: a plain minimum).
-    auto note = [&](float m, int j) {
-        unsigned long long lt1, lt2;
-        asm("v_cmp_lt_f32_e64 %0, %1, %2" : "=s"(lt1) : "v"(m), "v"(b1));
-        asm("v_cmp_lt_f32_e64 %0, %1, %2" : "=s"(lt2) : "v"(m), "v"(b2));
-        b3 = __builtin_amdgcn_fmed3f(b2, b3, m);
-        b2 = __builtin_amdgcn_fmed3f(b1, b2, m);
-        int jn;
-        asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(jn) : "v"(j2), "v"(j), "s"(lt2));   // lt2 ? j : j2
-        asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(j2) : "v"(jn), "v"(j1), "s"(lt1));  // lt1 ? j1 : jn
-        asm("v_min_f32_e32 %0, %1, %2" : "=v"(b1) : "v"(b1), "v"(m));                     // lt1 ? m : b1
-        asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(j1) : "v"(j1), "v"(j), "s"(lt1));   // lt1 ? j : j1
-    };
-#else
-    auto note = [&](float m, int j) {
-        const bool lt1 = m < b1, lt2 = m < b2;
-        b3 = __builtin_amdgcn_fmed3f(b2, b3, m);
-        b2 = __builtin_amdgcn_fmed3f(b1, b2, m);
-        const int jn = lt2 ? j : j2;  // (two selects, no branch)
-        j2 = lt1 ? j1 : jn;
-        b1 = lt1 ? m : b1;
-        j1 = lt1 ? j : j1;
-    };
-#endif
-    // Candidate delivery.  A run (the points of one cell) is copied into a wave-private LDS tile with ONE coalesced vector
-    // load per 64 points and read back with wave-uniform (broadcast) ds_reads, four candidates per group.  The first
-    // version fetched the candidates with scalar loads (s_load, candidate in SGPRs): the scalar cache misses on this
-    // stream (rocprofv3 SQC counters: 75 % of the requests), so every group of four paid an L2 round trip that 8 waves
-    // per SIMD could not hide (68 % VALU issue).
-    float4 *tile = s_tile[threadIdx.x >> 6];
-    double ox = 0, oy = 0, oz = 0;  // the round's local origin (wave-uniform)
-    // A run is padded to a multiple of four with records of rank +inf: no scalar tail loop (with 6-point cells most runs end
-    // in a partial group, and a lone candidate costs a whole note()).
+    // Candidate delivery (round 10).  The non-empty slots of the round's table become a run list {start, stream offset}
+    // (wave_run_list: slot order) and the round's candidates ONE stream, cut into chunks of 64 positions whatever run they fall
+    // into: one coalesced vector load per chunk — every lane busy but in the stream's last chunk —, one FP32 record per lane into
+    // the wave-private LDS tile, read back with wave-uniform (broadcast) ds_reads.  The finest grid's cells hold ~6 points: staged
+    // run by run (through round 9) a round of ~450 candidates took ~24 loads of ~19 lanes, each with the whole wave's record
+    // arithmetic and two fences, and every run was padded to a multiple of four (8 % of the ranked records were padding, a fifth
+    // of the note() calls half-groups).  Now ~8 loads, and only the stream's LAST chunk is padded, with records of rank +inf to a
+    // multiple of eight: every other group is eight real candidates.
+    // Which run holds stream position base + l (as k_mme3, me_mme.hip): s_r0 (scalar) = the run that holds `base`; the lanes read
+    // the offsets of the next 64 runs, those that begin at base + 1 .. base + 64 (at most 64 of them: a run holds a point) set bit
+    // (offset - base - 1) of the chunk's head mask in LDS, and lane l's run is s_r0 + the bits below l (v_mbcnt); the mask's
+    // population advances s_r0 to the run that holds base + 64.  No bound on a run's or the stream's length, no search.
+    // (The first version fetched the candidates with scalar loads: the scalar cache misses on this stream — rocprofv3 SQC
+    // counters: 75 % of the requests —, so every group of four paid an L2 round trip that 8 waves per SIMD could not hide.)
     // (Measured and rejected: candidates stored in pairs and ranked two at a time with v_pk_fma_f32 — 19 instead of 25
     // instructions per group of four, yet 13.8 ms against 13.0: the packed FMA does not issue faster than two plain ones.)
-    auto rank = [&](int j) {
-        const float4 c = tile[j];
-        return fmaf(c.x, ax, fmaf(c.y, ay, fmaf(c.z, az, c.w)));
-    };
-    // (ranks are never NaN: min3 / med3 rather than fminf, which canonicalises its operands first)
-    auto min3 = [](float a, float b, float c) { return __builtin_amdgcn_fmed3f(-INFINITY, a, __builtin_amdgcn_fmed3f(-INFINITY, b, c)); };
-    // One staged chunk (<= 64 points of one run, or of several runs that are contiguous in the sorted array): the lane's point of the
-    // chunk arrives in (px64, py64, pz64) — loaded ONE CHUNK AHEAD (round 6, below) — is shifted to the round's origin, written to
-    // the tile as an FP32 record and ranked by every lane of the group.
-    double px64 = 0, py64 = 0, pz64 = 0;
-    auto load_chunk = [&](int base, int n) {
-        if (lane < n && ME_NN_DBG != 2) {
-            const SPoint p = rsp[(ME_NN_DBG == 5) ? ((base + lane) & 4095) : (base + lane)];  // (5: staging from a cache-resident stretch)
-            px64 = p.x;
-            py64 = p.y;
-            pz64 = p.z;
-        }
-    };
-    auto stage_chunk = [&](int n) {
-        const int n4 = (n + 3) & ~3;
-        if (lane < n4 && ME_NN_DBG != 2) {
-            float4 rec = make_float4(0.0f, 0.0f, 0.0f, INFINITY);
-            if (lane < n) {
-                const double px = px64 - ox, py = py64 - oy, pz = pz64 - oz;
-                rec = make_float4((float) px, (float) py, (float) pz, (float) fma(pz, pz, fma(py, py, px * px)));
-            }
-            tile[lane] = rec;
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-    };
-    auto rank_chunk = [&](int base, int n) {
-        const int n4 = (n + 3) & ~3;
-        // Groups of EIGHT stream-consecutive candidates per note() (round 6; four through round 5): the three-smallest update
-        // and its position selects cost 11 vector instructions whatever the group holds — 25 per four candidates, 37 per eight —
-        // and the epilogue pays with eight exact fp64 evaluations per kept group instead of four.  A run's last four (n4 % 8)
-        // are noted as a group of their own; the epilogue evaluates eight positions from any group's start (positions past a
-        // group belong to the next cell along the curve: real reference points all the same).
-        // The group predicate is the EXEC mask of the ranking loop (lanes outside the round's group rank nothing), not a +inf
-        // bias added to every group's minimum.
-        if (in_round && ME_NN_DBG != 1 && ME_NN_DBG != 2) {
-            int j = 0;
-#if ME_NN_DBG == 4
-            float acc = 0.0f;
-            for (; j < n4; ++j) acc += rank(j);
-            if (acc == 12345.0f) note(acc, base);
-            j = n4;
-#endif
-            for (; j + 8 <= n4; j += 8) {
-                const float m0 = min3(rank(j), rank(j + 1), rank(j + 2));
-                const float m1 = min3(rank(j + 3), rank(j + 4), rank(j + 5));
-                note(min3(m0, m1, fminf_raw(rank(j + 6), rank(j + 7))), base + j);
-            }
-            if (j < n4) note(min3(rank(j), rank(j + 1), fminf_raw(rank(j + 2), rank(j + 3))), base + j);
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();  // the tile is overwritten by the next chunk
-    };
+    float4 *tile = s_tile[threadIdx.x >> 6];
+    __shared__ unsigned int s_head[4][2];  // per wave: which positions of the chunk being looked up begin a run (bit d: position d + 1)
+    unsigned int *head = s_head[threadIdx.x >> 6];
     // (the candidate set of a round is a superset of the lane's own 3x3x3 block; extra candidates only help)
     int2 *tab = s_tab[threadIdx.x >> 6];
     while (__ballot(!done)) {
@@ -294,12 +229,14 @@ k_nn_grid(const SPoint *__restrict__ qsp, long long q_begin, long long q_end, co
         // (cull: a run adjacent to no lane of the group is in nobody's 3x3x3 block, so nobody's resolution test needs it)
         const bool in = wave_group_table<1, true, kGroupR, false, true>(!done, mcx, mcy, mcz, g, cell_lim, lane, tab, bx, &nk,
                                                   reinterpret_cast<unsigned int *>(tile));
-        ox = uniform_f64(fr.ox + (double) bx.x0 * cell_h);  // (scalar registers: wave-uniform)
-        oy = uniform_f64(fr.oy + (double) bx.y0 * cell_h);
-        oz = uniform_f64(fr.oz + (double) bx.z0 * cell_h);
+        // the round's local origin (wave-uniform: scalar registers)
+        const double ox = uniform_f64(fr.ox + (double) bx.x0 * cell_h);
+        const double oy = uniform_f64(fr.oy + (double) bx.y0 * cell_h);
+        const double oz = uniform_f64(fr.oz + (double) bx.z0 * cell_h);
+        float ax = 0, ay = 0, az = 0;
         if (in) {
             // (the query point is NOT carried through the ranking loop — six vector registers the prefetched chunk point needs: it is
-            // loaded again where it is used, here and in the epilogue; an L2 hit)
+            // loaded again where it is used, here and at the end of the round; an L2 hit)
             unsigned int qo = qoff;
             asm volatile("" : "+v"(qo));
             const SPoint q = qsp[q_begin + (long long) qo];
@@ -307,110 +244,217 @@ k_nn_grid(const SPoint *__restrict__ qsp, long long q_begin, long long q_end, co
             ay = (float) (-2.0 * (q.y - oy));
             az = (float) (-2.0 * (q.z - oz));
         }
-        in_round = in;
-        // The chunks of the round, from an explicit iterator over the run table (wave-uniform state: scalar registers) with the NEXT
-        // chunk's load in flight while the current one is ranked (round 6): with the load issued after the previous chunk's ranking
-        // the wave sat out an L2 / HBM round trip ~20 times per round — 1.4 of 12.2 ms per step (ME_NN_DBG=5: the same kernel staging
-        // from a cache-resident stretch).  Runs that are contiguous in the sorted array (the curve visits cell x + 1 right after cell
-        // x) are streamed as one, as wave_for_each_run<MERGE> did.
-        int it_blk = -64, it_pos = 0, it_end = 0;
-        unsigned long long it_m = 0;
-        auto next_chunk = [&](int &cbase, int &cn) -> bool {
-            if (it_pos >= it_end) {
-                while (!it_m) {
-                    it_blk += 64;
-                    if (it_blk >= nk) return false;
-                    const int t = it_blk + lane;
-                    const int cnt = (t < nk) ? tab[t].y : 0;
-                    it_m = __ballot(cnt > 0);
+        float b1 = INFINITY, b2 = INFINITY, b3 = INFINITY;  // the three smallest group ranks seen
+        int j1 = -1, j2 = -1;  // positions in the round's stream of the groups that produced b1 and b2 (multiples of eight)
+        // (b1 <= b2 <= b3 are the three smallest ranks seen: the new second is the median of {b1, b2, m}, the new third the
+        // median of {b2, b3, m} — one v_med3_f32 each; fminf/fmaxf chains cost three times as many instructions, most of them
+        // NaN canonicalisations of values that are never NaN)
+#if ME_TUNE_NN_SGPR_MASKS
+        // The two compare masks go to SCALAR register pairs and the selects read them from there (VOP3 encodings, written out: the
+        // compiler puts both masks through vcc).  A v_cndmask_b32 that takes its mask from vcc right after the v_cmp that wrote it
+        // costs ~11 issue cycles on gfx950, 4.2 with the mask in an SGPR pair (profiles/r04_issue_rates.txt) — four of them per
+        // group; b1 needs no select at all (ranks are never NaN: a plain minimum).
+        auto note = [&](float m, int j) {
+            unsigned long long lt1, lt2;
+            asm("v_cmp_lt_f32_e64 %0, %1, %2" : "=s"(lt1) : "v"(m), "v"(b1));
+            asm("v_cmp_lt_f32_e64 %0, %1, %2" : "=s"(lt2) : "v"(m), "v"(b2));
+            b3 = __builtin_amdgcn_fmed3f(b2, b3, m);
+            b2 = __builtin_amdgcn_fmed3f(b1, b2, m);
+            int jn;
+            asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(jn) : "v"(j2), "v"(j), "s"(lt2));   // lt2 ? j : j2
+            asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(j2) : "v"(jn), "v"(j1), "s"(lt1));  // lt1 ? j1 : jn
+            asm("v_min_f32_e32 %0, %1, %2" : "=v"(b1) : "v"(b1), "v"(m));                     // lt1 ? m : b1
+            asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(j1) : "v"(j1), "v"(j), "s"(lt1));   // lt1 ? j : j1
+        };
+#else
+        auto note = [&](float m, int j) {
+            const bool lt1 = m < b1, lt2 = m < b2;
+            b3 = __builtin_amdgcn_fmed3f(b2, b3, m);
+            b2 = __builtin_amdgcn_fmed3f(b1, b2, m);
+            const int jn = lt2 ? j : j2;  // (two selects, no branch)
+            j2 = lt1 ? j1 : jn;
+            b1 = lt1 ? m : b1;
+            j1 = lt1 ? j : j1;
+        };
+#endif
+        auto rank = [&](int j) {
+            const float4 c = tile[j];
+            return fmaf(c.x, ax, fmaf(c.y, ay, fmaf(c.z, az, c.w)));
+        };
+        // (ranks are never NaN: min3 / med3 rather than fminf, which canonicalises its operands first)
+        auto min3 = [](float a, float b, float c) { return __builtin_amdgcn_fmed3f(-INFINITY, a, __builtin_amdgcn_fmed3f(-INFINITY, b, c)); };
+
+        int n_runs = 0;
+        const int total = wave_run_list(tab, nk, lane, &n_runs);  // the stream's length (scalar)
+        int s_r0 = 0;  // the run that holds the first position of the next chunk to be looked up (scalar)
+        // One chunk: positions [base, base + 64) of the stream.  The lane's point of the chunk arrives in (px64, py64, pz64) — looked up
+        // and loaded ONE CHUNK AHEAD (round 6: with the load issued after the previous chunk's ranking the wave sat out an L2 / HBM
+        // round trip per chunk, 1.4 of 12.2 ms per step; ME_NN_DBG=5, the same kernel staging from a cache-resident stretch) —, is
+        // shifted to the round's origin, written to the tile as an FP32 record and ranked by every lane of the group.
+        double px64 = 0, py64 = 0, pz64 = 0;
+        auto load_chunk = [&](int base) {
+            if (ME_NN_DBG == 2) return;
+            if (lane < 2) head[lane] = 0u;
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            if (s_r0 + 1 + lane < n_runs) {
+                const int d = tab[s_r0 + 1 + lane].y - base - 1;  // >= 0: run s_r0 + 1 begins after `base`
+                if (d < 64) atomicOr(&head[d >> 5], 1u << (d & 31));
+            }
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            const unsigned int h0 = (unsigned int) __builtin_amdgcn_readfirstlane((int) head[0]);
+            const unsigned int h1 = (unsigned int) __builtin_amdgcn_readfirstlane((int) head[1]);
+            if (base + lane < total) {
+                const int2 run = tab[s_r0 + (int) __builtin_amdgcn_mbcnt_hi(h1, __builtin_amdgcn_mbcnt_lo(h0, 0u))];
+                const int gi = run.x + (base + lane - run.y);  // inside its run: inside the cloud
+                const SPoint p = rsp[(ME_NN_DBG == 5) ? (gi & 4095) : gi];  // (5: staging from a cache-resident stretch)
+                px64 = p.x;
+                py64 = p.y;
+                pz64 = p.z;
+            }
+            s_r0 += __popc(h0) + __popc(h1);
+        };
+        auto stage_chunk = [&](int n) {
+            const int n8 = (n + 7) & ~7;
+            if (lane < n8 && ME_NN_DBG != 2) {
+                float4 rec = make_float4(0.0f, 0.0f, 0.0f, INFINITY);  // (padding of the stream's last group: never the minimum)
+                if (lane < n) {
+                    const double px = px64 - ox, py = py64 - oy, pz = pz64 - oz;
+                    rec = make_float4((float) px, (float) py, (float) pz, (float) fma(pz, pz, fma(py, py, px * px)));
                 }
-                const int sidx = __ffsll((long long) it_m) - 1;
-                it_m &= it_m - 1;
-                const int2 run = tab[it_blk + sidx];
-                it_pos = __builtin_amdgcn_readfirstlane(run.x);
-                it_end = it_pos + __builtin_amdgcn_readfirstlane(run.y);
-                while (it_m) {  // contiguous successors inside this block of the table
-                    const int s2 = __ffsll((long long) it_m) - 1;
-                    const int2 nx = tab[it_blk + s2];
-                    if (__builtin_amdgcn_readfirstlane(nx.x) != it_end) break;
-                    it_end += __builtin_amdgcn_readfirstlane(nx.y);
-                    it_m &= it_m - 1;
+                tile[lane] = rec;
+            }
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+        };
+        auto rank_chunk = [&](int base, int n) {
+            const int n8 = (n + 7) & ~7;
+            // Groups of EIGHT stream-consecutive candidates per note() (round 6; four through round 5): the three-smallest update
+            // and its position selects cost 11 vector instructions whatever the group holds — 25 per four candidates, 37 per eight —
+            // and the exact evaluation pays with eight fp64 distances per kept group instead of four.
+            // The group predicate is the EXEC mask of the ranking loop (lanes outside the round's group rank nothing), not a +inf
+            // bias added to every group's minimum.
+            if (in && ME_NN_DBG != 1 && ME_NN_DBG != 2) {
+                int j = 0;
+#if ME_NN_DBG == 4
+                float acc = 0.0f;
+                for (; j < n8; ++j) acc += rank(j);
+                if (acc == 12345.0f) note(acc, base);
+                j = n8;
+#endif
+                for (; j + 8 <= n8; j += 8) {
+                    const float m0 = min3(rank(j), rank(j + 1), rank(j + 2));
+                    const float m1 = min3(rank(j + 3), rank(j + 4), rank(j + 5));
+                    note(min3(m0, m1, fminf_raw(rank(j + 6), rank(j + 7))), base + j);
                 }
             }
-            cbase = it_pos;
-            cn = min(64, it_end - it_pos);
-            it_pos += cn;
-            return true;
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            __builtin_amdgcn_wave_barrier();  // the tile is overwritten by the next chunk
         };
-        int cb = 0, cn = 0;
-        bool have = next_chunk(cb, cn);
-        if (have) load_chunk(cb, cn);
-        while (have) {
-            stage_chunk(cn);
-            int nb2 = 0, nn2 = 0;
-            const bool nhave = next_chunk(nb2, nn2);
-            if (nhave) load_chunk(nb2, nn2);  // lands under the ranking below
-            rank_chunk(cb, cn);
-            have = nhave;
-            cb = nb2;
-            cn = nn2;
+#ifdef ME_NN_STATS
+        int st_chunks = 0, st_rec = 0;
+#endif
+        if (total > 0) load_chunk(0);
+        for (int base = 0; base < total; base += 64) {
+            const int n = min(64, total - base);
+            stage_chunk(n);
+            if (base + 64 < total) load_chunk(base + 64);  // lands under the ranking below
+            rank_chunk(base, n);
+#ifdef ME_NN_STATS
+            ++st_chunks;
+            st_rec += (n + 7) & ~7;
+#endif
         }
-        if (in) done = true;
-        __builtin_amdgcn_wave_barrier();
-    }
-
-    bool unresolved = false;
-    if (active) {
-        unresolved = true;
+#ifdef ME_NN_STATS
         {
-            unsigned int qo = qoff;
-            asm volatile("" : "+v"(qo));
-            const SPoint q = qsp[q_begin + (long long) qo];
-            qx = q.x;
-            qy = q.y;
-            qz = q.z;
+            const int served = __popcll(__ballot(in));
+            if (lane == 0) {
+                unsigned long long *st = g_nn_stat + (FROM_LIST ? 8 : 0);
+                atomicAdd(&st[0], 1ULL);
+                atomicAdd(&st[1], (unsigned long long) st_chunks);
+                atomicAdd(&st[2], (unsigned long long) total);
+                atomicAdd(&st[3], (unsigned long long) st_rec);
+                atomicAdd(&st[4], (unsigned long long) (st_rec >> 3));
+                atomicAdd(&st[6], (unsigned long long) served);
+            }
         }
-        // exact distances of the two best groups (positions past a group's run belong to cells outside the candidate set:
-        // real reference points all the same, so a closer one among them is a better answer, not an error)
-        double best_x = INFINITY;
-        long long best_i = 0x7fffffffffffffffLL;
-        auto exact_group = [&](int jg) {
-            if (jg < 0 || ME_NN_DBG == 3) return;
+#endif
+        // The lane's answer, while the round's run list is still in LDS (the next round's table overwrites it): a kept group is
+        // eight positions of the STREAM from j — it may straddle several runs, up to eight of one point each —, translated through
+        // the run list: the run that holds j by bisection over the stream offsets (<= 9 probes for <= 343 runs), then forward
+        // across the run boundaries (a run holds a point: at most one boundary per position).  Positions at or past the stream's
+        // length are the padding of its last group: skipped.  A group's members are exactly the stream's candidates.
+        if (in) {
+            double qx, qy, qz;
+            {
+                unsigned int qo = qoff;
+                asm volatile("" : "+v"(qo));
+                const SPoint q = qsp[q_begin + (long long) qo];
+                qx = q.x;
+                qy = q.y;
+                qz = q.z;
+            }
+            double best_x = INFINITY;
+            long long best_i = 0x7fffffffffffffffLL;
+            const int step0 = 1 << (31 - __clz(n_runs | 1));  // (scalar) the largest power of two <= n_runs
+            auto exact_group = [&](int jg) {
+                if (jg < 0 || ME_NN_DBG == 3) return;
+                int r = 0;  // the last run whose offset is <= jg
+                for (int step = step0; step; step >>= 1) {
+                    const int c = r + step;
+                    if (c < n_runs && tab[c].y <= jg) r = c;
+                }
+                int2 cur = tab[r];
+                int nxt = tab[r + 1].y;  // (the list is closed by {0, stream length})
 #pragma unroll
-            for (int t = 0; t < 8; ++t) {
-                const long long pos = (long long) jg + t;
-                if (pos < nr) {
-                    const SPoint p = rsp[pos];
-                    const double e = dist2_exact(qx, qy, qz, p.x, p.y, p.z);
-                    if (e < best_x || (e == best_x && p.idx < best_i)) {
-                        best_x = e;
-                        best_i = p.idx;
+                for (int t = 0; t < 8; ++t) {
+                    const int pos = jg + t;
+                    if (pos < total) {
+                        if (pos >= nxt) {  // pos < total: run r + 1 exists
+                            ++r;
+                            cur = tab[r];
+                            nxt = tab[r + 1].y;
+                        }
+                        const SPoint p = rsp[cur.x + (pos - cur.y)];
+                        const double e = dist2_exact(qx, qy, qz, p.x, p.y, p.z);
+                        if (e < best_x || (e == best_x && p.idx < best_i)) {
+                            best_x = e;
+                            best_i = p.idx;
+                        }
                     }
                 }
+            };
+            exact_group(j1);
+            // The second group is evaluated only where it can matter (round 6): when b2 - b1 exceeds the rank tolerance every candidate
+            // outside the best group — the second group's included — is strictly farther than the best group's minimum, in exact
+            // arithmetic too.  Eight scattered 32-byte loads per lane less for the large majority of the lanes (the vector memory
+            // pipe's cost of a load follows its active lanes): with groups of eight the exact evaluation moved 25 GB per 50 M-query
+            // launch through L1 / L2 and ate what the ranking loop had saved.
+            if (!(b2 - b1 > rank_tol)) exact_group(j2);
+            const bool ranking_safe = b3 - b1 > rank_tol;
+            if (j1 >= 0 && ranking_safe) {
+                // distance from q to the faces of the 3x3x3 cell block around its cell (>= one cell edge... minus where
+                // q sits in its cell); anything outside the block is at least that far away
+                // (the faces are computed HERE, once per lane: the asm keeps the compiler from hoisting six doubles that depend only
+                // on the lane's cell out of the round loop, where they are spilled)
+                int ux = mcx, uy = mcy, uz = mcz;
+                asm volatile("" : "+v"(ux), "+v"(uy), "+v"(uz));
+                const double lox = fr.ox + (double) (ux - 1) * cell_h, hix = fr.ox + (double) (ux + 2) * cell_h;
+                const double loy = fr.oy + (double) (uy - 1) * cell_h, hiy = fr.oy + (double) (uy + 2) * cell_h;
+                const double loz = fr.oz + (double) (uz - 1) * cell_h, hiz = fr.oz + (double) (uz + 2) * cell_h;
+                double gmin = fmin(fmin(qx - lox, hix - qx), fmin(fmin(qy - loy, hiy - qy), fmin(qz - loz, hiz - qz)));
+                gmin *= (1.0 - 1e-9);  // rounding slack of the cell assignment
+                unresolved = !(gmin > 0.0 && best_x < gmin * gmin);
             }
-        };
-        exact_group(j1);
-        // The second group is evaluated only where it can matter (round 6): when b2 - b1 exceeds the rank tolerance every candidate
-        // outside the best group — the second group's included — is strictly farther than the best group's minimum, in exact
-        // arithmetic too.  Eight scattered 32-byte loads per lane less for the large majority of the lanes (the vector memory
-        // pipe's cost of a load follows its active lanes): with groups of eight the epilogue moved 25 GB per 50 M-query launch
-        // through L1 / L2 and ate what the ranking loop had saved.
-        if (!(b2 - b1 > rank_tol)) exact_group(j2);
-        const bool ranking_safe = b3 - b1 > rank_tol;
-        if (in_grid && j1 >= 0 && ranking_safe) {
-            // distance from q to the faces of the 3x3x3 cell block around its cell (>= one cell edge... minus where
-            // q sits in its cell); anything outside the block is at least that far away
-            const double lox = fr.ox + (double) (mcx - 1) * cell_h, hix = fr.ox + (double) (mcx + 2) * cell_h;
-            const double loy = fr.oy + (double) (mcy - 1) * cell_h, hiy = fr.oy + (double) (mcy + 2) * cell_h;
-            const double loz = fr.oz + (double) (mcz - 1) * cell_h, hiz = fr.oz + (double) (mcz + 2) * cell_h;
-            double gmin = fmin(fmin(qx - lox, hix - qx), fmin(fmin(qy - loy, hiy - qy), fmin(qz - loz, hiz - qz)));
-            gmin *= (1.0 - 1e-9);  // rounding slack of the cell assignment
-            unresolved = !(gmin > 0.0 && best_x < gmin * gmin);
+            unsigned int qo = qoff;
+            asm volatile("" : "+v"(qo));
+            d2_out[q_begin + (long long) qo] = best_x;  // final if resolved, initial bound otherwise
+            idx_out[q_begin + (long long) qo] = (j1 >= 0) ? (int) best_i : -1;
+            done = true;
         }
-        unsigned int qo = qoff;
-        asm volatile("" : "+v"(qo));
-        d2_out[q_begin + (long long) qo] = best_x;  // final if resolved, initial bound otherwise
-        idx_out[q_begin + (long long) qo] = (j1 >= 0) ? (int) best_i : -1;
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();  // the next round's table overwrites the run list
     }
     if (ME_NN_DBG) unresolved = false;  // (measurement builds: nothing goes to the octree pass)
     if (!FROM_LIST && flag_out) {
@@ -1192,6 +1236,19 @@ int nn_search(me_ctx *ctx, int qslot, int rslot) {
                                    ctx->timers_on ? ctx->nn1_dbg() : nullptr, (const double *) nullptr, 0);
             }
         }
+#ifdef ME_NN_STATS
+        {
+            unsigned long long st[16] = {0}, zero[16] = {0};
+            ME_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+            (void) hipMemcpyFromSymbol(st, HIP_SYMBOL(g_nn_stat), sizeof st);
+            (void) hipMemcpyToSymbol(HIP_SYMBOL(g_nn_stat), zero, sizeof zero);
+            for (int k = 0; k < 2; ++k) {
+                const unsigned long long *t = st + 8 * k;
+                if (t[0]) std::fprintf(stderr, "[nn stats] %s queries=%lld rounds=%llu per round: chunks=%.2f lanes/load=%.2f candidates=%.1f ranked records=%.1f note8=%.2f note4=%.2f lanes served=%.1f\n",
+                    k ? "list" : "grid", (long long) (e - b), t[0], (double) t[1] / t[0], (double) t[2] / (double) (t[1] ? t[1] : 1), (double) t[2] / t[0], (double) t[3] / t[0], (double) t[4] / t[0], (double) t[5] / t[0], (double) t[6] / t[0]);
+            }
+        }
+#endif
         if (ctx->timers_on) {  // fallback share, for the bench report
             unsigned int h = 0;
             ME_TRY(copy_d2h(ctx, &h, d_cnt, 4));
