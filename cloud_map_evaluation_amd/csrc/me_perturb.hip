@@ -136,12 +136,18 @@ int perturb_cloud(me_ctx *ctx, int dst_slot, int src_slot, const me_perturb_para
         return ctx->fail(ME_ERR_ARG, "me_perturb_cloud: sparse_ratio, dense_ratio and outlier_ratio must lie in [0, 1]");
     if (!(p->outlier_range >= 0) || !std::isfinite(p->outlier_range))
         return ctx->fail(ME_ERR_ARG, "me_perturb_cloud: outlier_range must be finite and >= 0");
+    const bool deform_on = p->deform_radius > 0 && p->deform_strength != 0;
+    if (deform_on && (!std::isfinite(p->deform_strength) || !std::isfinite(p->deform_center[0]) || !std::isfinite(p->deform_center[1]) ||
+                      !std::isfinite(p->deform_center[2])))  // (radius = +inf stays legal: w = 1, a rigid push by strength)
+        return ctx->fail(ME_ERR_ARG, "me_perturb_cloud: deform_strength and deform_center must be finite while the deform stage is on");
     Cloud &S = ctx->cloud[src_slot];
     if (!S.uploaded) return ctx->fail(ME_ERR_STATE, "me_perturb_cloud: source cloud not uploaded");
+    if (S.n == 0)  // (a me_mesh_scan without a hit leaves this, as need_single_gpu_cloud notes: nothing to scan, no pos[n - 1] to read)
+        return ctx->fail(ME_ERR_STATE, "me_perturb_cloud: the slot's cloud is empty");
     ME_CHECK(ctx, hipSetDevice(ctx->device));
     const long long n = S.n;
     PerturbK k{};
-    k.deform = p->deform_radius > 0 && p->deform_strength != 0;
+    k.deform = deform_on;
     k.cx = p->deform_center[0];
     k.cy = p->deform_center[1];
     k.cz = p->deform_center[2];

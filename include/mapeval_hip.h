@@ -274,8 +274,11 @@ int me_transform_cloud(me_ctx *ctx, int slot, const double *T_rowmajor4x4);
  * point gets the same noise whatever the density stage dropped, and nothing depends on the launch shape.
  * dst gets the upload-time reset (index rebuilt on the source's cell size; NN, MME, voxel state invalidated; normals and
  * covariances dropped; the other slot's NN result invalidated); src is left untouched unless dst == src (in place works).
- * *n_out = points in dst.  ME_ERR_ARG: p NULL, slab or shard mode, noise_std < 0, a ratio outside [0, 1], outlier_range < 0, an
- * output of 2^31 points or more, or no survivor.  Device timer "perturb". */
+ * *n_out = points in dst.  ME_ERR_ARG: p NULL, slab or shard mode, noise_std < 0 or non-finite, a ratio outside [0, 1],
+ * outlier_range < 0 or non-finite, a non-finite deform_strength or deform_center while the deform stage is on (deform_radius =
+ * +inf is legal: w = 1, every point is pushed by deform_strength along its direction; a NaN deform_radius or region_size
+ * switches its stage off), an output of 2^31 points or more, or no survivor.  ME_ERR_STATE: src not uploaded, or uploaded but
+ * empty (a me_mesh_scan without a hit).  A refused call leaves dst as it was.  Device timer "perturb". */
 typedef struct me_perturb_params {
     double noise_std;                    /* addGaussianNoise noise_std_dev (map_eval.cpp:1746)            (0 = off)    */
     double sparse_ratio, dense_ratio;    /* addNonUniformDensity keep probabilities (:1758-1759)                       */

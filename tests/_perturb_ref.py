@@ -119,6 +119,18 @@ def outlier_offsets(m: int, range_: float, seed: int) -> np.ndarray:
     return range_ * np.stack([nx, ny, nz], axis=1)
 
 
+# ---- the bounds of the device tests (test_gpu_perturb.py, test_gpu_perturb_edges.py): one place, so that the two cannot drift -------
+def survivor_bound(sigma: float, deformed: np.ndarray, strength: float) -> np.ndarray:
+    """|(device survivor - model's deformed point) - model's noise| stays below this: 1e-12 sigma (a log, sqrt, sin or cos that differs
+    by an ulp) plus the rounding of the subtraction and of a deform cos that may differ by an ulp."""
+    return 1e-12 * sigma + (2 * np.spacing(np.abs(deformed)) + 4 * np.spacing(abs(strength)))
+
+
+def outlier_bound(range_: float, outliers: np.ndarray) -> np.ndarray:
+    """|(device outlier - its base point as downloaded) - model's N(0, range^2) offset| stays below this."""
+    return 1e-12 * range_ + 2 * np.spacing(np.abs(outliers))
+
+
 def perturb(src: np.ndarray, *, noise_std=0.0, sparse_ratio=1.0, dense_ratio=1.0, region_size=0.0, outlier_ratio=0.0,
             outlier_range=0.0, deform_radius=0.0, deform_strength=0.0, deform_center=(0.0, 0.0, 0.0), seed=0) -> dict:
     """The whole pipeline: deform -> density -> noise -> outliers.  Returns the points and what the tests compare: the survivors'

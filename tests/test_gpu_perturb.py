@@ -69,8 +69,8 @@ def test_stage_matches_the_numpy_model(scene, case):
     # survivor k of the device is the model's survivor k (source index src_index[k]): its offset from the model's deformed point is the
     # model's noise of that source index, within 1e-12 sigma plus the rounding of the subtraction (and of a cos that may differ by an ulp)
     sigma = kw.get("noise_std", 0.0)
-    spacing = 2 * np.spacing(np.abs(ref["deformed"])) + 4 * np.spacing(abs(kw.get("deform_strength", 0.0)))
-    np.testing.assert_array_less(np.abs((kept - ref["deformed"]) - ref["noise"]), 1e-12 * sigma + spacing)
+    np.testing.assert_array_less(np.abs((kept - ref["deformed"]) - ref["noise"]),
+                                 R.survivor_bound(sigma, ref["deformed"], kw.get("deform_strength", 0.0)))
     if case == "density":  # no arithmetic on the survivors at all: bit-exact copies of the source points
         assert np.array_equal(_bits(kept), _bits(scene[ref["src_index"]]))
         assert nk < len(scene)
@@ -82,7 +82,7 @@ def test_stage_matches_the_numpy_model(scene, case):
     if m:  # the outliers' base indices: outlier j - its model base point = the model's N(0, range^2) offset
         off = outl - kept[ref["bases"]]
         rng = kw["outlier_range"]
-        np.testing.assert_array_less(np.abs(off - R.outlier_offsets(m, rng, SEED)), 1e-12 * rng + 2 * np.spacing(np.abs(outl)))
+        np.testing.assert_array_less(np.abs(off - R.outlier_offsets(m, rng, SEED)), R.outlier_bound(rng, outl))
         assert m == int(nk * kw["outlier_ratio"])
 
 
