@@ -44,7 +44,7 @@ __global__ void __launch_bounds__(256) k_bbox(const double *__restrict__ xyz, lo
         for (int d = 0; d < 3; ++d) {
             const double v = xyz[3 * i + d];
             lo[d] = fmin(lo[d], v);
-            hi[d] = fmax(hi[d], v);
+            hi[d] = fmax(hi[d], isnan(v) ? INFINITY : v);  // (fmin / fmax drop a NaN: it has to reach the host's isfinite test)
         }
     }
     __shared__ double sm[4][6];
@@ -116,7 +116,7 @@ k_ingest(const double *__restrict__ in, long long n, int has_T, Mat4 T, double *
         for (int d = 0; d < 3; ++d) {
             out[3 * i + d] = p[d];
             lo[d] = fmin(lo[d], p[d]);
-            hi[d] = fmax(hi[d], p[d]);
+            hi[d] = fmax(hi[d], isnan(p[d]) ? INFINITY : p[d]);  // (as k_bbox: a NaN must not be dropped)
         }
     }
     __shared__ double sm[4][6];
